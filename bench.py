@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py -- complex MS/s of the NRSC-5 shift + resample chain on MI355X (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, settles, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the
+`roofline` of the kernels the timed steps ran (HIP events inside the timed region, no run of their own).
+Every other leg -- host_end_to_end and its stub-sized batches, `extra`, `secondary` (configs[2], configs[3], the
+shipped presets, the 8-bit shapes) and `cpu_baseline` -- runs only with --full (its keys are null otherwise).
+--dump-outputs DIR writes what the last timed step handed its caller, as float32 .npy files (see dump_outputs).
 
 One process per GPU: under torch.distributed.run the ranks come from the environment; run plainly with
 --gpus N > 1 the script spawns its N workers itself (before anything touches the GPU) and rank 0's
@@ -100,7 +106,7 @@ def parse():
     ap.add_argument("--no-secondary", action="store_true", help="skip the `secondary` legs (BASELINE configs[2], configs[3], the preset with its AGC)")
     ap.add_argument("--secondary-steps", type=int, default=10)
     ap.add_argument("--preset-settle", type=float, default=0.4, help="seconds of untimed steps in front of each leg of secondary.presets")
-    ap.add_argument("--only-presets", action="store_true", help="diagnostic: skip the headline legs' extras and run secondary.presets only")
+    ap.add_argument("--only-presets", action="store_true", help="diagnostic: skip the headline legs' extras and run secondary.presets only (implies --full)")
     ap.add_argument("--presets", default="", help="diagnostic: comma-separated names of the shipped presets to run in secondary.presets (default: all seven)")
     ap.add_argument("--secondary-settle", type=float, default=0.7, help="seconds of untimed steps in front of each secondary leg")
     ap.add_argument("--host-log2-frames", type=int, default=30, help="frames per GPU streamed through pinned host buffers in the host_end_to_end leg")
@@ -111,12 +117,20 @@ def parse():
                     help="frames per submit() in the host_end_to_end_stub64 leg: the stub's batch when the reader queue is deep (64 reference chunks)")
     ap.add_argument("--stub-log2-frames", type=int, default=28, help="frames per GPU streamed in the host_end_to_end_stub leg")
     ap.add_argument("--no-extra", action="store_true", help="skip the `extra` legs (stub-sized host batches, block_samples = 262144, reference-binary probe)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline figure: host_end_to_end (+ stub batches), `extra`, `secondary` and "
+                         "cpu_baseline (each still subject to its --no-* switch).  Off by default: a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0) as DIR/<name>.npy, float32 / float64, "
+                         "a fixed seeded sample of the output frames (under 40 MB in all)")
     ap.add_argument("--dry-placement", action="store_true",
                     help="everything an N-GPU run does EXCEPT GPU work: spawn the N ranks, bind each to the NUMA node of its GPU (sysfs; "
                          "IQGPU_SYSFS_ROOT names a stand-in tree), rendezvous over gloo, gather and check the devices (N distinct PCI "
                          "addresses), size the pinned and HBM buffers of every leg, run the barrier + MAX plumbing on an empty step, print "
                          "ONE JSON line.  For rehearsing the first multi-GPU run on a machine without GPUs")
     a = ap.parse_args()
+    if a.only_presets:
+        a.full = True                                  # the presets are legs of `secondary`, which --full runs
     a.preset = a.config == "preset"
     a.config = 2 if a.preset else int(a.config)
     return a
@@ -300,10 +314,39 @@ def step_flops(info, frames, n_res, n_emit, desc_kw, ntaps, taps_complex):
     return f + executed, f + direct
 
 
-def run_case(args, dist, dev, local_rank, world, rank, config, preset, steps, warmup, settle_s, log2_frames, shipped=None):
+DUMP_HEAD_FRAMES = 1 << 20      # --dump-outputs: first and last frames of the last step's output, and a seeded sample of this many
+DUMP_SEED = 20261016
+
+
+def dump_outputs(out_dir, chain, d_out, n_frames):
+    """--dump-outputs: what the last timed step handed its caller -- n_frames output frames in d_out, in the chain's output format --
+    as float32 arrays of shape (frames, components): output_head / output_tail (the first and last DUMP_HEAD_FRAMES frames),
+    output_sample (DUMP_HEAD_FRAMES frames at positions drawn with a fixed seed, ascending; output_sample_index holds them, float64)
+    and output_frames (float64, the frame count the step returned): 32 MiB at most.  run_case resets the chain after the settle
+    period when it dumps, so the same arguments give the same inputs and the same stream position: the same files."""
+    import torch
+    from iq_tool_amd.chain import _NP_VIEW
+    os.makedirs(out_dir, exist_ok=True)
+    ob = chain.out_bytes
+    frames = d_out[:n_frames * ob].view(n_frames, ob)
+    np_dtype = _NP_VIEW[chain.desc.out_format]
+    k = min(n_frames, DUMP_HEAD_FRAMES)
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_frames, size=k, replace=False))
+
+    def host(rows):
+        return rows.contiguous().cpu().numpy().view(np_dtype).reshape(rows.shape[0], -1).astype(np.float32)
+
+    arrays = {"output_head": host(frames[:k]), "output_tail": host(frames[n_frames - k:]),
+              "output_sample": host(frames[torch.from_numpy(idx).to(d_out.device)]),
+              "output_sample_index": idx.astype(np.float64), "output_frames": np.array([n_frames], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def run_case(args, dist, dev, local_rank, world, rank, config, preset, steps, warmup, settle_s, log2_frames, shipped=None, dump_dir=None):
     """One timed leg: build the chain of `config` (2, 3, 4; preset = config 2 with the output AGC; shipped = the name of one of
     PRESETS), put its batch into HBM, settle, warm up, time `steps` steps between barriers.  Returns the raw figures; the caller
-    formats them."""
+    formats them.  dump_dir: write the last timed step's output there (dump_outputs), after the timing."""
     import torch
     import iq_tool_amd
     from iq_tool_amd import synth
@@ -344,6 +387,10 @@ def run_case(args, dist, dev, local_rank, world, rank, config, preset, steps, wa
             step()
         sync()
         out_frames.clear()
+    if dump_dir is not None:
+        # the settle period ran as many steps as the clock allowed: the stream starts afresh here so that the dumped step depends on
+        # the arguments alone (warm-up + timed steps from a reset chain)
+        chain.reset()
     for _ in range(warmup):
         step()
     sync()
@@ -353,6 +400,8 @@ def run_case(args, dist, dev, local_rank, world, rank, config, preset, steps, wa
     dt = timed_region(dist, sync, step, steps)
     prof = chain.profile()
     chain.set_profiling(False)
+    if dump_dir is not None and out_frames:
+        dump_outputs(dump_dir, chain, d_out, int(out_frames[-1]))
 
     front = prof["front"]
     k_ms = front["ms"] / max(front["launches"], 1)
@@ -655,7 +704,8 @@ def main():
         if any(d.get("pci_bus_id_error") for d in devices) or len(set(ids)) != world:
             raise SystemExit("bench.py: %d ranks do not sit on %d distinct GPUs: %s" % (world, world, devices))
 
-    case = run_case(args, dist, dev, local_rank, world, rank, args.config, args.preset, args.steps, args.warmup, args.settle_seconds, args.log2_frames)
+    case = run_case(args, dist, dev, local_rank, world, rank, args.config, args.preset, args.steps, args.warmup, args.settle_seconds, args.log2_frames,
+                    dump_dir=args.dump_outputs if rank == 0 else None)
     front_kernel = case["chain"].front_kernel()
     chain, seg, frames, dt, k_ms, prof, front, n_out_avg, alg_bytes, achieved, chain_kw, in_bps, workload = (
         case[k] for k in ("chain", "seg", "frames", "dt", "k_ms", "prof", "front", "n_out_avg", "alg_bytes", "achieved", "chain_kw", "in_bps", "workload"))
@@ -663,7 +713,7 @@ def main():
 
     # ---- second leg: the same chain fed from pinned host memory (PCIe-inclusive; never `value`) ----
     host = None
-    if not args.no_host_leg and args.config == 2 and not args.preset:
+    if args.full and not args.no_host_leg and args.config == 2 and not args.preset:
         chain.set_stream(0)                            # back to the chain's own stream
         chain.reset()
         h_dt, h_frames, h_up, h_down = host_leg(dist, chain, seg, 1 << args.host_log2_frames, 1 << args.host_batch_log2)
@@ -696,7 +746,7 @@ def main():
         line = {
             "metric": "complex MS/s end-to-end on NRSC-5 resample+filter chain; % HBM roofline",
             "value": round(value, 2), "unit": "MS/s", "value_is": "device_resident (inputs in HBM when the timed region starts; host_end_to_end is the PCIe-inclusive rate)",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(dt / args.steps * 1e3, 4), "settle_s": args.settle_seconds,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic (seeded 2^%d-frame cs16 segment, 3 tones + noise + DC, tiled in HBM to 2^%d frames per GPU)" % (int(np.log2(min(frames, 1 << SEGMENT_LOG2))), case["log2_frames"]),
@@ -731,7 +781,7 @@ def main():
     # ---- the other single-GPU BASELINE configs and the shipped preset: short legs of their own, after everything that feeds `value`
     # (N = 1 only: they are per-GPU figures, and a leg that failed on one rank of several would leave the others in a barrier)
     sec = extra = None
-    if args.config == 2 and not args.preset and world == 1:
+    if args.full and args.config == 2 and not args.preset and world == 1:
         case = chain = None
         torch.cuda.empty_cache()
         if not args.no_extra:
@@ -760,7 +810,7 @@ def main():
     if dist is not None:
         dist.barrier()
     if rank == 0:
-        if not args.no_cpu_baseline and args.config == 2 and not args.preset:
+        if args.full and not args.no_cpu_baseline and args.config == 2 and not args.preset:
             try:
                 line["cpu_baseline"] = cpu_baseline(args.cpu_frames_log2)
             except Exception as exc:

@@ -8,9 +8,15 @@
                        (the reference's liquid-dsp half cannot be built here): a regression pin of the
                        restatement, not a reference output.
   design.npz           half-band / polyphase / NCO / filter design constants of the oracle.
+  sample_convert_live.json
+                       sha256 of what the REFERENCE's sample_convert.c (oracle/_ref) returns for the seeded
+                       inputs of tests/test_oracle.py::test_convert_matches_reference_build_live, so that the
+                       test pins the oracle to the reference where oracle/_ref cannot be built.
 
 Run here (needs /root/reference for the first file):  python tests/golden/gen_golden.py
 """
+import hashlib
+import json
 import os
 import sys
 
@@ -23,6 +29,7 @@ from iq_tool_amd import synth  # noqa: E402
 from oracle import pyoracle as po  # noqa: E402
 
 FORMATS = ["cs8", "cu8", "cs16", "cu16", "sc16q11", "cs24", "cs32", "cu32", "cf32"]
+LIVE_GAINS = (1.0, 0.123, -7.0)
 
 
 def convert_vectors():
@@ -59,6 +66,35 @@ def convert_vectors():
     np.savez_compressed(os.path.join(HERE, "sample_convert.npz"), **out)
 
 
+def live_inputs(fmt):
+    """the seeded inputs of tests/test_oracle.py::test_convert_matches_reference_build_live (kept in step with it)"""
+    rng = np.random.default_rng(5)
+    n = 200003
+    raw = rng.integers(0, 256, n * po.BYTES[po.FMT[fmt]], dtype=np.uint8)
+    if fmt == "cf32":
+        raw = rng.standard_normal(2 * n).astype(np.float32).view(np.uint8)
+    x = ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.7).astype(np.complex64)
+    return raw, x
+
+
+def sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
+def live_digests():
+    assert po.ref_lib() is not None, "oracle/_ref/libsampleconvert_ref.so missing: run `make -C oracle` with the reference sources present"
+    out = {}
+    for f in FORMATS:
+        raw, x = live_inputs(f)
+        out[f] = {"unpack_in": sha(raw), "pack_in": sha(x),
+                  # (+ 0: -0.0 and +0.0 hash alike -- the test compares values, as np.array_equal does)
+                  "unpack_out": {repr(g): sha(po.ref_to_cf32(raw, f, g).view(np.float32) + np.float32(0)) for g in LIVE_GAINS},
+                  "pack_out": sha(po.ref_from_cf32(x, f))}
+    with open(os.path.join(HERE, "sample_convert_live.json"), "w") as fh:
+        json.dump(out, fh, indent=1, sort_keys=True)
+        fh.write("\n")
+
+
 def chain_vectors():
     raw = synth.raw_stream(65536, 2.4e6, 1, "cs16")
     kw = dict(in_format="cs16", out_format="cs16", input_rate_hz=2.4e6, target_rate_hz=744187.5, shift_hz=200e3)
@@ -80,7 +116,11 @@ def design_vectors():
 
 if __name__ == "__main__":
     po.build()
+    if "--live-digests" in sys.argv:        # only sample_convert_live.json
+        live_digests()
+        raise SystemExit(0)
     convert_vectors()
+    live_digests()
     chain_vectors()
     design_vectors()
     for f in sorted(os.listdir(HERE)):

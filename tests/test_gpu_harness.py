@@ -249,6 +249,47 @@ def test_bench_two_ranks_share_the_gpu():
     assert d["roofline"]["launches"] == 3 and d["roofline"]["kernel_ms"] > 0
 
 
+def _bench_dump(out_dir, *extra):
+    import sys
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        env.pop(k, None)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--log2-frames", "22",
+                        "--settle-seconds", "0.2", "--dump-outputs", str(out_dir), *extra],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(out_dir, f)) for f in sorted(os.listdir(out_dir))}
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):
+    """a plain bench.py run: the headline line with the --full legs null, `steps` timed steps, and --dump-outputs = what the last
+    timed step returned -- the same files from run to run, and the frames a fresh chain gives for the same stream position (the
+    chain restarts after the settle period when it dumps: warm-up + timed steps of the tiled seed-1 segment)"""
+    d, a = _bench_dump(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0 and d["full"] is False
+    assert d["roofline"]["launches"] == 2
+    assert d["host_end_to_end"] is None and d["cpu_baseline"] is None and d["secondary"] is None and d["extra"] is None
+    assert sorted(a) == ["output_frames", "output_head", "output_sample", "output_sample_index", "output_tail"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    _, b = _bench_dump(tmp_path / "b")
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+    seg = synth.raw_stream(1 << 22, 2.4e6, 1, "cs16")
+    ch = gpu.Chain(**NRSC5)
+    for _ in range(2):
+        ch.process(seg)
+    last = ch.process(seg).reshape(-1, 2).astype(np.float32)
+    assert int(a["output_frames"][0]) == last.shape[0]
+    k = a["output_head"].shape[0]
+    assert np.array_equal(a["output_head"], last[:k]) and np.array_equal(a["output_tail"], last[-k:])
+    assert np.array_equal(a["output_sample"], last[a["output_sample_index"].astype(np.int64)])
+
+
 def test_harness_two_devices(gpu, oracle, tmp_path):
     """iqgpu_run --shards 4 --devices 2: shards dealt round-robin over two cards, stitched in file order -- against the
     concatenation of four ORACLE shard outputs, like every other shard test (the first multi-GPU box must not compare HIP with

@@ -1,13 +1,16 @@
 """CPU tests of the parity oracle (oracle/iq_oracle.c).
 
 Pinned part: sample_convert against golden vectors produced by the reference's own
-src/sample_convert.c (tests/golden/sample_convert.npz, made by tests/golden/gen_golden.py) and, when
+src/sample_convert.c (tests/golden/sample_convert.npz, made by tests/golden/gen_golden.py), against the
+digests of that code's outputs on larger seeded inputs (tests/golden/sample_convert_live.json) and, when
 oracle/_ref is present, against that build live.
 
 Unpinned part (liquid-dsp is absent from the reference tree and this image): every liquid-derived
 operator is cross-checked against an independent numpy / scipy formulation of the same published
 algorithm, so that an indexing, gain or phase mistake in the C restatement cannot hide.
 """
+import hashlib
+import json
 import math
 import os
 
@@ -50,19 +53,39 @@ def test_bytes_per_sample_matches_reference_golden(oracle, gold_convert):
         assert oracle.lib().orc_bytes_per_sample(int(fid)) == int(nbytes)
 
 
+@pytest.fixture(scope="module")
+def gold_convert_live():
+    with open(os.path.join(GOLD, "sample_convert_live.json")) as fh:
+        return json.load(fh)
+
+
+def _sha(a):
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()
+
+
 @pytest.mark.parametrize("fmt", FORMATS)
-def test_convert_matches_reference_build_live(oracle, fmt):
-    if oracle.ref_lib() is None:
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
+def test_convert_matches_reference_build_live(oracle, gold_convert_live, fmt):
+    """the oracle against the reference's own sample_convert.c on 200003 seeded frames: always against the sha256 of that build's
+    outputs on these inputs (tests/golden/sample_convert_live.json, tests/golden/gen_golden.py), and live where oracle/_ref is built"""
+    want = gold_convert_live[fmt]
+    live = oracle.ref_lib() is not None
     rng = np.random.default_rng(5)
     n = 200003
     raw = rng.integers(0, 256, n * oracle.BYTES[oracle.FMT[fmt]], dtype=np.uint8)
     if fmt == "cf32":
         raw = rng.standard_normal(2 * n).astype(np.float32).view(np.uint8)
+    assert _sha(raw) == want["unpack_in"], "numpy's seeded stream changed: regenerate sample_convert_live.json"
     for g in (1.0, 0.123, -7.0):
-        assert np.array_equal(oracle.to_cf32(raw, fmt, g).view(np.float32), oracle.ref_to_cf32(raw, fmt, g).view(np.float32))
+        got = oracle.to_cf32(raw, fmt, g).view(np.float32)
+        assert _sha(got + np.float32(0)) == want["unpack_out"][repr(g)], (fmt, g)      # (+ 0: -0.0 == +0.0, as in np.array_equal)
+        if live:
+            assert np.array_equal(got, oracle.ref_to_cf32(raw, fmt, g).view(np.float32))
     x = ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.7).astype(np.complex64)
-    assert np.array_equal(oracle.from_cf32(x, fmt), oracle.ref_from_cf32(x, fmt))
+    assert _sha(x) == want["pack_in"], "numpy's seeded stream changed: regenerate sample_convert_live.json"
+    got = oracle.from_cf32(x, fmt)
+    assert _sha(got) == want["pack_out"], fmt
+    if live:
+        assert np.array_equal(got, oracle.ref_from_cf32(x, fmt))
 
 
 def test_synth_quantiser_is_the_reference_rule(oracle):

@@ -5,7 +5,7 @@ cd "$REPO"; mkdir -p gpurun_out/r5_presets_ab
 for i in 1 2; do
   for v in "$@"; do
     L=iq_tool_amd/lib/libiqgpu_$v.so; [ $v = new ] && L=iq_tool_amd/lib/libiqgpu.so
-    IQGPU_LIB=$REPO/$L python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-leg --no-extra 2>/dev/null | python3 -c "
+    IQGPU_LIB=$REPO/$L python3 bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-leg --no-extra 2>/dev/null | python3 -c "
 import sys,json; d=json.loads(sys.stdin.read()); s=d['secondary']
 print('$v', {k: s[k].get('ms_per_step') for k in ('config3','config4','preset')}, {k: (v.get('ms_per_step'), v.get('kernels', {}).get('filter')) for k, v in s['presets'].items()})"
   done

@@ -27,7 +27,7 @@ for cfg in 3 4 preset; do
   echo "stats cfg $cfg done"
 done
 # ---- the seven shipped presets (secondary.presets), and the cs16-fm-nrsc5 preset through submit / collect (verdict on the host)
-rocprofv3 --kernel-trace --stats -d "$OUT/stats_presets" -o stats --output-format csv -- python3 $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-host-leg --no-extra --only-presets > "$OUT/stats_presets.log" 2>&1
+rocprofv3 --kernel-trace --stats -d "$OUT/stats_presets" -o stats --output-format csv -- python3 $REPO/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-host-leg --no-extra --only-presets > "$OUT/stats_presets.log" 2>&1
 echo "stats presets done"
 rocprofv3 --kernel-trace --stats -d "$OUT/stats_preset_submit" -o stats --output-format csv -- python3 $REPO/tools/gpu/r5_preset_pipe.py > "$OUT/stats_preset_submit.log" 2>&1
 echo "stats preset submit done"
