@@ -27,6 +27,7 @@ static const char *const kDebugNames[] = {
     "force_generic", "no_fast", "agc_nofuse", "no_raw0", "no_kt", "fft_no_r16", "no_fat", "force_fat", "fat", "mid8", "no_s2",
     "no_fused_move", "no_p0", "no_casc2", "no_mid_8bit", "fuse_filter", "tap_fold", "steal", "steal_min", "steal_rounds",
     "steal_stride", "steal_lanes", "run_weights", "cus", "fft_log2n", "fft_threads", "fft_geometry", "casc2_min_run", "sysfs_root",
+    "nco_hold",
 };
 static std::mutex g_dbg_mu;
 static std::map<std::string, std::string> &dbg_table() { static std::map<std::string, std::string> t; return t; }
@@ -193,6 +194,8 @@ int design_chain(iqgpu_chain *c, const iqgpu_chain_desc *d)
         if (!(v = debug_value("run_weights")).empty()) { int x = 0, y = 0, z = 0; if (sscanf(v.c_str(), "%d,%d,%d", &x, &y, &z) == 3
             && x >= 0 && y >= 0 && z >= 0) { c->run_wt[0] = x; c->run_wt[1] = y; c->run_wt[2] = z; } }
         { const int x = atoi(debug_value("casc2_min_run").c_str()); cascade2_set_min_run(x > 0 ? x : 0); }
+        // (on by default: "0" makes k_front_mid look its phasors up on every tile, as before the hold)
+        if (!(v = debug_value("nco_hold")).empty()) c->nco_hold = v[0] != '0';
     }
 
     // ---- ratio (src/setup.c:91-122) ----
@@ -231,6 +234,8 @@ int design_chain(iqgpu_chain *c, const iqgpu_chain_desc *d)
         const int mode = d->shift_hz >= 0 ? +1 : -1;
         if (d->shift_after_resample) c->pnco_mode = mode; else c->nco_mode = mode;
     }
+    c->nco_hold6 = c->nco_hold && c->nco_mode != 0 ? front_mid_nco_hold(c->nco_dtheta, 6) : 0;
+    c->nco_hold8 = c->nco_hold && c->nco_mode != 0 ? front_mid_nco_hold(c->nco_dtheta, 8) : 0;
 
     // ---- resampler (src/resampler.c:20-34, 60 dB include/constants.h:137) ----
     std::string err;

@@ -205,6 +205,9 @@ struct iqgpu_chain {
     // placement of the arms in the tap planes of k_front_mid / k_front_fat for this chain's step (front_tap_fold);
     // IQGPU_TAP_FOLD=0|1 overrides
     int tap_fold6 = 0, tap_fold8 = 0, tap_fold_env = -1;
+    // NCO phasor hold of k_front_mid for this chain's phase step at 6 / 8 outputs per lane (front_mid_nco_hold); nco_hold=0 turns it off
+    bool nco_hold = true;
+    int nco_hold6 = 0, nco_hold8 = 0;
     // profiling
     bool profiling = false;
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending_events;

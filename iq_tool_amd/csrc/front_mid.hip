@@ -24,6 +24,8 @@
 // Edge tiles run on the scalar-load run_tiles (front_tiles.hpp): runs of two 768-frame tiles = three of its 512-frame ones.
 #include "front_tiles.hpp"
 #include "front_fat_common.hpp"
+#include <algorithm>
+#include <vector>
 
 namespace iqgpu {
 
@@ -176,23 +178,20 @@ __device__ __forceinline__ void run_mid(const FrontArgs &a, const MidLds &w, con
     // scalar unit -- a v_mul_lo_u32 per chunk and tile is a quarter-rate instruction each (4 of the tile's ~340 VALU instructions,
     // the time of 16)
     const uint32_t th_lane = a.nco_theta0 + (uint32_t)(4 * lane) * a.nco_dtheta;
-    const uint32_t tho_lane = a.nco_theta0 + (uint32_t)(2 * NL * lane - 19) * a.nco_dtheta;
-#ifdef IQGPU_DIAG_NCOHOLD
-    // DIAGNOSTIC build (timing only, wrong bytes): the phasors are looked up for the run's first tile and then HELD -- the most a
-    // scheme that re-reads a lane's phasors only when their table index moves on could save (round 6, profiles/r06_headline.md)
-    bool diag_nco_first = true;
-#endif
+    // Phasor hold (a.nco_hold, chosen per chain by front_mid_nco_hold): a phasor is table entry (theta + 2^21) >> 22, and from one tile
+    // to the next every phase of the wave moves by the same D = TILE dtheta (mod 2^32).  Behind a lookup the wave works out how many
+    // tiles pass before ANY of the 384 odd-stream indices moves -- per phase the distance to its cell's edge in the direction of D,
+    // over |D| -- and on those tiles the odd stream's six phasors stay in their registers (the same entries would come back; they are
+    // live across most of the tile anyway).  The even stream's six are looked up every tile: holding them too keeps 12 more registers
+    // live through the polyphase, past the 168 of three waves per SIMD.  For the shifts on the 3.125 kHz grid at 2.4 MS/s
+    // (rate / 768) the phases fall into three narrow clusters (frame mod 3) and |D| is a small multiple of 4096, so the odd lookups
+    // run on ~1 % of the tiles (+200 kHz: 24 of 1999).  hold_to (wave-uniform): the last tile the held phasors are valid for.
+    // (not in the 8-per-lane experiment, nor with both the fused AGC and run stealing: no registers are left to hold anything there)
+    constexpr bool kHold = NL == 6 && !(AGC && STEAL);
+    const bool hold = kHold && a.nco_hold;
+    int64_t hold_to = T_begin - 1;
+    const int32_t hold_d = (int32_t)((uint32_t)G::TILE * a.nco_dtheta);
     auto nco_lookup = [&](int64_t T) {
-#ifdef IQGPU_DIAG_NCOHOLD
-        if (!diag_nco_first) {
-#pragma unroll
-            for (int c = 0; c < G::NC; ++c) { asm volatile("" : "+v"(cs_n[c][0])); asm volatile("" : "+v"(cs_n[c][1])); }
-#pragma unroll
-            for (int i = 0; i < NL; ++i) asm volatile("" : "+v"(cs_o[i]));
-            return;
-        }
-        diag_nco_first = false;
-#endif
         const uint32_t tb = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(T * G::TILE) * a.nco_dtheta));
 #pragma unroll
         for (int c = 0; c < G::NC; ++c) {
@@ -200,11 +199,26 @@ __device__ __forceinline__ void run_mid(const FrontArgs &a, const MidLds &w, con
             cs_n[c][0] = nco_phasor2(w.nco, th, 0);
             cs_n[c][1] = nco_phasor2(w.nco, th + 2u * a.nco_dtheta, 0);
         }
-        uint32_t tho = tho_lane + tb;
+        if (hold && T <= hold_to) return;         // (scalar branch: a kernel argument and a scalar tile index)
+        // the lane's least distance to a cell edge ahead: 2^22 - 1 - (u mod 2^22) for D > 0, u mod 2^22 for D < 0 (u = theta + 2^21)
+        const uint32_t flip = hold_d > 0 ? 0x3fffffu : 0u;
+        uint32_t room = 0x3fffffu;
+        // (the lane's share of the phase made opaque: derived here, on the tiles that look up, rather than held across the tile loop)
+        int lo = 2 * NL * lane - 19;
+        asm volatile("" : "+v"(lo));
+        uint32_t tho = a.nco_theta0 + (uint32_t)lo * a.nco_dtheta + tb;
 #pragma unroll
         for (int i = 0; i < NL; ++i) {
             cs_o[i] = nco_phasor2(w.nco, tho, 1);               // the odd stream only meets the centre tap 0.5: half-scaled copy
+            if (hold) room = min(room, ((tho + (1u << 21)) ^ flip) & 0x3fffffu);
             tho += 2u * a.nco_dtheta;
+        }
+        if (hold) {
+#pragma unroll
+            for (int k = 32; k >= 1; k >>= 1) room = min(room, (uint32_t)__shfl_xor((int)room, k));
+            const uint32_t r = (uint32_t)__builtin_amdgcn_readfirstlane((int)room);
+            const uint32_t ad = hold_d < 0 ? (uint32_t)0 - (uint32_t)hold_d : (uint32_t)hold_d;
+            hold_to = T + (ad == 0u ? (int64_t)0x7fffffff : (int64_t)(r / ad));   // (|D| >= 2^22: 0, the next tile looks up again)
         }
     };
     load_even(T_begin); load_odd(T_begin);
@@ -766,6 +780,30 @@ int front_tap_fold(const uint32_t step, const int nl)
 {
     if (nl != 6 && nl != 8) return 0;
     return tap_gather_cycles(step, nl, true) + 1.5 < tap_gather_cycles(step, nl, false) ? 1 : 0;
+}
+
+// The phasor hold (run_mid) pays where the odd stream's phasors seldom change their table index.  A wave's odd phases sit at fixed
+// offsets f dtheta from each other (f = 2 nl lane - 19 + 2 i: the frames whose phasors are held) and all move by D = 128 nl dtheta per
+// tile; a tile needs a lookup when a cell edge lies in the arc [p, p + |D|) of one of them.  Over tile positions the share of such
+// tiles is the measure of the union of those arcs over the cell (2^22): the sum of min(gap, |D|) over the sorted offsets.  A held
+// tile saves six lookups (~24 VALU, 6 LDS reads), a looked-up one pays ~20 VALU and a wave reduction for its countdown: hold where at
+// most a quarter of the tiles look up.  NRSC-5's +200 kHz at 6 per lane: 1.2 %.  (Six per lane only: run_mid holds nothing at 8.)
+int front_mid_nco_hold(const uint32_t dtheta, const int nl)
+{
+    if (nl != 6) return 0;
+    const int32_t d = (int32_t)((uint32_t)(128 * nl) * dtheta);
+    const uint64_t ad = d < 0 ? (uint64_t)(-(int64_t)d) : (uint64_t)d;
+    if (ad >= (1u << 22)) return 0;                  // every tile moves every index
+    std::vector<uint32_t> p;
+    for (int lane = 0; lane < 64; ++lane)
+        for (int i = 0; i < nl; ++i) p.push_back(((uint32_t)(2 * nl * lane - 19 + 2 * i) * dtheta) & 0x3fffffu);
+    std::sort(p.begin(), p.end());
+    uint64_t cover = 0;
+    for (size_t k = 0; k < p.size(); ++k) {
+        const uint64_t gap = k + 1 < p.size() ? (uint64_t)(p[k + 1] - p[k]) : (uint64_t)(p[0] + (1u << 22) - p[k]);
+        cover += gap < ad ? gap : ad;
+    }
+    return 4 * cover <= ((uint64_t)1 << 22) ? 1 : 0;
 }
 
 // step classes: lo_3 = floor(3 s), lo_4 = floor(4 s) with s = step / 2^24.  Six per lane (four slots) takes 1.5 <= s < 2, eight per

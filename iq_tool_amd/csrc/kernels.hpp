@@ -99,6 +99,7 @@ struct FrontArgs {
     uint32_t    nco_theta0;   // phase of input sample i_rel = 0
     uint32_t    nco_dtheta;
     const cf2  *nco_tab;      // 1024 x {cos, sin}
+    uint32_t    nco_hold;     // k_front_mid: hold the odd stream's phasors over the tiles on which none of their table indices moves (front_mid_nco_hold())
     // resampler
     int32_t     mode;         // 0 = no resampler (pointwise only), 1 = decimating msresamp
     int32_t     S;
@@ -251,6 +252,9 @@ int front_mid_tile(int nl);              // its tile: 128 nl frames
 // placement of the arms in the tap planes for a chain's step and nl outputs per lane: 1 = folded, 0 = linear (whichever a model of
 // the half-wave's bank pairs prices lower, the fold's two extra instructions per slot counted)
 int front_tap_fold(uint32_t step, int nl);
+// whether the NCO phasor hold of k_front_mid pays for a chain's phase step at nl outputs per lane: 1 when a wave's odd-stream
+// phasors change their table index on at most a quarter of its tiles (a model of the wave's phase offsets), else 0 (every tile looks them up)
+int front_mid_nco_hold(uint32_t dtheta, int nl);
 hipError_t launch_front_mid(const FrontArgs &a, hipStream_t s);
 // chains without a half-band stage as an output-major polyphase kernel with register-resident taps (front_p0.hip)
 int front_p0_waves();
