@@ -60,7 +60,7 @@ enum {
     IQGPU_EFILTER = -7,     /* filter band beyond output Nyquist, fft size too small, too many stages (src/filter.c:80-84, 321-325) */
     IQGPU_ECAPACITY = -8,   /* out_capacity_bytes too small for this call */
     IQGPU_EHIP = -9,        /* a HIP runtime call failed */
-    IQGPU_EUNSUPPORTED = -10/* valid for the reference but not built (nothing on the path returns it since round 2) */
+    IQGPU_EUNSUPPORTED = -10/* no sample path returns it; the placement calls do when a *_VISIBLE_DEVICES list is not plain indices */
 };
 
 typedef struct iqgpu_chain iqgpu_chain; /* opaque, like resampler_t (include/resampler.h:25-26) */
@@ -300,8 +300,9 @@ const char *iqgpu_chain_front_kernel(const iqgpu_chain *c);
 
 /* Diagnostic switches (ABI v6; no reference counterpart).  The library reads NO switch from the environment: kernel selection and
  * plan overrides used by the parity tests and the A/B tools go through this one entry point.  A chain takes the table as it
- * stands when iqgpu_chain_create runs; later changes do not touch existing chains.  name: "no_fast", "agc_nofuse", "force_generic",
- * "fft_log2n", ... (abi.cpp kDebugNames; an unknown name is IQGPU_EINVAL); value NULL or "" clears the switch, name NULL clears all.
+ * stands when iqgpu_chain_create runs, in one snapshot; later changes do not touch existing chains, and iqgpu_design_probe /
+ * iqgpu_design_out_frames read the table without any effect on them.  name: "no_fast", "agc_nofuse", "force_generic",
+ * "fft_log2n", ... (abi.cpp kSwitches; an unknown name is IQGPU_EINVAL); value NULL or "" clears the switch, name NULL clears all.
  * iqgpu_debug_list writes "name=value;name=value" of what is set (bench.py records it in config.debug). */
 int    iqgpu_debug_set(const char *name, const char *value);
 int    iqgpu_debug_list(char *buf, size_t cap);

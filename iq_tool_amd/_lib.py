@@ -186,16 +186,22 @@ DEBUG_NAMES = ("force_generic", "no_fast", "agc_nofuse", "no_raw0", "no_kt", "ff
                "no_s2", "no_fused_move", "no_p0", "no_casc2", "no_mid_8bit", "fuse_filter", "tap_fold", "steal", "steal_min",
                "steal_rounds", "steal_stride", "steal_lanes", "run_weights", "cus", "fft_log2n", "fft_threads", "fft_geometry", "casc2_min_run",
                "sysfs_root", "nco_hold")
+_forwarded = set()      # names whose switch apply_debug_env set from the environment and has not cleared since
 
 
 def apply_debug_env():
-    """sets the library's diagnostic switches to what this process's IQGPU_<NAME> variables say (all others cleared)"""
+    """forwards this process's IQGPU_<NAME> variables to the library's diagnostic switches: an exported variable sets its switch,
+    one that went away clears the switch it had set, and every other switch (set directly through iqgpu_debug_set) stays.  The
+    table is never cleared as a whole, so concurrent calls under the same environment agree and no caller sees it emptied."""
     lib = load()
-    check(lib.iqgpu_debug_set(None, None))
     for name in DEBUG_NAMES:
         v = os.environ.get("IQGPU_" + name.upper())
         if v:
             check(lib.iqgpu_debug_set(name.encode(), v.encode()))
+            _forwarded.add(name)
+        elif name in _forwarded:
+            check(lib.iqgpu_debug_set(name.encode(), None))
+            _forwarded.discard(name)
 
 
 def debug_switches():

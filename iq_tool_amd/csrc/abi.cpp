@@ -21,16 +21,48 @@ int fail(int code, const char *fmt, ...)
 // ------------------------------------------------------------------------------------------------
 // diagnostic switches: ONE explicit entry point, iqgpu_debug_set(name, value).  The library never reads its switches from the
 // environment (round 6, VERDICT r5 item 7: a production library whose kernel selection hangs on the caller's environment is a
-// support problem); a chain takes the table as it stands when iqgpu_chain_create runs, and nothing on the launch path looks at it.
+// support problem); a chain takes the table as it stands when it is designed (debug_switches, once), and nothing on the launch
+// path looks at it.
 // ------------------------------------------------------------------------------------------------
-static const char *const kDebugNames[] = {
-    "force_generic", "no_fast", "agc_nofuse", "no_raw0", "no_kt", "fft_no_r16", "no_fat", "force_fat", "fat", "mid8", "no_s2",
-    "no_fused_move", "no_p0", "no_casc2", "no_mid_8bit", "fuse_filter", "tap_fold", "steal", "steal_min", "steal_rounds",
-    "steal_stride", "steal_lanes", "run_weights", "cus", "fft_log2n", "fft_threads", "fft_geometry", "casc2_min_run", "sysfs_root",
-    "nco_hold",
+// every switch with its parse rule: v is the value as set (never empty).  Booleans are on only for a value that starts with '1'; a
+// value out of range leaves the default.  nullptr: a process-level switch, read where it is used (debug_value)
+template <uint32_t kBit> static void dbg_bit(DebugSwitches &s, const char *v) { if (v[0] == '1') s.dbg |= kBit; }
+static void set_in(int &dst, const char *v, int lo, int hi) { const int x = atoi(v); if (x >= lo && x <= hi) dst = x; }
+static const struct { const char *name; void (*parse)(DebugSwitches &, const char *); } kSwitches[] = {
+    {"force_generic", [](DebugSwitches &s, const char *v) { s.force_generic = v[0] == '1'; }},
+    {"no_fast", dbg_bit<kDbgNoFast>}, {"agc_nofuse", dbg_bit<kDbgAgcNoFuse>}, {"no_raw0", dbg_bit<kDbgNoRaw0>},
+    {"no_kt", dbg_bit<kDbgNoKT>}, {"fft_no_r16", dbg_bit<kDbgFftNoR16>}, {"no_fat", dbg_bit<kDbgNoFat>},
+    {"force_fat", dbg_bit<kDbgForceFat>}, {"fat", dbg_bit<kDbgUseFat>}, {"mid8", dbg_bit<kDbgMid8>}, {"no_s2", dbg_bit<kDbgNoS2>},
+    {"no_fused_move", dbg_bit<kDbgNoFusedMove>}, {"no_p0", dbg_bit<kDbgNoP0>}, {"no_casc2", dbg_bit<kDbgNoCasc2>},
+    {"no_mid_8bit", dbg_bit<kDbgNoMid8bit>}, {"fuse_filter", dbg_bit<kDbgFuseFilter>},
+    {"tap_fold", [](DebugSwitches &s, const char *v) { s.tap_fold = atoi(v) != 0 ? 1 : 0; }},
+    {"steal", [](DebugSwitches &s, const char *v) { s.steal = v[0] == '1'; }},
+    {"steal_min", [](DebugSwitches &s, const char *v) { set_in(s.steal_min, v, 2, 99999); }},
+    {"steal_rounds", [](DebugSwitches &s, const char *v) { set_in(s.steal_rounds, v, 1, 64); }},
+    {"steal_stride", [](DebugSwitches &s, const char *v) { set_in(s.steal_stride, v, 1, 8192); }},
+    {"steal_lanes", [](DebugSwitches &s, const char *v) { set_in(s.steal_lanes, v, 1, 64); }},
+    {"run_weights", [](DebugSwitches &s, const char *v) {
+        int x = 0, y = 0, z = 0;
+        if (sscanf(v, "%d,%d,%d", &x, &y, &z) == 3 && x >= 0 && y >= 0 && z >= 0) { s.run_wt[0] = x; s.run_wt[1] = y; s.run_wt[2] = z; } }},
+    {"cus", [](DebugSwitches &s, const char *v) { s.cus = atoi(v); }},                  // (upper bound: the device's, at create)
+    {"fft_log2n", [](DebugSwitches &s, const char *v) { const int x = atoi(v); if (x >= 1 && x < 31 && (1 << x) <= kMaxFftN) s.fft_log2n = x; }},
+    {"fft_threads", [](DebugSwitches &s, const char *v) { s.fft_threads = atoi(v); }},
+    {"fft_geometry", [](DebugSwitches &s, const char *v) { s.fft_keep_geometry = !strcmp(v, "keep"); }},
+    {"casc2_min_run", [](DebugSwitches &s, const char *v) { const int x = atoi(v); s.casc2_min_run = x > 0 ? x : 0; }},
+    {"nco_hold", [](DebugSwitches &s, const char *v) { s.nco_hold = v[0] != '0'; }},
+    {"sysfs_root", nullptr},                                                              // topology.cpp
 };
 static std::mutex g_dbg_mu;
 static std::map<std::string, std::string> &dbg_table() { static std::map<std::string, std::string> t; return t; }
+
+DebugSwitches debug_switches()
+{
+    DebugSwitches s;
+    std::lock_guard<std::mutex> g(g_dbg_mu);
+    for (const auto &kv : dbg_table())
+        for (const auto &sw : kSwitches) if (sw.parse && kv.first == sw.name) sw.parse(s, kv.second.c_str());
+    return s;
+}
 
 // value of switch `name` ("" when unset); a copy: the table may change under another thread
 std::string debug_value(const char *name)
@@ -39,14 +71,13 @@ std::string debug_value(const char *name)
     const auto it = dbg_table().find(name);
     return it == dbg_table().end() ? std::string() : it->second;
 }
-static bool debug_on(const char *name) { const std::string v = debug_value(name); return !v.empty() && v[0] == '1'; }
 
 extern "C" int iqgpu_debug_set(const char *name, const char *value)
 {
     std::lock_guard<std::mutex> g(g_dbg_mu);
     if (!name) { dbg_table().clear(); return IQGPU_OK; }
     bool known = false;
-    for (const char *k : kDebugNames) known = known || !strcmp(k, name);
+    for (const auto &sw : kSwitches) known = known || !strcmp(sw.name, name);
     if (!known) return fail(IQGPU_EINVAL, "iqgpu_debug_set: unknown switch '%s'", name);
     if (!value || !value[0]) dbg_table().erase(name);
     else dbg_table()[name] = value;
@@ -172,31 +203,9 @@ int design_chain(iqgpu_chain *c, const iqgpu_chain_desc *d)
         return fail(IQGPU_EINVAL, "input_rate_hz must be positive");
     c->desc = *d;
     c->device = d->device_ordinal;
-    {   // every diagnostic switch is taken HERE, once per chain, from the table iqgpu_debug_set keeps (never from the environment):
-        // process() and the launch functions look at the handle only
-        c->force_generic = debug_on("force_generic");
-        // (booleans: only "1..." switches one on -- "0" or an empty value leaves the default kernel selection alone)
-        auto on = [](const char *name) { return debug_on(name); };
-        c->dbg = (on("no_fast") ? kDbgNoFast : 0u) | (on("agc_nofuse") ? kDbgAgcNoFuse : 0u) |
-                 (on("no_raw0") ? kDbgNoRaw0 : 0u) | (on("no_kt") ? kDbgNoKT : 0u) |
-                 (on("fft_no_r16") ? kDbgFftNoR16 : 0u) | (on("no_fat") ? kDbgNoFat : 0u) |
-                 (on("force_fat") ? kDbgForceFat : 0u) | (on("fat") ? kDbgUseFat : 0u) | (on("mid8") ? kDbgMid8 : 0u) |
-                 (on("no_s2") ? kDbgNoS2 : 0u) | (on("no_fused_move") ? kDbgNoFusedMove : 0u) | (on("no_p0") ? kDbgNoP0 : 0u) |
-                 (on("no_casc2") ? kDbgNoCasc2 : 0u) | (on("no_mid_8bit") ? kDbgNoMid8bit : 0u) |
-                 (on("fuse_filter") ? kDbgFuseFilter : 0u);
-        std::string v;
-        if (!(v = debug_value("tap_fold")).empty()) c->tap_fold_env = atoi(v.c_str()) != 0 ? 1 : 0;
-        if (!(v = debug_value("steal")).empty()) c->steal = v[0] == '1';
-        if (!(v = debug_value("steal_min")).empty()) { const int x = atoi(v.c_str()); if (x >= 2 && x < 100000) c->steal_min = x; }
-        if (!(v = debug_value("steal_rounds")).empty()) { const int x = atoi(v.c_str()); if (x >= 1 && x <= 64) c->steal_rounds = x; }
-        if (!(v = debug_value("steal_stride")).empty()) { const int x = atoi(v.c_str()); if (x >= 1 && x <= 8192) c->steal_stride = x; }
-        if (!(v = debug_value("steal_lanes")).empty()) { const int x = atoi(v.c_str()); if (x >= 1 && x <= 64) c->steal_lanes = x; }
-        if (!(v = debug_value("run_weights")).empty()) { int x = 0, y = 0, z = 0; if (sscanf(v.c_str(), "%d,%d,%d", &x, &y, &z) == 3
-            && x >= 0 && y >= 0 && z >= 0) { c->run_wt[0] = x; c->run_wt[1] = y; c->run_wt[2] = z; } }
-        { const int x = atoi(debug_value("casc2_min_run").c_str()); cascade2_set_min_run(x > 0 ? x : 0); }
-        // (on by default: "0" makes k_front_mid look its phasors up on every tile, as before the hold)
-        if (!(v = debug_value("nco_hold")).empty()) c->nco_hold = v[0] != '0';
-    }
+    // every diagnostic switch is taken HERE, once per chain, from the table iqgpu_debug_set keeps (never from the environment):
+    // the rest of the design, create, process() and the launch functions look at c->sw only
+    c->sw = debug_switches();
 
     // ---- ratio (src/setup.c:91-122) ----
     const double in_rate = d->input_rate_hz > 0.0 ? d->input_rate_hz : 1.0;
@@ -234,16 +243,16 @@ int design_chain(iqgpu_chain *c, const iqgpu_chain_desc *d)
         const int mode = d->shift_hz >= 0 ? +1 : -1;
         if (d->shift_after_resample) c->pnco_mode = mode; else c->nco_mode = mode;
     }
-    c->nco_hold6 = c->nco_hold && c->nco_mode != 0 ? front_mid_nco_hold(c->nco_dtheta, 6) : 0;
-    c->nco_hold8 = c->nco_hold && c->nco_mode != 0 ? front_mid_nco_hold(c->nco_dtheta, 8) : 0;
+    c->nco_hold6 = c->sw.nco_hold && c->nco_mode != 0 ? front_mid_nco_hold(c->nco_dtheta, 6) : 0;
+    c->nco_hold8 = c->sw.nco_hold && c->nco_mode != 0 ? front_mid_nco_hold(c->nco_dtheta, 8) : 0;
 
     // ---- resampler (src/resampler.c:20-34, 60 dB include/constants.h:137) ----
     std::string err;
     if (c->resample) {
         if (!make_resample_plan(c->ratio, 60.0f, c->rp, err)) return fail(IQGPU_ERATIO, "%s", err.c_str());
         if (c->rp.S >= kMaxS) return fail(IQGPU_ERATIO, "too many half-band stages");
-        c->tap_fold6 = c->tap_fold_env >= 0 ? c->tap_fold_env : front_tap_fold(c->rp.step, 6);
-        c->tap_fold8 = c->tap_fold_env >= 0 ? c->tap_fold_env : front_tap_fold(c->rp.step, 8);
+        c->tap_fold6 = c->sw.tap_fold >= 0 ? c->sw.tap_fold : front_tap_fold(c->rp.step, 6);
+        c->tap_fold8 = c->sw.tap_fold >= 0 ? c->sw.tap_fold : front_tap_fold(c->rp.step, 8);
     }
 
     // ---- user filter (src/filter.c:138-393) ----
@@ -258,7 +267,7 @@ int design_chain(iqgpu_chain *c, const iqgpu_chain_desc *d)
     c->S = c->decim ? c->rp.S : 0;
     c->D = 1 << c->S;
     c->TG = kTile >> c->S;
-    if (c->decim && c->S >= 2 && !c->force_generic) {
+    if (c->decim && c->S >= 2 && !c->sw.force_generic) {
         int mm[kMaxS];
         for (int i = 0; i < c->S; ++i) mm[i] = c->rp.stages[(size_t)i].m;
         c->cascade = cascade_supported(mm, c->S);
@@ -353,7 +362,7 @@ extern "C" int iqgpu_chain_create(const iqgpu_chain_desc *d, iqgpu_chain **out)
             int ncu = 0;
             if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && ncu > 0) c->n_cu = ncu;
             // (diagnostic: cus=n plans every launch for n CUs -- how does a CU's throughput depend on how many of them work?)
-            { const std::string v = debug_value("cus"); if (!v.empty()) { const int x = atoi(v.c_str()); if (x >= 8 && x <= c->n_cu) c->n_cu = x; } }
+            if (c->sw.cus >= 8 && c->sw.cus <= c->n_cu) c->n_cu = c->sw.cus;
         }
         CREATE_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
         c->stream = c->own_stream;
@@ -409,7 +418,7 @@ extern "C" int iqgpu_chain_create(const iqgpu_chain_desc *d, iqgpu_chain **out)
             }
             // the fused path exists for the specialised front kernel: the shipped cs16 NRSC-5 preset shape
             FrontArgs fa{};
-            fa.dbg = c->dbg;
+            fa.dbg = c->sw.dbg;
             fa.S = c->S; fa.in_fmt = c->desc.in_format; fa.out_fmt = c->desc.out_format; fa.gain = c->desc.gain;
             fa.iq_enable = c->desc.iq_correct_enable ? 1 : 0; fa.dc_enable = c->dc ? 1 : 0;
             fa.nco_mode = c->nco_mode; fa.pnco_mode = c->pnco_mode; fa.agc_chunk_frames = c->agc_chunk; fa.agc_shift = c->S;
@@ -420,21 +429,21 @@ extern "C" int iqgpu_chain_create(const iqgpu_chain_desc *d, iqgpu_chain **out)
                 CREATE_RC(c->agc_hist.ensure(((size_t)c->agc_rms_warm + 1) * sizeof(cf2)));
                 CREATE_TRY(hipMemset(c->agc_hist.p, 0, c->agc_hist.cap));
             }
-            c->agc_fusable = c->agc_rms_alpha == 0.0f && c->decim && !c->late && !c->force_generic && !c->fp.enabled &&
+            c->agc_fusable = c->agc_rms_alpha == 0.0f && c->decim && !c->late && !c->sw.force_generic && !c->fp.enabled &&
                              (c->cascade || c->S == 0 || (c->S == 1 && c->rp.stages[0].m == 10)) && front_s1_agc_fusable(fa);
         }
         if (c->fp.enabled) CREATE_RC(upload(&c->d_ftaps, (const cf2 *)c->fp.taps.data(), c->fp.taps.size()));
         // overlap-save path: every FFT-kind filter, and FIR-kind ones long enough that two transforms
         // per window beat the direct form (the two are the same linear convolution, SPEC B.3)
         const size_t Lt = c->fp.taps.size();
-        if (c->fp.enabled && !c->force_generic && Lt >= 2 && 2 * (Lt - 1) <= (size_t)kMaxFftN &&
+        if (c->fp.enabled && !c->sw.force_generic && Lt >= 2 && 2 * (Lt - 1) <= (size_t)kMaxFftN &&
             (c->fp.block > 0 || Lt >= (size_t)kFftMinTaps)) {
             // N = 4 (L-1) rounded up to a power of two in [256, 4096], larger (up to 16384, in place in LDS) only
             // when the taps need it; measured with k_fftconv16 (round 4: first and last pass in registers) on config 3 (1025 taps):
             // N 2048 0.25 ms, 4096 0.15, 8192 0.16, 16384 0.21; on config 4 (4097 taps): N 8192 0.105 ms, 16384 0.114
             // (from 1024 points up: the radix-16 kernel.  Round 5: the 97-tap band-pass of the cs16 -usb / -lsb presets ran the
             //  radix-4 ping-pong kernel at N = 512 and took 1.49 ms for 83 M outputs; at N = 1024 it takes a fifth of that)
-            int lg = (c->dbg & kDbgFftNoR16) ? 8 : 10;
+            int lg = (c->sw.dbg & kDbgFftNoR16) ? 8 : 10;
             while ((size_t)(1 << lg) < 4 * (Lt - 1) && (1 << lg) < 4096) ++lg;
             while ((size_t)(1 << lg) < 2 * (Lt - 1)) ++lg;
             // round 6: a chain WITHOUT a half-band stage whose filter stands behind the resampler CAN run both in one kernel (k_p0fft16,
@@ -445,21 +454,18 @@ extern "C" int iqgpu_chain_create(const iqgpu_chain_desc *d, iqgpu_chain **out)
             // chain's transform is then that size on either path
             // (diagnostics: "fft_geometry" = "keep" runs the two kernels at the fused kernel's transform size and on its windows -- win
             //  stream samples and vout outputs per block -- so that the two paths can be compared byte for byte)
-            c->fft_keep_geometry = debug_value("fft_geometry") == "keep";
-            if (c->decim && c->S == 0 && !c->late && c->fp.post_resample && !(c->dbg & (kDbgFftNoR16 | kDbgNoP0 | kDbgNoFusedMove)) &&
-                ((c->dbg & kDbgFuseFilter) || c->fft_keep_geometry)) {
+            if (c->decim && c->S == 0 && !c->late && c->fp.post_resample && !(c->sw.dbg & (kDbgFftNoR16 | kDbgNoP0 | kDbgNoFusedMove)) &&
+                ((c->sw.dbg & kDbgFuseFilter) || c->sw.fft_keep_geometry)) {
                 FrontArgs ff{};
-                ff.dbg = c->dbg; ff.S = 0; ff.in_fmt = c->desc.in_format; ff.gain = c->desc.gain;
+                ff.dbg = c->sw.dbg; ff.S = 0; ff.in_fmt = c->desc.in_format; ff.gain = c->desc.gain;
                 ff.iq_enable = c->desc.iq_correct_enable ? 1 : 0; ff.dc_enable = c->dc ? 1 : 0; ff.nco_mode = c->nco_mode; ff.pnco_mode = 0;
                 ff.step = c->rp.step;
                 const int lgf = lg < 12 ? 12 : lg;
                 if (p0fft_shape(ff, lgf, (int)Lt) && p0fft_geometry(lgf, (int)Lt, &c->fuse_win, &c->fuse_vout)) {
-                    c->fuse_filter = (c->dbg & kDbgFuseFilter) != 0; lg = lgf;
+                    c->fuse_filter = (c->sw.dbg & kDbgFuseFilter) != 0; lg = lgf;
                 }
             }
-            { const std::string e = debug_value("fft_log2n"); if (!e.empty()) { const int v = atoi(e.c_str()); if (v >= 1 && (1 << v) <= kMaxFftN
-                && (size_t)(1 << v) >= 2 * (Lt - 1)) lg = v; } }
-            { const std::string e = debug_value("fft_threads"); if (!e.empty()) c->fft_threads = atoi(e.c_str()); }
+            if (c->sw.fft_log2n && (size_t)(1 << c->sw.fft_log2n) >= 2 * (Lt - 1)) lg = c->sw.fft_log2n;
             if (c->fuse_win > 0 && !p0fft_geometry(lg, (int)Lt, &c->fuse_win, &c->fuse_vout)) { c->fuse_filter = false; c->fuse_win = c->fuse_vout = 0; }   // (a transform size forced by hand)
             const int N = 1 << lg;
             c->fft_log2n = lg;
@@ -486,8 +492,8 @@ extern "C" int iqgpu_chain_create(const iqgpu_chain_desc *d, iqgpu_chain **out)
         // the digital AGC behind a post-resample filter on the overlap-save path: gain and per-chunk peaks in k_fftconv16's epilogue past
         // the lock.  A block of the filter must not hold more than one chunk boundary: a chunk's outputs (less the block quantisation's
         // slack) have to outnumber a workgroup's
-        if (c->agc && c->agc_rms_alpha == 0.0f && c->decim && !c->late && !c->force_generic && c->fp.enabled && c->fp.post_resample && c->d_hfreq &&
-            fftconv_agc_fusable(c->fft_log2n, (int)c->fp.taps.size(), c->dbg)) {
+        if (c->agc && c->agc_rms_alpha == 0.0f && c->decim && !c->late && !c->sw.force_generic && c->fp.enabled && c->fp.post_resample && c->d_hfreq &&
+            fftconv_agc_fusable(c->fft_log2n, (int)c->fp.taps.size(), c->sw.dbg)) {
             const double chunk_out = (double)c->agc_chunk * (double)c->ratio - (double)c->fp.block - 2.0;
             c->agc_fusable_filter = chunk_out >= (double)(1 << c->fft_log2n);
         }

@@ -110,14 +110,11 @@ bool cascade2_shape(const FrontArgs &a)
     return true;
 }
 
-static int g_casc2_min_run = 0;                       // process-wide diagnostic override, set at iqgpu_chain_create
-void cascade2_set_min_run(int n) { g_casc2_min_run = n; }
-
 // ... and the call: streaming runs of two tiles and more, the tile in front of the first run's warm-up loadable, the slice sized for both layouts
-bool cascade2_applies(const FrontArgs &a)
+bool cascade2_applies(const FrontArgs &a, int min_run)
 {
-    // (iqgpu_debug_set("casc2_min_run", n): diagnostics -- where the two-tile trips start to pay, tools/gpu/r5_casc2_min.py)
-    const int min_run = g_casc2_min_run > 0 ? g_casc2_min_run : kCasc2MinRun;
+    // (min_run > 0: the chain's iqgpu_debug_set("casc2_min_run", n) -- where the two-tile trips start to pay, tools/gpu/r5_casc2_min.py)
+    if (min_run <= 0) min_run = kCasc2MinRun;
     if (!cascade2_shape(a) || a.w_n_stream <= 0 || a.w_run_q < min_run) return false;
     if ((a.w_edge_ta - a.w_warm_tiles - 1) * (int64_t)kWTile - a.rem0 < 0) return false;
     return a.casc_wave_lds >= cascade2_wave_lds(a.casc_K, a.in_fmt);
@@ -283,9 +280,9 @@ __global__ __launch_bounds__((Casc2<KT, BPF>::WAVES * 64)) void k_cascade2(const
     }
 }
 
-hipError_t launch_cascade2(const FrontArgs &a, hipStream_t s)
+hipError_t launch_cascade2(const FrontArgs &a, int min_run, hipStream_t s)
 {
-    if (!cascade2_applies(a)) return hipErrorInvalidValue;
+    if (!cascade2_applies(a, min_run)) return hipErrorInvalidValue;
     const int waves = cascade_waves(a);
     const size_t lds = (size_t)waves * a.casc_wave_lds;
     const int64_t n_items = a.w_n_edge + a.w_n_stream;

@@ -110,9 +110,9 @@ int cascade_waves(const FrontArgs &a)
     return w > cap ? cap : (w < 4 ? 4 : w);
 }
 
-hipError_t launch_cascade(const FrontArgs &a, hipStream_t s)
+hipError_t launch_cascade(const FrontArgs &a, int casc2_min_run, hipStream_t s)
 {
-    if (cascade2_applies(a)) return launch_cascade2(a, s);
+    if (cascade2_applies(a, casc2_min_run)) return launch_cascade2(a, casc2_min_run, s);
     const int waves = cascade_waves(a);
     const size_t lds = (size_t)casc_nco_bytes(a) + (size_t)waves * a.casc_wave_lds;
     const int64_t n_items = a.w_n_edge + a.w_n_stream;

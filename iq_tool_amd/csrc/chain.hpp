@@ -29,7 +29,6 @@ using namespace iqgpu;
 // ---- error reporting (abi.cpp) ----
 int fail(int code, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
 const char *last_error_text();
-std::string debug_value(const char *name);             // abi.cpp: the table iqgpu_debug_set keeps ("" when unset)
 #define HIP_TRY(expr)                                                                                   \
     do {                                                                                                \
         hipError_t e_ = (expr);                                                                         \
@@ -53,6 +52,27 @@ inline size_t bytes_per_frame(int fmt)
     default: return 0;
     }
 }
+
+// ---- diagnostic switches (iqgpu_debug_set; parse rules: abi.cpp kSwitches): one chain's snapshot, with the defaults ----
+struct DebugSwitches {
+    bool force_generic = false;   // "force_generic": always use the workgroup-tiled k_front
+    uint32_t dbg = 0;             // kDbg* kernel-selection switches (kernels.hpp), carried in the launch arguments
+    int tap_fold = -1;            // "tap_fold" 0 | 1: arm placement in the tap planes of k_front_mid / k_front_fat (-1: front_tap_fold)
+    // run stealing in k_front_mid (kernels.hpp, FrontArgs::w_steal): "steal" turns it on, "steal_min" / "_rounds" / "_stride" /
+    // "_lanes" tune it.  (off by default: measured neutral, profiles/r04_steal.md -- the launch tail it removes turned out to be free)
+    bool steal = false; int steal_min = 6, steal_rounds = 6, steal_stride = 544, steal_lanes = 16;   // stride in 8-byte words: 4352 B
+    // weights of the runs of the first / second / third wave of a SIMD in k_front_mid ("run_weights" = "a,b,c"; 0 = equal runs)
+    int32_t run_wt[4] = {1300, 1000, 700, 0};
+    bool nco_hold = true;         // "nco_hold" = "0": k_front_mid looks its phasors up on every tile, as before the hold
+    int cus = 0;                  // "cus": plan every launch for this many CUs (applies in [8, the device's CU count]; 0 = all)
+    int fft_log2n = 0;            // "fft_log2n": overlap-save transform size (applies when it holds the taps; 0 = chosen)
+    int fft_threads = 0;          // "fft_threads": k_fftconv16's workgroup size (0 = chosen)
+    bool fft_keep_geometry = false;   // "fft_geometry" = "keep": the two filter kernels on k_p0fft16's transform size and windows
+    int casc2_min_run = 0;        // "casc2_min_run": shortest streaming run (tiles) that takes k_cascade2 (0 = the built-in bound)
+};
+DebugSwitches debug_switches();                        // abi.cpp: the table as it stands, under one lock
+std::string debug_value(const char *name);             // ... one raw value ("" when unset): process-level switches only (sysfs_root)
+
 // ------------------------------------------------------------------------------------------------
 // the chain object
 // ------------------------------------------------------------------------------------------------
@@ -97,6 +117,7 @@ struct iqgpu_chain {
     bool late = false;           // resampler behind the front stage / pre filter: k_interp (r >= 1)
     ResamplePlan rp;
     FilterPlan fp;
+    DebugSwitches sw;            // the diagnostic switches as the table stood when the chain was designed
     // operator constants
     bool dc = false; float dc_alpha = 0.0f, dc_c = 1.0f; double dc_logc = 0.0;
     float iq_mag = 0.0f, iq_phase = 0.0f;
@@ -119,7 +140,7 @@ struct iqgpu_chain {
     // device state
     hipStream_t own_stream = nullptr, stream = nullptr;
     cf2 *d_nco_tab = nullptr; float *d_arb = nullptr; float *d_hb = nullptr; cf2 *d_ftaps = nullptr;
-    cf2 *d_hfreq = nullptr, *d_twiddle = nullptr; int fft_log2n = 0, fft_threads = 0;   // overlap-save path of FFT-kind filters
+    cf2 *d_hfreq = nullptr, *d_twiddle = nullptr; int fft_log2n = 0;   // overlap-save path of FFT-kind filters
     cf2 *d_hist[2] = {nullptr, nullptr}; int hist_cur = 0;
     // S >= 2 without a dc blocker: k_cascade (stages 0 .. S-2) -> mid -> k_front_s1 (last stage + polyphase)
     bool cascade = false; int hist2_cap = 0, casc_warm = 1;
@@ -127,11 +148,9 @@ struct iqgpu_chain {
     DevBuf mid;
     cd2 *d_dc_state = nullptr;
     void *d_sink = nullptr;      // diagnostic scratch of k_front_s1 (iqgpu_chain_debug_read_scratch)
-    // run stealing in k_front_mid (kernels.hpp, FrontArgs::w_steal): one descriptor per wave of a launch; all exhausted between
-    // launches (zeroed when the array is (re)allocated).  IQGPU_STEAL=1 turns it on, IQGPU_STEAL_MIN / _ROUNDS / _LANES / _STRIDE tune it.
+    // run descriptors of k_front_mid (kernels.hpp, FrontArgs::w_steal; sw.steal*): one per wave of a launch; all exhausted between
+    // launches (zeroed when the array is (re)allocated)
     DevBuf steal_buf;
-    // (off by default: measured neutral, profiles/r04_steal.md -- the launch tail it removes turned out to be free)
-    bool steal = false; int steal_min = 6, steal_rounds = 6, steal_stride = 544, steal_lanes = 16;   // stride in 8-byte words: 4352 B
     DevBuf dc_agg, dc_carry;
     DevBuf fbuf[2]; int fcur = 0;
     // output AGC (digital profile)
@@ -164,7 +183,7 @@ struct iqgpu_chain {
     bool agc_fusable_filter = false;
     // round 6: resampler -> post-resample overlap-save filter in ONE kernel (k_p0fft16, fftconv.hip): the chain's shape allows it,
     // with the window geometry it runs (fuse_win stream samples per block, fuse_vout outputs)
-    bool fuse_filter = false; int fuse_win = 0, fuse_vout = 0; bool fft_keep_geometry = false;
+    bool fuse_filter = false; int fuse_win = 0, fuse_vout = 0;
     DevBuf ibuf[2]; int icur = 0;  // k_interp input: [ihist history][new samples]
     InterpArgs ia{};              // geometry of the r >= 1 path
     int ihist = 0;
@@ -198,15 +217,9 @@ struct iqgpu_chain {
     cf2 probe_last[1024];
     char front_kernel[48] = "";   // which front kernel the last call launched (iqgpu_chain_front_kernel)
     bool poisoned = false;        // a call failed after device state had been touched: reset() clears it
-    bool force_generic = false;   // IQGPU_FORCE_GENERIC=1: always use the workgroup-tiled k_front
-    uint32_t dbg = 0;             // kDbg* diagnostic switches, read from the environment once at create
-    // weights of the runs of the first / second / third wave of a SIMD in k_front_mid (IQGPU_RUN_WEIGHTS=a,b,c; 0 = equal runs)
-    int32_t run_wt[4] = {1300, 1000, 700, 0};
-    // placement of the arms in the tap planes of k_front_mid / k_front_fat for this chain's step (front_tap_fold);
-    // IQGPU_TAP_FOLD=0|1 overrides
-    int tap_fold6 = 0, tap_fold8 = 0, tap_fold_env = -1;
-    // NCO phasor hold of k_front_mid for this chain's phase step at 6 / 8 outputs per lane (front_mid_nco_hold); nco_hold=0 turns it off
-    bool nco_hold = true;
+    // placement of the arms in the tap planes of k_front_mid / k_front_fat for this chain's step (front_tap_fold, or sw.tap_fold)
+    int tap_fold6 = 0, tap_fold8 = 0;
+    // NCO phasor hold of k_front_mid for this chain's phase step at 6 / 8 outputs per lane (front_mid_nco_hold; off with sw.nco_hold)
     int nco_hold6 = 0, nco_hold8 = 0;
     // profiling
     bool profiling = false;

@@ -833,7 +833,7 @@ int front_mid_nl(const FrontArgs &a)
           !a.iq_enable && !a.dc_enable && a.pnco_mode == 0 && !(a.dbg & (kDbgNoFast | kDbgNoFat)))) return 0;
     int l3, l4;
     for (int nl : {8, 6}) {
-        // 8 per lane is an experiment (IQGPU_MID8=1): in 168 VGPRs it has no room to fetch a phase ahead, and without that it runs
+        // 8 per lane is an experiment (iqgpu_debug_set("mid8", "1")): in 168 VGPRs it has no room to fetch a phase ahead, and without that it runs
         // 0.440 ms against 0.384 for 6 per lane on the NRSC-5 chain; with the fused AGC it does not fit at all
         if (nl == 8 && (!(a.dbg & kDbgMid8) || a.agc_fused || cf32_out || any8)) continue;
         if (!mid_class(a.step, nl, &l3, &l4)) continue;

@@ -28,7 +28,7 @@
 // for a store wherever its registers are written again); the folded arm placement (consecutive lanes are 16 arms apart for
 // this step: linear planes put a slot's re-reading lanes into two bank pairs); the chunk sorting of the fused AGC only in the
 // one step in thirty that holds a boundary.  368 VALU instructions and 179 LDS cycles per step: at two waves per SIMD (round 5) the
-// kernel took their sum, at three (round 6) it overlaps them.  IQGPU_NO_P0=1 keeps k_front_s1<S0>.
+// kernel took their sum, at three (round 6) it overlaps them.  iqgpu_debug_set("no_p0", "1") keeps k_front_s1<S0>.
 //
 // Three waves per SIMD since round 6 (80 VGPRs of taps + 44 of window + ONE step of frames in flight; two waves with two steps until then).  Edge tiles -- the stream
 // history in front of the call, the tail that becomes the next call's history -- are run by the scalar-load instantiation of

@@ -60,16 +60,16 @@ struct cd2 { double x, y; };
 // k_front: raw -> [unpack, gain] -> [dc block] -> [iq correct] -> [pre NCO] -> [half-band cascade ->
 //          arbitrary polyphase] -> [post NCO] -> [pack] -> out
 // ---------------------------------------------------------------------------------------------
-// diagnostic switches (IQGPU_NO_FAST, IQGPU_AGC_NOFUSE, IQGPU_NO_RAW0, IQGPU_NO_KT, IQGPU_FFT_NO_R16): read from the
-// environment ONCE, in iqgpu_chain_create, and carried in the launch arguments -- the launch path itself never calls getenv
+// kernel-selection switches (iqgpu_debug_set("no_fast", "1"), ...: abi.cpp kSwitches): taken ONCE per chain, when it is designed,
+// and carried in the launch arguments -- the launch path never looks at the switch table
 enum : uint32_t { kDbgNoFast = 1u, kDbgAgcNoFuse = 2u, kDbgNoRaw0 = 4u, kDbgNoKT = 8u, kDbgFftNoR16 = 16u, kDbgNoFat = 32u, kDbgForceFat = 64u, kDbgUseFat = 128u, kDbgMid8 = 256u,
-                  kDbgNoS2 = 512u,         // IQGPU_NO_S2=1: two-stage chains keep k_cascade + k_front_s1 instead of the fused k_front_s2
-                  kDbgNoMid8bit = 8192u,   // IQGPU_NO_MID_8BIT=1: S = 1 chains with 8-bit frames on either side keep k_front_s1 instead of k_front_mid
-                  kDbgNoCasc2 = 4096u,     // IQGPU_NO_CASC2=1: raw cu8 cascades keep k_cascade's one tile per trip instead of k_cascade2's two
-                  kDbgNoP0 = 2048u,        // IQGPU_NO_P0=1: chains without a half-band stage keep k_front_s1<S0> instead of k_front_p0
-                  kDbgFuseFilter = 16384u, // fuse_filter=1: S = 0 chains with a filter behind the resampler run k_p0fft16 (one kernel, no cf32 stream) instead of
+                  kDbgNoS2 = 512u,         // no_s2: two-stage chains keep k_cascade + k_front_s1 instead of the fused k_front_s2
+                  kDbgNoMid8bit = 8192u,   // no_mid_8bit: S = 1 chains with 8-bit frames on either side keep k_front_s1 instead of k_front_mid
+                  kDbgNoCasc2 = 4096u,     // no_casc2: raw cu8 cascades keep k_cascade's one tile per trip instead of k_cascade2's two
+                  kDbgNoP0 = 2048u,        // no_p0: chains without a half-band stage keep k_front_s1<S0> instead of k_front_p0
+                  kDbgFuseFilter = 16384u, // fuse_filter: S = 0 chains with a filter behind the resampler run k_p0fft16 (one kernel, no cf32 stream) instead of
                                            // k_front_p0 + k_fftconv16 -- opt-in: parity-green and SLOWER than the two kernels (profiles/r06_fused_filter.md)
-                  kDbgNoFusedMove = 1024u }; // IQGPU_NO_FUSED_MOVE=1: the filter's history moves by a copy kernel, not inside the filter kernel
+                  kDbgNoFusedMove = 1024u }; // no_fused_move: the filter's history moves by a copy kernel, not inside the filter kernel
 
 struct FrontArgs {
     uint32_t    dbg;          // kDbg* switches of the chain
@@ -223,15 +223,14 @@ hipError_t launch_front(const FrontArgs &a, int n_blocks, hipStream_t s);
 constexpr int kCascMaxK = 4;
 bool cascade_supported(const int *m_run_order, int S);
 size_t cascade_wave_lds(const FrontArgs &a, bool two_tile_trips = true);   // (false: k_cascade's own layout only)
-hipError_t launch_cascade(const FrontArgs &a, hipStream_t s);
+hipError_t launch_cascade(const FrontArgs &a, int casc2_min_run, hipStream_t s);   // (k_cascade2 where it applies)
 int cascade_waves(const FrontArgs &a);    // needs casc_wave_lds
 // ... with two tiles per trip of a streaming wave for raw cu8 frames (cascade2.hip): the chain shape (needs in_fmt, gain, the
 // pointwise switches, casc_K, m[]); the call (needs the run geometry and casc_wave_lds too); bytes of a wave's slice
 bool cascade2_shape(const FrontArgs &a);
-bool cascade2_applies(const FrontArgs &a);
-void cascade2_set_min_run(int n);                       // diagnostics (iqgpu_debug_set "casc2_min_run"); 0 = the built-in bound
+bool cascade2_applies(const FrontArgs &a, int min_run);   // min_run: shortest streaming run in tiles (0 = the built-in bound)
 int cascade2_wave_lds(int K, int in_fmt);
-hipError_t launch_cascade2(const FrontArgs &a, hipStream_t s);
+hipError_t launch_cascade2(const FrontArgs &a, int min_run, hipStream_t s);
 // one half-band stage (m = 10), no dc blocker: wave-autonomous kernel (front_wave.hip)
 size_t front_s1_lds_bytes();
 hipError_t launch_front_s1(const FrontArgs &a, hipStream_t s);

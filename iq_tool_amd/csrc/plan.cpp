@@ -107,14 +107,14 @@ void Call::plan_geometry()
 
     // run geometry of the wave-autonomous kernels (needed by the dc carries as well)
     //   S >= 2: k_cascade (stages 0 .. S-2) + k_front_s1 (last stage);  S == 1: k_front_s1;  S == 0: its S0 variant
-    casc = c->cascade && !c->force_generic;
-    fast_s0 = c->decim && c->S == 0 && !c->force_generic;          // polyphase only, 256-frame tiles
-    fast_s1 = fast_s0 || (c->decim && c->S == 1 && c->rp.stages[0].m == 10 && !c->force_generic);
+    casc = c->cascade && !c->sw.force_generic;
+    fast_s0 = c->decim && c->S == 0 && !c->sw.force_generic;          // polyphase only, 256-frame tiles
+    fast_s1 = fast_s0 || (c->decim && c->S == 1 && c->rp.stages[0].m == 10 && !c->sw.force_generic);
     wtile = fast_s0 ? 256 : kWTile;
     casc_K = c->S - 1;
     rem_k = casc ? (c->rem & ((1 << casc_K) - 1)) : c->rem;
     cplan = FrontArgs{};
-    cplan.dbg = c->dbg;
+    cplan.dbg = c->sw.dbg;
     if (casc || fast_s1) {
         cplan.frames_in = (int64_t)frames_in; cplan.rem0 = rem_k; cplan.hist_cap = c->hist_cap;
         cplan.in_fmt = c->desc.in_format; cplan.out_fmt = (casc || filt) ? (int)IQGPU_FMT_CF32 : fin_fmt;
@@ -132,7 +132,7 @@ void Call::plan_geometry()
         // the preset shape on a call long enough to give every one of the 8 x CUs fat waves a run of tiles: k_front_fat
         // (shorter calls keep k_front_s1's 16 x CUs waves of 512-frame tiles: what counts for them is latency; same bytes either way)
         const bool fat_ok = !casc && !fast_s0 && front_fat_shape(cplan) &&
-              ((c->dbg & kDbgForceFat) || (int64_t)frames_in >= (int64_t)kFatMinTilesPerWave * kFatTile * wave_slots(front_fat_waves()));
+              ((c->sw.dbg & kDbgForceFat) || (int64_t)frames_in >= (int64_t)kFatMinTilesPerWave * kFatTile * wave_slots(front_fat_waves()));
         const int mid_nl = (!casc && !fast_s0) ? front_mid_nl(cplan) : 0;
         // (run descriptors hold tile indices in 32 bits)
         // (k_front_mid from 6 tiles per wave on: measured round 4 at 2^21 .. 2^25 frames, kernel ms k_front_s1 / k_front_mid:
@@ -140,11 +140,11 @@ void Call::plan_geometry()
         //  = 3.6 and 7.1 tiles per wave; the pipelined host path's 2^24-frame batches now run the headline kernel)
         constexpr int kMidMinTilesPerWave = 6;
         const bool mid_ok = mid_nl != 0 && (int64_t)frames_in < ((int64_t)1 << 40) &&
-              ((c->dbg & kDbgForceFat)
+              ((c->sw.dbg & kDbgForceFat)
                   || (int64_t)frames_in >= (int64_t)kMidMinTilesPerWave * front_mid_tile(mid_nl) * wave_slots(front_mid_waves()));
         // (measured on one box, 2^28 frames: k_front_s1 0.437 ms, k_front_fat 0.404, k_front_mid 0.381: the 12-wave kernel is the
-        //  default; IQGPU_FAT=1 selects the 8-wave one where its step class applies)
-        fat = fat_ok && ((c->dbg & kDbgUseFat) || !mid_ok);
+        //  default; iqgpu_debug_set("fat", "1") selects the 8-wave one where its step class applies)
+        fat = fat_ok && ((c->sw.dbg & kDbgUseFat) || !mid_ok);
         mid = mid_ok && !fat;
         if (fat) wtile = kFatTile;
         if (mid) wtile = front_mid_tile(mid_nl);
@@ -161,13 +161,13 @@ void Call::plan_geometry()
                       mid ? kMidLead : (casc && cascade2_shape(cplan)) ? kWTile : 0);
         // (a raw cascade whose call turns out too short for k_cascade2's two-tile trips: k_cascade's own slice -- more waves per CU -- and
         //  no lead)
-        if (casc && cascade2_shape(cplan) && !cascade2_applies(cplan)) {
+        if (casc && cascade2_shape(cplan) && !cascade2_applies(cplan, c->sw.casc2_min_run)) {
             cplan.casc_wave_lds = (int)cascade_wave_lds(cplan, false);
             plan_front_s1(cplan, wave_slots(cascade_waves(cplan)), ftpw, warm, mid_align, wtile, mid_align, 0);
         }
         // k_front_mid: the three waves of a SIMD get runs in proportion to the speed their age buys them (kernels.hpp, weight_runs)
-        if (mid && ftpw == 0 && cplan.w_n_edge <= front_mid_max_edge_waves() && c->run_wt[0] > 0) weight_runs(cplan, front_mid_waves(),
-            c->run_wt);
+        if (mid && ftpw == 0 && cplan.w_n_edge <= front_mid_max_edge_waves() && c->sw.run_wt[0] > 0) weight_runs(cplan, front_mid_waves(),
+            c->sw.run_wt);
         if (mid && cplan.w_n_edge > front_mid_max_edge_waves()) {
             // (an unaligned buffer, a call that is all edges: k_front_mid keeps LDS for a handful of edge waves only)
             mid = false; wtile = kWTile;
@@ -179,9 +179,9 @@ void Call::plan_geometry()
         // outputs (shorter calls keep k_front_s1<S0>: same bytes).  Planned as k_front_s1's 256-frame tiles -- the edge runs are its
         // run_tiles -- with the streaming tiles' OUTPUTS dealt out as steps
         p0 = false;
-        if (fast_s0 && !casc && !(c->dbg & kDbgNoP0)) {
+        if (fast_s0 && !casc && !(c->sw.dbg & kDbgNoP0)) {
             cplan.phi0 = c->phi;
-            if (front_p0_shape(cplan) && ((int64_t)frames_in >= ((int64_t)1 << 22) || (c->dbg & kDbgForceFat))) {
+            if (front_p0_shape(cplan) && ((int64_t)frames_in >= ((int64_t)1 << 22) || (c->sw.dbg & kDbgForceFat))) {
                 FrontArgs q = cplan;
                 plan_front_s1(q, wave_slots(front_p0_waves()), 0, warm, front_p0_edge_tpw(), 256);
                 if (q.w_n_edge <= front_p0_max_edge_waves() && q.w_edge_tb > q.w_edge_ta) {
@@ -195,7 +195,7 @@ void Call::plan_geometry()
         // front (history + pending samples) is recomputed by one workgroup, so it has to be short
         fusef = false;
         if (c->fuse_filter && filt && fast_s0 && !casc && p.n_emit > 0 && (int64_t)(L1 + p.fpending_next) <= kP0FftMaxKeep &&
-            ((int64_t)frames_in >= ((int64_t)1 << 22) || (c->dbg & kDbgForceFat))) {
+            ((int64_t)frames_in >= ((int64_t)1 << 22) || (c->sw.dbg & kDbgForceFat))) {
             fusef = true; p0 = false;
         }
                 // S == 2: both stages in ONE kernel (k_front_s2, front_s2.hip), planned in tiles of the LAST stage -- 512 intermediate samples
@@ -204,7 +204,7 @@ void Call::plan_geometry()
         // to leave behind, keep the two kernels (same bytes either way).
         s2 = false;
         const int64_t n_mid = (int64_t)frames_in >> 1;
-        if (casc && casc_K == 1 && c->rem == 0 && cplan.raw_aligned && !front_fused() && !(c->dbg & kDbgNoS2) && front_s2_shape(cplan) &&
+        if (casc && casc_K == 1 && c->rem == 0 && cplan.raw_aligned && !front_fused() && !(c->sw.dbg & kDbgNoS2) && front_s2_shape(cplan) &&
             (int64_t)frames_in >= (int64_t)c->hist_cap && n_mid >= (int64_t)c->hist2_cap) {
             FrontArgs p2{};
             p2.frames_in = n_mid; p2.rem0 = 0; p2.hist_cap = c->hist2_cap; p2.in_fmt = IQGPU_FMT_CF32; p2.out_fmt = filt ? (int)IQGPU_FMT_CF32 : fin_fmt;

@@ -75,10 +75,10 @@ int Call::prepare_buffers()
         int rc = c->mid.ensure(((size_t)n_mid + 8) * sizeof(cf2)); if (rc) return rc;
     }
     // run descriptors of k_front_mid: a fresh array starts exhausted (all zero), a used one is left exhausted by every launch
-    if (mid && (c->steal || fixed_tpw() != 0)) {
+    if (mid && (c->sw.steal || fixed_tpw() != 0)) {
         const void *was = c->steal_buf.p;
         const size_t slots = (size_t)(fixed_tpw() != 0 ? wave_slots(front_mid_waves()) + cplan.w_n_edge : cplan.w_n_edge + cplan.w_n_stream) + 64;
-        int rc = c->steal_buf.ensure(slots * (size_t)c->steal_stride * sizeof(unsigned long long)); if (rc) return rc;
+        int rc = c->steal_buf.ensure(slots * (size_t)c->sw.steal_stride * sizeof(unsigned long long)); if (rc) return rc;
         if (c->steal_buf.p != was && hipMemsetAsync(c->steal_buf.p, 0, c->steal_buf.cap, c->stream) != hipSuccess)
             return fail(IQGPU_EHIP, "hipMemsetAsync failed");
     }
@@ -109,7 +109,7 @@ int Call::stage_front()
         return IQGPU_OK;
     }
     FrontArgs a{};
-    a.dbg = c->dbg;
+    a.dbg = c->sw.dbg;
     a.raw = d_raw_in;
     a.hist_in = c->d_hist[c->hist_cur]; a.hist_out = c->d_hist[c->hist_cur ^ 1];
     a.frames_in = (int64_t)frames_in; a.hist_cap = c->hist_cap; a.rem0 = c->rem;
@@ -167,13 +167,13 @@ int Call::stage_front()
         if (s2) a1.w_total_tiles = s2_in_tiles;          // (the fused kernel is planned in the last stage's tiles: cplan is a2's)
         else {
             copy_plan(a1);
-            casc2 = cascade2_applies(a1);                // (launch_cascade's own test: raw cu8 frames, long runs -- cascade2.hip)
-            KernelTimer kt(c, IQGPU_K_CASCADE); HIP_TRY(launch_cascade(a1, c->stream));
+            casc2 = cascade2_applies(a1, c->sw.casc2_min_run);   // (launch_cascade's own test: raw cu8 frames, long runs -- cascade2.hip)
+            KernelTimer kt(c, IQGPU_K_CASCADE); HIP_TRY(launch_cascade(a1, c->sw.casc2_min_run, c->stream));
         }
         // ---- last stage + polyphase: a one-stage chain on the intermediate stream ----
         if (n_mid > 0) {
             FrontArgs a2{};
-            a2.dbg = c->dbg;
+            a2.dbg = c->sw.dbg;
             a2.raw = c->mid.p; a2.hist_in = c->d_hist2[c->hist2_cur]; a2.hist_out = c->d_hist2[c->hist2_cur ^ 1];
             a2.frames_in = n_mid; a2.hist_cap = c->hist2_cap; a2.rem0 = rem_1;
             a2.in_fmt = IQGPU_FMT_CF32; a2.gain = 1.0f; a2.raw_aligned = 1;
@@ -207,18 +207,18 @@ int Call::stage_front()
             a.agc_chunk_frames = c->agc_chunk; a.agc_shift = c->S; a.agc_rem = c->rem;
             HIP_TRY(clean_agc_peaks());
         }
-        // k_front_mid, IQGPU_STEAL=1, one run per resident wave: every wave claims its tiles through its run descriptor and waves
+        // k_front_mid, "steal" on, one run per resident wave: every wave claims its tiles through its run descriptor and waves
         // that finish early split the runs of those that are behind (front_mid.hip; off by default, profiles/r04_steal.md)
-        if (mid && c->steal && fixed_tpw() == 0 && a.w_n_stream >= 64 * (int64_t)front_mid_waves()) {
-            a.w_steal = (unsigned long long *)c->steal_buf.p; a.w_steal_min = c->steal_min;
-            a.w_steal_stride = c->steal_stride; a.w_steal_lanes = c->steal_lanes; a.w_steal_rounds = c->steal_rounds;
+        if (mid && c->sw.steal && fixed_tpw() == 0 && a.w_n_stream >= 64 * (int64_t)front_mid_waves()) {
+            a.w_steal = (unsigned long long *)c->steal_buf.p; a.w_steal_min = c->sw.steal_min;
+            a.w_steal_stride = c->sw.steal_stride; a.w_steal_lanes = c->sw.steal_lanes; a.w_steal_rounds = c->sw.steal_rounds;
         } else if (mid && front_mid_nl(a) == 6 && fixed_tpw() != 0 && a.w_n_stream > wave_slots(front_mid_waves()) - a.w_n_edge) {
-            // (the multi-run instantiation exists for six outputs per lane only: the 8-per-lane experiment, IQGPU_MID8=1, keeps one
+            // (the multi-run instantiation exists for six outputs per lane only: the 8-per-lane experiment, "mid8", keeps one
             //  static run per wave over as many rounds of workgroups as the runs need -- ADVICE r4)
             // block_samples != 0 (BASELINE configs[1] as worded: "256 k-sample blocks"): more fixed-length runs than resident waves --
             // one round of workgroups, every streaming wave takes runs s, s + stride, ... through the multi-run instantiation
-            a.w_steal = (unsigned long long *)c->steal_buf.p; a.w_steal_min = c->steal_min;
-            a.w_steal_stride = c->steal_stride; a.w_steal_lanes = c->steal_lanes; a.w_steal_rounds = 0;
+            a.w_steal = (unsigned long long *)c->steal_buf.p; a.w_steal_min = c->sw.steal_min;
+            a.w_steal_stride = c->sw.steal_stride; a.w_steal_lanes = c->sw.steal_lanes; a.w_steal_rounds = 0;
             a.w_run_stride = wave_slots(front_mid_waves()) - a.w_n_edge;
         }
         const int mid_nl = mid ? front_mid_nl(a) : 0;
@@ -259,14 +259,14 @@ int Call::stage_filter()
     // next call's buffer front: history (L-1) + still-pending samples, into the other buffer of the pair -- by the filter kernel's
     // last workgroup when one is launched (nobody reads that buffer meanwhile), else by a copy kernel
     const size_t keep = L1 + (size_t)p.fpending_next;
-    const bool fused_move = n_filt > 0 && !(c->dbg & kDbgNoFusedMove);
+    const bool fused_move = n_filt > 0 && !(c->sw.dbg & kDbgNoFusedMove);
     if (fused_move) { fa.move_dst = (cf2 *)c->fbuf[c->fcur ^ 1].p; fa.move_src = fcur + n_filt; fa.move_n = (int64_t)keep; }
     if (c->d_hfreq) {
         FftConvArgs ca{};
-        ca.dbg = c->dbg;
+        ca.dbg = c->sw.dbg;
         ca.fbuf = fcur; ca.fbuf_len = (int64_t)(L1 + (size_t)c->fpending + (size_t)p.n_res);
         ca.hfreq = c->d_hfreq; ca.twiddle = c->d_twiddle; ca.ntaps = fa.ntaps;
-        ca.log2n = c->fft_log2n; ca.threads = c->fft_threads; ca.n_emit = n_filt;
+        ca.log2n = c->fft_log2n; ca.threads = c->sw.fft_threads; ca.n_emit = n_filt;
         ca.pnco_mode = fa.pnco_mode; ca.pnco_theta0 = fa.pnco_theta0; ca.pnco_dtheta = fa.pnco_dtheta; ca.nco_tab = fa.nco_tab;
         ca.out_fmt = fa.out_fmt; ca.out = fa.out;
         ca.move_dst = fa.move_dst; ca.move_src = fa.move_src; ca.move_n = fa.move_n;
@@ -327,7 +327,7 @@ int Call::stage_late_resampler()
     ia.out_fmt = fin_fmt; ia.out = fin_out;
     // the next call's history (the last ihist resampler inputs) into the other buffer of the pair: by k_interp's last workgroup
     // when it is launched, else by a copy kernel
-    const bool fused_move = p.n_emit > 0 && !(c->dbg & kDbgNoFusedMove);
+    const bool fused_move = p.n_emit > 0 && !(c->sw.dbg & kDbgNoFusedMove);
     ia.move_dst = nullptr; ia.move_src = nullptr; ia.move_n = 0;
     if (fused_move) { ia.move_dst = (cf2 *)c->ibuf[c->icur ^ 1].p; ia.move_src = icur + p.n_x; ia.move_n = (int64_t)c->ihist; }
     { KernelTimer kt(c, IQGPU_K_FRONT); HIP_TRY(launch_interp(ia, c->n_cu, c->stream)); }

@@ -1417,6 +1417,37 @@ def test_two_tile_trips_equal_the_one_tile_cascade(gpu, oracle, monkeypatch, in_
         int_close(got, want, min_same=0.998)
 
 
+def test_a_chain_keeps_the_switches_it_was_created_with(gpu, monkeypatch):
+    """casc2_min_run was a process-wide global that every create, iqgpu_design_probe and iqgpu_design_out_frames rewrote,
+    so a later create moved a live chain between k_cascade and k_cascade2.  Each chain now takes one snapshot of the switch table:
+    chain A, created with the bound out of reach, keeps k_cascade after B (the default) is created behind a design call; both give
+    the same bytes; and a switch set after B's create (no_casc2) does not move B either."""
+    from iq_tool_amd import _lib
+    lib = _lib.load()
+    for k in ("IQGPU_CASC2_MIN_RUN", "IQGPU_NO_CASC2"):
+        monkeypatch.delenv(k, raising=False)
+    n = (1 << 22) + 16384 * 3 + 8
+    kw = dict(in_format="cu8", out_format="cu8", input_rate_hz=20e6, target_rate_hz=1488375.0, block_samples=36 * 8192)
+    raw = synth.raw_stream(n, 20e6, 77, "cu8")
+    try:
+        _lib.check(lib.iqgpu_debug_set(b"casc2_min_run", b"1000000"))
+        a = gpu.Chain(**kw)
+        _lib.check(lib.iqgpu_debug_set(b"casc2_min_run", None))
+        gpu.design_out_frames(n, **kw)
+        b = gpu.Chain(**kw)
+        got_a, got_b = a.process(raw), b.process(raw)
+        assert (a.front_kernel(), b.front_kernel()) == ("k_cascade+k_front_s1", "k_cascade2+k_front_s1")
+        assert got_a.size == got_b.size and np.array_equal(got_a, got_b)
+        _lib.check(lib.iqgpu_debug_set(b"no_casc2", b"1"))
+        b.reset()
+        again = b.process(raw)
+        assert b.front_kernel() == "k_cascade2+k_front_s1"
+        assert np.array_equal(again, got_b)
+    finally:
+        lib.iqgpu_debug_set(b"casc2_min_run", None)
+        lib.iqgpu_debug_set(b"no_casc2", None)
+
+
 @pytest.mark.parametrize("shift_hz,agc", [(200e3, False), (0.0, False), (-150e3, True)])
 def test_dc_blocker_chain_with_its_switches_compiled_in(gpu, oracle, monkeypatch, shift_hz, agc):
     """Late round 5: the headline chain with `--dc-block` on k_front_s1<4, .., VAR = 5 | 6> (cs16 in and out, unit gain, dc blocker on,

@@ -473,6 +473,41 @@ def test_diagnostic_switches_go_through_one_entry_point_not_the_environment(monk
     assert lib.iqgpu_debug_set(None, None) == 0
 
 
+def test_the_environment_mirror_leaves_a_directly_set_switch_alone(monkeypatch):
+    """apply_debug_env (run by every make_desc, Chain() and bind_thread_to_device) used to clear the whole table first, so a
+    switch a caller had set through iqgpu_debug_set was gone by the next create.  It now touches only the names it forwards."""
+    from iq_tool_amd import _lib
+    lib = _lib.load()
+    monkeypatch.delenv("IQGPU_STEAL", raising=False)
+    assert lib.iqgpu_debug_set(None, None) == 0
+    try:
+        assert lib.iqgpu_debug_set(b"steal", b"1") == 0
+        _lib.apply_debug_env()
+        assert _lib.debug_switches() == {"steal": "1"}
+        _lib.apply_debug_env()
+        assert _lib.debug_switches() == {"steal": "1"}
+    finally:
+        assert lib.iqgpu_debug_set(None, None) == 0
+
+
+def test_the_environment_mirror_clears_what_it_forwarded_once_the_variable_goes(monkeypatch):
+    """... and a switch it did forward still goes away with its variable, next to one set directly, which stays."""
+    from iq_tool_amd import _lib
+    lib = _lib.load()
+    monkeypatch.delenv("IQGPU_STEAL", raising=False)
+    assert lib.iqgpu_debug_set(None, None) == 0
+    try:
+        assert lib.iqgpu_debug_set(b"steal", b"1") == 0
+        monkeypatch.setenv("IQGPU_CASC2_MIN_RUN", "7")
+        _lib.apply_debug_env()
+        assert _lib.debug_switches() == {"steal": "1", "casc2_min_run": "7"}
+        monkeypatch.delenv("IQGPU_CASC2_MIN_RUN")
+        _lib.apply_debug_env()
+        assert _lib.debug_switches() == {"steal": "1"}
+    finally:
+        assert lib.iqgpu_debug_set(None, None) == 0
+
+
 # --------------------------------------------------------------------------------------------
 # NUMA placement of the process / thread that feeds a GPU (iqgpu_device_numa_node, iqgpu_bind_thread_to_device: topology.cpp)
 # against a stand-in sysfs tree shaped like the 8-GPU, two-socket boxes of this pool (IQGPU_SYSFS_ROOT)
