@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define IQGPU_ABI_VERSION 6
+#define IQGPU_ABI_VERSION 7
 
 /* Sample formats: numerically equal to the reference's format_t (include/common_types.h:33-37) */
 enum {
@@ -60,7 +60,8 @@ enum {
     IQGPU_EFILTER = -7,     /* filter band beyond output Nyquist, fft size too small, too many stages (src/filter.c:80-84, 321-325) */
     IQGPU_ECAPACITY = -8,   /* out_capacity_bytes too small for this call */
     IQGPU_EHIP = -9,        /* a HIP runtime call failed */
-    IQGPU_EUNSUPPORTED = -10/* no sample path returns it; the placement calls do when a *_VISIBLE_DEVICES list is not plain indices */
+    IQGPU_EUNSUPPORTED = -10/* the placement calls when a *_VISIBLE_DEVICES list is not plain indices; iqgpu_chain_seek and the two    */
+                            /* seamless-sharding design calls for a chain with the output AGC (no finite warm-up bounds its state) */
 };
 
 typedef struct iqgpu_chain iqgpu_chain; /* opaque, like resampler_t (include/resampler.h:25-26) */
@@ -177,8 +178,33 @@ int    iqgpu_design_probe(const iqgpu_chain_desc *d, iqgpu_chain_info *info,
 
 /* frames a FRESH chain of this description emits for a stream of frames_in frames (no device needed): the
  * closed form of the resampler law and the FFT-block quantisation on whichever side of the resampler the filter
- * sits.  What a stitching writer uses to place the outputs of independent shards (8 iq_tool runs + cat). */
+ * sits.  What a stitching writer uses to place the outputs of independent shards (8 iq_tool runs + cat); for shards that
+ * continue ONE stream see iqgpu_design_out_frames_range below. */
 int    iqgpu_design_out_frames(const iqgpu_chain_desc *d, size_t frames_in, size_t *frames_out);
+
+/* ---- seamless range sharding (ABI v7): start a chain at any position of ONE stream ----
+ * Everything a chain carries from call to call is either a closed form of the number of input frames consumed (open decimation
+ * group, resampler phase, both NCO phases, pending FFT-block samples) or finite FIR memory (half-band, polyphase, user-filter
+ * and overlap-save histories).  iqgpu_chain_seek sets the first from the position and refills the second by running the frames
+ * in front of the position through the ordinary kernels with the output dropped.  N chains that each seek to the start of their
+ * range and process it then write, stitched in order, the stream ONE chain writes: byte for byte on every chain without a DC
+ * blocker.  The DC blocker is a decaying IIR: its state is warmed up over ceil(ln(1e6) / alpha) extra frames.  A state error e
+ * decays as (1 - alpha)^n and reaches the output as alpha * e, and |state| <= max|x| / alpha, so behind that warm-up the output
+ * differs from the single stream's by at most 1e-6 of full scale (a tenth of the 1e-5 parity bar) and less with every frame;
+ * a seek whose warm-up starts at frame 0 is exact.  The output AGC is a function of the whole prefix of the stream (scan / lock /
+ * creep of the digital profile, agc_crcf's loop of dx / local): no warm-up bounds it, and these calls refuse such chains with
+ * IQGPU_EUNSUPPORTED.  Positions are 64-bit; first_frame + frames_in beyond 2^39 frames is IQGPU_EINVAL (the 24-bit fixed-point
+ * phase arithmetic holds that far and is never allowed to wrap).
+ *
+ * iqgpu_design_preroll_frames: input frames in front of a seam that a chain of this description has to see (output discarded)
+ * so that everything it emits afterwards is what the single stream emits: its FIR memory expressed in input frames (plus the DC
+ * warm-up).  0 for a pointwise chain.  No device; same validation and error codes as iqgpu_chain_create.
+ * iqgpu_design_out_frames_range: what ONE stream of this description emits while it consumes input frames
+ * [first_frame, first_frame + frames_in): index of the first of those output frames in the stream's output, and how many.  For
+ * any cut points the ranges tile the output: frames_out sums to iqgpu_design_out_frames of the whole.  No device. */
+int    iqgpu_design_preroll_frames(const iqgpu_chain_desc *d, uint64_t *frames);
+int    iqgpu_design_out_frames_range(const iqgpu_chain_desc *d, uint64_t first_frame, uint64_t frames_in,
+                                     uint64_t *out_first, uint64_t *frames_out);
 
 /* ---- per-chunk: replaces pre_processor_apply_chain (src/pre_processor.c:10), resampler_execute
  *      (include/resampler.h:48) and post_processor_apply_chain (src/post_processor.c:9) in one call ---- */
@@ -211,6 +237,18 @@ int    iqgpu_chain_collect(iqgpu_chain *c, uint64_t ticket);
 int    iqgpu_chain_pipeline_depth(void);
 /* == pre_processor_reset + resampler_reset + post_processor_reset (stream discontinuity) */
 int    iqgpu_chain_reset(iqgpu_chain *c);
+/* Puts the chain at stream frame first_frame.  preroll: the preroll_frames input frames that END at first_frame, in host memory
+ * (_device: in device memory of the chain's device); preroll_frames <= first_frame, and at least
+ * min(first_frame, iqgpu_design_preroll_frames) -- a shorter warm-up would be a silent seam and is IQGPU_EINVAL; longer is
+ * allowed.  It does what iqgpu_chain_reset does (batches in flight and a pending AGC verdict are resolved first, histories and
+ * the DC state are zeroed, a poisoned handle is cleared), drops pending FFT-block samples as well, sets the stream position to the
+ * closed form at first_frame - preroll_frames and runs the preroll through the ordinary per-call path into a buffer the chain
+ * owns.  Both variants return with the chain's stream idle.  Afterwards process / process_device / submit behave as if the chain
+ * had consumed frames [0, first_frame) of the stream (to the DC bound above).  first_frame == 0 without a preroll leaves a fresh
+ * chain.  When an argument is refused the chain is left reset (at frame 0).  IQGPU_EUNSUPPORTED for first_frame > 0 on a chain
+ * with the output AGC. */
+int    iqgpu_chain_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames);
+int    iqgpu_chain_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames);
 /* what the I/Q optimiser thread publishes (src/iq_correct.c:141-152 reads them once per chunk) */
 int    iqgpu_chain_set_iq_factors(iqgpu_chain *c, float mag, float phase);
 /* synchronises the chain's stream and reports the AGC state (agc.c keeps it in AppResources) */

@@ -74,6 +74,24 @@ def design_out_frames(frames_in, **kw):
     return int(n.value)
 
 
+def design_preroll_frames(**kw):
+    """input frames in front of a seam that a chain of this description has to see, output dropped, so that what it emits afterwards
+    is what the single stream emits (iqgpu_design_preroll_frames; no device needed)"""
+    d = make_desc(**kw)
+    n = C.c_uint64(0)
+    check(_lib.load().iqgpu_design_preroll_frames(C.byref(d), C.byref(n)))
+    return int(n.value)
+
+
+def design_out_frames_range(first_frame, frames_in, **kw):
+    """(out_first, frames_out): what ONE stream of this description emits while it consumes input frames
+    [first_frame, first_frame + frames_in) -- where a seamless shard's output goes and how long it is (no device needed)"""
+    d = make_desc(**kw)
+    first, n = C.c_uint64(0), C.c_uint64(0)
+    check(_lib.load().iqgpu_design_out_frames_range(C.byref(d), int(first_frame), int(frames_in), C.byref(first), C.byref(n)))
+    return int(first.value), int(n.value)
+
+
 def bind_thread_to_device(ordinal):
     """iqgpu_bind_thread_to_device: the calling thread onto the NUMA node of HIP device `ordinal` (sysfs only, no HIP call --
     meant to run before the first GPU call and before pinned buffers are allocated).  Returns (node, pci_bus_id, error): node -1
@@ -191,6 +209,18 @@ class Chain:
 
     def reset(self):
         check(self._lib.iqgpu_chain_reset(self._h))
+
+    def seek(self, first_frame, preroll_raw=None):
+        """puts the chain at frame first_frame of the stream: preroll_raw is a numpy array with the input frames that END at
+        first_frame (at least min(first_frame, design_preroll_frames) of them); what the chain emits afterwards is what one chain
+        emits behind frames [0, first_frame) (iqgpu_chain_seek)"""
+        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
+        n = raw.nbytes // self.in_bytes
+        check(self._lib.iqgpu_chain_seek(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n))
+
+    def seek_device(self, first_frame, d_preroll, preroll_frames):
+        """seek() with the preroll already in device memory of this chain's GPU (a device address as an int)"""
+        check(self._lib.iqgpu_chain_seek_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames)))
 
     def agc_state(self):
         """dict of the AGC fields the reference keeps in AppResources (synchronises)"""

@@ -189,6 +189,7 @@ struct iqgpu_chain {
     int ihist = 0;
     float *d_ihb = nullptr;
     DevBuf stage_in, stage_out;
+    DevBuf seek_sink;             // where iqgpu_chain_seek's warm-up run writes what it emits (dropped)
     // pipelined host entry point (iqgpu_chain_submit / _collect): kPipeSlots batches in flight.  H2D copies, kernels
     // (the chain's stream) and D2H copies each have their own stream; a batch moves to the next stage inside a later
     // submit / collect, once the host has seen the previous stage finish (no device-side event waits: see pipe_advance)
@@ -249,6 +250,14 @@ struct CallPlan {
 struct StreamPos { int rem = 0; uint64_t phi = 0; uint64_t fpending = 0; };
 CallPlan plan_call_at(const iqgpu_chain *c, const StreamPos &at, size_t frames_in);      // plan.cpp
 CallPlan plan_call(const iqgpu_chain *c, size_t frames_in);                               // ... from the chain's own position
+
+// ---- a chain at ANY stream position (seamless range sharding, plan.cpp): all five position words of the chain after `frames` input
+// frames of one stream from zero, and the outputs emitted in front of that position
+constexpr uint64_t kMaxStreamFrames = (uint64_t)1 << 39;      // (groups << 24) and (outputs * step) stay inside 64 bits up to here
+struct StreamAt { StreamPos pos; uint64_t n_out = 0; uint32_t nco_theta = 0, pnco_theta = 0; };
+StreamAt stream_at(const iqgpu_chain *c, uint64_t frames);
+// the chain's FIR memory in input frames (+ the DC blocker's warm-up): what a seek has to run in front of its position
+uint64_t seek_preroll_frames(const iqgpu_chain *c);
 
 // ---- profiling (process.cpp): HIP events around every launch while profiling is on ----
 hipEvent_t get_event(iqgpu_chain *c);

@@ -19,10 +19,17 @@
  * the NUMA node of its GPU before its first GPU call and before it allocates its pinned buffers (iqgpu_bind_thread_to_device),
  * and fails when the frames its chain produced differ from the count its output offset was planned with.
  *
+ * --shards N --seamless cuts ONE stream instead: shard starts are s * (frames / N) rounded down to a multiple of 4096 frames (every
+ * 2^S decimation group the ratio range allows and 16 bytes of every input format divide it, so each shard starts on a group and on
+ * an aligned word), every shard thread reads the iqgpu_design_preroll_frames frames in front of its start, puts its chain there with
+ * iqgpu_chain_seek and runs its usual chunk loop; output offsets come from iqgpu_design_out_frames_range.  The stitched file is the
+ * file --shards 1 writes (iqgpu.h: byte for byte without --dc-block, to 1e-6 of full scale with it; refused with an AGC option).
+ *
  * --synthetic FRAMES [--synthetic-hash SEED]: no input file.  Without a seed one constant pinned buffer is sent again and again
  * (the PCIe-inclusive rate of the path, nothing else); with one, shard s is the stream frame n -> splitmix64((SEED + s) * K + n)
  * of its own (iq_tool_amd/synth.py hash_stream restates it): configs[4] at its real size -- 8 x 2.5 G frames -- without 80 GB of
- * files, every range of every shard reproducible by the checker.
+ * files, every range of every shard reproducible by the checker.  With --seamless the job is ONE stream of seed SEED indexed by the
+ * global frame number.
  */
 #define _GNU_SOURCE
 #define _FILE_OFFSET_BITS 64
@@ -51,6 +58,7 @@ typedef struct {
     long long synthetic_frames;       /* > 0: no input file, reuse one pinned buffer (PCIe-inclusive rate) */
     int have_hash; unsigned long long hash_seed;   /* ... or generate shard s as the counter-hash stream of seed hash_seed + s */
     int no_bind;                      /* --no-numa-bind */
+    int seamless;                     /* --seamless: the shards continue ONE stream (iqgpu_chain_seek behind a preroll) */
     int dry;                          /* --dry-placement: plan, bind, size the buffers, report -- no GPU call */
     int quiet;
 } Options;
@@ -62,6 +70,7 @@ typedef struct {
     long long out_offset_bytes;       /* where this shard's output starts in the output file */
     long long frames_out;             /* result */
     long long planned_out;            /* iqgpu_design_out_frames(frames): what out_offset_bytes of the NEXT shard was computed from */
+    long long preroll_frames;         /* --seamless: input frames in front of first_frame the chain is warmed up on */
     int device, numa_node;            /* where it ran; -1 = the host does not say / not bound */
     char bus_id[64]; int cpus_allowed; long long pinned_bytes, hbm_bytes;   /* --dry-placement's report */
     double seconds, stream_seconds;   /* whole shard incl. set-up / copy-process-copy loop only */
@@ -125,6 +134,7 @@ static void *run_shard(void *arg)
     void *e_in[NBUF] = {0}, *e_k[NBUF] = {0}, *e_out[NBUF] = {0};
     size_t out_frames[NBUF] = {0};
     int in_fd = -1, out_fd = -1;
+    void *pre = NULL;
     const double t0 = now_s();
 
     /* this thread -- and with it the pages it touches first and the buffers it pins -- onto the socket of its GPU, before anything
@@ -175,6 +185,26 @@ static void *run_shard(void *arg)
         if (out_fd < 0) { snprintf(sh->err, sizeof(sh->err), "open %s: %s", o->out_path, strerror(errno)); sh->rc = -1; goto done; }
     }
 
+    if (o->seamless && sh->first_frame > 0) {
+        /* the frames in front of this shard's start, read like any other range of the stream, warm the chain's histories up; the
+         * chain then stands at first_frame of the ONE stream (iqgpu_chain_seek) */
+        const size_t np = (size_t)sh->preroll_frames, nb = np * ibps;
+        const long long from = sh->first_frame - sh->preroll_frames;
+        pre = malloc(nb ? nb : 1);
+        if (!pre) { snprintf(sh->err, sizeof(sh->err), "out of memory for a preroll of %zu frames", np); sh->rc = -1; goto done; }
+        if (in_fd >= 0) {
+            size_t got = 0;
+            while (got < nb) {
+                ssize_t r = pread(in_fd, (char *)pre + got, nb - got, from * (long long)ibps + (long long)got);
+                if (r <= 0) { snprintf(sh->err, sizeof(sh->err), "pread: %s", r < 0 ? strerror(errno) : "short file"); sh->rc = -1; goto done; }
+                got += (size_t)r;
+            }
+        } else if (o->have_hash) hash_fill(pre, d.in_format, ibps, o->hash_seed, from, np);
+        else memset(pre, 0x11, nb);
+        CK(iqgpu_chain_seek(chain, (uint64_t)sh->first_frame, pre, np));
+        free(pre); pre = NULL;
+    }
+
     long long done_in = 0, written = 0;
     const double t_loop = now_s();
     long long n_chunks = (sh->frames + (long long)chunk - 1) / (long long)chunk;
@@ -196,7 +226,8 @@ static void *run_shard(void *arg)
                 }
             } else if (o->have_hash) {
                 /* (buffer b is free: chunk i - 2, its last user, retired in the iteration before this one) */
-                hash_fill(h_in[b], d.in_format, ibps, o->hash_seed + (uint64_t)sh->shard, done_in, n);
+                if (o->seamless) hash_fill(h_in[b], d.in_format, ibps, o->hash_seed, sh->first_frame + done_in, n);
+                else hash_fill(h_in[b], d.in_format, ibps, o->hash_seed + (uint64_t)sh->shard, done_in, n);
             }
             CK(iqgpu_memcpy_h2d_async(d_in[b], h_in[b], n * ibps, s_in));
             CK(iqgpu_event_record(e_in[b], s_in));
@@ -228,6 +259,7 @@ static void *run_shard(void *arg)
         sh->rc = -1;
     }
 done:
+    free(pre);
     if (chain) iqgpu_chain_synchronize(chain);
     for (int b = 0; b < NBUF; b++) {
         if (e_in[b]) iqgpu_event_destroy(e_in[b]);
@@ -256,6 +288,7 @@ static void usage(void)
             "          [--iq-factors MAG:PHASE] [--no-resample] [--lowpass HZ] [--highpass HZ] [--pass-range A:B] [--stopband A:B]\n"
             "          [--transition-width HZ] [--attenuation DB] [--filter-taps N] [--filter-type fir|fft] [--filter-fft-size N]\n"
             "          [--chunk-frames N (default 4194304)] [--shards N] [--devices N] [--device D] [--synthetic FRAMES [--synthetic-hash SEED]]\n"
+            "          [--seamless (with --shards: the shards continue ONE stream -- the stitched output is what --shards 1 writes)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
             "          [--dry-placement (plan the shards, bind every shard thread, size its buffers, report as JSON: no GPU call)]\n");
 }
@@ -310,6 +343,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--synthetic-hash")) { o.have_hash = 1; o.hash_seed = strtoull(NEXT, NULL, 0); }
         else if (!strcmp(a, "--no-numa-bind")) o.no_bind = 1;
         else if (!strcmp(a, "--dry-placement")) o.dry = 1;
+        else if (!strcmp(a, "--seamless")) o.seamless = 1;
         else if (!strcmp(a, "--debug")) {              /* --debug name=value -> iqgpu_debug_set (the library reads no environment) */
             char kv[512]; snprintf(kv, sizeof(kv), "%s", NEXT);
             char *eq = strchr(kv, '=');
@@ -342,7 +376,23 @@ int main(int argc, char **argv)
         if (rc != IQGPU_OK) { fprintf(stderr, "%s\n", iqgpu_last_error()); return 1; }
     }
     long long per = total_frames / o.shards, off = 0;
-    for (int s = 0; s < o.shards; s++) {
+    uint64_t preroll = 0;
+    if (o.seamless && iqgpu_design_preroll_frames(&o.desc, &preroll) != IQGPU_OK) { fprintf(stderr, "--seamless: %s\n", iqgpu_last_error()); return 1; }
+    for (int s = 0; s < o.shards && o.seamless; s++) {
+        /* ONE stream cut at multiples of 4096 frames (the last shard takes the rest): place and count from the stream's closed form */
+        const long long next = (s == o.shards - 1) ? total_frames : ((long long)(s + 1) * per) & ~4095ll;
+        sh[s].opt = &o; sh[s].shard = s;
+        sh[s].first_frame = ((long long)s * per) & ~4095ll;
+        sh[s].frames = next - sh[s].first_frame;
+        sh[s].preroll_frames = sh[s].first_frame < (long long)preroll ? sh[s].first_frame : (long long)preroll;
+        uint64_t first_out = 0, nout = 0;
+        if (iqgpu_design_out_frames_range(&o.desc, (uint64_t)sh[s].first_frame, (uint64_t)sh[s].frames, &first_out, &nout) != IQGPU_OK) {
+            fprintf(stderr, "%s\n", iqgpu_last_error()); return 1;
+        }
+        sh[s].out_offset_bytes = (long long)first_out * (long long)obps;
+        sh[s].planned_out = (long long)nout;
+    }
+    for (int s = 0; s < o.shards && !o.seamless; s++) {
         sh[s].opt = &o; sh[s].shard = s;
         sh[s].first_frame = (long long)s * per;
         sh[s].frames = (s == o.shards - 1) ? total_frames - sh[s].first_frame : per;
@@ -373,25 +423,31 @@ int main(int argc, char **argv)
         /* one JSON line: the placement as planned; `distinct_devices` is what an N-shard job on N GPUs must show */
         int distinct = 0;
         for (int s = 0; s < o.shards; s++) { int seen = 0; for (int q = 0; q < s; q++) if (!strcmp(sh[q].bus_id, sh[s].bus_id) && sh[q].device == sh[s].device) seen = 1; if (!seen) distinct++; }
-        printf("{\"dry_placement\": true, \"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"distinct_devices\": %d, \"per_shard\": [",
-               total_frames, frames_out, o.shards, o.devices, distinct);
-        for (int s = 0; s < o.shards; s++)
+        printf("{\"dry_placement\": true, %s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"distinct_devices\": %d, \"per_shard\": [",
+               o.seamless ? "\"seamless\": true, " : "", total_frames, frames_out, o.shards, o.devices, distinct);
+        for (int s = 0; s < o.shards; s++) {
+            char pre_kv[64] = "";
+            if (o.seamless) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld", sh[s].preroll_frames);
             printf("%s{\"shard\": %d, \"device\": %d, \"pci_bus_id\": \"%s\", \"numa_node\": %d, \"cpus_allowed\": %d, \"first_frame\": %lld, \"frames_in\": %lld, \"planned_out\": %lld, "
-                   "\"out_offset_bytes\": %lld, \"pinned_bytes\": %lld, \"hbm_bytes\": %lld}", s ? ", " : "", s, sh[s].device, sh[s].bus_id, sh[s].numa_node, sh[s].cpus_allowed,
-                   sh[s].first_frame, sh[s].frames, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].pinned_bytes, sh[s].hbm_bytes);
+                   "\"out_offset_bytes\": %lld, \"pinned_bytes\": %lld, \"hbm_bytes\": %lld%s}", s ? ", " : "", s, sh[s].device, sh[s].bus_id, sh[s].numa_node, sh[s].cpus_allowed,
+                   sh[s].first_frame, sh[s].frames, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].pinned_bytes, sh[s].hbm_bytes, pre_kv);
+        }
         printf("]}\n");
         free(th); free(sh);
         return rc;
     }
     if (!o.quiet) {
-        printf("{\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"seconds\": %.6f, \"msps_end_to_end\": %.3f, \"stream_seconds\": %.6f, \"msps_streaming\": %.3f, "
+        printf("{%s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"seconds\": %.6f, \"msps_end_to_end\": %.3f, \"stream_seconds\": %.6f, \"msps_streaming\": %.3f, "
                "\"h2d_GBs\": %.3f, \"d2h_GBs\": %.3f, \"in_bytes_per_frame\": %zu, \"out_bytes_per_frame\": %zu, \"input\": \"%s\", \"per_shard\": [",
-               total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
+               o.seamless ? "\"seamless\": true, " : "", total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
                stream_s > 0 ? (double)total_frames * (double)ibps / stream_s / 1e9 : 0.0, stream_s > 0 ? (double)frames_out * (double)obps / stream_s / 1e9 : 0.0, ibps, obps,
                o.synthetic_frames <= 0 ? "file" : o.have_hash ? "synthetic-hash" : "synthetic-constant");
-        for (int s = 0; s < o.shards; s++)
-            printf("%s{\"shard\": %d, \"device\": %d, \"numa_node\": %d, \"first_frame\": %lld, \"frames_in\": %lld, \"frames_out\": %lld, \"planned_out\": %lld, \"out_offset_bytes\": %lld, \"seconds\": %.6f}",
-                   s ? ", " : "", s, sh[s].device, sh[s].numa_node, sh[s].first_frame, sh[s].frames, sh[s].frames_out, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].stream_seconds);
+        for (int s = 0; s < o.shards; s++) {
+            char pre_kv[64] = "";
+            if (o.seamless) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld", sh[s].preroll_frames);
+            printf("%s{\"shard\": %d, \"device\": %d, \"numa_node\": %d, \"first_frame\": %lld, \"frames_in\": %lld, \"frames_out\": %lld, \"planned_out\": %lld, \"out_offset_bytes\": %lld, \"seconds\": %.6f%s}",
+                   s ? ", " : "", s, sh[s].device, sh[s].numa_node, sh[s].first_frame, sh[s].frames, sh[s].frames_out, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].stream_seconds, pre_kv);
+        }
         printf("]}\n");
     }
     free(th); free(sh);

@@ -74,6 +74,92 @@ extern "C" int iqgpu_design_out_frames(const iqgpu_chain_desc *d, size_t frames_
     return rc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// seamless range sharding: the stream position as a closed form of the frames consumed, and the chain's memory in input frames
+// ------------------------------------------------------------------------------------------------
+StreamAt stream_at(const iqgpu_chain *c, uint64_t frames)
+{
+    StreamAt at;
+    const CallPlan p = plan_call_at(c, StreamPos{}, (size_t)frames);
+    at.pos.rem = p.rem_next; at.pos.phi = p.phi_next;
+    at.pos.fpending = (c->fp.enabled && c->fp.block) ? p.fpending_next : 0;
+    at.n_out = (uint64_t)p.n_emit;
+    at.nco_theta = (uint32_t)frames * c->nco_dtheta;              // (mod 2^32, as the calls advance it)
+    at.pnco_theta = (uint32_t)at.n_out * c->nco_dtheta;
+    return at;
+}
+
+// Input frames a chain has to have seen for every history it keeps to hold stream data only.  Derived from the plans:
+//   decimating front    d_hist holds the last hist_cap processed input frames (the warm-up tiles of every half-band level and of
+//                       the polyphase window, plus the open group); behind k_cascade d_hist2 holds hist2_cap samples at rate / 2^(S-1),
+//                       each of which needs the casc_warm warm-up tiles of the first S-1 stages in front of it
+//   r >= 1              the front is pointwise; k_interp keeps ihist samples at the input rate
+//   user filter         L - 1 taps of history, and for the FFT kind one block more (the samples pending at the position are then
+//                       resampler outputs made from stream data) -- at the input rate in front of the resampler or without one, in
+//                       resampler outputs behind it: n outputs span ceil(n step / 2^24) + 1 groups of 2^S frames
+//   dc blocker          ceil(ln(1e6) / alpha) frames in front of all that: the state error decays as (1 - alpha)^n and reaches the
+//                       output as alpha * e with |e| <= max|x| / alpha -- 1e-6 of full scale after that many frames (iqgpu.h)
+uint64_t seek_preroll_frames(const iqgpu_chain *c)
+{
+    uint64_t n = 0;
+    if (c->decim) {
+        n = (uint64_t)c->hist_cap;
+        if (c->cascade) {
+            const uint64_t via_mid = ((uint64_t)c->hist2_cap << (c->S - 1)) + (uint64_t)c->casc_warm * kWTile + (uint64_t)c->D;
+            if (via_mid > n) n = via_mid;
+        }
+    }
+    if (c->late) n = (uint64_t)c->ihist;
+    if (c->fp.enabled) {
+        uint64_t f = (uint64_t)(c->fp.taps.size() - 1) + (uint64_t)c->fp.block;
+        if (c->decim) f = (((f * (uint64_t)c->rp.step + (((uint64_t)1 << 24) - 1)) >> 24) + 1) << c->S;
+        n += f;
+    }
+    if (c->dc) n += (uint64_t)std::ceil(std::log(1e6) / (double)c->dc_alpha);
+    return n;
+}
+
+// design of a throw-away chain for the two calls below: create's validation first, then what seamless sharding cannot do
+static int design_for_seek(iqgpu_chain *c, const iqgpu_chain_desc *d)
+{
+    const int rc = design_chain(c, d);
+    if (rc != IQGPU_OK) return rc;
+    if (c->agc) return fail(IQGPU_EUNSUPPORTED, "seamless sharding does not cover the output AGC: its state depends on the whole stream "
+                                                "in front of a position, not on a bounded warm-up");
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_design_preroll_frames(const iqgpu_chain_desc *d, uint64_t *frames)
+{
+    if (!d || !frames) return fail(IQGPU_EINVAL, "iqgpu_design_preroll_frames: NULL argument");
+    *frames = 0;
+    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
+    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
+    const int rc = design_for_seek(c, d);
+    if (rc == IQGPU_OK) *frames = seek_preroll_frames(c);
+    delete c;
+    return rc;
+}
+
+extern "C" int iqgpu_design_out_frames_range(const iqgpu_chain_desc *d, uint64_t first_frame, uint64_t frames_in,
+                                             uint64_t *out_first, uint64_t *frames_out)
+{
+    if (!d || !out_first || !frames_out) return fail(IQGPU_EINVAL, "iqgpu_design_out_frames_range: NULL argument");
+    *out_first = 0; *frames_out = 0;
+    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
+    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
+    int rc = design_for_seek(c, d);
+    if (rc == IQGPU_OK && (first_frame > kMaxStreamFrames || frames_in > kMaxStreamFrames - first_frame))
+        rc = fail(IQGPU_EINVAL, "stream position %llu + %llu frames is beyond 2^39 frames", (unsigned long long)first_frame,
+                  (unsigned long long)frames_in);
+    if (rc == IQGPU_OK) {
+        *out_first = stream_at(c, first_frame).n_out;
+        *frames_out = stream_at(c, first_frame + frames_in).n_out - *out_first;
+    }
+    delete c;
+    return rc;
+}
+
 extern "C" size_t iqgpu_chain_max_out_frames(const iqgpu_chain *c, size_t frames_in)
 {
     if (!c) return 0;

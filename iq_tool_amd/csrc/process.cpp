@@ -488,3 +488,68 @@ extern "C" int iqgpu_chain_process(iqgpu_chain *c, const void *raw_in, size_t fr
     *frames_out = produced;
     return IQGPU_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// iqgpu_chain_seek: the chain at stream frame first_frame -- reset, the closed-form position preroll_frames earlier, and the
+// preroll through the ordinary per-call path with its output dropped (seamless range sharding, iqgpu.h)
+// ------------------------------------------------------------------------------------------------
+static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, bool on_device)
+{
+    if (!c) return fail(IQGPU_EINVAL, "iqgpu_chain_seek: NULL chain");
+    // what iqgpu_chain_reset does comes first: batches in flight and a pending verdict resolved, histories and dc state zeroed,
+    // the poison cleared -- a refused argument below leaves the chain reset
+    int rc = iqgpu_chain_reset(c); if (rc) return rc;
+    c->fpending = 0;                                          // (reset keeps the FFT remainder queued: a seek starts a stream)
+    if (first_frame > kMaxStreamFrames) return fail(IQGPU_EINVAL, "iqgpu_chain_seek: frame %llu is beyond 2^39 frames",
+        (unsigned long long)first_frame);
+    if ((uint64_t)preroll_frames > first_frame) return fail(IQGPU_EINVAL, "iqgpu_chain_seek: a preroll of %zu frames would start in front of "
+        "frame 0 (first_frame %llu)", preroll_frames, (unsigned long long)first_frame);
+    if (first_frame == 0) return IQGPU_OK;                    // a fresh chain
+    if (c->agc) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
+        "not on a bounded warm-up");
+    const uint64_t memory = seek_preroll_frames(c), need = first_frame < memory ? first_frame : memory;
+    if ((uint64_t)preroll_frames < need) return fail(IQGPU_EINVAL, "iqgpu_chain_seek: preroll of %zu frames is shorter than the %llu "
+        "this chain needs at frame %llu", preroll_frames, (unsigned long long)need, (unsigned long long)first_frame);
+    if (preroll_frames && !preroll) return fail(IQGPU_EINVAL, "iqgpu_chain_seek: NULL preroll");
+
+    const StreamAt from = stream_at(c, first_frame - (uint64_t)preroll_frames);
+    if (c->fp.enabled) {
+        // [L-1 history][pending]: zeros stand for the samples in front of the warm-up
+        const size_t front = c->fp.taps.size() - 1 + (size_t)from.pos.fpending;
+        rc = c->fbuf[c->fcur].ensure((front + 1) * sizeof(cf2)); if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(c->fbuf[c->fcur].p, 0, front * sizeof(cf2), c->stream));
+    }
+    c->rem = from.pos.rem; c->phi = from.pos.phi; c->fpending = from.pos.fpending;
+    c->nco_theta = from.nco_theta; c->pnco_theta = from.pnco_theta;
+
+    if (preroll_frames) {
+        const size_t ibps = bytes_per_frame(c->desc.in_format), obps = bytes_per_frame(c->desc.out_format);
+        const void *d_in = preroll;
+        if (!on_device) {
+            rc = c->stage_in.ensure(preroll_frames * ibps); if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(c->stage_in.p, preroll, preroll_frames * ibps, hipMemcpyHostToDevice, c->stream));
+            d_in = c->stage_in.p;
+        }
+        rc = c->seek_sink.ensure((size_t)plan_call(c, preroll_frames).n_emit * obps + 16); if (rc) return rc;
+        size_t dropped = 0;
+        rc = process_device_impl(c, d_in, preroll_frames, c->seek_sink.p, c->seek_sink.cap, &dropped); if (rc) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    // the warm-up has walked the position forward call-wise: it has to stand on the closed form at first_frame
+    const StreamAt to = stream_at(c, first_frame);
+    if (c->rem != to.pos.rem || c->phi != to.pos.phi || c->fpending != to.pos.fpending || c->nco_theta != to.nco_theta ||
+        c->pnco_theta != to.pnco_theta) {
+        c->poisoned = true;
+        return fail(IQGPU_EINVAL, "internal: the position behind the preroll is not the closed form at frame %llu", (unsigned long long)first_frame);
+    }
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_chain_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames)
+{
+    return seek_impl(c, first_frame, preroll, preroll_frames, false);
+}
+extern "C" int iqgpu_chain_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames)
+{
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, true);
+}

@@ -82,7 +82,8 @@ def agc_envelope_signal(n, rate_hz, seed):
 
 def hash_stream(n, seed, fmt="cs16", first=0):
     """Frames [first, first + n) of the counter-hash stream the harness generates with `--synthetic FRAMES --synthetic-hash SEED`
-    (iq_tool_amd/csrc/harness/iqgpu_run.c hash_fill; shard s of a run uses seed SEED + s and counts from its own frame 0):
+    (iq_tool_amd/csrc/harness/iqgpu_run.c hash_fill; shard s of a run uses seed SEED + s and counts from its own frame 0; a --seamless run is ONE stream of seed SEED
+    counted from the job's frame 0):
     frame k -> splitmix64(seed * 0xD1342543DE82EF95 + k); cs16 takes the two low 16-bit words as signed values >> 2 (quarter
     scale), every other integer format the low bytes of the hash as they are.  Any range of a 2.5 G-frame shard is reproducible
     without the shard."""
