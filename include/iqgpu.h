@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define IQGPU_ABI_VERSION 7
+#define IQGPU_ABI_VERSION 8
 
 /* Sample formats: numerically equal to the reference's format_t (include/common_types.h:33-37) */
 enum {
@@ -61,7 +61,9 @@ enum {
     IQGPU_ECAPACITY = -8,   /* out_capacity_bytes too small for this call */
     IQGPU_EHIP = -9,        /* a HIP runtime call failed */
     IQGPU_EUNSUPPORTED = -10/* the placement calls when a *_VISIBLE_DEVICES list is not plain indices; iqgpu_chain_seek and the two    */
-                            /* seamless-sharding design calls for a chain with the output AGC (no finite warm-up bounds its state) */
+                            /* seamless-sharding design calls for a chain with the output AGC (no finite warm-up bounds its state:     */
+                            /* the digital profile goes through iqgpu_chain_measure / _agc_advance / _seek_agc instead); those three  */
+                            /* v8 calls for the profiles dx / local and for IQGPU_AGC_CLOCK_WALL                                       */
 };
 
 typedef struct iqgpu_chain iqgpu_chain; /* opaque, like resampler_t (include/resampler.h:25-26) */
@@ -249,6 +251,56 @@ int    iqgpu_chain_reset(iqgpu_chain *c);
  * with the output AGC. */
 int    iqgpu_chain_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames);
 int    iqgpu_chain_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames);
+/* ---- seamless range sharding of chains with the DIGITAL output AGC (ABI v8): two passes ----
+ * The calls above refuse a chain with the output AGC, and keep doing so: its state at a position is a function of the whole stream in
+ * front of it.  For the digital profile that function factors.  What agc_apply measures of a chunk is the chunk's peak max |x| BEFORE
+ * the gain, which does not depend on the AGC state; the state (iqgpu_agc_state) then advances chunk by chunk as a function of
+ * (state, that chunk's peak, that chunk's output length) alone, with IQGPU_AGC_CLOCK_SAMPLES; and the gain of a chunk follows from
+ * the state in front of it and its own peak.  So a capture of F frames is cut over N chains (one per GPU) like this, and the
+ * stitched output is, byte for byte, what ONE chain writes (to the DC bound above on chains with the DC blocker):
+ *   0. Placement does not depend on the AGC.  With `na` = a copy of the description with agc_enable = 0:
+ *      P = iqgpu_design_preroll_frames(&na), and iqgpu_design_out_frames_range(&na, first, frames, ...) places every range's output.
+ *      Cut points are multiples of lcm(agc_chunk_frames, the frames per process call) -- the digital AGC works on the chunks of each
+ *      call, so every call of every chain has to lie on the single stream's call and chunk grid -- and of 4096 (see above).
+ *   1. Measure (all ranges but the last, in parallel): iqgpu_chain_seek_agc(c, first, preroll, P', NULL) with P' = min(first, P),
+ *      then iqgpu_chain_measure over the range in the calls the single stream would make.  Every call yields one iqgpu_agc_chunk row
+ *      per chunk; keep them in order.
+ *   2. Walk (any one chain, a fraction of a second): st = iqgpu_chain_agc_initial_state; for every range s in order:
+ *      entry[s] = st, then iqgpu_chain_agc_advance(c, &st, rows of range s, n, NULL).
+ *   3. Process (all ranges in parallel): iqgpu_chain_seek_agc(c, first, preroll, P', &entry[s]), then the ordinary process /
+ *      process_device / submit loop over the range in the same calls as pass 1.
+ * iqgpu_chain_measure, _agc_advance and _seek_agc: IQGPU_EINVAL on a chain without the output AGC, IQGPU_EUNSUPPORTED for the profiles dx / local (agc_crcf's
+ * loop forgets its past only approximately: no table of per-chunk figures carries its state exactly) and for IQGPU_AGC_CLOCK_WALL
+ * (a wall clock has no value at a stream position). */
+typedef struct {
+    double   peak2;                     /* max re^2 + im^2 (exact products and sum, in double) over the chunk's frames in front of the AGC */
+    uint32_t frames_out;                /* how many frames that is (0: an empty chunk, which never reaches agc_apply) */
+    uint32_t reserved;
+} iqgpu_agc_chunk;
+/* The chain consumes the frames exactly as iqgpu_chain_process would (position, histories, NCO phases, FFT remainder and DC state all
+ * advance), emits nothing, leaves the AGC state alone, and reports one row per agc_chunk_frames-sized chunk of THIS call, cut from
+ * its first frame like process(): ceil(frames_in / agc_chunk_frames) rows; IQGPU_ECAPACITY when cap is below that.  On the device: the
+ * chain's fastest unfused kernels, one reduction pass over their cf32 output, one copy of the rows to the host -- no scan, no gain,
+ * no pack, no samples to the host.  Both variants return with the chain's stream idle and the rows in `rows` (host memory). */
+int    iqgpu_chain_measure(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows);
+int    iqgpu_chain_measure_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows);
+/* agc_apply's state machine over a table: *st is advanced over rows[0 .. n) (rows with frames_out == 0 are skipped, as empty chunks
+ * never reach agc_apply); gains, if not NULL, receives the gain every row is multiplied with (n floats).  It runs the kernel that
+ * walks the chunks of an ordinary call, so the state and the gains are the ordinary path's bit for bit, however the rows are grouped
+ * into calls.  Uses the chain's target level, rate and device; does not touch the chain's own AGC state or stream position.
+ * Rows of iqgpu_chain_measure always qualify; a table built by hand must keep peak2 >= 0 (no NaN) and the frames_out of any 64
+ * consecutive rows below 2^31 in sum (the walk adds 64 lengths in 32 bits: the bound iqgpu_chain_create puts on agc_chunk_frames),
+ * else IQGPU_EINVAL. */
+int    iqgpu_chain_agc_advance(iqgpu_chain *c, iqgpu_agc_state *st, const iqgpu_agc_chunk *rows, size_t n, float *gains);
+/* counterpart of iqgpu_chain_get_agc_state for a fresh stream: what agc_create / agc_reset leave (no device call) */
+int    iqgpu_chain_agc_initial_state(const iqgpu_chain *c, iqgpu_agc_state *st);
+/* iqgpu_chain_seek for chains with the digital AGC; arguments, preroll length rules and what is reset are iqgpu_chain_seek's.  The
+ * preroll runs with the AGC out of the way: nothing it emits is kept and the AGC state is not advanced by it.  entry != NULL: the
+ * chain then carries *entry as its AGC state (on the device and in every host mirror of it), as if it had processed
+ * [0, first_frame).  entry == NULL: the AGC state is the fresh one -- what a measuring chain needs, which never reads it. */
+int    iqgpu_chain_seek_agc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, const iqgpu_agc_state *entry);
+int    iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
+                                   const iqgpu_agc_state *entry);
 /* what the I/Q optimiser thread publishes (src/iq_correct.c:141-152 reads them once per chunk) */
 int    iqgpu_chain_set_iq_factors(iqgpu_chain *c, float mag, float phase);
 /* synchronises the chain's stream and reports the AGC state (agc.c keeps it in AppResources) */

@@ -42,6 +42,11 @@ class AgcState(C.Structure):
                 ("reserved", C.c_int), ("last_strong_peak_time", C.c_double), ("samples_seen", C.c_uint64)]
 
 
+class AgcChunk(C.Structure):
+    """iqgpu_agc_chunk: one row of iqgpu_chain_measure's table"""
+    _fields_ = [("peak2", C.c_double), ("frames_out", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ChainInfo(C.Structure):
     _fields_ = [("ratio", C.c_float), ("interp", C.c_int), ("num_halfband_stages", C.c_int),
                 ("stage_m", C.c_int * 16), ("rate_arb", C.c_float), ("arb_step", C.c_uint32),
@@ -110,6 +115,12 @@ SYMBOLS = [
     ("iqgpu_chain_reset", C.c_int, [_vp]),
     ("iqgpu_chain_seek", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
     ("iqgpu_chain_seek_device", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
+    ("iqgpu_chain_measure", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_chain_measure_device", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_chain_agc_advance", C.c_int, [_vp, C.POINTER(AgcState), _vp, _sz, _vp]),
+    ("iqgpu_chain_agc_initial_state", C.c_int, [_vp, C.POINTER(AgcState)]),
+    ("iqgpu_chain_seek_agc", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(AgcState)]),
+    ("iqgpu_chain_seek_agc_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(AgcState)]),
     ("iqgpu_chain_get_agc_state", C.c_int, [_vp, C.POINTER(AgcState)]),
     ("iqgpu_chain_set_iq_factors", C.c_int, [_vp, C.c_float, C.c_float]),
     ("iqgpu_chain_max_out_frames", _sz, [_vp, _sz]),
@@ -189,7 +200,7 @@ def load():
 DEBUG_NAMES = ("force_generic", "no_fast", "agc_nofuse", "no_raw0", "no_kt", "fft_no_r16", "no_fat", "force_fat", "fat", "mid8",
                "no_s2", "no_fused_move", "no_p0", "no_casc2", "no_mid_8bit", "fuse_filter", "tap_fold", "steal", "steal_min",
                "steal_rounds", "steal_stride", "steal_lanes", "run_weights", "cus", "fft_log2n", "fft_threads", "fft_geometry", "casc2_min_run",
-               "sysfs_root", "nco_hold")
+               "sysfs_root", "nco_hold", "measure_route")
 _forwarded = set()      # names whose switch apply_debug_env set from the environment and has not cleared since
 
 

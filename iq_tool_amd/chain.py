@@ -11,6 +11,8 @@ from ._lib import (BYTES_PER_FRAME, FILTER, FILTER_IMPL, FMT, AgcState, ChainDes
                    IqgpuError, Profile, check)
 
 AGC_PROFILE = {"off": 0, "dx": 1, "local": 2, "digital": 3}
+# iqgpu_agc_chunk as a numpy record: what Chain.measure returns and Chain.agc_advance takes
+AGC_ROW = np.dtype([("peak2", np.float64), ("frames_out", np.uint32), ("reserved", np.uint32)])
 
 _NP_VIEW = {8: np.uint8, 9: np.int8, 10: np.uint16, 11: np.int16, 16: np.int16, 12: np.uint8,
             13: np.uint32, 14: np.int32, 15: np.float32}
@@ -221,6 +223,62 @@ class Chain:
     def seek_device(self, first_frame, d_preroll, preroll_frames):
         """seek() with the preroll already in device memory of this chain's GPU (a device address as an int)"""
         check(self._lib.iqgpu_chain_seek_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames)))
+
+    # ---- seamless sharding of digital-AGC chains: measure, walk, seek with the walked state (include/iqgpu.h, ABI v8) ----
+    def measure(self, raw):
+        """consumes raw exactly as process() would, emits nothing, leaves the AGC state alone; returns one AGC_ROW record per
+        agc_chunk_frames-sized chunk of this call: the peak (squared, double) in front of the gain and the chunk's frames"""
+        raw = np.ascontiguousarray(raw)
+        n = raw.nbytes // self.in_bytes
+        chunk = int(self.desc.agc_chunk_frames) or 16384
+        rows = np.zeros(-(-n // chunk), AGC_ROW)
+        got = C.c_size_t(0)
+        check(self._lib.iqgpu_chain_measure(self._h, raw.ctypes.data_as(C.c_void_p) if n else None, n,
+                                            rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
+        return rows[:got.value]
+
+    def measure_device(self, d_in, frames_in):
+        """measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
+        chunk = int(self.desc.agc_chunk_frames) or 16384
+        rows = np.zeros(-(-int(frames_in) // chunk), AGC_ROW)
+        got = C.c_size_t(0)
+        check(self._lib.iqgpu_chain_measure_device(self._h, C.c_void_p(d_in), int(frames_in), rows.ctypes.data_as(C.c_void_p), rows.size,
+                                                   C.byref(got)))
+        return rows[:got.value]
+
+    def agc_initial_state(self):
+        """the AGC state of a fresh stream as an AgcState (what agc_advance and seek_agc take)"""
+        st = AgcState()
+        check(self._lib.iqgpu_chain_agc_initial_state(self._h, C.byref(st)))
+        return st
+
+    def agc_advance(self, state, rows, gains=False):
+        """agc_apply's state machine over a table of measure() rows: returns the AgcState behind them (state itself is not
+        changed), or (state, gains) with the gain every row is multiplied with"""
+        rows = np.ascontiguousarray(rows, AGC_ROW)
+        st = AgcState.from_buffer_copy(bytes(state))
+        g = np.zeros(rows.size, np.float32) if gains else None
+        check(self._lib.iqgpu_chain_agc_advance(self._h, C.byref(st), rows.ctypes.data_as(C.c_void_p) if rows.size else None, rows.size,
+                                                g.ctypes.data_as(C.c_void_p) if gains and rows.size else None))
+        return (st, g) if gains else st
+
+    def seek_agc(self, first_frame, preroll_raw=None, entry=None):
+        """seek() for a chain with the digital AGC: the preroll runs with the AGC out of the way, then the chain carries `entry`
+        (an AgcState from agc_advance) as its AGC state; entry None leaves the fresh state, which is all a measuring chain needs"""
+        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
+        n = raw.nbytes // self.in_bytes
+        check(self._lib.iqgpu_chain_seek_agc(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n,
+                                             C.byref(entry) if entry is not None else None))
+
+    def seek_agc_device(self, first_frame, d_preroll, preroll_frames, entry=None):
+        check(self._lib.iqgpu_chain_seek_agc_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames),
+                                                    C.byref(entry) if entry is not None else None))
+
+    def agc_state_raw(self):
+        """the chain's AGC state as an AgcState structure: every field with its bits (synchronises)"""
+        st = AgcState()
+        check(self._lib.iqgpu_chain_get_agc_state(self._h, C.byref(st)))
+        return st
 
     def agc_state(self):
         """dict of the AGC fields the reference keeps in AppResources (synchronises)"""

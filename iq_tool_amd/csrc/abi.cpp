@@ -49,6 +49,7 @@ static const struct { const char *name; void (*parse)(DebugSwitches &, const cha
     {"fft_threads", [](DebugSwitches &s, const char *v) { s.fft_threads = atoi(v); }},
     {"fft_geometry", [](DebugSwitches &s, const char *v) { s.fft_keep_geometry = !strcmp(v, "keep"); }},
     {"casc2_min_run", [](DebugSwitches &s, const char *v) { const int x = atoi(v); s.casc2_min_run = x > 0 ? x : 0; }},
+    {"measure_route", [](DebugSwitches &s, const char *v) { s.measure_route = !strcmp(v, "s1") ? 1 : !strcmp(v, "unfused") ? 0 : -1; }},
     {"nco_hold", [](DebugSwitches &s, const char *v) { s.nco_hold = v[0] != '0'; }},
     {"sysfs_root", nullptr},                                                              // topology.cpp
 };
@@ -151,6 +152,7 @@ static void free_device_state(iqgpu_chain *c)
     if (c->d_ihb) (void)hipFree(c->d_ihb);
     if (c->d_agc_state) (void)hipFree(c->d_agc_state);
     c->abuf.release(); c->agc_peak.release(); c->agc_gain.release(); c->agc_peak_b.release(); c->agc_hist.release();
+    c->agc_rows.release(); c->agc_walk.release(); c->agc_scratch.release();
     if (c->d_agc_flag) (void)hipFree(c->d_agc_flag);
     if (c->h_agc_verdict) (void)hipHostFree((void *)c->h_agc_verdict);
     if (c->d_twiddle) (void)hipFree(c->d_twiddle);

@@ -8,6 +8,7 @@
 //                phase = speculate "gain unchanged" over 64 chunks at a time and serialise only at the
 //                chunks that ratchet or creep,
 //   k_agc_apply  x * gain[chunk] -> pack.
+// k_agc_measure is k_agc_peak on its own for the measure pass of seamless sharding: peak and length of every chunk into one row.
 // Chunk boundaries in the output come from agc_out_end() (kernels.hpp), the same closed form the
 // host uses for frames_out.
 #include <hip/hip_runtime.h>
@@ -80,6 +81,19 @@ __device__ __forceinline__ float wave_scan_max(float x)      // x >= 0
     v = max(v, IQGPU_DPP(v, 0x118, 0xf)); v = max(v, IQGPU_DPP(v, 0x142, 0xa)); v = max(v, IQGPU_DPP(v, 0x143, 0xc));
     return __int_as_float(v);
 }
+// maximum of a 64-bit pattern over the wave, valid in lane 63: the same ladder on both halves (lanes a step does not reach read 0,
+// the neutral element)
+#define IQGPU_DPP64(v, ctrl, rmask) \
+    (((unsigned long long)(unsigned)IQGPU_DPP((int)(unsigned)((v) >> 32), ctrl, rmask) << 32) | (unsigned)IQGPU_DPP((int)(unsigned)(v), ctrl, rmask))
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
+{
+    unsigned long long o;
+    o = IQGPU_DPP64(v, 0x111, 0xf); v = o > v ? o : v; o = IQGPU_DPP64(v, 0x112, 0xf); v = o > v ? o : v;
+    o = IQGPU_DPP64(v, 0x114, 0xf); v = o > v ? o : v; o = IQGPU_DPP64(v, 0x118, 0xf); v = o > v ? o : v;
+    o = IQGPU_DPP64(v, 0x142, 0xa); v = o > v ? o : v; o = IQGPU_DPP64(v, 0x143, 0xc); v = o > v ? o : v;
+    return v;
+}
+#undef IQGPU_DPP64
 #undef IQGPU_DPP
 
 __global__ __launch_bounds__(64) void k_agc_scan(const AgcArgs a)
@@ -167,6 +181,90 @@ __global__ __launch_bounds__(64) void k_agc_scan(const AgcArgs a)
         end_prev = e_last;
     }
     if (lane == 0) *a.state = st;
+}
+
+// ---- the measure pass of seamless sharding (iqgpu_chain_measure, iqgpu.h) --------------------------------------------------
+// What agc_apply MEASURES of every chunk of a call -- the peak in front of the gain, and how many frames -- in one pass over the
+// cf32 stream the chain's last stage left in abuf: k_agc_peak's reduction (exact products and sum in double, a maximum: the order
+// of a maximum does not reach the bits) over the same (chunk, split) grid, with the chunk length into the same row.  Two frames
+// per 16-byte load, four loads in flight per lane; the wave's maximum on the data-parallel-primitive path (non-negative doubles
+// order like their bit patterns: wave_max_u64 next to the scans above), one atomic per wave and chunk.
+__device__ __forceinline__ double agc_p2(float re, float im) { return (double)re * (double)re + (double)im * (double)im; }
+
+__global__ __launch_bounds__(kThreads) void k_agc_measure(const AgcMeasureArgs a)
+{
+    const int64_t n_items = (int64_t)a.geom.n_chunks * a.splits;
+    for (int64_t w = blockIdx.x; w < n_items; w += gridDim.x) {
+        const int c = (int)(w / a.splits), sy = (int)(w % a.splits);
+        const int64_t b = agc_out_end(a.geom, (int64_t)c - 1), e = agc_out_end(a.geom, c);
+        const int64_t len = e - b;
+        if (sy == 0 && threadIdx.x == 0) a.rows[c].frames_out = (uint32_t)(len > 0 ? len : 0);
+        if (len <= 0) continue;
+        const int64_t per = (len + a.splits - 1) / a.splits;
+        const int64_t lo = b + (int64_t)sy * per;
+        int64_t hi = lo + per; if (hi > e) hi = e;
+        if (lo >= hi) continue;
+        // [lo, hi) = an odd frame in front, pairs of frames on 16-byte words, an odd frame behind
+        const int64_t lo2 = (lo + 1) & ~(int64_t)1, hi2 = hi & ~(int64_t)1;
+        double m = 0.0;
+        if (threadIdx.x == 0 && lo < lo2) { const cf2 v = a.x[lo]; m = agc_p2(v.x, v.y); }
+        if (threadIdx.x == 1 && hi2 < hi) { const cf2 v = a.x[hi - 1]; m = agc_p2(v.x, v.y); }
+        const float4 *x4 = reinterpret_cast<const float4 *>(a.x + lo2);
+        const int64_t n4 = hi2 > lo2 ? (hi2 - lo2) >> 1 : 0;
+        int64_t i = threadIdx.x;
+        for (; i + 3 * kThreads < n4; i += 4 * kThreads) {
+            float4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = x4[i + k * kThreads];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const double d0 = agc_p2(v[k].x, v[k].y), d1 = agc_p2(v[k].z, v[k].w);
+                m = d0 > m ? d0 : m; m = d1 > m ? d1 : m;
+            }
+        }
+        for (; i < n4; i += kThreads) {
+            const float4 v = x4[i];
+            const double d0 = agc_p2(v.x, v.y), d1 = agc_p2(v.z, v.w);
+            m = d0 > m ? d0 : m; m = d1 > m ? d1 : m;
+        }
+        const unsigned long long mw = wave_max_u64((unsigned long long)__double_as_longlong(m));
+        if ((threadIdx.x & 63) == 63 && mw != 0ull) atomicMax(&a.rows[c].peak2, mw);
+    }
+}
+
+// ... and where k_front_s1<.., AGC> has left the exact peaks in its own array: the rows from that array and the chunk map
+__global__ __launch_bounds__(256) void k_agc_rows(const AgcMeasureArgs a)
+{
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= a.geom.n_chunks) return;
+    const int64_t len = agc_out_end(a.geom, c) - agc_out_end(a.geom, (int64_t)c - 1);
+    AgcRow r;
+    r.peak2 = len > 0 ? a.peak_in[c] : 0ull; r.frames_out = (uint32_t)(len > 0 ? len : 0); r.reserved = 0u;
+    a.rows[c] = r;
+    a.peak_in[c] = 0ull;
+}
+
+hipError_t launch_agc_measure(const AgcMeasureArgs &a, hipStream_t s)
+{
+    if (a.geom.n_chunks <= 0) return hipSuccess;
+    if (!a.x) {
+        hipLaunchKernelGGL(k_agc_rows, dim3((unsigned)((a.geom.n_chunks + 255) / 256)), dim3(256), 0, s, a);
+        return hipGetLastError();
+    }
+    const hipError_t e = hipMemsetAsync(a.rows, 0, (size_t)a.geom.n_chunks * sizeof(AgcRow), s);
+    if (e != hipSuccess) return e;
+    const int64_t n_items = (int64_t)a.geom.n_chunks * a.splits;
+    const unsigned grid = (unsigned)(n_items < (int64_t)(1 << 20) ? n_items : (int64_t)(1 << 20));
+    hipLaunchKernelGGL(k_agc_measure, dim3(grid), dim3(kThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+// the walk of an ordinary call on its own, over a table the caller has put into device memory (iqgpu_chain_agc_advance)
+hipError_t launch_agc_walk(const AgcArgs &a, hipStream_t s)
+{
+    if (a.geom.n_chunks <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_agc_scan, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
 }
 
 __global__ __launch_bounds__(kThreads) void k_agc_apply(const AgcArgs a)

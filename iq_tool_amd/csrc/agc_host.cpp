@@ -64,6 +64,33 @@ int Call::stage_agc()
     return IQGPU_OK;
 }
 
+// the measure pass (iqgpu_chain_measure): the call's last stage has left cf32 in abuf as in front of the lock; one kernel reads it
+// once and leaves the call's rows in agc_rows.  The AGC state, its host mirrors and the peak arrays of the ordinary path stay as
+// they are.
+int Call::stage_agc_measure()
+{
+    AgcMeasureArgs ma{};
+    ma.geom = agc_geom();
+    ma.x = (const cf2 *)c->abuf.p; ma.rows = (AgcRow *)c->agc_rows.p;
+    const int64_t avg = p.n_emit / ma.geom.n_chunks + 1;
+    int64_t splits = (avg + 16383) / 16384; if (splits > 1024) splits = 1024;
+    ma.splits = (int)splits;
+    KernelTimer kt(c, IQGPU_K_AGC);
+    HIP_TRY(launch_agc_measure(ma, c->stream));
+    return IQGPU_OK;
+}
+
+// ... on the other route (kAgcMeasureS1): k_front_s1<.., AGC> has left the exact peaks in agc_peak
+int Call::stage_agc_rows_from_peaks()
+{
+    AgcMeasureArgs ma{};
+    ma.geom = agc_geom();
+    ma.rows = (AgcRow *)c->agc_rows.p; ma.peak_in = (unsigned long long *)c->agc_peak.p; ma.splits = 1;
+    KernelTimer kt(c, IQGPU_K_AGC);
+    HIP_TRY(launch_agc_measure(ma, c->stream));
+    return IQGPU_OK;
+}
+
 // behind a fused front launch: the verifier, then the unfused kernels -- same input, same history buffers, the untouched AGC
 // state -- either queued right behind it as launches that do nothing unless the verifier raised its flag (iqgpu_chain_process_device:
 // the caller owns the stream, nothing may be left for later), or kept here until the host has read the verdict from its pinned word

@@ -68,6 +68,7 @@ struct DebugSwitches {
     int fft_log2n = 0;            // "fft_log2n": overlap-save transform size (applies when it holds the taps; 0 = chosen)
     int fft_threads = 0;          // "fft_threads": k_fftconv16's workgroup size (0 = chosen)
     bool fft_keep_geometry = false;   // "fft_geometry" = "keep": the two filter kernels on k_p0fft16's transform size and windows
+    int measure_route = -1;       // "measure_route" = "unfused" | "s1": the route of iqgpu_chain_measure (-1: the faster one measured for the shape, measure_impl in process.cpp)
     int casc2_min_run = 0;        // "casc2_min_run": shortest streaming run (tiles) that takes k_cascade2 (0 = the built-in bound)
 };
 DebugSwitches debug_switches();                        // abi.cpp: the table as it stands, under one lock
@@ -163,6 +164,17 @@ struct iqgpu_chain {
     DevBuf agc_hist; int64_t agc_rms_warm = 0; uint64_t agc_rms_pos = 0;
     // agc_peak is all zero: what a fused front launch needs (k_agc_classify hands it back zeroed, agc_peak_b too; the unfused kernels do not)
     bool agc_peak_clean = false;
+    // seamless sharding of digital-AGC chains (ABI v8, process.cpp).  agc_bypass != 0: a call runs the chain's ordinary UNFUSED route
+    // -- its last stage leaves cf32 in abuf -- and the AGC itself stays out: no scan, no apply, no pack, the AGC state and its host
+    // mirrors untouched.  kAgcMeasure: k_agc_measure then writes one row per chunk into agc_rows (iqgpu_chain_measure);
+    // kAgcDrop: nothing reads abuf (the preroll of iqgpu_chain_seek_agc).  agc_walk: the tables and the scratch state of
+    // iqgpu_chain_agc_advance.
+    // kAgcMeasureS1: the other route of the measure pass, for agc_fusable chains: k_front_s1<.., AGC> -- their fallback kernel, which
+    // reduces the exact peak in front of the gain in its epilogue -- as it is, with the packed output into seek_sink and a scratch AGC
+    // state (agc_scratch); the rows are then put together from its peak array.  Half the traffic of kAgcMeasure, a slower kernel.
+    enum { kAgcOrdinary = 0, kAgcMeasure = 1, kAgcDrop = 2, kAgcMeasureS1 = 3 };
+    int agc_bypass = kAgcOrdinary;
+    DevBuf agc_rows, agc_walk, agc_scratch;
     // fused AGC of the locked phase (k_front_s1<.., AGC> + k_agc_verify): which chains qualify, the host's mirror of
     // "has the stream locked" (a closed form: the first chunk that starts after AGC_DIGITAL_LOCK_TIME of output), the
     // flag the verifier leaves for the fallback launches
@@ -344,6 +356,8 @@ struct Call {
     int stage_filter();
     int stage_late_resampler();
     int stage_agc();
+    int stage_agc_measure();
+    int stage_agc_rows_from_peaks();
     int stage_agc_verify_and_fallback(const FrontArgs &spec);
     int stage_agc_verify_and_fallback_filter(const FftConvArgs &spec);
     AgcArgs agc_args() const;

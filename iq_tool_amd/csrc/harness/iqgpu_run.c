@@ -25,6 +25,14 @@
  * iqgpu_chain_seek and runs its usual chunk loop; output offsets come from iqgpu_design_out_frames_range.  The stitched file is the
  * file --shards 1 writes (iqgpu.h: byte for byte without --dc-block, to 1e-6 of full scale with it; refused with an AGC option).
  *
+ * --shards N --seamless-agc is --seamless for chains with the digital output AGC (every shipped preset), in the two passes of
+ * iqgpu.h's v8 block.  Shard starts are s * (frames / N) rounded down to a multiple of lcm(4096, AGC chunk, --chunk-frames): the
+ * digital AGC works on the chunks of each call, so every call of every shard has to lie on the single stream's call and chunk grid.
+ * Pass 1: shards 0 .. N-2 put their chain at their start (iqgpu_chain_seek_agc, no entry state) and measure their range batch by
+ * batch (iqgpu_chain_measure; the last shard's range is in front of nobody).  One walk over the tables in order
+ * (iqgpu_chain_agc_advance) then gives the AGC state at the start of shards 1 .. N-1.  Pass 2: every shard seeks again, now with
+ * its entry state, and runs the usual chunk loop.  Preroll and output placement come from the description with the AGC off.
+ *
  * --synthetic FRAMES [--synthetic-hash SEED]: no input file.  Without a seed one constant pinned buffer is sent again and again
  * (the PCIe-inclusive rate of the path, nothing else); with one, shard s is the stream frame n -> splitmix64((SEED + s) * K + n)
  * of its own (iq_tool_amd/synth.py hash_stream restates it): configs[4] at its real size -- 8 x 2.5 G frames -- without 80 GB of
@@ -59,6 +67,7 @@ typedef struct {
     int have_hash; unsigned long long hash_seed;   /* ... or generate shard s as the counter-hash stream of seed hash_seed + s */
     int no_bind;                      /* --no-numa-bind */
     int seamless;                     /* --seamless: the shards continue ONE stream (iqgpu_chain_seek behind a preroll) */
+    int seamless_agc;                 /* --seamless-agc: --seamless for digital-AGC chains, in two passes (measure, walk, process) */
     int dry;                          /* --dry-placement: plan, bind, size the buffers, report -- no GPU call */
     int quiet;
 } Options;
@@ -74,9 +83,19 @@ typedef struct {
     int device, numa_node;            /* where it ran; -1 = the host does not say / not bound */
     char bus_id[64]; int cpus_allowed; long long pinned_bytes, hbm_bytes;   /* --dry-placement's report */
     double seconds, stream_seconds;   /* whole shard incl. set-up / copy-process-copy loop only */
+    /* --seamless-agc */
+    iqgpu_agc_chunk *rows; long long agc_rows;   /* pass 1: this shard's table (planned count with --dry-placement) */
+    iqgpu_agc_state entry; int have_entry;       /* the AGC state at first_frame, from the walk */
+    double measure_seconds;
+    int barriers;                     /* how many of the two rendezvous of the passes this thread has been through */
     int rc;
     char err[256];
 } Shard;
+
+/* --seamless-agc: all shard threads meet behind pass 1 and again behind the walk, which shard 0's thread does in between */
+static pthread_barrier_t g_pass;
+static Shard *g_shards;
+static volatile int g_walk_ok;
 
 static double now_s(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; }
 
@@ -117,6 +136,22 @@ static int fmt_from_name(const char *s)
         {"sc16q11", IQGPU_FMT_SC16Q11}};
     for (size_t i = 0; i < sizeof(t) / sizeof(t[0]); i++) if (!strcmp(s, t[i].n)) return t[i].v;
     return -1;
+}
+
+/* n frames of the job's input from stream frame `first` into dst: the file, the counter-hash stream, or the constant filling */
+static int read_frames(const Options *o, int in_fd, int fmt, size_t ibps, long long first, size_t n, void *dst, char *err, size_t errcap)
+{
+    const size_t nb = n * ibps;
+    if (in_fd >= 0) {
+        size_t got = 0;
+        while (got < nb) {
+            ssize_t r = pread(in_fd, (char *)dst + got, nb - got, first * (long long)ibps + (long long)got);
+            if (r <= 0) { snprintf(err, errcap, "pread: %s", r < 0 ? strerror(errno) : "short file"); return -1; }
+            got += (size_t)r;
+        }
+    } else if (o->have_hash) hash_fill(dst, fmt, ibps, o->hash_seed, first, n);
+    else memset(dst, 0x11, nb);
+    return 0;
 }
 
 #define CK(call) do { int rc_ = (call); if (rc_ != IQGPU_OK) { snprintf(sh->err, sizeof(sh->err), "%s: %s", #call, iqgpu_last_error()); sh->rc = rc_; goto done; } } while (0)
@@ -185,6 +220,54 @@ static void *run_shard(void *arg)
         if (out_fd < 0) { snprintf(sh->err, sizeof(sh->err), "open %s: %s", o->out_path, strerror(errno)); sh->rc = -1; goto done; }
     }
 
+    if (o->seamless_agc) {
+        /* pass 1: the chain at the start of the range with the AGC out of the way, then the range measured in the calls pass 2
+         * will make.  The last shard measures nothing: nobody starts behind it */
+        const size_t np = (size_t)sh->preroll_frames;
+        const size_t agc_chunk = d.agc_chunk_frames ? d.agc_chunk_frames : 16384;
+        const double t_m = now_s();
+        if (np) {
+            pre = malloc(np * ibps);
+            if (!pre) { snprintf(sh->err, sizeof(sh->err), "out of memory for a preroll of %zu frames", np); sh->rc = -1; goto done; }
+            if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame - sh->preroll_frames, np, pre, sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
+        }
+        if (sh->shard < o->shards - 1) {
+            const size_t cap = (size_t)((sh->frames + (long long)chunk - 1) / (long long)chunk) * ((chunk + agc_chunk - 1) / agc_chunk) + 1;
+            sh->rows = (iqgpu_agc_chunk *)malloc(cap * sizeof(iqgpu_agc_chunk));
+            if (!sh->rows) { snprintf(sh->err, sizeof(sh->err), "out of memory for a table of %zu rows", cap); sh->rc = -1; goto done; }
+            CK(iqgpu_chain_seek_agc(chain, (uint64_t)sh->first_frame, pre, np, NULL));
+            for (long long at = 0; at < sh->frames; at += (long long)chunk) {
+                size_t n = chunk, got = 0;
+                if ((long long)n > sh->frames - at) n = (size_t)(sh->frames - at);
+                if (o->synthetic_frames <= 0 || o->have_hash) {
+                    if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame + at, n, h_in[0], sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
+                }
+                CK(iqgpu_chain_measure(chain, h_in[0], n, sh->rows + sh->agc_rows, cap - (size_t)sh->agc_rows, &got));
+                sh->agc_rows += (long long)got;
+            }
+        }
+        sh->measure_seconds = now_s() - t_m;
+        /* the walk: one thread, the tables in shard order, the state in front of every shard kept */
+        pthread_barrier_wait(&g_pass); sh->barriers = 1;
+        if (sh->shard == 0) {
+            int ok = 1;
+            iqgpu_agc_state st;
+            for (int q = 0; q < o->shards; q++) if (g_shards[q].rc) ok = 0;
+            if (ok && iqgpu_chain_agc_initial_state(chain, &st) != IQGPU_OK) ok = 0;
+            for (int q = 0; q < o->shards && ok; q++) {
+                g_shards[q].entry = st; g_shards[q].have_entry = 1;
+                if (q < o->shards - 1 && iqgpu_chain_agc_advance(chain, &st, g_shards[q].rows, (size_t)g_shards[q].agc_rows, NULL) != IQGPU_OK) {
+                    snprintf(sh->err, sizeof(sh->err), "iqgpu_chain_agc_advance: %s", iqgpu_last_error()); sh->rc = -1; ok = 0;
+                }
+            }
+            g_walk_ok = ok;
+        }
+        pthread_barrier_wait(&g_pass); sh->barriers = 2;
+        if (!g_walk_ok) { if (!sh->rc) { snprintf(sh->err, sizeof(sh->err), "the measure pass or the walk of another shard failed"); sh->rc = -1; } goto done; }
+        /* pass 2: the same position again, now carrying the stream's AGC state there */
+        CK(iqgpu_chain_seek_agc(chain, (uint64_t)sh->first_frame, pre, np, &sh->entry));
+        free(pre); pre = NULL;
+    }
     if (o->seamless && sh->first_frame > 0) {
         /* the frames in front of this shard's start, read like any other range of the stream, warm the chain's histories up; the
          * chain then stands at first_frame of the ONE stream (iqgpu_chain_seek) */
@@ -226,7 +309,7 @@ static void *run_shard(void *arg)
                 }
             } else if (o->have_hash) {
                 /* (buffer b is free: chunk i - 2, its last user, retired in the iteration before this one) */
-                if (o->seamless) hash_fill(h_in[b], d.in_format, ibps, o->hash_seed, sh->first_frame + done_in, n);
+                if (o->seamless || o->seamless_agc) hash_fill(h_in[b], d.in_format, ibps, o->hash_seed, sh->first_frame + done_in, n);
                 else hash_fill(h_in[b], d.in_format, ibps, o->hash_seed + (uint64_t)sh->shard, done_in, n);
             }
             CK(iqgpu_memcpy_h2d_async(d_in[b], h_in[b], n * ibps, s_in));
@@ -259,6 +342,8 @@ static void *run_shard(void *arg)
         sh->rc = -1;
     }
 done:
+    /* (a shard that fails early still keeps the rendezvous of the two passes: the others wait there) */
+    while (o->seamless_agc && !o->dry && sh->barriers < 2) { pthread_barrier_wait(&g_pass); sh->barriers++; }
     free(pre);
     if (chain) iqgpu_chain_synchronize(chain);
     for (int b = 0; b < NBUF; b++) {
@@ -289,6 +374,7 @@ static void usage(void)
             "          [--transition-width HZ] [--attenuation DB] [--filter-taps N] [--filter-type fir|fft] [--filter-fft-size N]\n"
             "          [--chunk-frames N (default 4194304)] [--shards N] [--devices N] [--device D] [--synthetic FRAMES [--synthetic-hash SEED]]\n"
             "          [--seamless (with --shards: the shards continue ONE stream -- the stitched output is what --shards 1 writes)]\n"
+            "          [--seamless-agc (--seamless for chains with the digital output AGC: a measure pass, one walk, then the ordinary pass)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
             "          [--dry-placement (plan the shards, bind every shard thread, size its buffers, report as JSON: no GPU call)]\n");
 }
@@ -344,6 +430,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--no-numa-bind")) o.no_bind = 1;
         else if (!strcmp(a, "--dry-placement")) o.dry = 1;
         else if (!strcmp(a, "--seamless")) o.seamless = 1;
+        else if (!strcmp(a, "--seamless-agc")) o.seamless_agc = 1;
         else if (!strcmp(a, "--debug")) {              /* --debug name=value -> iqgpu_debug_set (the library reads no environment) */
             char kv[512]; snprintf(kv, sizeof(kv), "%s", NEXT);
             char *eq = strchr(kv, '=');
@@ -392,7 +479,51 @@ int main(int argc, char **argv)
         sh[s].out_offset_bytes = (long long)first_out * (long long)obps;
         sh[s].planned_out = (long long)nout;
     }
-    for (int s = 0; s < o.shards && !o.seamless; s++) {
+    if (o.seamless_agc) {
+        /* what the library would refuse at the first v8 call, before anything is planned (its own words) */
+        if (o.seamless) { fprintf(stderr, "--seamless and --seamless-agc exclude each other\n"); return 2; }
+        if (!o.desc.agc_enable) { fprintf(stderr, "--seamless-agc: the chain has no output AGC (use --seamless)\n"); return 1; }
+        /* the two passes have to read the SAME stream: the constant filling of a bare --synthetic is no stream (its buffers differ) */
+        if (o.synthetic_frames > 0 && !o.have_hash) { fprintf(stderr, "--seamless-agc needs a stream it can read twice: an input file, or --synthetic with --synthetic-hash\n"); return 2; }
+        if (o.desc.agc_profile != IQGPU_AGC_DIGITAL) {
+            fprintf(stderr, "--seamless-agc: the AGC profiles dx / local carry a per-sample loop state that no table of per-chunk figures reproduces exactly; "
+                            "only the digital profile is sharded seamlessly\n");
+            return 1;
+        }
+        /* preroll and placement do not depend on the AGC: from the description with the AGC off (iqgpu.h) */
+        iqgpu_chain_desc na = o.desc;
+        na.agc_enable = 0;
+        if (iqgpu_design_preroll_frames(&na, &preroll) != IQGPU_OK) { fprintf(stderr, "--seamless-agc: %s\n", iqgpu_last_error()); return 1; }
+        /* cut points: multiples of lcm(4096, AGC chunk, --chunk-frames) */
+        long long grid = 4096, agc_chunk = o.desc.agc_chunk_frames ? (long long)o.desc.agc_chunk_frames : 16384;
+        const long long parts[2] = {agc_chunk, (long long)o.chunk_frames};
+        for (int k = 0; k < 2; k++) { long long x = grid, y = parts[k]; while (y) { const long long t = x % y; x = y; y = t; } grid = grid / x * parts[k]; }
+        for (int s = 0; s < o.shards; s++) {
+            const long long next = (s == o.shards - 1) ? total_frames : ((long long)(s + 1) * per) / grid * grid;
+            sh[s].opt = &o; sh[s].shard = s;
+            sh[s].first_frame = ((long long)s * per) / grid * grid;
+            sh[s].frames = next - sh[s].first_frame;
+            if (sh[s].frames <= 0) {
+                fprintf(stderr, "--seamless-agc: %lld frames are too few for %d shards on a grid of %lld frames (lcm of 4096, the AGC chunk and --chunk-frames): "
+                                "shard %d would be empty\n", total_frames, o.shards, grid, s);
+                return 1;
+            }
+            sh[s].preroll_frames = sh[s].first_frame < (long long)preroll ? sh[s].first_frame : (long long)preroll;
+            uint64_t first_out = 0, nout = 0;
+            if (iqgpu_design_out_frames_range(&na, (uint64_t)sh[s].first_frame, (uint64_t)sh[s].frames, &first_out, &nout) != IQGPU_OK) {
+                fprintf(stderr, "%s\n", iqgpu_last_error()); return 1;
+            }
+            sh[s].out_offset_bytes = (long long)first_out * (long long)obps;
+            sh[s].planned_out = (long long)nout;
+            if (o.dry && s < o.shards - 1) {        /* rows pass 1 will record: one per AGC chunk of every call */
+                const long long cf = (long long)o.chunk_frames, full = sh[s].frames / cf, rest = sh[s].frames % cf;
+                sh[s].agc_rows = full * ((cf + agc_chunk - 1) / agc_chunk) + (rest + agc_chunk - 1) / agc_chunk;
+            }
+        }
+        g_shards = sh;
+        if (!o.dry && pthread_barrier_init(&g_pass, NULL, (unsigned)o.shards) != 0) { fprintf(stderr, "pthread_barrier_init failed\n"); return 1; }
+    }
+    for (int s = 0; s < o.shards && !o.seamless && !o.seamless_agc; s++) {
         sh[s].opt = &o; sh[s].shard = s;
         sh[s].first_frame = (long long)s * per;
         sh[s].frames = (s == o.shards - 1) ? total_frames - sh[s].first_frame : per;
@@ -424,10 +555,11 @@ int main(int argc, char **argv)
         int distinct = 0;
         for (int s = 0; s < o.shards; s++) { int seen = 0; for (int q = 0; q < s; q++) if (!strcmp(sh[q].bus_id, sh[s].bus_id) && sh[q].device == sh[s].device) seen = 1; if (!seen) distinct++; }
         printf("{\"dry_placement\": true, %s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"distinct_devices\": %d, \"per_shard\": [",
-               o.seamless ? "\"seamless\": true, " : "", total_frames, frames_out, o.shards, o.devices, distinct);
+               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : "", total_frames, frames_out, o.shards, o.devices, distinct);
         for (int s = 0; s < o.shards; s++) {
-            char pre_kv[64] = "";
+            char pre_kv[96] = "";
             if (o.seamless) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld", sh[s].preroll_frames);
+            if (o.seamless_agc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"agc_rows\": %lld", sh[s].preroll_frames, sh[s].agc_rows);
             printf("%s{\"shard\": %d, \"device\": %d, \"pci_bus_id\": \"%s\", \"numa_node\": %d, \"cpus_allowed\": %d, \"first_frame\": %lld, \"frames_in\": %lld, \"planned_out\": %lld, "
                    "\"out_offset_bytes\": %lld, \"pinned_bytes\": %lld, \"hbm_bytes\": %lld%s}", s ? ", " : "", s, sh[s].device, sh[s].bus_id, sh[s].numa_node, sh[s].cpus_allowed,
                    sh[s].first_frame, sh[s].frames, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].pinned_bytes, sh[s].hbm_bytes, pre_kv);
@@ -439,17 +571,22 @@ int main(int argc, char **argv)
     if (!o.quiet) {
         printf("{%s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"seconds\": %.6f, \"msps_end_to_end\": %.3f, \"stream_seconds\": %.6f, \"msps_streaming\": %.3f, "
                "\"h2d_GBs\": %.3f, \"d2h_GBs\": %.3f, \"in_bytes_per_frame\": %zu, \"out_bytes_per_frame\": %zu, \"input\": \"%s\", \"per_shard\": [",
-               o.seamless ? "\"seamless\": true, " : "", total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
+               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : "", total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
                stream_s > 0 ? (double)total_frames * (double)ibps / stream_s / 1e9 : 0.0, stream_s > 0 ? (double)frames_out * (double)obps / stream_s / 1e9 : 0.0, ibps, obps,
                o.synthetic_frames <= 0 ? "file" : o.have_hash ? "synthetic-hash" : "synthetic-constant");
         for (int s = 0; s < o.shards; s++) {
-            char pre_kv[64] = "";
+            char pre_kv[512] = "";
             if (o.seamless) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld", sh[s].preroll_frames);
+            if (o.seamless_agc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"measure_seconds\": %.6f, \"agc_rows\": %lld, \"entry\": {\"locked\": %d, "
+                "\"peak_memory\": %.9g, \"current_gain\": %.9g, \"last_strong_peak_time\": %.17g, \"samples_seen\": %llu}", sh[s].preroll_frames, sh[s].measure_seconds,
+                sh[s].agc_rows, sh[s].entry.locked, (double)sh[s].entry.peak_memory, (double)sh[s].entry.current_gain, sh[s].entry.last_strong_peak_time,
+                (unsigned long long)sh[s].entry.samples_seen);
             printf("%s{\"shard\": %d, \"device\": %d, \"numa_node\": %d, \"first_frame\": %lld, \"frames_in\": %lld, \"frames_out\": %lld, \"planned_out\": %lld, \"out_offset_bytes\": %lld, \"seconds\": %.6f%s}",
                    s ? ", " : "", s, sh[s].device, sh[s].numa_node, sh[s].first_frame, sh[s].frames, sh[s].frames_out, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].stream_seconds, pre_kv);
         }
         printf("]}\n");
     }
+    for (int s = 0; s < o.shards; s++) free(sh[s].rows);
     free(th); free(sh);
     return rc;
 }

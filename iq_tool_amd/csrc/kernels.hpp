@@ -555,6 +555,24 @@ struct AgcArgs {
 };
 hipError_t launch_agc(const AgcArgs &a, hipStream_t s);
 
+// The measure pass of seamless sharding (iqgpu_chain_measure): what agc_apply would MEASURE of every chunk of a call, and nothing
+// else -- k_agc_measure reads the call's cf32 output once and leaves one row per chunk (k_agc_peak's reduction, k_agc_peak's bits).
+struct AgcRow {            // == iqgpu_agc_chunk
+    unsigned long long peak2;   // max re^2 + im^2 of the chunk, double bits (0 for an empty chunk)
+    uint32_t frames_out;        // frames that enter agc_apply for the chunk
+    uint32_t reserved;
+};
+struct AgcMeasureArgs {
+    AgcGeom    geom;
+    const cf2 *x;             // the call's output samples before the AGC (cf32), 16-byte aligned
+    AgcRow    *rows;          // [n_chunks], zeroed on the stream before the launch
+    int32_t    splits;        // workgroups per chunk
+    unsigned long long *peak_in;   // x == NULL: the peaks are here already (k_front_s1<.., AGC> left them); handed back zeroed
+};
+hipError_t launch_agc_measure(const AgcMeasureArgs &a, hipStream_t s);
+// k_agc_scan alone over a table that is already in device memory (a.peak2, a.chunk_len; a.state, a.gain): iqgpu_chain_agc_advance
+hipError_t launch_agc_walk(const AgcArgs &a, hipStream_t s);
+
 // RMS profiles dx / local (liquid agc_crcf): chunk-parallel with warm-up, then verified / repaired (agc.hip)
 struct AgcRmsArgs {
     const cf2 *x;             // the call's output samples before the AGC (cf32); x[-hist_valid .. -1] = the samples in front of them

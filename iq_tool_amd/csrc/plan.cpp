@@ -217,7 +217,8 @@ void Call::plan_geometry()
         cplan.step = c->rp.step;
         // the preset shape on a call long enough to give every one of the 8 x CUs fat waves a run of tiles: k_front_fat
         // (shorter calls keep k_front_s1's 16 x CUs waves of 512-frame tiles: what counts for them is latency; same bytes either way)
-        const bool fat_ok = !casc && !fast_s0 && front_fat_shape(cplan) &&
+        const bool s1_only = c->agc_bypass == iqgpu_chain::kAgcMeasureS1;      // (the measure pass on k_front_s1<.., AGC>, chain.hpp)
+        const bool fat_ok = !s1_only && !casc && !fast_s0 && front_fat_shape(cplan) &&
               ((c->sw.dbg & kDbgForceFat) || (int64_t)frames_in >= (int64_t)kFatMinTilesPerWave * kFatTile * wave_slots(front_fat_waves()));
         const int mid_nl = (!casc && !fast_s0) ? front_mid_nl(cplan) : 0;
         // (run descriptors hold tile indices in 32 bits)
@@ -225,7 +226,7 @@ void Call::plan_geometry()
         //  0.014 / 0.023, 0.017 / 0.023, 0.023 / 0.028, 0.039 / 0.036, 0.067 / 0.055 -- the crossover lies between 2^23 and 2^24 frames
         //  = 3.6 and 7.1 tiles per wave; the pipelined host path's 2^24-frame batches now run the headline kernel)
         constexpr int kMidMinTilesPerWave = 6;
-        const bool mid_ok = mid_nl != 0 && (int64_t)frames_in < ((int64_t)1 << 40) &&
+        const bool mid_ok = !s1_only && mid_nl != 0 && (int64_t)frames_in < ((int64_t)1 << 40) &&
               ((c->sw.dbg & kDbgForceFat)
                   || (int64_t)frames_in >= (int64_t)kMidMinTilesPerWave * front_mid_tile(mid_nl) * wave_slots(front_mid_waves()));
         // (measured on one box, 2^28 frames: k_front_s1 0.437 ms, k_front_fat 0.404, k_front_mid 0.381: the 12-wave kernel is the
@@ -265,7 +266,7 @@ void Call::plan_geometry()
         // outputs (shorter calls keep k_front_s1<S0>: same bytes).  Planned as k_front_s1's 256-frame tiles -- the edge runs are its
         // run_tiles -- with the streaming tiles' OUTPUTS dealt out as steps
         p0 = false;
-        if (fast_s0 && !casc && !(c->sw.dbg & kDbgNoP0)) {
+        if (fast_s0 && !casc && !s1_only && !(c->sw.dbg & kDbgNoP0)) {
             cplan.phi0 = c->phi;
             if (front_p0_shape(cplan) && ((int64_t)frames_in >= ((int64_t)1 << 22) || (c->sw.dbg & kDbgForceFat))) {
                 FrontArgs q = cplan;

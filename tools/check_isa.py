@@ -238,6 +238,7 @@ HOT = {
     "front_s2.hip": [("_ZN5iqgpu10k_front_s2ILi4ELi5ELi1EEEvNS_6S2ArgsE", 168),                    # config 3 (12 waves; its switch set compiled in)
                      ("_ZN5iqgpu10k_front_s2ILi4ELi5ELi0EEEvNS_6S2ArgsE", 168),                    # ... and with run-time switches
                      ("_ZN5iqgpu10k_front_s2ILi2ELi5ELi0EEEvNS_6S2ArgsE", 168)],
+    "agc.hip": [("_ZN5iqgpu13k_agc_measureENS_14AgcMeasureArgsE", 64)],                              # the measure pass of seamless AGC sharding (4 x 16-byte loads in flight + double maxima)
 }
 
 
@@ -261,12 +262,12 @@ def check_hot(lines_by_src):
 def main():
     from concurrent.futures import ThreadPoolExecutor
     csrc = os.path.join(HERE, "..", "iq_tool_amd", "csrc")
-    names = ["front_wave.hip", "cascade_wave.hip", "front_s2.hip", "front_mid.hip", "front_fat.hip", "front_p0.hip", "cascade2.hip", "p0fft_cu8.hip"]
+    names = ["front_wave.hip", "cascade_wave.hip", "front_s2.hip", "front_mid.hip", "front_fat.hip", "front_p0.hip", "cascade2.hip", "p0fft_cu8.hip", "agc.hip"]
     with ThreadPoolExecutor(max_workers=min(len(names), max(2, (os.cpu_count() or 4) - 1))) as ex:     # (front_mid.hip alone takes 2 min 40 s)
         isa = dict(zip(names, ex.map(lambda nm: compile_isa(os.path.join(csrc, nm)), names)))
     lines = isa["front_wave.hip"]
     errors, n = check(lines)
-    errors += check_hot({k: isa[k] for k in ("front_wave.hip", "cascade_wave.hip", "front_s2.hip")})
+    errors += check_hot({k: isa[k] for k in ("front_wave.hip", "cascade_wave.hip", "front_s2.hip", "agc.hip")})
     errors += check_no_read2_b32(lines, "front_wave.hip")
     errors += check_no_read2_b32(isa["cascade_wave.hip"], "cascade_wave.hip")
     errors += check_no_read2_b32(isa["cascade2.hip"], "cascade2.hip")
