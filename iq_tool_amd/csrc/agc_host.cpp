@@ -14,6 +14,13 @@ AgcGeom Call::agc_geom() const
     return g;
 }
 
+// pieces a chunk is cut into for the per-chunk reductions (k_agc_peak, k_agc_measure): about 16384 outputs each
+static int agc_splits(int64_t n_emit, int n_chunks)
+{
+    const int64_t splits = (n_emit / n_chunks + 1 + 16383) / 16384;
+    return (int)(splits > 1024 ? 1024 : splits);
+}
+
 AgcArgs Call::agc_args() const
 {
     AgcArgs ga{};
@@ -28,9 +35,7 @@ AgcArgs Call::agc_args() const
     ga.target = c->agc_target; ga.rate = c->target_rate;
     ga.clock_wall = c->desc.agc_clock == IQGPU_AGC_CLOCK_WALL ? 1 : 0;
     ga.t_wall = ga.clock_wall ? monotonic_sec() : 0.0;
-    const int64_t avg = p.n_emit / g.n_chunks + 1;
-    int64_t splits = (avg + 16383) / 16384; if (splits > 1024) splits = 1024;
-    ga.splits = (int)splits;
+    ga.splits = agc_splits(p.n_emit, g.n_chunks);
     ga.out_fmt = c->desc.out_format; ga.out = d_out;
     return ga;
 }
@@ -72,15 +77,13 @@ int Call::stage_agc_measure()
     AgcMeasureArgs ma{};
     ma.geom = agc_geom();
     ma.x = (const cf2 *)c->abuf.p; ma.rows = (AgcRow *)c->agc_rows.p;
-    const int64_t avg = p.n_emit / ma.geom.n_chunks + 1;
-    int64_t splits = (avg + 16383) / 16384; if (splits > 1024) splits = 1024;
-    ma.splits = (int)splits;
+    ma.splits = agc_splits(p.n_emit, ma.geom.n_chunks);
     KernelTimer kt(c, IQGPU_K_AGC);
     HIP_TRY(launch_agc_measure(ma, c->stream));
     return IQGPU_OK;
 }
 
-// ... on the other route (kAgcMeasureS1): k_front_s1<.., AGC> has left the exact peaks in agc_peak
+// ... on the other route (AgcMode::MeasureS1): k_front_s1<.., AGC> has left the exact peaks in agc_peak
 int Call::stage_agc_rows_from_peaks()
 {
     AgcMeasureArgs ma{};
@@ -94,7 +97,7 @@ int Call::stage_agc_rows_from_peaks()
 // behind a fused front launch: the verifier, then the unfused kernels -- same input, same history buffers, the untouched AGC
 // state -- either queued right behind it as launches that do nothing unless the verifier raised its flag (iqgpu_chain_process_device:
 // the caller owns the stream, nothing may be left for later), or kept here until the host has read the verdict from its pinned word
-// (defer_fallback: iqgpu_chain_process and submit / collect, where the host waits for the call anyway; agc_resolve_pending)
+// (CallOpts::host_verdict: iqgpu_chain_process and submit / collect, where the host waits for the call anyway; agc_resolve_pending)
 static hipError_t launch_agc_fallback(iqgpu_chain *c, const FrontArgs &fb, const AgcArgs &ga)
 {
     hipError_t e = launch_front_s1(fb, c->stream);
@@ -102,17 +105,29 @@ static hipError_t launch_agc_fallback(iqgpu_chain *c, const FrontArgs &fb, const
     return launch_agc(ga, c->stream);
 }
 
-int Call::stage_agc_verify_and_fallback(const FrontArgs &spec)
+// the half both fused launches share: the verifier's arguments, the host's verdict word armed, k_agc_verify queued.  *ga: the unfused
+// AGC kernels of the fallback -- the verifier's chunk map, peaks into the second array, run only when the flag is up
+int Call::stage_agc_verify(int peak_approx, AgcArgs *ga)
 {
-    const bool defer = c->defer_fallback && c->h_agc_verdict != nullptr;
     AgcArgs va = agc_args();
     va.verify_flag = c->d_agc_flag;
-    va.peak_approx = (mid || p0) ? 1 : 0;
+    va.peak_approx = peak_approx;
     va.peak2_fallback = (unsigned long long *)c->agc_peak_b.p;
-    va.verdict_host = defer ? c->d_agc_verdict : nullptr;
-    KernelTimer kt(c, IQGPU_K_AGC);
-    if (defer) c->h_agc_verdict[0] = -1;               // (written before the launch is queued: the kernel's store comes later)
+    va.verdict_host = verdict_on_host() ? c->d_agc_verdict : nullptr;
+    if (verdict_on_host()) c->h_agc_verdict[0] = -1;   // (written before the launch is queued: the kernel's store comes later)
     HIP_TRY(launch_agc_verify(va, c->stream));
+    *ga = va;
+    ga->peak2_fallback = nullptr; ga->verdict_host = nullptr;
+    ga->peak2 = (unsigned long long *)c->agc_peak_b.p;
+    ga->run_if = c->d_agc_flag; ga->verify_flag = nullptr;
+    return IQGPU_OK;
+}
+
+int Call::stage_agc_verify_and_fallback(const FrontArgs &spec)
+{
+    KernelTimer kt(c, IQGPU_K_AGC);
+    AgcArgs ga;
+    const int rc = stage_agc_verify((mid || p0) ? 1 : 0, &ga); if (rc) return rc;
     FrontArgs fb = spec;
     fb.agc_fused = 0; fb.agc_state = nullptr; fb.agc_peak2 = nullptr; fb.w_steal = nullptr; fb.w_run_stride = 0;
     fb.out_fmt = IQGPU_FMT_CF32; fb.out = c->abuf.p;
@@ -126,11 +141,7 @@ int Call::stage_agc_verify_and_fallback(const FrontArgs &spec)
         if (warm < 1) warm = 1;
         plan_front_s1(fb, wave_slots(front_s1_waves(fb)), fixed_tpw(), warm, 1, ft);
     }
-    AgcArgs ga = va;
-    ga.peak2_fallback = nullptr; ga.verdict_host = nullptr;
-    ga.peak2 = (unsigned long long *)c->agc_peak_b.p;
-    ga.run_if = c->d_agc_flag; ga.verify_flag = nullptr;
-    if (defer) {
+    if (verdict_on_host()) {
         c->pend.valid = true; c->pend.filter = false; c->pend.fb = fb; c->pend.ga = ga;
         return IQGPU_OK;
     }
@@ -142,26 +153,16 @@ int Call::stage_agc_verify_and_fallback(const FrontArgs &spec)
 // AGC's buffer (no history move: the fused launch made it) and the unfused AGC kernels
 int Call::stage_agc_verify_and_fallback_filter(const FftConvArgs &spec)
 {
-    const bool defer = c->defer_fallback && c->h_agc_verdict != nullptr;
-    AgcArgs va = agc_args();
-    va.verify_flag = c->d_agc_flag;
-    va.peak_approx = 1;                                  // float peaks, as k_front_mid's
-    va.peak2_fallback = (unsigned long long *)c->agc_peak_b.p;
-    va.verdict_host = defer ? c->d_agc_verdict : nullptr;
     KernelTimer kt(c, IQGPU_K_AGC);
-    if (defer) c->h_agc_verdict[0] = -1;
-    HIP_TRY(launch_agc_verify(va, c->stream));
+    AgcArgs ga;
+    const int rc = stage_agc_verify(1, &ga); if (rc) return rc;      // (float peaks, as k_front_mid's)
     FftConvArgs fc = spec;
     fc.agc_fused = 0; fc.agc_state = nullptr; fc.agc_peak2 = nullptr;
     fc.out_fmt = IQGPU_FMT_CF32; fc.out = c->abuf.p;
     fc.move_dst = nullptr; fc.move_src = nullptr; fc.move_n = 0;
     fc.feed.write_state = 0;                              // (k_p0fft16: the fused launch has left the next call's state)
     fc.run_if = c->d_agc_flag;
-    AgcArgs ga = va;
-    ga.peak2_fallback = nullptr; ga.verdict_host = nullptr;
-    ga.peak2 = (unsigned long long *)c->agc_peak_b.p;
-    ga.run_if = c->d_agc_flag; ga.verify_flag = nullptr;
-    if (defer) {
+    if (verdict_on_host()) {
         c->pend.valid = true; c->pend.filter = true; c->pend.fc = fc; c->pend.ga = ga;
         return IQGPU_OK;
     }

@@ -3,6 +3,7 @@
 //   abi.cpp        library / lifecycle / state entry points, create-time design (design_chain)
 //   plan.cpp       stream-position arithmetic (plan_call), per-call run geometry of the wave kernels (Call::plan_geometry)
 //   process.cpp    one process() call: buffers, the stages in stream order, iqgpu_chain_process[_device]
+//   seek.cpp       seamless range sharding: iqgpu_chain_seek[_agc], iqgpu_chain_measure, iqgpu_chain_agc_initial_state / _advance
 //   agc_host.cpp   host side of the output AGC: chunk map, fused / unfused split, verifier + fallback launches
 //   pipeline.cpp   iqgpu_chain_submit / _collect (pinned host buffers, three stages moved along by the host)
 #pragma once
@@ -68,7 +69,7 @@ struct DebugSwitches {
     int fft_log2n = 0;            // "fft_log2n": overlap-save transform size (applies when it holds the taps; 0 = chosen)
     int fft_threads = 0;          // "fft_threads": k_fftconv16's workgroup size (0 = chosen)
     bool fft_keep_geometry = false;   // "fft_geometry" = "keep": the two filter kernels on k_p0fft16's transform size and windows
-    int measure_route = -1;       // "measure_route" = "unfused" | "s1": the route of iqgpu_chain_measure (-1: the faster one measured for the shape, measure_impl in process.cpp)
+    int measure_route = -1;       // "measure_route" = "unfused" | "s1": the route of iqgpu_chain_measure (-1: the faster one measured for the shape, measure_impl in seek.cpp)
     int casc2_min_run = 0;        // "casc2_min_run": shortest streaming run (tiles) that takes k_cascade2 (0 = the built-in bound)
 };
 DebugSwitches debug_switches();                        // abi.cpp: the table as it stands, under one lock
@@ -164,16 +165,8 @@ struct iqgpu_chain {
     DevBuf agc_hist; int64_t agc_rms_warm = 0; uint64_t agc_rms_pos = 0;
     // agc_peak is all zero: what a fused front launch needs (k_agc_classify hands it back zeroed, agc_peak_b too; the unfused kernels do not)
     bool agc_peak_clean = false;
-    // seamless sharding of digital-AGC chains (ABI v8, process.cpp).  agc_bypass != 0: a call runs the chain's ordinary UNFUSED route
-    // -- its last stage leaves cf32 in abuf -- and the AGC itself stays out: no scan, no apply, no pack, the AGC state and its host
-    // mirrors untouched.  kAgcMeasure: k_agc_measure then writes one row per chunk into agc_rows (iqgpu_chain_measure);
-    // kAgcDrop: nothing reads abuf (the preroll of iqgpu_chain_seek_agc).  agc_walk: the tables and the scratch state of
-    // iqgpu_chain_agc_advance.
-    // kAgcMeasureS1: the other route of the measure pass, for agc_fusable chains: k_front_s1<.., AGC> -- their fallback kernel, which
-    // reduces the exact peak in front of the gain in its epilogue -- as it is, with the packed output into seek_sink and a scratch AGC
-    // state (agc_scratch); the rows are then put together from its peak array.  Half the traffic of kAgcMeasure, a slower kernel.
-    enum { kAgcOrdinary = 0, kAgcMeasure = 1, kAgcDrop = 2, kAgcMeasureS1 = 3 };
-    int agc_bypass = kAgcOrdinary;
+    // seamless sharding of digital-AGC chains (ABI v8, seek.cpp; AgcMode): the rows of a measure pass, the tables and the scratch
+    // state of iqgpu_chain_agc_advance, the scratch AGC state of the measure pass on k_front_s1
     DevBuf agc_rows, agc_walk, agc_scratch;
     // fused AGC of the locked phase (k_front_s1<.., AGC> + k_agc_verify): which chains qualify, the host's mirror of
     // "has the stream locked" (a closed form: the first chunk that starts after AGC_DIGITAL_LOCK_TIME of output), the
@@ -188,7 +181,6 @@ struct iqgpu_chain {
     // only when it is set.  iqgpu_chain_process_device keeps the queued scheme: its caller owns the stream and its synchronisation.
     // h_agc_verdict[0]: -1 = a verdict is awaited, 0 / 1 = k_agc_classify's answer
     volatile int32_t *h_agc_verdict = nullptr; int32_t *d_agc_verdict = nullptr;   // the same word, host and device address
-    bool defer_fallback = false;                // set around process_device_impl by the host-ordered entry points
     struct PendingVerdict { bool valid = false; bool filter = false; FrontArgs fb; FftConvArgs fc; AgcArgs ga; } pend;
     // ... and the AGC fused into the user filter's epilogue (k_fftconv16) where a filter stands between the resampler and the AGC:
     // the shipped -usb / -lsb presets
@@ -220,7 +212,6 @@ struct iqgpu_chain {
     uint64_t pipe_copied = 0;     // tickets whose D2H copy has been queued (<= pipe_launched)
     // stream position behind the last ticket (valid while pipe_launched < pipe_seq)
     int pipe_rem = 0; uint64_t pipe_phi = 0, pipe_fpending = 0;
-    bool iq_pinned = false; float iq_pin_mag = 0.0f, iq_pin_phase = 0.0f;   // factors of the batch being launched
     // I/Q optimiser probe: first 1024 pre-processed samples of a call (device -> pinned host), src/pipeline.c:468-476
     // (the optimiser runs on ITS OWN thread beside the stage thread: aux_mu guards the factors and the probe state;
     //  a block in flight or not yet read is never overwritten -- the optimiser takes at most two a second)
@@ -287,15 +278,27 @@ struct KernelTimer {
 };
 
 // ------------------------------------------------------------------------------------------------
-// one process() call
-// ------------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------------
 // one process() call: per-call geometry, then the stages in stream order
 //   [dc carries] -> front (k_front | k_front_s1 | k_cascade + k_front_s1) -> [filter] -> [k_interp] -> [agc]
 // ------------------------------------------------------------------------------------------------
+// Seamless sharding of digital-AGC chains (ABI v8, seek.cpp).  Other than Ordinary: a call runs the chain's ordinary UNFUSED route
+// -- its last stage leaves cf32 in abuf -- and the AGC itself stays out: no scan, no apply, no pack, the AGC state and its host
+// mirrors untouched, nothing written to the caller's output.  Measure: k_agc_measure then writes one row per chunk into agc_rows
+// (iqgpu_chain_measure); Drop: nothing reads abuf (the preroll of iqgpu_chain_seek_agc).
+// MeasureS1: the other route of the measure pass, for agc_fusable chains: k_front_s1<.., AGC> -- their fallback kernel, which
+// reduces the exact peak in front of the gain in its epilogue -- as it is, with the packed output into seek_sink and a scratch AGC
+// state (agc_scratch); the rows are then put together from its peak array.  Half the traffic of Measure, a slower kernel.
+enum class AgcMode { Ordinary, Measure, Drop, MeasureS1 };
+struct CallOpts {                 // what an entry point asks of ONE call (process_device_impl).  The default: an ordinary call
+    AgcMode agc = AgcMode::Ordinary;
+    bool host_verdict = false;    // the host-ordered entry points: the verdict of a fused launch on the host (iqgpu_chain::h_agc_verdict)
+    bool iq_fixed = false; float iq_mag = 0.0f, iq_phase = 0.0f;   // a pipelined batch: the correction factors as of its submit()
+};
+
 struct Call {
     iqgpu_chain *c;
     const void *d_raw_in; size_t frames_in; void *d_out;
+    CallOpts o;
     CallPlan p;
     bool filt; size_t L1; uint64_t fpending0;
     void *fin_out; int fin_fmt;              // where the LAST stage writes (d_out, or the AGC's cf32 buffer)
@@ -309,8 +312,9 @@ struct Call {
     int64_t s2_in_tiles = 0;                 //   ... and this the number of 512-frame input tiles of the call
     int wtile, casc_K, rem_k;
     float iq_mag = 0.0f, iq_phase = 0.0f;    // the correction factors this call applies (snapshot under aux_mu)
-    bool agc_fused = false;                  // this call: gain applied in the front kernel -- or, with a filter behind it, in the filter's epilogue -- and verified behind it
+    bool agc_fused = false;                  // this call: gain applied in the front kernel -- or, with a filter behind it, in the filter's epilogue -- and verified behind it (AgcMode::MeasureS1: that front kernel, no verdict)
     bool front_fused() const { return agc_fused && !filt; }
+    bool verdict_on_host() const { return o.host_verdict && c->h_agc_verdict != nullptr; }   // the fallback behind a fused launch waits for the host
     FrontArgs cplan;                         // run geometry of the wave-autonomous kernel that sees the raw input
     cf2 *fcur = nullptr, *icur = nullptr;    // filter-input / k_interp-input buffers of this call
 
@@ -346,6 +350,13 @@ struct Call {
         if (e == hipSuccess) c->agc_peak_clean = true;
         return e;
     }
+    // the fused-AGC fields of a front launch (the measure pass on that kernel: the gain of a scratch state), and its peak array zeroed
+    hipError_t wire_fused_agc(FrontArgs &a)
+    {
+        a.agc_fused = 1; a.agc_state = o.agc == AgcMode::MeasureS1 ? (const AgcState *)c->agc_scratch.p : c->d_agc_state;
+        a.agc_peak2 = (unsigned long long *)c->agc_peak.p; a.agc_chunk_frames = c->agc_chunk; a.agc_shift = c->S; a.agc_rem = c->rem;
+        return clean_agc_peaks();
+    }
 
     void plan_geometry();
     DcGeom dc_geom() const;
@@ -358,6 +369,7 @@ struct Call {
     int stage_agc();
     int stage_agc_measure();
     int stage_agc_rows_from_peaks();
+    int stage_agc_verify(int peak_approx, AgcArgs *ga);
     int stage_agc_verify_and_fallback(const FrontArgs &spec);
     int stage_agc_verify_and_fallback_filter(const FftConvArgs &spec);
     AgcArgs agc_args() const;
@@ -365,7 +377,8 @@ struct Call {
 
 // ---- entry points shared across translation units ----
 int process_device_impl(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, void *d_out, size_t out_capacity_bytes,
-                        size_t *frames_out);                                              // process.cpp
+                        size_t *frames_out, const CallOpts &o = CallOpts());              // process.cpp
+int stage_host_input(iqgpu_chain *c, const void *in, size_t frames, const void **d_in);   // process.cpp: host frames into stage_in, *d_in
 size_t agc_unfused_head(const iqgpu_chain *c, size_t frames_in, bool *locks);             // agc_host.cpp
 // behind a fused launch whose fallback waits for the verdict on the host: waits for the word, launches the fallback when it is set
 // (*ran = true then).  No-op without a pending verdict.

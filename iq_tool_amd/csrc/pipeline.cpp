@@ -49,13 +49,11 @@ int pipe_advance(iqgpu_chain *c, uint64_t upto)
         if (ps.frames_in) {
             HIP_TRY(hipEventSynchronize(ps.in_done));
             size_t produced = 0;
-            c->iq_pinned = true; c->iq_pin_mag = ps.iq_mag; c->iq_pin_phase = ps.iq_phase;
+            CallOpts o; o.iq_fixed = true; o.iq_mag = ps.iq_mag; o.iq_phase = ps.iq_phase;
             // (the host orders every stage of a batch: the AGC verdict of a fused launch is read on the host -- by the next batch's
             //  launch or by this batch's D2H copy, whichever comes first -- and the fallback kernels are launched only when it is set)
-            c->defer_fallback = true;
-            rc = process_device_impl(c, ps.d_in.p, ps.frames_in, ps.d_out.p, ps.d_out.cap, &produced);
-            c->defer_fallback = false;
-            c->iq_pinned = false;
+            o.host_verdict = true;
+            rc = process_device_impl(c, ps.d_in.p, ps.frames_in, ps.d_out.p, ps.d_out.cap, &produced, o);
             if (!rc && produced != ps.n_emit) rc = fail(IQGPU_EHIP, "internal: batch produced %zu frames, planned %zu", produced,
                 ps.n_emit);
             if (rc) ps.n_emit = 0;                               // nothing of a failed batch is copied back

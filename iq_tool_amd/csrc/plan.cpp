@@ -217,7 +217,7 @@ void Call::plan_geometry()
         cplan.step = c->rp.step;
         // the preset shape on a call long enough to give every one of the 8 x CUs fat waves a run of tiles: k_front_fat
         // (shorter calls keep k_front_s1's 16 x CUs waves of 512-frame tiles: what counts for them is latency; same bytes either way)
-        const bool s1_only = c->agc_bypass == iqgpu_chain::kAgcMeasureS1;      // (the measure pass on k_front_s1<.., AGC>, chain.hpp)
+        const bool s1_only = o.agc == AgcMode::MeasureS1;      // (the measure pass on k_front_s1<.., AGC>, chain.hpp)
         const bool fat_ok = !s1_only && !casc && !fast_s0 && front_fat_shape(cplan) &&
               ((c->sw.dbg & kDbgForceFat) || (int64_t)frames_in >= (int64_t)kFatMinTilesPerWave * kFatTile * wave_slots(front_fat_waves()));
         const int mid_nl = (!casc && !fast_s0) ? front_mid_nl(cplan) : 0;
@@ -285,7 +285,7 @@ void Call::plan_geometry()
             ((int64_t)frames_in >= ((int64_t)1 << 22) || (c->sw.dbg & kDbgForceFat))) {
             fusef = true; p0 = false;
         }
-                // S == 2: both stages in ONE kernel (k_front_s2, front_s2.hip), planned in tiles of the LAST stage -- 512 intermediate samples
+        // S == 2: both stages in ONE kernel (k_front_s2, front_s2.hip), planned in tiles of the LAST stage -- 512 intermediate samples
         // = 1024 input frames -- on the intermediate stream's own geometry.  Its streaming waves read the input as whole 16-byte
         // words from the start of a decimation group; calls that do not start on one, or are shorter than the histories they have
         // to leave behind, keep the two kernels (same bytes either way).

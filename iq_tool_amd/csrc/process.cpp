@@ -109,7 +109,7 @@ int Call::stage_front()
         return IQGPU_OK;
     }
     // (the measure pass on k_front_s1<.., AGC>: the gain of a scratch state, no verdict -- only the kernel's peak array is wanted)
-    const bool measure_s1 = c->agc_bypass == iqgpu_chain::kAgcMeasureS1;
+    const bool measure_s1 = o.agc == AgcMode::MeasureS1;
     FrontArgs a{};
     a.dbg = c->sw.dbg;
     a.raw = d_raw_in;
@@ -191,11 +191,7 @@ int Call::stage_front()
             else plan_front_s1(a2, wave_slots(front_s1_waves(a2)), fixed_tpw(), 1, 1);
             for (int q = 0; q < 20; ++q) a2.hb0[q] = 0.5f * c->rp.stages[(size_t)K].branch[(size_t)q];
             a2.sink = c->d_sink;
-            if (front_fused()) {
-                a2.agc_fused = 1; a2.agc_state = measure_s1 ? (const AgcState *)c->agc_scratch.p : c->d_agc_state; a2.agc_peak2 = (unsigned long long *)c->agc_peak.p;
-                a2.agc_chunk_frames = c->agc_chunk; a2.agc_shift = c->S; a2.agc_rem = c->rem;
-                HIP_TRY(clean_agc_peaks());
-            }
+            if (front_fused()) HIP_TRY(wire_fused_agc(a2));
             { KernelTimer kt(c, IQGPU_K_FRONT); HIP_TRY(s2 ? launch_front_s2(a1, a2, c->stream) : launch_front_s1(a2, c->stream)); }
             if (front_fused() && !measure_s1) { const int rc = stage_agc_verify_and_fallback(a2); if (rc) return rc; }
             c->hist2_cur ^= 1;
@@ -204,11 +200,7 @@ int Call::stage_front()
         // wave-autonomous kernel: one half-band stage (m = 10), or none
         copy_plan(a);
         if (!fast_s0) for (int q = 0; q < 20; ++q) a.hb0[q] = 0.5f * c->rp.stages[0].branch[(size_t)q];
-        if (front_fused()) {
-            a.agc_fused = 1; a.agc_state = measure_s1 ? (const AgcState *)c->agc_scratch.p : c->d_agc_state; a.agc_peak2 = (unsigned long long *)c->agc_peak.p;
-            a.agc_chunk_frames = c->agc_chunk; a.agc_shift = c->S; a.agc_rem = c->rem;
-            HIP_TRY(clean_agc_peaks());
-        }
+        if (front_fused()) HIP_TRY(wire_fused_agc(a));
         // k_front_mid, "steal" on, one run per resident wave: every wave claims its tiles through its run descriptor and waves
         // that finish early split the runs of those that are behind (front_mid.hip; off by default, profiles/r04_steal.md)
         if (mid && c->sw.steal && fixed_tpw() == 0 && a.w_n_stream >= 64 * (int64_t)front_mid_waves()) {
@@ -340,61 +332,13 @@ int Call::stage_late_resampler()
     c->icur ^= 1;
     return IQGPU_OK;
 }
-extern "C" int iqgpu_chain_process_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
-                                          void *d_out, size_t out_capacity_bytes, size_t *frames_out)
-{
-    if (!c || !frames_out) return fail(IQGPU_EINVAL, "iqgpu_chain_process_device: NULL argument");
-    int rc = pipe_advance(c, c->pipe_seq); if (rc) return rc;     // batches submitted earlier come first (same stream)
-    rc = agc_resolve_pending(c); if (rc) return rc;               // ... with whatever their last fused launch still owes
-    return process_device_impl(c, d_raw_in, frames_in, d_out, out_capacity_bytes, frames_out);
-}
-static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
-                       void *d_out, size_t out_capacity_bytes, size_t *frames_out, bool agc_fused);
-
-int process_device_impl(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
-                               void *d_out, size_t out_capacity_bytes, size_t *frames_out)
-{
-    if (!c || !frames_out) return fail(IQGPU_EINVAL, "iqgpu_chain_process_device: NULL argument");
-    // (a measuring or seeking chain keeps the AGC out of the call: the whole call on the unfused route, process_one)
-    if (!(c->agc_fusable || c->agc_fusable_filter) || frames_in == 0 || c->agc_bypass)
-        return process_one(c, d_raw_in, frames_in, d_out, out_capacity_bytes, frames_out, c->agc_bypass == iqgpu_chain::kAgcMeasureS1);
-    // output AGC on the specialised front kernel: the scanning phase (and the chunk that locks) through the unfused
-    // kernels, everything behind it fused
-    *frames_out = 0;
-    bool locks = false;
-    size_t head = agc_unfused_head(c, frames_in, &locks);
-    // with a user filter between the resampler and the AGC the call that holds the lock stays whole: cutting it at the locking chunk
-    // would move the filter's overlap-save windows on the stream (other roundings: the bytes of the unfused path would be missed by a
-    // code here and there); the fused epilogue starts with the next call
-    if (c->agc_fusable_filter && head > 0 && head < frames_in) head = frames_in;
-    const size_t ibps = bytes_per_frame(c->desc.in_format), obps = bytes_per_frame(c->desc.out_format);
-    if ((size_t)plan_call(c, frames_in).n_emit * obps > out_capacity_bytes)
-        return fail(IQGPU_ECAPACITY, "output buffer too small: need %zu bytes, have %zu", (size_t)plan_call(c, frames_in).n_emit * obps,
-            out_capacity_bytes);
-    size_t n1 = 0, n2 = 0;
-    if (head > 0) {
-        const int rc = process_one(c, d_raw_in, head, d_out, out_capacity_bytes, &n1, false);
-        if (rc) return rc;
-        c->agc_seen_host += n1;
-        if (locks) c->agc_locked_host = true;
-    }
-    if (head < frames_in) {
-        const int rc = process_one(c, (const char *)d_raw_in + head * ibps, frames_in - head, (char *)d_out + n1 * obps,
-                                   out_capacity_bytes - n1 * obps, &n2, true);
-        if (rc) return rc;
-        c->agc_seen_host += n2;
-    }
-    *frames_out = n1 + n2;
-    return IQGPU_OK;
-}
 
 static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
-                       void *d_out, size_t out_capacity_bytes, size_t *frames_out, bool agc_fused)
-{
-    if (!c || !frames_out) return fail(IQGPU_EINVAL, "iqgpu_chain_process_device: NULL argument");
+                       void *d_out, size_t out_capacity_bytes, size_t *frames_out, const CallOpts &o, bool past_lock)
+{   // past_lock: the part of an ordinary call behind the AGC's lock, on a chain whose last kernel applies the gain itself
     *frames_out = 0;
     if (frames_in == 0) return IQGPU_OK;
-    const bool bypass = c->agc && c->agc_bypass != iqgpu_chain::kAgcOrdinary;      // nothing of such a call reaches d_out
+    const bool bypass = c->agc && o.agc != AgcMode::Ordinary;      // nothing of such a call reaches d_out
     if (!d_raw_in || (!d_out && !bypass)) return fail(IQGPU_EINVAL, "iqgpu_chain_process_device: NULL buffer");
     if (frames_in > ((size_t)1 << 40)) return fail(IQGPU_EINVAL, "frames_in too large");
     if (c->poisoned) return fail(IQGPU_EHIP,
@@ -404,7 +348,7 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     { const int prc = agc_resolve_pending(c); if (prc) return prc; }
 
     Call k{};
-    k.c = c; k.d_raw_in = d_raw_in; k.frames_in = frames_in; k.d_out = d_out;
+    k.c = c; k.d_raw_in = d_raw_in; k.frames_in = frames_in; k.d_out = d_out; k.o = o;
     k.p = plan_call(c, frames_in);
     const size_t obps = bytes_per_frame(c->desc.out_format);
     if (!bypass && (size_t)k.p.n_emit * obps > out_capacity_bytes)
@@ -415,17 +359,19 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     // with the AGC on, the last stage leaves cf32 in abuf and k_agc_apply packs -- unless the call is past the lock
     // on a chain whose front kernel applies the gain itself (fused: packed output straight to the caller)
     k.fin_out = d_out; k.fin_fmt = c->desc.out_format;
+    // (the measure pass on k_front_s1<.., AGC>: the fused front launch as it is, against a scratch state and with no verdict -- stage_front)
+    const bool agc_fused = past_lock || o.agc == AgcMode::MeasureS1;
     k.agc_fused = agc_fused;
     if (c->agc && !agc_fused) {
         // (dx / local: the AGC's input of earlier calls stands in front of this call's, see stage_agc)
         const size_t lead = c->agc_rms_alpha > 0.0f ? (size_t)c->agc_rms_warm : 0;
         int rc = c->abuf.ensure((lead + (size_t)k.p.n_emit + 1) * sizeof(cf2)); if (rc) return rc;
         k.fin_out = (cf2 *)c->abuf.p + lead; k.fin_fmt = IQGPU_FMT_CF32;
-        if (c->agc_bypass == iqgpu_chain::kAgcMeasure) {
+        if (o.agc == AgcMode::Measure) {
             rc = c->agc_rows.ensure((((size_t)frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk) * sizeof(AgcRow)); if (rc) return rc;
         }
     }
-    if (c->agc_bypass == iqgpu_chain::kAgcMeasureS1) {
+    if (o.agc == AgcMode::MeasureS1) {
         // the packed output nobody keeps, the scratch state (the fresh one: gain 1) and the table
         int rc = c->seek_sink.ensure((size_t)k.p.n_emit * obps + 16); if (rc) return rc;
         k.fin_out = c->seek_sink.p;
@@ -435,7 +381,7 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
         rc = c->agc_rows.ensure((((size_t)frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk) * sizeof(AgcRow)); if (rc) return rc;
     }
     k.plan_geometry();
-    if (c->iq_pinned) { k.iq_mag = c->iq_pin_mag; k.iq_phase = c->iq_pin_phase; }                  // a pipelined batch: as of its submit()
+    if (o.iq_fixed) { k.iq_mag = o.iq_mag; k.iq_phase = o.iq_phase; }                              // a pipelined batch: as of its submit()
     else { std::lock_guard<std::mutex> g(c->aux_mu); k.iq_mag = c->iq_mag; k.iq_phase = c->iq_phase; }   // read once per call
 
     // every buffer the stages need is sized before the first launch, so that an allocation failure leaves the
@@ -466,9 +412,9 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     if ((rc = k.stage_front()) != IQGPU_OK) { c->poisoned = true; return rc; }
     if (k.filt && (rc = k.stage_filter()) != IQGPU_OK) { c->poisoned = true; return rc; }
     if (c->late && (rc = k.stage_late_resampler()) != IQGPU_OK) { c->poisoned = true; return rc; }
-    if (c->agc && !agc_fused && c->agc_bypass != iqgpu_chain::kAgcDrop &&
-        (rc = c->agc_bypass == iqgpu_chain::kAgcMeasure ? k.stage_agc_measure() : k.stage_agc()) != IQGPU_OK) { c->poisoned = true; return rc; }
-    if (c->agc_bypass == iqgpu_chain::kAgcMeasureS1 && (rc = k.stage_agc_rows_from_peaks()) != IQGPU_OK) { c->poisoned = true; return rc; }
+    if (c->agc && !agc_fused && o.agc != AgcMode::Drop &&
+        (rc = o.agc == AgcMode::Measure ? k.stage_agc_measure() : k.stage_agc()) != IQGPU_OK) { c->poisoned = true; return rc; }
+    if (o.agc == AgcMode::MeasureS1 && (rc = k.stage_agc_rows_from_peaks()) != IQGPU_OK) { c->poisoned = true; return rc; }
 
     // ---- advance the stream position ----
     c->nco_theta += (uint32_t)frames_in * c->nco_dtheta;
@@ -476,6 +422,60 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     c->rem = k.p.rem_next;
     c->phi = k.p.phi_next;
     *frames_out = (size_t)k.p.n_emit;
+    return IQGPU_OK;
+}
+
+int process_device_impl(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
+                               void *d_out, size_t out_capacity_bytes, size_t *frames_out, const CallOpts &o)
+{
+    // (a measuring or seeking call keeps the AGC out: the whole call in one piece, process_one)
+    if (!(c->agc_fusable || c->agc_fusable_filter) || frames_in == 0 || o.agc != AgcMode::Ordinary)
+        return process_one(c, d_raw_in, frames_in, d_out, out_capacity_bytes, frames_out, o, false);
+    // output AGC on the specialised front kernel: the scanning phase (and the chunk that locks) through the unfused
+    // kernels, everything behind it fused
+    *frames_out = 0;
+    bool locks = false;
+    size_t head = agc_unfused_head(c, frames_in, &locks);
+    // with a user filter between the resampler and the AGC the call that holds the lock stays whole: cutting it at the locking chunk
+    // would move the filter's overlap-save windows on the stream (other roundings: the bytes of the unfused path would be missed by a
+    // code here and there); the fused epilogue starts with the next call
+    if (c->agc_fusable_filter && head > 0 && head < frames_in) head = frames_in;
+    const size_t ibps = bytes_per_frame(c->desc.in_format), obps = bytes_per_frame(c->desc.out_format);
+    if ((size_t)plan_call(c, frames_in).n_emit * obps > out_capacity_bytes)
+        return fail(IQGPU_ECAPACITY, "output buffer too small: need %zu bytes, have %zu", (size_t)plan_call(c, frames_in).n_emit * obps,
+            out_capacity_bytes);
+    size_t n1 = 0, n2 = 0;
+    if (head > 0) {
+        const int rc = process_one(c, d_raw_in, head, d_out, out_capacity_bytes, &n1, o, false);
+        if (rc) return rc;
+        c->agc_seen_host += n1;
+        if (locks) c->agc_locked_host = true;
+    }
+    if (head < frames_in) {
+        const int rc = process_one(c, (const char *)d_raw_in + head * ibps, frames_in - head, (char *)d_out + n1 * obps,
+                                   out_capacity_bytes - n1 * obps, &n2, o, true);
+        if (rc) return rc;
+        c->agc_seen_host += n2;
+    }
+    *frames_out = n1 + n2;
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_chain_process_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
+                                          void *d_out, size_t out_capacity_bytes, size_t *frames_out)
+{
+    if (!c || !frames_out) return fail(IQGPU_EINVAL, "iqgpu_chain_process_device: NULL argument");
+    int rc = pipe_advance(c, c->pipe_seq); if (rc) return rc;     // batches submitted earlier come first (same stream)
+    rc = agc_resolve_pending(c); if (rc) return rc;               // ... with whatever their last fused launch still owes
+    return process_device_impl(c, d_raw_in, frames_in, d_out, out_capacity_bytes, frames_out);
+}
+
+int stage_host_input(iqgpu_chain *c, const void *in, size_t frames, const void **d_in)
+{
+    const size_t bytes = frames * bytes_per_frame(c->desc.in_format);
+    const int rc = c->stage_in.ensure(bytes); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->stage_in.p, in, bytes, hipMemcpyHostToDevice, c->stream));
+    *d_in = c->stage_in.p;
     return IQGPU_OK;
 }
 
@@ -488,250 +488,21 @@ extern "C" int iqgpu_chain_process(iqgpu_chain *c, const void *raw_in, size_t fr
     if (!raw_in || !out) return fail(IQGPU_EINVAL, "iqgpu_chain_process: NULL buffer");
     HIP_TRY(hipSetDevice(c->device));
     int rc = pipe_advance(c, c->pipe_seq); if (rc) return rc;     // batches submitted earlier come first
-    const size_t ibps = bytes_per_frame(c->desc.in_format), obps = bytes_per_frame(c->desc.out_format);
+    const size_t obps = bytes_per_frame(c->desc.out_format);
     const size_t n_emit = (size_t)plan_call(c, frames_in).n_emit;
     if (n_emit * obps > out_capacity_bytes)
         return fail(IQGPU_ECAPACITY, "output buffer too small: need %zu bytes, have %zu", n_emit * obps, out_capacity_bytes);
-    rc = c->stage_in.ensure(frames_in * ibps); if (rc) return rc;
-    rc = c->stage_out.ensure(n_emit * obps + 16); if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->stage_in.p, raw_in, frames_in * ibps, hipMemcpyHostToDevice, c->stream));
+    rc = c->stage_out.ensure(n_emit * obps + 16); if (rc) return rc;         // (both buffers sized before anything is queued)
+    const void *d_in = nullptr;
+    rc = stage_host_input(c, raw_in, frames_in, &d_in); if (rc) return rc;
     size_t produced = 0;
     // the host waits for this call's bytes anyway: the AGC verdict is read here and the fallback launched only when it is set
-    c->defer_fallback = true;
-    rc = process_device_impl(c, c->stage_in.p, frames_in, c->stage_out.p, c->stage_out.cap, &produced);
-    c->defer_fallback = false;
+    CallOpts o; o.host_verdict = true;
+    rc = process_device_impl(c, d_in, frames_in, c->stage_out.p, c->stage_out.cap, &produced, o);
     if (rc) return rc;
     rc = agc_resolve_pending(c); if (rc) return rc;
     if (produced) HIP_TRY(hipMemcpyAsync(out, c->stage_out.p, produced * obps, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     *frames_out = produced;
-    return IQGPU_OK;
-}
-
-// ------------------------------------------------------------------------------------------------
-// iqgpu_chain_seek: the chain at stream frame first_frame -- reset, the closed-form position preroll_frames earlier, and the
-// preroll through the ordinary per-call path with its output dropped (seamless range sharding, iqgpu.h)
-// ------------------------------------------------------------------------------------------------
-// what the v8 calls ask of a chain: the digital output AGC on the sample clock
-static int agc_two_pass_check(const iqgpu_chain *c, const char *who)
-{
-    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
-    if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC", who);
-    if (c->agc_rms_alpha > 0.0f) return fail(IQGPU_EUNSUPPORTED, "%s: the AGC profiles dx / local carry a per-sample loop state that no "
-        "table of per-chunk figures reproduces exactly; only the digital profile is sharded seamlessly", who);
-    if (c->desc.agc_clock == IQGPU_AGC_CLOCK_WALL) return fail(IQGPU_EUNSUPPORTED, "%s: IQGPU_AGC_CLOCK_WALL has no value at a stream "
-        "position; use IQGPU_AGC_CLOCK_SAMPLES", who);
-    return IQGPU_OK;
-}
-
-// agc_variant: iqgpu_chain_seek_agc -- the preroll with the AGC out of the way, then *entry (or the fresh state) installed
-static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, bool on_device,
-                     bool agc_variant = false, const iqgpu_agc_state *entry = nullptr)
-{
-    const char *who = agc_variant ? "iqgpu_chain_seek_agc" : "iqgpu_chain_seek";
-    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
-    // what iqgpu_chain_reset does comes first: batches in flight and a pending verdict resolved, histories and dc state zeroed,
-    // the poison cleared -- a refused argument below leaves the chain reset
-    int rc = iqgpu_chain_reset(c); if (rc) return rc;
-    c->fpending = 0;                                          // (reset keeps the FFT remainder queued: a seek starts a stream)
-    if (agc_variant) {
-        rc = agc_two_pass_check(c, who); if (rc) return rc;
-        if (entry && (entry->locked != 0 && entry->locked != 1)) return fail(IQGPU_EINVAL, "%s: entry state with locked = %d", who, entry->locked);
-    }
-    if (first_frame > kMaxStreamFrames) return fail(IQGPU_EINVAL, "%s: frame %llu is beyond 2^39 frames", who,
-        (unsigned long long)first_frame);
-    if ((uint64_t)preroll_frames > first_frame) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames would start in front of "
-        "frame 0 (first_frame %llu)", who, preroll_frames, (unsigned long long)first_frame);
-    if (first_frame > 0) {
-        if (c->agc && !agc_variant) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
-            "not on a bounded warm-up");
-        const uint64_t memory = seek_preroll_frames(c), need = first_frame < memory ? first_frame : memory;
-        if ((uint64_t)preroll_frames < need) return fail(IQGPU_EINVAL, "%s: preroll of %zu frames is shorter than the %llu "
-            "this chain needs at frame %llu", who, preroll_frames, (unsigned long long)need, (unsigned long long)first_frame);
-        if (preroll_frames && !preroll) return fail(IQGPU_EINVAL, "%s: NULL preroll", who);
-
-        const StreamAt from = stream_at(c, first_frame - (uint64_t)preroll_frames);
-        if (c->fp.enabled) {
-            // [L-1 history][pending]: zeros stand for the samples in front of the warm-up
-            const size_t front = c->fp.taps.size() - 1 + (size_t)from.pos.fpending;
-            rc = c->fbuf[c->fcur].ensure((front + 1) * sizeof(cf2)); if (rc) return rc;
-            HIP_TRY(hipMemsetAsync(c->fbuf[c->fcur].p, 0, front * sizeof(cf2), c->stream));
-        }
-        c->rem = from.pos.rem; c->phi = from.pos.phi; c->fpending = from.pos.fpending;
-        c->nco_theta = from.nco_theta; c->pnco_theta = from.pnco_theta;
-
-        if (preroll_frames) {
-            const size_t ibps = bytes_per_frame(c->desc.in_format), obps = bytes_per_frame(c->desc.out_format);
-            const void *d_in = preroll;
-            if (!on_device) {
-                rc = c->stage_in.ensure(preroll_frames * ibps); if (rc) return rc;
-                HIP_TRY(hipMemcpyAsync(c->stage_in.p, preroll, preroll_frames * ibps, hipMemcpyHostToDevice, c->stream));
-                d_in = c->stage_in.p;
-            }
-            size_t dropped = 0;
-            if (agc_variant) {
-                // nothing of the preroll is kept and the AGC must not see it: the unfused route into abuf, no AGC kernel behind it
-                c->agc_bypass = iqgpu_chain::kAgcDrop;
-                rc = process_device_impl(c, d_in, preroll_frames, nullptr, 0, &dropped);
-                c->agc_bypass = iqgpu_chain::kAgcOrdinary;
-            } else {
-                rc = c->seek_sink.ensure((size_t)plan_call(c, preroll_frames).n_emit * obps + 16); if (rc) return rc;
-                rc = process_device_impl(c, d_in, preroll_frames, c->seek_sink.p, c->seek_sink.cap, &dropped);
-            }
-            if (rc) return rc;
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        // the warm-up has walked the position forward call-wise: it has to stand on the closed form at first_frame
-        const StreamAt to = stream_at(c, first_frame);
-        if (c->rem != to.pos.rem || c->phi != to.pos.phi || c->fpending != to.pos.fpending || c->nco_theta != to.nco_theta ||
-            c->pnco_theta != to.pnco_theta) {
-            c->poisoned = true;
-            return fail(IQGPU_EINVAL, "internal: the position behind the preroll is not the closed form at frame %llu", (unsigned long long)first_frame);
-        }
-    }
-    if (agc_variant && entry) {
-        // The AGC state of the stream at first_frame, everywhere the chain keeps it: the device state the kernels read, and the host's
-        // mirrors of "has the stream locked" and of samples_seen, from which the fused / unfused split of every later call follows
-        // (agc_unfused_head).  The reset above has left the rest as on a chain that arrived here by processing: no pending verdict,
-        // the verifier's eight words at their initial values (no healthy chunk recorded for the call to come), the peak array marked
-        // dirty so that the first fused launch clears it.
-        static_assert(sizeof(iqgpu_agc_state) == sizeof(AgcState), "AGC state layout");
-        AgcState st;
-        memcpy(&st, entry, sizeof(st));
-        st.reserved = 0;
-        HIP_TRY(hipMemcpyAsync(c->d_agc_state, &st, sizeof(AgcState), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        c->agc_locked_host = st.locked != 0;
-        c->agc_seen_host = st.seen;
-    }
-    return IQGPU_OK;
-}
-
-extern "C" int iqgpu_chain_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames)
-{
-    return seek_impl(c, first_frame, preroll, preroll_frames, false);
-}
-extern "C" int iqgpu_chain_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames)
-{
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, true);
-}
-extern "C" int iqgpu_chain_seek_agc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames,
-                                    const iqgpu_agc_state *entry)
-{
-    return seek_impl(c, first_frame, preroll, preroll_frames, false, true, entry);
-}
-extern "C" int iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
-                                           const iqgpu_agc_state *entry)
-{
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, true, true, entry);
-}
-
-// ------------------------------------------------------------------------------------------------
-// seamless sharding of digital-AGC chains (ABI v8): the measure pass, and the walk over its tables
-// ------------------------------------------------------------------------------------------------
-static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows, bool on_device)
-{
-    static_assert(sizeof(iqgpu_agc_chunk) == sizeof(AgcRow) && sizeof(AgcRow) == 16, "AGC row layout");
-    int rc = agc_two_pass_check(c, "iqgpu_chain_measure"); if (rc) return rc;
-    if (!n_rows) return fail(IQGPU_EINVAL, "iqgpu_chain_measure: NULL argument");
-    *n_rows = 0;
-    if (frames_in == 0) return IQGPU_OK;
-    if (!in || !rows) return fail(IQGPU_EINVAL, "iqgpu_chain_measure: NULL buffer");
-    const size_t n = (frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk;
-    if (cap < n) return fail(IQGPU_ECAPACITY, "iqgpu_chain_measure: %zu frames are %zu chunks, the table holds %zu rows", frames_in, n, cap);
-    HIP_TRY(hipSetDevice(c->device));
-    rc = pipe_advance(c, c->pipe_seq); if (rc) return rc;         // batches submitted earlier come first (same stream)
-    rc = agc_resolve_pending(c); if (rc) return rc;
-    const void *d_in = in;
-    if (!on_device) {
-        const size_t ibps = bytes_per_frame(c->desc.in_format);
-        rc = c->stage_in.ensure(frames_in * ibps); if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(c->stage_in.p, in, frames_in * ibps, hipMemcpyHostToDevice, c->stream));
-        d_in = c->stage_in.p;
-    }
-    size_t dropped = 0;
-    // which route: chain.hpp (agc_bypass); the faster one measured per shape (tools/bench_measure.py, DESIGN 5.1, 2^28 frames).
-    // Chains without a half-band stage (the cu8-nrsc5 presets: one output per 1.6 input frames, so the cf32 stream of the unfused
-    // route is its largest) take k_front_s1<.., AGC>: 0.665 ms against 0.747.  With a half-band stage the unfused route wins
-    // (NRSC-5 cs16: 0.576 against 0.655); cascades were not timed and keep it.  The "measure_route" switch overrides.
-    const bool s1 = c->agc_fusable && (c->sw.measure_route == 1 || (c->sw.measure_route < 0 && c->S == 0 && !c->cascade));
-    c->agc_bypass = s1 ? iqgpu_chain::kAgcMeasureS1 : iqgpu_chain::kAgcMeasure;
-    rc = process_device_impl(c, d_in, frames_in, nullptr, 0, &dropped);
-    c->agc_bypass = iqgpu_chain::kAgcOrdinary;
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(rows, c->agc_rows.p, n * sizeof(AgcRow), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    *n_rows = n;
-    return IQGPU_OK;
-}
-
-extern "C" int iqgpu_chain_measure(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows)
-{
-    return measure_impl(c, raw_in, frames_in, rows, cap, n_rows, false);
-}
-extern "C" int iqgpu_chain_measure_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap,
-                                          size_t *n_rows)
-{
-    return measure_impl(c, d_raw_in, frames_in, rows, cap, n_rows, true);
-}
-
-extern "C" int iqgpu_chain_agc_initial_state(const iqgpu_chain *c, iqgpu_agc_state *st)
-{
-    if (!c || !st) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_initial_state: NULL argument");
-    if (!c->agc) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_initial_state: the chain has no output AGC");
-    AgcState s0 = c->agc_init;
-    if (c->desc.agc_clock != IQGPU_AGC_CLOCK_WALL) s0.last_strong = 0.0;
-    memcpy(st, &s0, sizeof(s0));
-    return IQGPU_OK;
-}
-
-// One definition of the walk: the tables go to device memory and k_agc_scan -- the kernel behind every unfused call -- walks them
-// from a scratch copy of *st, a batch of 2^20 rows per launch (the kernel's chunk index is 32-bit; a whole stream of 2^39 frames
-// can hold 2^25 rows).  The kernel carries its state from launch to launch exactly as from call to call.
-extern "C" int iqgpu_chain_agc_advance(iqgpu_chain *c, iqgpu_agc_state *st, const iqgpu_agc_chunk *rows, size_t n, float *gains)
-{
-    int rc = agc_two_pass_check(c, "iqgpu_chain_agc_advance"); if (rc) return rc;
-    if (!st || (n && !rows)) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_advance: NULL argument");
-    if (n == 0) return IQGPU_OK;
-    // (k_agc_scan adds the lengths of the 64 rows of a batch in 32 bits: the bound chain_create puts on agc_chunk_frames, here on
-    //  any 64 consecutive rows of a table the caller may have built)
-    uint64_t window = 0;
-    for (size_t i = 0; i < n; ++i) {
-        if (rows[i].frames_out > 0x7fffffffu || !(rows[i].peak2 >= 0.0)) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_advance: row %zu is "
-            "not a row of iqgpu_chain_measure (frames_out %u, peak2 %g)", i, rows[i].frames_out, rows[i].peak2);
-        window += rows[i].frames_out;
-        if (i >= 64) window -= rows[i - 64].frames_out;
-        if (window >= 0x80000000ull) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_advance: the 64 rows that end at row %zu hold %llu "
-            "frames (64 consecutive rows must stay below 2^31)", i, (unsigned long long)window);
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    constexpr size_t kBatch = (size_t)1 << 20;
-    const size_t nb_max = n < kBatch ? n : kBatch;
-    // [state][peak2 x nb_max][len x nb_max][gain x nb_max]
-    rc = c->agc_walk.ensure(64 + nb_max * (sizeof(unsigned long long) + sizeof(int32_t) + sizeof(float))); if (rc) return rc;
-    AgcState *d_st = (AgcState *)c->agc_walk.p;
-    unsigned long long *d_p2 = (unsigned long long *)((char *)c->agc_walk.p + 64);
-    int32_t *d_len = (int32_t *)(d_p2 + nb_max);
-    float *d_gain = (float *)(d_len + nb_max);
-    std::vector<unsigned long long> h_p2(nb_max);
-    std::vector<int32_t> h_len(nb_max);
-    HIP_TRY(hipMemcpyAsync(d_st, st, sizeof(AgcState), hipMemcpyHostToDevice, c->stream));
-    for (size_t done = 0; done < n; done += kBatch) {
-        const size_t nb = n - done < kBatch ? n - done : kBatch;
-        for (size_t i = 0; i < nb; ++i) {
-            memcpy(&h_p2[i], &rows[done + i].peak2, sizeof(double));
-            h_len[i] = (int32_t)rows[done + i].frames_out;
-        }
-        HIP_TRY(hipMemcpyAsync(d_p2, h_p2.data(), nb * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(d_len, h_len.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        AgcArgs a{};
-        a.geom.n_chunks = (int32_t)nb;
-        a.peak2 = d_p2; a.chunk_len = d_len; a.gain = d_gain; a.state = d_st;
-        a.target = c->agc_target; a.rate = c->target_rate;
-        HIP_TRY(launch_agc_walk(a, c->stream));
-        if (gains) HIP_TRY(hipMemcpyAsync(gains + done, d_gain, nb * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));             // (the staging vectors are reused by the next batch)
-    }
-    HIP_TRY(hipMemcpy(st, d_st, sizeof(AgcState), hipMemcpyDeviceToHost));
     return IQGPU_OK;
 }

@@ -1,0 +1,217 @@
+// seek.cpp -- seamless range sharding: a chain started mid-stream, the AGC measure pass (both: modes of process.cpp's call), the AGC walk
+#include "chain.hpp"
+
+// ------------------------------------------------------------------------------------------------
+// iqgpu_chain_seek: the chain at stream frame first_frame -- reset, the closed-form position preroll_frames earlier, and the
+// preroll through the ordinary per-call path with its output dropped (seamless range sharding, iqgpu.h)
+// ------------------------------------------------------------------------------------------------
+// what the v8 calls ask of a chain: the digital output AGC on the sample clock
+static int agc_two_pass_check(const iqgpu_chain *c, const char *who)
+{
+    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
+    if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC", who);
+    if (c->agc_rms_alpha > 0.0f) return fail(IQGPU_EUNSUPPORTED, "%s: the AGC profiles dx / local carry a per-sample loop state that no "
+        "table of per-chunk figures reproduces exactly; only the digital profile is sharded seamlessly", who);
+    if (c->desc.agc_clock == IQGPU_AGC_CLOCK_WALL) return fail(IQGPU_EUNSUPPORTED, "%s: IQGPU_AGC_CLOCK_WALL has no value at a stream "
+        "position; use IQGPU_AGC_CLOCK_SAMPLES", who);
+    return IQGPU_OK;
+}
+
+// agc_variant: iqgpu_chain_seek_agc -- the preroll with the AGC out of the way, then *entry (or the fresh state) installed
+static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, bool on_device,
+                     bool agc_variant = false, const iqgpu_agc_state *entry = nullptr)
+{
+    const char *who = agc_variant ? "iqgpu_chain_seek_agc" : "iqgpu_chain_seek";
+    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
+    // what iqgpu_chain_reset does comes first: batches in flight and a pending verdict resolved, histories and dc state zeroed,
+    // the poison cleared -- a refused argument below leaves the chain reset
+    int rc = iqgpu_chain_reset(c); if (rc) return rc;
+    c->fpending = 0;                                          // (reset keeps the FFT remainder queued: a seek starts a stream)
+    if (agc_variant) {
+        rc = agc_two_pass_check(c, who); if (rc) return rc;
+        if (entry && (entry->locked != 0 && entry->locked != 1)) return fail(IQGPU_EINVAL, "%s: entry state with locked = %d", who, entry->locked);
+    }
+    if (first_frame > kMaxStreamFrames) return fail(IQGPU_EINVAL, "%s: frame %llu is beyond 2^39 frames", who,
+        (unsigned long long)first_frame);
+    if ((uint64_t)preroll_frames > first_frame) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames would start in front of "
+        "frame 0 (first_frame %llu)", who, preroll_frames, (unsigned long long)first_frame);
+    if (first_frame > 0) {
+        if (c->agc && !agc_variant) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
+            "not on a bounded warm-up");
+        const uint64_t memory = seek_preroll_frames(c), need = first_frame < memory ? first_frame : memory;
+        if ((uint64_t)preroll_frames < need) return fail(IQGPU_EINVAL, "%s: preroll of %zu frames is shorter than the %llu "
+            "this chain needs at frame %llu", who, preroll_frames, (unsigned long long)need, (unsigned long long)first_frame);
+        if (preroll_frames && !preroll) return fail(IQGPU_EINVAL, "%s: NULL preroll", who);
+
+        const StreamAt from = stream_at(c, first_frame - (uint64_t)preroll_frames);
+        if (c->fp.enabled) {
+            // [L-1 history][pending]: zeros stand for the samples in front of the warm-up
+            const size_t front = c->fp.taps.size() - 1 + (size_t)from.pos.fpending;
+            rc = c->fbuf[c->fcur].ensure((front + 1) * sizeof(cf2)); if (rc) return rc;
+            HIP_TRY(hipMemsetAsync(c->fbuf[c->fcur].p, 0, front * sizeof(cf2), c->stream));
+        }
+        c->rem = from.pos.rem; c->phi = from.pos.phi; c->fpending = from.pos.fpending;
+        c->nco_theta = from.nco_theta; c->pnco_theta = from.pnco_theta;
+
+        if (preroll_frames) {
+            const size_t obps = bytes_per_frame(c->desc.out_format);
+            const void *d_in = preroll;
+            if (!on_device) { rc = stage_host_input(c, preroll, preroll_frames, &d_in); if (rc) return rc; }
+            size_t dropped = 0;
+            if (agc_variant) {
+                // nothing of the preroll is kept and the AGC must not see it: the unfused route into abuf, no AGC kernel behind it
+                rc = process_device_impl(c, d_in, preroll_frames, nullptr, 0, &dropped, CallOpts{AgcMode::Drop});
+            } else {
+                rc = c->seek_sink.ensure((size_t)plan_call(c, preroll_frames).n_emit * obps + 16); if (rc) return rc;
+                rc = process_device_impl(c, d_in, preroll_frames, c->seek_sink.p, c->seek_sink.cap, &dropped);
+            }
+            if (rc) return rc;
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        // the warm-up has walked the position forward call-wise: it has to stand on the closed form at first_frame
+        const StreamAt to = stream_at(c, first_frame);
+        if (c->rem != to.pos.rem || c->phi != to.pos.phi || c->fpending != to.pos.fpending || c->nco_theta != to.nco_theta ||
+            c->pnco_theta != to.pnco_theta) {
+            c->poisoned = true;
+            return fail(IQGPU_EINVAL, "internal: the position behind the preroll is not the closed form at frame %llu", (unsigned long long)first_frame);
+        }
+    }
+    if (agc_variant && entry) {
+        // The AGC state of the stream at first_frame, everywhere the chain keeps it: the device state the kernels read, and the host's
+        // mirrors of "has the stream locked" and of samples_seen, from which the fused / unfused split of every later call follows
+        // (agc_unfused_head).  The reset above has left the rest as on a chain that arrived here by processing: no pending verdict,
+        // the verifier's eight words at their initial values (no healthy chunk recorded for the call to come), the peak array marked
+        // dirty so that the first fused launch clears it.
+        static_assert(sizeof(iqgpu_agc_state) == sizeof(AgcState), "AGC state layout");
+        AgcState st;
+        memcpy(&st, entry, sizeof(st));
+        st.reserved = 0;
+        HIP_TRY(hipMemcpyAsync(c->d_agc_state, &st, sizeof(AgcState), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        c->agc_locked_host = st.locked != 0;
+        c->agc_seen_host = st.seen;
+    }
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_chain_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames)
+{
+    return seek_impl(c, first_frame, preroll, preroll_frames, false);
+}
+extern "C" int iqgpu_chain_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames)
+{
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, true);
+}
+extern "C" int iqgpu_chain_seek_agc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames,
+                                    const iqgpu_agc_state *entry)
+{
+    return seek_impl(c, first_frame, preroll, preroll_frames, false, true, entry);
+}
+extern "C" int iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
+                                           const iqgpu_agc_state *entry)
+{
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, true, true, entry);
+}
+
+// ------------------------------------------------------------------------------------------------
+// seamless sharding of digital-AGC chains (ABI v8): the measure pass, and the walk over its tables
+// ------------------------------------------------------------------------------------------------
+static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows, bool on_device)
+{
+    static_assert(sizeof(iqgpu_agc_chunk) == sizeof(AgcRow) && sizeof(AgcRow) == 16, "AGC row layout");
+    int rc = agc_two_pass_check(c, "iqgpu_chain_measure"); if (rc) return rc;
+    if (!n_rows) return fail(IQGPU_EINVAL, "iqgpu_chain_measure: NULL argument");
+    *n_rows = 0;
+    if (frames_in == 0) return IQGPU_OK;
+    if (!in || !rows) return fail(IQGPU_EINVAL, "iqgpu_chain_measure: NULL buffer");
+    const size_t n = (frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk;
+    if (cap < n) return fail(IQGPU_ECAPACITY, "iqgpu_chain_measure: %zu frames are %zu chunks, the table holds %zu rows", frames_in, n, cap);
+    HIP_TRY(hipSetDevice(c->device));
+    rc = pipe_advance(c, c->pipe_seq); if (rc) return rc;         // batches submitted earlier come first (same stream)
+    rc = agc_resolve_pending(c); if (rc) return rc;
+    const void *d_in = in;
+    if (!on_device) { rc = stage_host_input(c, in, frames_in, &d_in); if (rc) return rc; }
+    size_t dropped = 0;
+    // which route: chain.hpp (AgcMode); the faster one measured per shape (tools/bench_measure.py, DESIGN 5.1, 2^28 frames).
+    // Chains without a half-band stage (the cu8-nrsc5 presets: one output per 1.6 input frames, so the cf32 stream of the unfused
+    // route is its largest) take k_front_s1<.., AGC>: 0.665 ms against 0.747.  With a half-band stage the unfused route wins
+    // (NRSC-5 cs16: 0.576 against 0.655); cascades were not timed and keep it.  The "measure_route" switch overrides.
+    const bool s1 = c->agc_fusable && (c->sw.measure_route == 1 || (c->sw.measure_route < 0 && c->S == 0 && !c->cascade));
+    rc = process_device_impl(c, d_in, frames_in, nullptr, 0, &dropped, CallOpts{s1 ? AgcMode::MeasureS1 : AgcMode::Measure});
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(rows, c->agc_rows.p, n * sizeof(AgcRow), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    *n_rows = n;
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_chain_measure(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows)
+{
+    return measure_impl(c, raw_in, frames_in, rows, cap, n_rows, false);
+}
+extern "C" int iqgpu_chain_measure_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap,
+                                          size_t *n_rows)
+{
+    return measure_impl(c, d_raw_in, frames_in, rows, cap, n_rows, true);
+}
+
+extern "C" int iqgpu_chain_agc_initial_state(const iqgpu_chain *c, iqgpu_agc_state *st)
+{
+    if (!c || !st) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_initial_state: NULL argument");
+    if (!c->agc) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_initial_state: the chain has no output AGC");
+    AgcState s0 = c->agc_init;
+    if (c->desc.agc_clock != IQGPU_AGC_CLOCK_WALL) s0.last_strong = 0.0;
+    memcpy(st, &s0, sizeof(s0));
+    return IQGPU_OK;
+}
+
+// One definition of the walk: the tables go to device memory and k_agc_scan -- the kernel behind every unfused call -- walks them
+// from a scratch copy of *st, a batch of 2^20 rows per launch (the kernel's chunk index is 32-bit; a whole stream of 2^39 frames
+// can hold 2^25 rows).  The kernel carries its state from launch to launch exactly as from call to call.
+extern "C" int iqgpu_chain_agc_advance(iqgpu_chain *c, iqgpu_agc_state *st, const iqgpu_agc_chunk *rows, size_t n, float *gains)
+{
+    int rc = agc_two_pass_check(c, "iqgpu_chain_agc_advance"); if (rc) return rc;
+    if (!st || (n && !rows)) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_advance: NULL argument");
+    if (n == 0) return IQGPU_OK;
+    // (k_agc_scan adds the lengths of the 64 rows of a batch in 32 bits: the bound chain_create puts on agc_chunk_frames, here on
+    //  any 64 consecutive rows of a table the caller may have built)
+    uint64_t window = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (rows[i].frames_out > 0x7fffffffu || !(rows[i].peak2 >= 0.0)) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_advance: row %zu is "
+            "not a row of iqgpu_chain_measure (frames_out %u, peak2 %g)", i, rows[i].frames_out, rows[i].peak2);
+        window += rows[i].frames_out;
+        if (i >= 64) window -= rows[i - 64].frames_out;
+        if (window >= 0x80000000ull) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_advance: the 64 rows that end at row %zu hold %llu "
+            "frames (64 consecutive rows must stay below 2^31)", i, (unsigned long long)window);
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    constexpr size_t kBatch = (size_t)1 << 20;
+    const size_t nb_max = n < kBatch ? n : kBatch;
+    // [state][peak2 x nb_max][len x nb_max][gain x nb_max]
+    rc = c->agc_walk.ensure(64 + nb_max * (sizeof(unsigned long long) + sizeof(int32_t) + sizeof(float))); if (rc) return rc;
+    AgcState *d_st = (AgcState *)c->agc_walk.p;
+    unsigned long long *d_p2 = (unsigned long long *)((char *)c->agc_walk.p + 64);
+    int32_t *d_len = (int32_t *)(d_p2 + nb_max);
+    float *d_gain = (float *)(d_len + nb_max);
+    std::vector<unsigned long long> h_p2(nb_max);
+    std::vector<int32_t> h_len(nb_max);
+    HIP_TRY(hipMemcpyAsync(d_st, st, sizeof(AgcState), hipMemcpyHostToDevice, c->stream));
+    for (size_t done = 0; done < n; done += kBatch) {
+        const size_t nb = n - done < kBatch ? n - done : kBatch;
+        for (size_t i = 0; i < nb; ++i) {
+            memcpy(&h_p2[i], &rows[done + i].peak2, sizeof(double));
+            h_len[i] = (int32_t)rows[done + i].frames_out;
+        }
+        HIP_TRY(hipMemcpyAsync(d_p2, h_p2.data(), nb * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(d_len, h_len.data(), nb * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        AgcArgs a{};
+        a.geom.n_chunks = (int32_t)nb;
+        a.peak2 = d_p2; a.chunk_len = d_len; a.gain = d_gain; a.state = d_st;
+        a.target = c->agc_target; a.rate = c->target_rate;
+        HIP_TRY(launch_agc_walk(a, c->stream));
+        if (gains) HIP_TRY(hipMemcpyAsync(gains + done, d_gain, nb * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));             // (the staging vectors are reused by the next batch)
+    }
+    HIP_TRY(hipMemcpy(st, d_st, sizeof(AgcState), hipMemcpyDeviceToHost));
+    return IQGPU_OK;
+}
