@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define IQGPU_ABI_VERSION 8
+#define IQGPU_ABI_VERSION 9
 
 /* Sample formats: numerically equal to the reference's format_t (include/common_types.h:33-37) */
 enum {
@@ -60,10 +60,9 @@ enum {
     IQGPU_EFILTER = -7,     /* filter band beyond output Nyquist, fft size too small, too many stages (src/filter.c:80-84, 321-325) */
     IQGPU_ECAPACITY = -8,   /* out_capacity_bytes too small for this call */
     IQGPU_EHIP = -9,        /* a HIP runtime call failed */
-    IQGPU_EUNSUPPORTED = -10/* the placement calls when a *_VISIBLE_DEVICES list is not plain indices; iqgpu_chain_seek and the two    */
-                            /* seamless-sharding design calls for a chain with the output AGC (no finite warm-up bounds its state:     */
-                            /* the digital profile goes through iqgpu_chain_measure / _agc_advance / _seek_agc instead); those three  */
-                            /* v8 calls for the profiles dx / local and for IQGPU_AGC_CLOCK_WALL                                       */
+    IQGPU_EUNSUPPORTED = -10/* the placement calls: a *_VISIBLE_DEVICES list that is not plain indices                */
+                            /* iqgpu_chain_seek and the two range-design calls: a chain with the output AGC              */
+                            /* the AGC two-pass calls (measure*, agc_advance, seek_agc*): profile dx / local, CLOCK_WALL */
 };
 
 typedef struct iqgpu_chain iqgpu_chain; /* opaque, like resampler_t (include/resampler.h:25-26) */
@@ -263,7 +262,8 @@ int    iqgpu_chain_seek_device(iqgpu_chain *c, uint64_t first_frame, const void 
  *      Cut points are multiples of lcm(agc_chunk_frames, the frames per process call) -- the digital AGC works on the chunks of each
  *      call, so every call of every chain has to lie on the single stream's call and chunk grid -- and of 4096 (see above).
  *   1. Measure (all ranges but the last, in parallel): iqgpu_chain_seek_agc(c, first, preroll, P', NULL) with P' = min(first, P),
- *      then iqgpu_chain_measure over the range in the calls the single stream would make.  Every call yields one iqgpu_agc_chunk row
+ *      then iqgpu_chain_measure (from host memory: iqgpu_chain_measure_submit / _collect) over the range in the calls the single
+ *      stream would make.  Every call yields one iqgpu_agc_chunk row
  *      per chunk; keep them in order.
  *   2. Walk (any one chain, a fraction of a second): st = iqgpu_chain_agc_initial_state; for every range s in order:
  *      entry[s] = st, then iqgpu_chain_agc_advance(c, &st, rows of range s, n, NULL).
@@ -284,6 +284,20 @@ typedef struct {
  * no pack, no samples to the host.  Both variants return with the chain's stream idle and the rows in `rows` (host memory). */
 int    iqgpu_chain_measure(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows);
 int    iqgpu_chain_measure_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows);
+/* Pipelined form of iqgpu_chain_measure (ABI v9), as iqgpu_chain_submit is of iqgpu_chain_process: pass 1 of a host-fed job at the
+ * rate of the copy engine instead of copy, kernels and row copy one after the other.  The batch takes a slot of the SAME pipeline
+ * as iqgpu_chain_submit -- same tickets, same iqgpu_chain_pipeline_depth() -- and is collected with iqgpu_chain_collect(c, ticket).
+ * *n_rows = ceil(frames_in / agc_chunk_frames) is exact on return; the rows themselves are copied into `rows` (host memory, pinned
+ * for the copy to be asynchronous) by the batch's drain step and are there once the ticket is collected.  raw_in and rows must stay
+ * untouched until then.  Batches run in submit order on the chain's stream, and measure batches may be mixed with iqgpu_chain_submit
+ * batches on one chain: they advance the one stream position in order, as mixed process / measure calls do.  A measure batch neither
+ * reads nor writes the AGC state, so its launch never waits for an AGC verdict of its own; the verdict a process batch in front of
+ * it still owes is resolved first, as before any batch.  frames_in == 0 takes a ticket and yields no rows.  Errors: those of
+ * iqgpu_chain_measure (IQGPU_EINVAL without the output AGC, IQGPU_EUNSUPPORTED for dx / local and the wall clock, IQGPU_ECAPACITY
+ * when cap is below the row count) and the pipeline's (IQGPU_EINVAL when every slot is in flight; a kernel failure is reported by
+ * the call that launches the batch); a refused call leaves the handle exactly as it was. */
+int    iqgpu_chain_measure_submit(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap,
+                                  size_t *n_rows, uint64_t *ticket);
 /* agc_apply's state machine over a table: *st is advanced over rows[0 .. n) (rows with frames_out == 0 are skipped, as empty chunks
  * never reach agc_apply); gains, if not NULL, receives the gain every row is multiplied with (n floats).  It runs the kernel that
  * walks the chunks of an ordinary call, so the state and the gains are the ordinary path's bit for bit, however the rows are grouped

@@ -117,6 +117,7 @@ SYMBOLS = [
     ("iqgpu_chain_seek_device", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
     ("iqgpu_chain_measure", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     ("iqgpu_chain_measure_device", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_chain_measure_submit", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64)]),
     ("iqgpu_chain_agc_advance", C.c_int, [_vp, C.POINTER(AgcState), _vp, _sz, _vp]),
     ("iqgpu_chain_agc_initial_state", C.c_int, [_vp, C.POINTER(AgcState)]),
     ("iqgpu_chain_seek_agc", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(AgcState)]),

@@ -224,7 +224,7 @@ class Chain:
         """seek() with the preroll already in device memory of this chain's GPU (a device address as an int)"""
         check(self._lib.iqgpu_chain_seek_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames)))
 
-    # ---- seamless sharding of digital-AGC chains: measure, walk, seek with the walked state (include/iqgpu.h, ABI v8) ----
+    # ---- seamless sharding of digital-AGC chains: measure, walk, seek with the walked state (include/iqgpu.h, ABI v8 / v9) ----
     def measure(self, raw):
         """consumes raw exactly as process() would, emits nothing, leaves the AGC state alone; returns one AGC_ROW record per
         agc_chunk_frames-sized chunk of this call: the peak (squared, double) in front of the gain and the chunk's frames"""
@@ -245,6 +245,46 @@ class Chain:
         check(self._lib.iqgpu_chain_measure_device(self._h, C.c_void_p(d_in), int(frames_in), rows.ctypes.data_as(C.c_void_p), rows.size,
                                                    C.byref(got)))
         return rows[:got.value]
+
+    def measure_submit(self, in_ptr, frames_in, rows_ptr, cap):
+        """measure() through the pipeline of submit(): queues one batch (host addresses, preferably pinned; rows_ptr holds cap
+        AGC_ROW records) and returns (n_rows, ticket) at once; the rows are there once collect(ticket) returns"""
+        got, ticket = C.c_size_t(0), C.c_uint64(0)
+        check(self._lib.iqgpu_chain_measure_submit(self._h, C.c_void_p(in_ptr), int(frames_in), C.c_void_p(rows_ptr), int(cap),
+                                                   C.byref(got), C.byref(ticket)))
+        return got.value, ticket.value
+
+    def measure_pipelined(self, raw, batch_frames):
+        """measure() through measure_submit / collect: the stream in batches of batch_frames (each cut into AGC chunks from its
+        first frame, like a measure() call of that batch) with up to iqgpu_chain_pipeline_depth() of them in flight, pinned
+        buffers on both sides.  Returns the rows of all batches in order."""
+        raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
+        n = raw.nbytes // self.in_bytes
+        depth = self._lib.iqgpu_chain_pipeline_depth()
+        chunk = int(self.desc.agc_chunk_frames) or 16384
+        cap = -(-int(batch_frames) // chunk)
+        slots = [(PinnedBuffer(batch_frames * self.in_bytes), PinnedBuffer(cap * AGC_ROW.itemsize)) for _ in range(depth)]
+        outs, flight = [], []
+
+        def drain_one():
+            t, got, rb = flight.pop(0)
+            self.collect(t)
+            outs.append(rb.array[:got * AGC_ROW.itemsize].view(AGC_ROW).copy())
+
+        pos = i = 0
+        while pos < n:
+            f = min(batch_frames, n - pos)
+            if len(flight) == depth:
+                drain_one()
+            ib, rb = slots[i % depth]
+            ib.array[:f * self.in_bytes] = raw[pos * self.in_bytes:(pos + f) * self.in_bytes]
+            got, t = self.measure_submit(ib.ptr, f, rb.ptr, cap)
+            flight.append((t, got, rb))
+            pos += f
+            i += 1
+        while flight:
+            drain_one()
+        return np.concatenate(outs) if outs else np.zeros(0, AGC_ROW)
 
     def agc_initial_state(self):
         """the AGC state of a fresh stream as an AgcState (what agc_advance and seek_agc take)"""

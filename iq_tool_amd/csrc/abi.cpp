@@ -170,7 +170,7 @@ static void free_device_state(iqgpu_chain *c)
     if (c->h_probe) (void)hipHostFree(c->h_probe);
     if (c->probe_done) (void)hipEventDestroy(c->probe_done);
     for (auto &ps : c->pipe) {
-        ps.d_in.release(); ps.d_out.release();
+        ps.d_in.release(); ps.d_out.release(); ps.d_rows.release();
         if (ps.in_done) (void)hipEventDestroy(ps.in_done);
         if (ps.k_done) (void)hipEventDestroy(ps.k_done);
         if (ps.all_done) (void)hipEventDestroy(ps.all_done);

@@ -70,13 +70,13 @@ int Call::stage_agc()
 }
 
 // the measure pass (iqgpu_chain_measure): the call's last stage has left cf32 in abuf as in front of the lock; one kernel reads it
-// once and leaves the call's rows in agc_rows.  The AGC state, its host mirrors and the peak arrays of the ordinary path stay as
+// once and leaves the call's rows in agc_rows (a pipelined batch: in its slot's table).  The AGC state, its host mirrors and the peak arrays of the ordinary path stay as
 // they are.
 int Call::stage_agc_measure()
 {
     AgcMeasureArgs ma{};
     ma.geom = agc_geom();
-    ma.x = (const cf2 *)c->abuf.p; ma.rows = (AgcRow *)c->agc_rows.p;
+    ma.x = (const cf2 *)c->abuf.p; ma.rows = measure_rows();
     ma.splits = agc_splits(p.n_emit, ma.geom.n_chunks);
     KernelTimer kt(c, IQGPU_K_AGC);
     HIP_TRY(launch_agc_measure(ma, c->stream));
@@ -88,7 +88,7 @@ int Call::stage_agc_rows_from_peaks()
 {
     AgcMeasureArgs ma{};
     ma.geom = agc_geom();
-    ma.rows = (AgcRow *)c->agc_rows.p; ma.peak_in = (unsigned long long *)c->agc_peak.p; ma.splits = 1;
+    ma.rows = measure_rows(); ma.peak_in = (unsigned long long *)c->agc_peak.p; ma.splits = 1;
     KernelTimer kt(c, IQGPU_K_AGC);
     HIP_TRY(launch_agc_measure(ma, c->stream));
     return IQGPU_OK;

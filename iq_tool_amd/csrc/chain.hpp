@@ -5,7 +5,7 @@
 //   process.cpp    one process() call: buffers, the stages in stream order, iqgpu_chain_process[_device]
 //   seek.cpp       seamless range sharding: iqgpu_chain_seek[_agc], iqgpu_chain_measure, iqgpu_chain_agc_initial_state / _advance
 //   agc_host.cpp   host side of the output AGC: chunk map, fused / unfused split, verifier + fallback launches
-//   pipeline.cpp   iqgpu_chain_submit / _collect (pinned host buffers, three stages moved along by the host)
+//   pipeline.cpp   iqgpu_chain_submit / _measure_submit / _collect (pinned host buffers, three stages moved along by the host)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -69,7 +69,7 @@ struct DebugSwitches {
     int fft_log2n = 0;            // "fft_log2n": overlap-save transform size (applies when it holds the taps; 0 = chosen)
     int fft_threads = 0;          // "fft_threads": k_fftconv16's workgroup size (0 = chosen)
     bool fft_keep_geometry = false;   // "fft_geometry" = "keep": the two filter kernels on k_p0fft16's transform size and windows
-    int measure_route = -1;       // "measure_route" = "unfused" | "s1": the route of iqgpu_chain_measure (-1: the faster one measured for the shape, measure_impl in seek.cpp)
+    int measure_route = -1;       // "measure_route" = "unfused" | "s1": the route of iqgpu_chain_measure (-1: the faster one measured for the shape, measure_route() in seek.cpp)
     int casc2_min_run = 0;        // "casc2_min_run": shortest streaming run (tiles) that takes k_cascade2 (0 = the built-in bound)
 };
 DebugSwitches debug_switches();                        // abi.cpp: the table as it stands, under one lock
@@ -194,14 +194,17 @@ struct iqgpu_chain {
     float *d_ihb = nullptr;
     DevBuf stage_in, stage_out;
     DevBuf seek_sink;             // where iqgpu_chain_seek's warm-up run writes what it emits (dropped)
-    // pipelined host entry point (iqgpu_chain_submit / _collect): kPipeSlots batches in flight.  H2D copies, kernels
-    // (the chain's stream) and D2H copies each have their own stream; a batch moves to the next stage inside a later
+    // pipelined host entry point (iqgpu_chain_submit / _measure_submit / _collect): kPipeSlots batches in flight.  H2D copies,
+    // kernels (the chain's stream) and D2H copies each have their own stream; a batch moves to the next stage inside a later
     // submit / collect, once the host has seen the previous stage finish (no device-side event waits: see pipe_advance)
     struct PipeSlot {
         hipEvent_t in_done = nullptr, k_done = nullptr, all_done = nullptr;
         DevBuf d_in, d_out; uint64_t ticket = 0; bool busy = false;
         size_t frames_in = 0, n_emit = 0; void *out = nullptr;
         float iq_mag = 0.0f, iq_phase = 0.0f;          // correction factors as of submit()
+        // a batch of the measure pass (iqgpu_chain_measure_submit): nothing of its n_emit frames is copied back; its n_rows rows go
+        // from the slot's own table (the chain's agc_rows would be overwritten by the next batch before the copy has run) to `rows`
+        bool measure = false; DevBuf d_rows; size_t n_rows = 0; iqgpu_agc_chunk *rows = nullptr;
     };
     PipeSlot pipe[kPipeSlots];
     static constexpr int kCopyStreams = 4;                // small copies rotate over them, large ones keep to the first
@@ -293,6 +296,7 @@ struct CallOpts {                 // what an entry point asks of ONE call (proce
     AgcMode agc = AgcMode::Ordinary;
     bool host_verdict = false;    // the host-ordered entry points: the verdict of a fused launch on the host (iqgpu_chain::h_agc_verdict)
     bool iq_fixed = false; float iq_mag = 0.0f, iq_phase = 0.0f;   // a pipelined batch: the correction factors as of its submit()
+    AgcRow *rows = nullptr;       // Measure / MeasureS1: where the rows go on the device (a pipelined batch: its slot's table; nullptr: agc_rows)
 };
 
 struct Call {
@@ -341,6 +345,7 @@ struct Call {
         dst.p0_k_a = cplan.p0_k_a; dst.p0_k_b = cplan.p0_k_b; dst.p0_f_max = cplan.p0_f_max;
     }
     int raw_aligned() const { return (((uintptr_t)d_raw_in) & 15u) == 0 ? 1 : 0; }
+    AgcRow *measure_rows() const { return o.rows ? o.rows : (AgcRow *)c->agc_rows.p; }   // the device table of a measuring call
     // the per-chunk peaks a fused front launch accumulates into start from zero: k_agc_classify zeroes what it has read (agc_peak
     // and agc_peak_b), so only the first fused call behind an unfused one (or behind a reallocation) pays for a fill
     hipError_t clean_agc_peaks()
@@ -383,5 +388,8 @@ size_t agc_unfused_head(const iqgpu_chain *c, size_t frames_in, bool *locks);   
 // behind a fused launch whose fallback waits for the verdict on the host: waits for the word, launches the fallback when it is set
 // (*ran = true then).  No-op without a pending verdict.
 int agc_resolve_pending(iqgpu_chain *c, bool *ran = nullptr);                             // agc_host.cpp
+// seek.cpp: what the two-pass calls ask of a chain (the digital output AGC on the sample clock), and the route of its measure pass
+int agc_two_pass_check(const iqgpu_chain *c, const char *who);
+AgcMode measure_route(const iqgpu_chain *c);
 int pipe_advance(iqgpu_chain *c, uint64_t upto);   // pipeline.cpp: queues the kernels of every submitted batch up to ticket `upto`
 int pipe_drain(iqgpu_chain *c, uint64_t upto);     // ... and their D2H copies

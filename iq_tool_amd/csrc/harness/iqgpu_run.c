@@ -233,18 +233,27 @@ static void *run_shard(void *arg)
         }
         if (sh->shard < o->shards - 1) {
             const size_t cap = (size_t)((sh->frames + (long long)chunk - 1) / (long long)chunk) * ((chunk + agc_chunk - 1) / agc_chunk) + 1;
-            sh->rows = (iqgpu_agc_chunk *)malloc(cap * sizeof(iqgpu_agc_chunk));
-            if (!sh->rows) { snprintf(sh->err, sizeof(sh->err), "out of memory for a table of %zu rows", cap); sh->rc = -1; goto done; }
+            /* (pinned: the rows of a batch are copied out asynchronously, behind the kernels of the next one) */
+            void *table = NULL;
+            if (iqgpu_host_malloc_pinned(cap * sizeof(iqgpu_agc_chunk), &table) != IQGPU_OK) { snprintf(sh->err, sizeof(sh->err), "out of memory for a table of %zu rows", cap); sh->rc = -1; goto done; }
+            sh->rows = (iqgpu_agc_chunk *)table;
             CK(iqgpu_chain_seek_agc(chain, (uint64_t)sh->first_frame, pre, np, NULL));
-            for (long long at = 0; at < sh->frames; at += (long long)chunk) {
+            /* the batch grid and the two pinned input buffers of the ordinary pass below, through the chain's own pipeline: batch i is
+             * read while the copy of batch i-1 and the kernels of batch i-2 run; buffer i % 2 is free once batch i-2 is collected */
+            uint64_t tk[NBUF] = {0};
+            long long i = 0;
+            for (long long at = 0; at < sh->frames; at += (long long)chunk, i++) {
+                const int b = (int)(i % NBUF);
                 size_t n = chunk, got = 0;
                 if ((long long)n > sh->frames - at) n = (size_t)(sh->frames - at);
+                if (tk[b]) { CK(iqgpu_chain_collect(chain, tk[b])); tk[b] = 0; }
                 if (o->synthetic_frames <= 0 || o->have_hash) {
-                    if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame + at, n, h_in[0], sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
+                    if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame + at, n, h_in[b], sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
                 }
-                CK(iqgpu_chain_measure(chain, h_in[0], n, sh->rows + sh->agc_rows, cap - (size_t)sh->agc_rows, &got));
+                CK(iqgpu_chain_measure_submit(chain, h_in[b], n, sh->rows + sh->agc_rows, cap - (size_t)sh->agc_rows, &got, &tk[b]));
                 sh->agc_rows += (long long)got;
             }
+            for (int b = 0; b < NBUF; b++) if (tk[b]) CK(iqgpu_chain_collect(chain, tk[b]));
         }
         sh->measure_seconds = now_s() - t_m;
         /* the walk: one thread, the tables in shard order, the state in front of every shard kept */
@@ -586,7 +595,7 @@ int main(int argc, char **argv)
         }
         printf("]}\n");
     }
-    for (int s = 0; s < o.shards; s++) free(sh[s].rows);
+    for (int s = 0; s < o.shards; s++) if (sh[s].rows) iqgpu_host_free_pinned(sh[s].rows);
     free(th); free(sh);
     return rc;
 }

@@ -1,4 +1,4 @@
-// pipeline.cpp -- iqgpu_chain_submit / _collect: the chain fed from pinned host memory, kPipeSlots batches in flight.
+// pipeline.cpp -- iqgpu_chain_submit / _measure_submit / _collect: the chain fed from pinned host memory, kPipeSlots batches in flight.
 #include "chain.hpp"
 
 // ---- pipelined host entry point ----------------------------------------------------------------------
@@ -53,10 +53,15 @@ int pipe_advance(iqgpu_chain *c, uint64_t upto)
             // (the host orders every stage of a batch: the AGC verdict of a fused launch is read on the host -- by the next batch's
             //  launch or by this batch's D2H copy, whichever comes first -- and the fallback kernels are launched only when it is set)
             o.host_verdict = true;
-            rc = process_device_impl(c, ps.d_in.p, ps.frames_in, ps.d_out.p, ps.d_out.cap, &produced, o);
+            if (ps.measure) {
+                // a batch of the measure pass: iqgpu_chain_measure's call (seek.cpp) with the rows into the slot's own table.  It reads
+                // and writes no AGC state and leaves no verdict; the position and the histories advance as for any batch
+                o.agc = measure_route(c); o.rows = (AgcRow *)ps.d_rows.p;
+                rc = process_device_impl(c, ps.d_in.p, ps.frames_in, nullptr, 0, &produced, o);
+            } else rc = process_device_impl(c, ps.d_in.p, ps.frames_in, ps.d_out.p, ps.d_out.cap, &produced, o);
             if (!rc && produced != ps.n_emit) rc = fail(IQGPU_EHIP, "internal: batch produced %zu frames, planned %zu", produced,
                 ps.n_emit);
-            if (rc) ps.n_emit = 0;                               // nothing of a failed batch is copied back
+            if (rc) ps.n_emit = ps.n_rows = 0;                   // nothing of a failed batch is copied back
         }
         ++c->pipe_launched;
         HIP_TRY(hipEventRecord(ps.k_done, c->stream));
@@ -65,17 +70,17 @@ int pipe_advance(iqgpu_chain *c, uint64_t upto)
     return IQGPU_OK;
 }
 
-// D2H copy of every launched batch up to ticket `upto`, on the D2H stream
+// D2H copy of every launched batch up to ticket `upto`, on the D2H stream: its output frames, or the rows of a measure batch
 int pipe_drain(iqgpu_chain *c, uint64_t upto)
 {
     if (!c->pipe_ready) return IQGPU_OK;
     if (upto > c->pipe_launched) upto = c->pipe_launched;
     while (c->pipe_copied < upto) {
         iqgpu_chain::PipeSlot &ps = c->pipe[c->pipe_copied % iqgpu_chain::kPipeSlots];
-        hipStream_t d2h = c->pipe_d2h[ps.n_emit * bytes_per_frame(c->desc.out_format) <= kSmallCopy
-            ? c->pipe_copied % (uint64_t)iqgpu_chain::kCopyStreams : 0];
+        const size_t bytes = ps.measure ? ps.n_rows * sizeof(AgcRow) : ps.n_emit * bytes_per_frame(c->desc.out_format);
+        hipStream_t d2h = c->pipe_d2h[bytes <= kSmallCopy ? c->pipe_copied % (uint64_t)iqgpu_chain::kCopyStreams : 0];
         HIP_TRY(hipSetDevice(c->device));
-        if (ps.n_emit) {
+        if (bytes) {
             HIP_TRY(hipEventSynchronize(ps.k_done));
             if (c->pend.valid && c->pipe_copied + 1 == c->pipe_launched) {
                 // the last batch launched is this one and its verdict is still out (no later launch has asked for it): read it now;
@@ -84,25 +89,23 @@ int pipe_drain(iqgpu_chain *c, uint64_t upto)
                 const int vrc = agc_resolve_pending(c, &ran); if (vrc) return vrc;
                 if (ran) HIP_TRY(hipStreamSynchronize(c->stream));
             }
-            HIP_TRY(hipMemcpyAsync(ps.out, ps.d_out.p, ps.n_emit * bytes_per_frame(c->desc.out_format), hipMemcpyDeviceToHost, d2h));
+            HIP_TRY(hipMemcpyAsync(ps.measure ? (void *)ps.rows : ps.out, ps.measure ? ps.d_rows.p : ps.d_out.p, bytes, hipMemcpyDeviceToHost, d2h));
         }
         ++c->pipe_copied;
-        HIP_TRY(hipEventRecord(ps.all_done, ps.n_emit ? d2h : c->stream));
+        HIP_TRY(hipEventRecord(ps.all_done, bytes ? d2h : c->stream));
     }
     return IQGPU_OK;
 }
 
-extern "C" int iqgpu_chain_submit(iqgpu_chain *c, const void *raw_in, size_t frames_in,
-                                  void *out, size_t out_capacity_bytes, size_t *frames_out, uint64_t *ticket)
+// One batch into the pipeline: iqgpu_chain_submit (n_emit frames come back in `out`) and
+// iqgpu_chain_measure_submit (measure: n_rows rows come back in `rows`).  The arguments have been checked; `who` names the entry point.
+static int pipe_submit(iqgpu_chain *c, const char *who, bool measure, const void *raw_in, size_t frames_in, void *out,
+                       size_t out_capacity_bytes, iqgpu_agc_chunk *rows, size_t n_rows, size_t *frames_out, uint64_t *ticket)
 {
-    if (!c || !frames_out || !ticket) return fail(IQGPU_EINVAL, "iqgpu_chain_submit: NULL argument");
-    *frames_out = 0; *ticket = 0;
-    if (frames_in != 0 && (!raw_in || !out)) return fail(IQGPU_EINVAL, "iqgpu_chain_submit: NULL buffer");
-    if (frames_in > ((size_t)1 << 40)) return fail(IQGPU_EINVAL, "frames_in too large");
     HIP_TRY(hipSetDevice(c->device));
     int rc = pipe_init(c); if (rc) return rc;
     iqgpu_chain::PipeSlot &ps = c->pipe[c->pipe_seq % iqgpu_chain::kPipeSlots];
-    if (ps.busy) return fail(IQGPU_EINVAL, "iqgpu_chain_submit: %d batches are in flight; collect ticket %llu first",
+    if (ps.busy) return fail(IQGPU_EINVAL, "%s: %d batches are in flight; collect ticket %llu first", who,
                              iqgpu_chain::kPipeSlots, (unsigned long long)ps.ticket);
     const size_t ibps = bytes_per_frame(c->desc.in_format), obps = bytes_per_frame(c->desc.out_format);
     // Everything that can refuse the batch comes first and touches nothing: the exact output count (a closed form of the
@@ -114,11 +117,12 @@ extern "C" int iqgpu_chain_submit(iqgpu_chain *c, const void *raw_in, size_t fra
     else { at.rem = c->pipe_rem; at.phi = c->pipe_phi; at.fpending = c->pipe_fpending; }
     const CallPlan plan = plan_call_at(c, at, frames_in);
     const size_t n_emit = (size_t)plan.n_emit;
-    if (n_emit * obps > out_capacity_bytes)
+    if (!measure && n_emit * obps > out_capacity_bytes)
         return fail(IQGPU_ECAPACITY, "output buffer too small: need %zu bytes, have %zu", n_emit * obps, out_capacity_bytes);
     if (frames_in) {
         rc = ps.d_in.ensure(frames_in * ibps); if (rc) return rc;
-        rc = ps.d_out.ensure(n_emit * obps + 16); if (rc) return rc;
+        // (a measure batch emits nothing: its last stage writes into buffers the chain owns, as in iqgpu_chain_measure)
+        rc = measure ? ps.d_rows.ensure(n_rows * sizeof(AgcRow)) : ps.d_out.ensure(n_emit * obps + 16); if (rc) return rc;
     }
     // this batch's copy next (it needs nothing but the slot), so that the copy stream never idles while the host
     // queues the previous batch's kernels
@@ -139,9 +143,39 @@ extern "C" int iqgpu_chain_submit(iqgpu_chain *c, const void *raw_in, size_t fra
         : at.fpending; }
     else { c->pipe_rem = at.rem; c->pipe_phi = at.phi; c->pipe_fpending = at.fpending; }
     ps.frames_in = frames_in; ps.n_emit = n_emit; ps.out = out;
+    ps.measure = measure; ps.rows = rows; ps.n_rows = frames_in ? n_rows : 0;
     { std::lock_guard<std::mutex> g(c->aux_mu); ps.iq_mag = c->iq_mag; ps.iq_phase = c->iq_phase; }
     ps.ticket = ++c->pipe_seq; ps.busy = true;
     *ticket = ps.ticket; *frames_out = n_emit;
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_chain_submit(iqgpu_chain *c, const void *raw_in, size_t frames_in,
+                                  void *out, size_t out_capacity_bytes, size_t *frames_out, uint64_t *ticket)
+{
+    if (!c || !frames_out || !ticket) return fail(IQGPU_EINVAL, "iqgpu_chain_submit: NULL argument");
+    *frames_out = 0; *ticket = 0;
+    if (frames_in != 0 && (!raw_in || !out)) return fail(IQGPU_EINVAL, "iqgpu_chain_submit: NULL buffer");
+    if (frames_in > ((size_t)1 << 40)) return fail(IQGPU_EINVAL, "frames_in too large");
+    return pipe_submit(c, "iqgpu_chain_submit", false, raw_in, frames_in, out, out_capacity_bytes, nullptr, 0, frames_out, ticket);
+}
+
+// The measure pass of seamless AGC sharding through the pipeline (ABI v9): iqgpu_chain_measure's checks, then a slot like any other
+extern "C" int iqgpu_chain_measure_submit(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap,
+                                          size_t *n_rows, uint64_t *ticket)
+{
+    static_assert(sizeof(iqgpu_agc_chunk) == sizeof(AgcRow) && sizeof(AgcRow) == 16, "AGC row layout");
+    if (n_rows) *n_rows = 0;
+    if (ticket) *ticket = 0;
+    int rc = agc_two_pass_check(c, "iqgpu_chain_measure_submit"); if (rc) return rc;
+    if (!n_rows || !ticket) return fail(IQGPU_EINVAL, "iqgpu_chain_measure_submit: NULL argument");
+    if (frames_in != 0 && (!raw_in || !rows)) return fail(IQGPU_EINVAL, "iqgpu_chain_measure_submit: NULL buffer");
+    if (frames_in > ((size_t)1 << 40)) return fail(IQGPU_EINVAL, "frames_in too large");
+    const size_t n = (frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk;
+    if (cap < n) return fail(IQGPU_ECAPACITY, "iqgpu_chain_measure_submit: %zu frames are %zu chunks, the table holds %zu rows", frames_in, n, cap);
+    size_t emitted = 0;                                          // (what the batch would emit: the look-ahead position needs it, nobody else)
+    rc = pipe_submit(c, "iqgpu_chain_measure_submit", true, raw_in, frames_in, nullptr, 0, rows, n, &emitted, ticket); if (rc) return rc;
+    *n_rows = n;
     return IQGPU_OK;
 }
 

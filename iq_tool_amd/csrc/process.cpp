@@ -367,7 +367,7 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
         const size_t lead = c->agc_rms_alpha > 0.0f ? (size_t)c->agc_rms_warm : 0;
         int rc = c->abuf.ensure((lead + (size_t)k.p.n_emit + 1) * sizeof(cf2)); if (rc) return rc;
         k.fin_out = (cf2 *)c->abuf.p + lead; k.fin_fmt = IQGPU_FMT_CF32;
-        if (o.agc == AgcMode::Measure) {
+        if (o.agc == AgcMode::Measure && !o.rows) {
             rc = c->agc_rows.ensure((((size_t)frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk) * sizeof(AgcRow)); if (rc) return rc;
         }
     }
@@ -378,7 +378,7 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
         const void *was = c->agc_scratch.p;
         rc = c->agc_scratch.ensure(sizeof(AgcState)); if (rc) return rc;
         if (c->agc_scratch.p != was) HIP_TRY(hipMemcpyAsync(c->agc_scratch.p, &c->agc_init, sizeof(AgcState), hipMemcpyHostToDevice, c->stream));
-        rc = c->agc_rows.ensure((((size_t)frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk) * sizeof(AgcRow)); if (rc) return rc;
+        if (!o.rows) { rc = c->agc_rows.ensure((((size_t)frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk) * sizeof(AgcRow)); if (rc) return rc; }
     }
     k.plan_geometry();
     if (o.iq_fixed) { k.iq_mag = o.iq_mag; k.iq_phase = o.iq_phase; }                              // a pipelined batch: as of its submit()

@@ -1,12 +1,13 @@
-// seek.cpp -- seamless range sharding: a chain started mid-stream, the AGC measure pass (both: modes of process.cpp's call), the AGC walk
+// seek.cpp -- seamless range sharding: a chain started mid-stream, the AGC measure pass (both: modes of process.cpp's call; its pipelined
+// form is in pipeline.cpp), the AGC walk
 #include "chain.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // iqgpu_chain_seek: the chain at stream frame first_frame -- reset, the closed-form position preroll_frames earlier, and the
 // preroll through the ordinary per-call path with its output dropped (seamless range sharding, iqgpu.h)
 // ------------------------------------------------------------------------------------------------
-// what the v8 calls ask of a chain: the digital output AGC on the sample clock
-static int agc_two_pass_check(const iqgpu_chain *c, const char *who)
+// what the v8 / v9 calls ask of a chain: the digital output AGC on the sample clock
+int agc_two_pass_check(const iqgpu_chain *c, const char *who)
 {
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
     if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC", who);
@@ -116,6 +117,16 @@ extern "C" int iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame,
 // ------------------------------------------------------------------------------------------------
 // seamless sharding of digital-AGC chains (ABI v8): the measure pass, and the walk over its tables
 // ------------------------------------------------------------------------------------------------
+// Which route a measuring call takes (chain.hpp, AgcMode): the faster one measured per shape (tools/bench_measure.py, DESIGN 5.1,
+// 2^28 frames).  Chains without a half-band stage (the cu8-nrsc5 presets: one output per 1.6 input frames, so the cf32 stream of the
+// unfused route is its largest) take k_front_s1<.., AGC>: 0.665 ms against 0.747.  With a half-band stage the unfused route wins
+// (NRSC-5 cs16: 0.576 against 0.655); cascades were not timed and keep it.  The "measure_route" switch overrides.
+AgcMode measure_route(const iqgpu_chain *c)
+{
+    const bool s1 = c->agc_fusable && (c->sw.measure_route == 1 || (c->sw.measure_route < 0 && c->S == 0 && !c->cascade));
+    return s1 ? AgcMode::MeasureS1 : AgcMode::Measure;
+}
+
 static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows, bool on_device)
 {
     static_assert(sizeof(iqgpu_agc_chunk) == sizeof(AgcRow) && sizeof(AgcRow) == 16, "AGC row layout");
@@ -132,12 +143,7 @@ static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_
     const void *d_in = in;
     if (!on_device) { rc = stage_host_input(c, in, frames_in, &d_in); if (rc) return rc; }
     size_t dropped = 0;
-    // which route: chain.hpp (AgcMode); the faster one measured per shape (tools/bench_measure.py, DESIGN 5.1, 2^28 frames).
-    // Chains without a half-band stage (the cu8-nrsc5 presets: one output per 1.6 input frames, so the cf32 stream of the unfused
-    // route is its largest) take k_front_s1<.., AGC>: 0.665 ms against 0.747.  With a half-band stage the unfused route wins
-    // (NRSC-5 cs16: 0.576 against 0.655); cascades were not timed and keep it.  The "measure_route" switch overrides.
-    const bool s1 = c->agc_fusable && (c->sw.measure_route == 1 || (c->sw.measure_route < 0 && c->S == 0 && !c->cascade));
-    rc = process_device_impl(c, d_in, frames_in, nullptr, 0, &dropped, CallOpts{s1 ? AgcMode::MeasureS1 : AgcMode::Measure});
+    rc = process_device_impl(c, d_in, frames_in, nullptr, 0, &dropped, CallOpts{measure_route(c)});
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(rows, c->agc_rows.p, n * sizeof(AgcRow), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

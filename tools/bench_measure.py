@@ -4,11 +4,18 @@ chain has both: the unfused route (the chain's fastest kernels with cf32 out + k
 packed output into a sink (iqgpu_debug_set("measure_route", "s1")).
 
     python tools/bench_measure.py [--log2 28] [--pairs 5] [--out FILE.json]
+    python tools/bench_measure.py --host-fed [--log2 28] [--batches 16,64] [--pairs 5] [--legs a,b,c] [--out FILE.json]
 
 Per shape: two warm ordinary calls (the first holds the lock), then `pairs` interleaved rounds of one call of each kind, host wall
 clock around call + synchronise (ms), and the library's per-kernel event times of one more call of each kind.  The rows of both
-routes are compared bit for bit."""
+routes are compared bit for bit.
+
+--host-fed: the job as a host sees it.  One range of NRSC-5 cs16 + digital AGC in pinned memory, cut into N batches, run three
+ways, interleaved, `pairs` rounds (at least five), medians: (a) the loop of iqgpu_chain_measure calls, (b) iqgpu_chain_measure_submit /
+_collect, (c) iqgpu_chain_submit / _collect of the ordinary pass, the yardstick -- it runs at the copy engine's rate.  Host wall clock
+around the whole range (ms, and GS/s of input), then the library's per-kernel event times of one more pass of (b) and (c)."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -35,12 +42,85 @@ def chain(kw, route):
     return ch
 
 
+def host_fed(args):
+    kw = dict(SHAPES["nrsc5-cs16+agc"])
+    n, chunk = 1 << args.log2, 16384
+    legs = args.legs.split(",")
+    seg = synth.raw_stream(min(n, 1 << 22), 2.4e6, 7, "cs16").view(np.uint8)
+    src = gpu.chain.PinnedBuffer(n * 4)
+    for at in range(0, src.nbytes, seg.nbytes):
+        src.array[at:at + seg.nbytes] = seg[:src.nbytes - at]
+    chains = {leg: gpu.Chain(**kw) for leg in legs}
+    depth = _lib.load().iqgpu_chain_pipeline_depth()
+    res = {}
+    for nb in [int(v) for v in args.batches.split(",")]:
+        per = n // nb
+        assert per * nb == n and per % chunk == 0, "batches must cut the range on the AGC chunk grid"
+        rows = gpu.chain.PinnedBuffer((n // chunk) * 16)
+        out_cap = chains[legs[0]].max_out_frames(per) * 4
+        out = gpu.chain.PinnedBuffer(out_cap * nb) if "c" in legs else None
+        rpb = per // chunk                                        # rows per batch
+
+        def leg_a(ch):
+            got = 0
+            for i in range(nb):
+                k = C.c_size_t(0)
+                _lib.check(ch._lib.iqgpu_chain_measure(ch._h, C.c_void_p(src.ptr + i * per * 4), per, C.c_void_p(rows.ptr + i * rpb * 16), rpb, C.byref(k)))
+                got += k.value
+            return got
+
+        def piped(ch, submit):
+            flight, got = [], 0
+            for i in range(nb):
+                if len(flight) == depth:
+                    ch.collect(flight.pop(0))
+                k, t = submit(ch, i)
+                got += k
+                flight.append(t)
+            for t in flight:
+                ch.collect(t)
+            return got
+
+        run = {"a": leg_a,
+               "b": lambda ch: piped(ch, lambda c, i: c.measure_submit(src.ptr + i * per * 4, per, rows.ptr + i * rpb * 16, rpb)),
+               "c": lambda ch: piped(ch, lambda c, i: c.submit(src.ptr + i * per * 4, per, out.ptr + i * out_cap, out_cap))}
+        t = {leg: [] for leg in legs}
+        for leg in legs:
+            run[leg](chains[leg])                                 # (buffers sized, the ordinary chain past its lock)
+        for _ in range(max(5, args.pairs)):
+            for leg in legs:
+                t0 = time.perf_counter(); run[leg](chains[leg])
+                t[leg].append((time.perf_counter() - t0) * 1e3)
+        o = {"frames": n, "batches": nb, "ms": {leg: [round(v, 3) for v in t[leg]] for leg in legs},
+             "median_ms": {leg: round(float(np.median(t[leg])), 3) for leg in legs},
+             "spread_ms": {leg: round(float(max(t[leg]) - min(t[leg])), 3) for leg in legs},
+             "median_gsps": {leg: round(n / float(np.median(t[leg])) / 1e6, 3) for leg in legs}}
+        for leg in legs:
+            if leg != "a":
+                chains[leg].set_profiling(True)
+                run[leg](chains[leg])
+                o["kernels_ms_" + leg] = {k: round(v["ms"], 4) for k, v in chains[leg].profile().items() if v["launches"]}
+                chains[leg].set_profiling(False)
+        res["host-fed-%d" % nb] = o
+        print("host-fed", json.dumps(o), flush=True)
+        rows.free()
+        if out is not None:
+            out.free()
+    if args.out:
+        json.dump(res, open(args.out, "w"), indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log2", type=int, default=28)
     ap.add_argument("--pairs", type=int, default=5)
     ap.add_argument("--out", default="")
+    ap.add_argument("--host-fed", action="store_true", help="the host-fed leg: measure loop / measure_submit / submit from pinned memory")
+    ap.add_argument("--batches", default="16,64", help="--host-fed: batches per range, comma-separated")
+    ap.add_argument("--legs", default="a,b,c", help="--host-fed: which of the three legs run")
     args = ap.parse_args()
+    if args.host_fed:
+        return host_fed(args)
     n = 1 << args.log2
     res = {}
     for name, kw in SHAPES.items():
