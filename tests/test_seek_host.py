@@ -26,7 +26,13 @@ SHAPES = {
                                        filters=(("lowpass", 200e3, 0.0),), filter_taps=257, filter_impl="fft"),
     "no_resample_fft": dict(input_rate_hz=2.4e6, no_resample=True, filters=(("passband", -300e3, 100e3),), transition_width_hz=20e3,
                             attenuation_db=70.0, filter_impl="fft", fft_size=2048),
+    # ratios beyond 2^+-5.5 (tests/test_gpu_far_ratios.py runs them on the device): seven and nine half-band stages down, eight up
+    "down_s7_10M_to_48k": dict(in_format="cs16", out_format="cs16", input_rate_hz=10e6, target_rate_hz=48e3, shift_hz=-25e3),
+    "down_s9_20M_to_20k2": dict(in_format="cs16", out_format="cs16", input_rate_hz=20e6, target_rate_hz=20.2e3, shift_hz=-28e3),
+    "up_s8_5k_to_2M4": dict(in_format="cu8", out_format="cs16", input_rate_hz=5e3, target_rate_hz=2.4e6),
 }
+# name -> (half-band stages, interpolating, stage semi-lengths in run order) of the deep chains
+DEEP = {"down_s7_10M_to_48k": (7, 0, [3, 3, 3, 3, 3, 5, 10]), "down_s9_20M_to_20k2": (9, 0, [3] * 7 + [5, 10]), "up_s8_5k_to_2M4": (8, 1, None)}
 POINTWISE = dict(in_format="cs16", out_format="cf32", input_rate_hz=2.4e6, no_resample=True, shift_hz=100e3)
 
 
@@ -97,6 +103,10 @@ def test_range_law_against_an_integer_restatement(lib, name):
         assert info.filter_ntaps == 4097 and info.filter_block == 0 and info.num_halfband_stages == 5
     if name == "up_2M0_to_2M4":
         assert info.interp == 1
+    if name in DEEP:
+        S, interp, m = DEEP[name]
+        assert (info.num_halfband_stages, info.interp) == (S, interp) and info.filter_ntaps == 0
+        assert m is None or [int(info.stage_m[g]) for g in range(S)] == m
     for a in positions(kw, info):
         for n in (0, 1, 4095, 131_072 + 5, 10**9 + 1):
             rc, first, count = out_range(lib, d, a, n)
@@ -167,6 +177,10 @@ def test_preroll_covers_the_tap_spans_and_grows_by_the_dc_warm_up(lib, name):
     assert rc == 0
     low = preroll_lower_bound(kw, info)
     assert low > 0 and p >= low, (name, p, low)
+    if name in DEEP:
+        assert info.num_halfband_stages == DEEP[name][0]
+        if not info.interp:
+            assert low > 26 << info.num_halfband_stages          # the last two stages (m = 5, 10) and the polyphase window alone
     d_dc, info_dc = probe(lib, **dict(kw, dc_block=True))
     rc, p_dc = preroll(lib, d_dc)
     assert rc == 0 and info_dc.dc_alpha > 0
