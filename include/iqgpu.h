@@ -315,6 +315,58 @@ int    iqgpu_chain_agc_initial_state(const iqgpu_chain *c, iqgpu_agc_state *st);
 int    iqgpu_chain_seek_agc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, const iqgpu_agc_state *entry);
 int    iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
                                    const iqgpu_agc_state *entry);
+/* ---- EXACT seamless range sharding of chains with the DC blocker: carry the blocker's state (additive, still ABI v9) ----
+ * iqgpu_chain_seek warms the DC blocker up over ceil(ln(1e6) / alpha) extra frames and meets the single stream to 1e-6 of full scale.
+ * The calls below meet it byte for byte and need no such warm-up.  The blocker is a one-pole recurrence, so what a process CALL does
+ * to its state v is an affine map, v_after = f * v_before + g, whose pair (f, g) -- computed in double by the kernel that computes the
+ * state of an ordinary call -- depends on the call's input frames and on how the call is cut into the front kernel's segments, and
+ * NOT on v_before.  So a range is measured without knowing its entering state, one row per call, at the cost of one read of the
+ * input (k_dc_prefix and the scan: no front kernel, no filter, no output); one walk over the rows gives the state in front of every
+ * call; and a seek that is handed that state replaces the warm-up.
+ * Contract.  The single stream is processed in calls on a grid of C frames (calls [k C, (k+1) C), the last one may be shorter).  Cut
+ * points are multiples of C and of 4096.  With `nd` = a copy of the description with dc_block_enable = 0 and
+ * P_fir = iqgpu_design_preroll_frames(&nd), the preroll of a range is the ceil(P_fir / C) whole grid calls in front of its cut (all
+ * of [0, cut) when that is less), passed with call_frames = C, and at_preroll_start is the walked state in front of the first of
+ * those calls.  Under these rules the stitched output equals the single stream's BYTE FOR BYTE: every call a shard makes is a call
+ * the single stream makes, from the same state.  (The segments of a call also depend on whether its input address is 16-byte
+ * aligned: the host variants stage every call as iqgpu_chain_process does; with the _device variants give every call the alignment
+ * the single stream's call has.)  A preroll off the grid keeps the DC state exact and leaves the histories, and so the first
+ * outputs, only within the bound of iqgpu_chain_seek.
+ * Recipe:
+ *   1. Measure (all ranges but the last, in parallel): iqgpu_chain_dc_measure for every grid call of the range, one row each, in order.
+ *   2. Walk (any one chain): st = {0, 0}; ONE iqgpu_chain_dc_advance over all rows with before[]: before[k] is the state in front of
+ *      grid call k.
+ *   3. Process (all ranges in parallel): iqgpu_chain_seek_dc(c, cut, preroll, n C, C, &before[cut / C - n]), then the ordinary
+ *      process / process_device / submit loop over the range on the grid.
+ * Errors: IQGPU_EINVAL for a chain without the DC blocker, a NULL argument, a position beyond 2^39 frames, a preroll shorter than
+ * min(first_frame, P_fir) or not a multiple of call_frames, and (dc_advance) a row whose f is not in (0, 1] or whose g is not finite;
+ * IQGPU_EUNSUPPORTED from dc_measure, dc_advance and seek_dc for a chain with the output AGC (its measure route may cut a call into
+ * other segments than its process route; such chains keep iqgpu_chain_seek_agc and the bound above).  iqgpu_chain_get_dc_state works
+ * on any chain with the blocker.  A refused iqgpu_chain_seek_dc leaves the chain as a refused iqgpu_chain_seek does: reset.
+ * Call length: f = (1 - alpha)^frames is computed in double and underflows to 0 once frames * alpha exceeds about 745 (alpha =
+ * 2 pi 10 Hz / rate: 1.18e8 frames at 10 MS/s, 2.8e7 at 2.4 MS/s).  iqgpu_chain_dc_measure still returns such a row -- f = 0 is then
+ * the true map in double, v_after = g -- but iqgpu_chain_dc_advance refuses it with the other rows no measurement of a walkable
+ * call gives: keep the calls of the grid below that length (the harness's default is 2^22 frames). */
+typedef struct { double re, im; } iqgpu_dc_state;                          /* the blocker's v, in double as the chain keeps it */
+typedef struct { double f, g_re, g_im; uint64_t frames; } iqgpu_dc_row;    /* one CALL: v_after = f * v_before + g */
+/* synchronises the chain's stream and reports the blocker's state behind the last call */
+int    iqgpu_chain_get_dc_state(iqgpu_chain *c, iqgpu_dc_state *st);
+/* The map of the call iqgpu_chain_process[_device] would make of these frames_in frames at stream position first_frame: planned as
+ * that call (same routing, same segments, the chain's switch snapshot), of which only k_dc_prefix and the scan are launched.  Returns
+ * with the stream idle and leaves the handle exactly as it was: position, histories, DC state and pipeline untouched. */
+int    iqgpu_chain_dc_measure(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, iqgpu_dc_row *row);
+int    iqgpu_chain_dc_measure_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, iqgpu_dc_row *row);
+/* *st walked over rows[0 .. n) on the device, by the expression behind the ordinary call's state update (one definition): the
+ * walked state is the ordinary path's bit for bit.  before, if not NULL, receives the state in front of every row (n entries); *st
+ * ends behind the last row.  Touches neither the chain's own DC state nor its position. */
+int    iqgpu_chain_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before);
+/* iqgpu_chain_seek with two differences: the preroll it asks for is min(first_frame, P_fir) -- no DC warm-up -- and
+ * *at_preroll_start (NULL: zero) becomes the blocker's state before the preroll runs.  The preroll runs through the ordinary path in
+ * calls of call_frames frames; call_frames == 0: one call. */
+int    iqgpu_chain_seek_dc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
+                           const iqgpu_dc_state *at_preroll_start);
+int    iqgpu_chain_seek_dc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames, size_t call_frames,
+                                  const iqgpu_dc_state *at_preroll_start);
 /* what the I/Q optimiser thread publishes (src/iq_correct.c:141-152 reads them once per chunk) */
 int    iqgpu_chain_set_iq_factors(iqgpu_chain *c, float mag, float phase);
 /* synchronises the chain's stream and reports the AGC state (agc.c keeps it in AppResources) */

@@ -47,6 +47,16 @@ class AgcChunk(C.Structure):
     _fields_ = [("peak2", C.c_double), ("frames_out", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DcState(C.Structure):
+    """iqgpu_dc_state: the DC blocker's state, in double as the chain keeps it"""
+    _fields_ = [("re", C.c_double), ("im", C.c_double)]
+
+
+class DcRow(C.Structure):
+    """iqgpu_dc_row: the map of one call, v_after = f * v_before + g"""
+    _fields_ = [("f", C.c_double), ("g_re", C.c_double), ("g_im", C.c_double), ("frames", C.c_uint64)]
+
+
 class ChainInfo(C.Structure):
     _fields_ = [("ratio", C.c_float), ("interp", C.c_int), ("num_halfband_stages", C.c_int),
                 ("stage_m", C.c_int * 16), ("rate_arb", C.c_float), ("arb_step", C.c_uint32),
@@ -123,6 +133,12 @@ SYMBOLS = [
     ("iqgpu_chain_seek_agc", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(AgcState)]),
     ("iqgpu_chain_seek_agc_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(AgcState)]),
     ("iqgpu_chain_get_agc_state", C.c_int, [_vp, C.POINTER(AgcState)]),
+    ("iqgpu_chain_get_dc_state", C.c_int, [_vp, C.POINTER(DcState)]),
+    ("iqgpu_chain_dc_measure", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
+    ("iqgpu_chain_dc_measure_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
+    ("iqgpu_chain_dc_advance", C.c_int, [_vp, C.POINTER(DcState), _vp, _sz, _vp]),
+    ("iqgpu_chain_seek_dc", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
+    ("iqgpu_chain_seek_dc_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
     ("iqgpu_chain_set_iq_factors", C.c_int, [_vp, C.c_float, C.c_float]),
     ("iqgpu_chain_max_out_frames", _sz, [_vp, _sz]),
     ("iqgpu_chain_next_out_frames", _sz, [_vp, _sz]),

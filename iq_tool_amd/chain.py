@@ -7,12 +7,15 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import (BYTES_PER_FRAME, FILTER, FILTER_IMPL, FMT, AgcState, ChainDesc, ChainInfo, FilterReq,
+from ._lib import (BYTES_PER_FRAME, FILTER, FILTER_IMPL, FMT, AgcState, ChainDesc, ChainInfo, DcState, FilterReq,
                    IqgpuError, Profile, check)
 
 AGC_PROFILE = {"off": 0, "dx": 1, "local": 2, "digital": 3}
 # iqgpu_agc_chunk as a numpy record: what Chain.measure returns and Chain.agc_advance takes
 AGC_ROW = np.dtype([("peak2", np.float64), ("frames_out", np.uint32), ("reserved", np.uint32)])
+# iqgpu_dc_state / iqgpu_dc_row as numpy records: what Chain.dc_state, .dc_measure and .dc_advance return and take
+DC_STATE = np.dtype([("re", np.float64), ("im", np.float64)])
+DC_ROW = np.dtype([("f", np.float64), ("g_re", np.float64), ("g_im", np.float64), ("frames", np.uint64)])
 
 _NP_VIEW = {8: np.uint8, 9: np.int8, 10: np.uint16, 11: np.int16, 16: np.int16, 12: np.uint8,
             13: np.uint32, 14: np.int32, 15: np.float32}
@@ -313,6 +316,63 @@ class Chain:
     def seek_agc_device(self, first_frame, d_preroll, preroll_frames, entry=None):
         check(self._lib.iqgpu_chain_seek_agc_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames),
                                                     C.byref(entry) if entry is not None else None))
+
+    # ---- exact seamless sharding of DC-blocker chains: measure, walk, seek with the walked state (include/iqgpu.h) ----
+    def dc_state(self):
+        """the DC blocker's state behind the last call as a DC_STATE record, every bit of it (synchronises)"""
+        st = np.zeros((), DC_STATE)
+        check(self._lib.iqgpu_chain_get_dc_state(self._h, st.ctypes.data_as(C.POINTER(DcState))))
+        return st
+
+    def dc_measure(self, first_frame, raw):
+        """the map v_after = f v_before + g of the call process(raw) would be at stream frame first_frame, as a DC_ROW record;
+        the chain itself stays exactly as it was"""
+        raw = np.ascontiguousarray(raw)
+        n = raw.nbytes // self.in_bytes
+        row = np.zeros((), DC_ROW)
+        check(self._lib.iqgpu_chain_dc_measure(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n,
+                                               row.ctypes.data_as(C.POINTER(_lib.DcRow))))
+        return row
+
+    def dc_measure_device(self, first_frame, d_in, frames_in):
+        """dc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
+        row = np.zeros((), DC_ROW)
+        check(self._lib.iqgpu_chain_dc_measure_device(self._h, int(first_frame), C.c_void_p(d_in), int(frames_in),
+                                                      row.ctypes.data_as(C.POINTER(_lib.DcRow))))
+        return row
+
+    def dc_advance(self, state, rows):
+        """walks a DC state (a DC_STATE record, or None for zero) over dc_measure() rows on the device: returns (state behind the
+        last row, before) where before[k] is the state in front of row k"""
+        rows = np.ascontiguousarray(rows, DC_ROW).reshape(-1)
+        st = np.zeros((), DC_STATE)
+        if state is not None:
+            st[...] = state
+        before = np.zeros(rows.size, DC_STATE)
+        check(self._lib.iqgpu_chain_dc_advance(self._h, st.ctypes.data_as(C.POINTER(DcState)),
+                                               rows.ctypes.data_as(C.c_void_p) if rows.size else None, rows.size,
+                                               before.ctypes.data_as(C.c_void_p) if rows.size else None))
+        return st, before
+
+    def seek_dc(self, first_frame, preroll_raw=None, call_frames=0, state=None):
+        """seek() for a chain with the DC blocker, exact: the preroll is only the filters' memory, it runs in calls of call_frames
+        (0: one call) and `state` (a DC_STATE record from dc_advance; None: zero) is the blocker's state in front of it"""
+        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
+        n = raw.nbytes // self.in_bytes
+        st = None
+        if state is not None:
+            st = np.zeros((), DC_STATE)
+            st[...] = state
+        check(self._lib.iqgpu_chain_seek_dc(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n, int(call_frames),
+                                            st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
+
+    def seek_dc_device(self, first_frame, d_preroll, preroll_frames, call_frames=0, state=None):
+        st = None
+        if state is not None:
+            st = np.zeros((), DC_STATE)
+            st[...] = state
+        check(self._lib.iqgpu_chain_seek_dc_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames), int(call_frames),
+                                                   st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
 
     def agc_state_raw(self):
         """the chain's AGC state as an AgcState structure: every field with its bits (synchronises)"""

@@ -162,7 +162,7 @@ static void free_device_state(iqgpu_chain *c)
     if (c->d_dc_state) (void)hipFree(c->d_dc_state);
     if (c->d_sink) (void)hipFree(c->d_sink);
     c->steal_buf.release();
-    c->dc_agg.release(); c->dc_carry.release();
+    c->dc_agg.release(); c->dc_carry.release(); c->dc_walk.release();
     c->fbuf[0].release(); c->fbuf[1].release();
     c->ibuf[0].release(); c->ibuf[1].release();
     c->stage_in.release(); c->stage_out.release(); c->seek_sink.release();
@@ -708,6 +708,19 @@ extern "C" int iqgpu_chain_get_agc_state(iqgpu_chain *c, iqgpu_agc_state *st)
     { const int rc = agc_resolve_pending(c); if (rc) return rc; }
     HIP_TRY(hipStreamSynchronize(c->stream));
     HIP_TRY(hipMemcpy(st, c->d_agc_state, sizeof(AgcState), hipMemcpyDeviceToHost));
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_chain_get_dc_state(iqgpu_chain *c, iqgpu_dc_state *st)
+{
+    if (!c || !st) return fail(IQGPU_EINVAL, "iqgpu_chain_get_dc_state: NULL argument");
+    if (!c->dc) return fail(IQGPU_EINVAL, "iqgpu_chain_get_dc_state: the chain has no DC blocker");
+    static_assert(sizeof(iqgpu_dc_state) == sizeof(cd2), "DC state layout");
+    HIP_TRY(hipSetDevice(c->device));
+    { const int rc = pipe_advance(c, c->pipe_seq); if (rc) return rc; }     // batches submitted and not yet collected
+    { const int rc = agc_resolve_pending(c); if (rc) return rc; }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipMemcpy(st, c->d_dc_state, sizeof(cd2), hipMemcpyDeviceToHost));
     return IQGPU_OK;
 }
 

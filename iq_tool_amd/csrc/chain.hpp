@@ -3,7 +3,8 @@
 //   abi.cpp        library / lifecycle / state entry points, create-time design (design_chain)
 //   plan.cpp       stream-position arithmetic (plan_call), per-call run geometry of the wave kernels (Call::plan_geometry)
 //   process.cpp    one process() call: buffers, the stages in stream order, iqgpu_chain_process[_device]
-//   seek.cpp       seamless range sharding: iqgpu_chain_seek[_agc], iqgpu_chain_measure, iqgpu_chain_agc_initial_state / _advance
+//   seek.cpp       seamless range sharding: iqgpu_chain_seek[_agc | _dc], iqgpu_chain_measure, iqgpu_chain_agc_initial_state / _advance,
+//                  iqgpu_chain_dc_measure / _dc_advance
 //   agc_host.cpp   host side of the output AGC: chunk map, fused / unfused split, verifier + fallback launches
 //   pipeline.cpp   iqgpu_chain_submit / _measure_submit / _collect (pinned host buffers, three stages moved along by the host)
 #pragma once
@@ -154,6 +155,8 @@ struct iqgpu_chain {
     // launches (zeroed when the array is (re)allocated)
     DevBuf steal_buf;
     DevBuf dc_agg, dc_carry;
+    // exact seamless sharding of DC-blocker chains (seek.cpp): the map of a measured call, the state and the tables of iqgpu_chain_dc_advance
+    DevBuf dc_walk;
     DevBuf fbuf[2]; int fcur = 0;
     // output AGC (digital profile)
     bool agc = false; float agc_target = 0.9f; int64_t agc_chunk = 16384;
@@ -263,7 +266,8 @@ constexpr uint64_t kMaxStreamFrames = (uint64_t)1 << 39;      // (groups << 24) 
 struct StreamAt { StreamPos pos; uint64_t n_out = 0; uint32_t nco_theta = 0, pnco_theta = 0; };
 StreamAt stream_at(const iqgpu_chain *c, uint64_t frames);
 // the chain's FIR memory in input frames (+ the DC blocker's warm-up): what a seek has to run in front of its position
-uint64_t seek_preroll_frames(const iqgpu_chain *c);
+// (with_dc = false: without that warm-up -- what iqgpu_chain_seek_dc asks for, which is handed the blocker's state)
+uint64_t seek_preroll_frames(const iqgpu_chain *c, bool with_dc = true);
 
 // ---- profiling (process.cpp): HIP events around every launch while profiling is on ----
 hipEvent_t get_event(iqgpu_chain *c);
@@ -384,6 +388,8 @@ struct Call {
 int process_device_impl(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, void *d_out, size_t out_capacity_bytes,
                         size_t *frames_out, const CallOpts &o = CallOpts());              // process.cpp
 int stage_host_input(iqgpu_chain *c, const void *in, size_t frames, const void **d_in);   // process.cpp: host frames into stage_in, *d_in
+// process.cpp: the DC blocker's map of the call process_device_impl would make of these frames at stream position `at`, into d_map[0 .. 2)
+int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, cd2 *d_map);
 size_t agc_unfused_head(const iqgpu_chain *c, size_t frames_in, bool *locks);             // agc_host.cpp
 // behind a fused launch whose fallback waits for the verdict on the host: waits for the word, launches the fallback when it is set
 // (*ran = true then).  No-op without a pending verdict.

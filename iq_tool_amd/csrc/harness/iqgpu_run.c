@@ -33,6 +33,14 @@
  * (iqgpu_chain_agc_advance) then gives the AGC state at the start of shards 1 .. N-1.  Pass 2: every shard seeks again, now with
  * its entry state, and runs the usual chunk loop.  Preroll and output placement come from the description with the AGC off.
  *
+ * --shards N --seamless-dc is the EXACT --seamless for chains with the DC blocker (--dc-block, no AGC option), in the three passes of
+ * iqgpu.h's DC block.  Shard starts are s * (frames / N) rounded down to a multiple of lcm(4096, --chunk-frames): every call of every
+ * shard is a call of the single stream.  Pass 1: shards 0 .. N-2 measure the map of every call of their range
+ * (iqgpu_chain_dc_measure: one read of the input, no front kernel, no output).  One walk over all rows (iqgpu_chain_dc_advance) then
+ * gives the blocker's state in front of every call.  Pass 2: every shard puts its chain at its start with iqgpu_chain_seek_dc -- the
+ * preroll is the filters' memory rounded up to whole chunks, with NO warm-up of the blocker, entered with the walked state -- and runs
+ * the usual chunk loop.  The stitched file is the file --shards 1 writes, byte for byte.
+ *
  * --synthetic FRAMES [--synthetic-hash SEED]: no input file.  Without a seed one constant pinned buffer is sent again and again
  * (the PCIe-inclusive rate of the path, nothing else); with one, shard s is the stream frame n -> splitmix64((SEED + s) * K + n)
  * of its own (iq_tool_amd/synth.py hash_stream restates it): configs[4] at its real size -- 8 x 2.5 G frames -- without 80 GB of
@@ -68,6 +76,8 @@ typedef struct {
     int no_bind;                      /* --no-numa-bind */
     int seamless;                     /* --seamless: the shards continue ONE stream (iqgpu_chain_seek behind a preroll) */
     int seamless_agc;                 /* --seamless-agc: --seamless for digital-AGC chains, in two passes (measure, walk, process) */
+    int seamless_dc;                  /* --seamless-dc: the exact --seamless for DC-blocker chains, in three passes (measure, walk, process) */
+    int have_shards;                  /* --shards was given */
     int dry;                          /* --dry-placement: plan, bind, size the buffers, report -- no GPU call */
     int quiet;
 } Options;
@@ -86,6 +96,9 @@ typedef struct {
     /* --seamless-agc */
     iqgpu_agc_chunk *rows; long long agc_rows;   /* pass 1: this shard's table (planned count with --dry-placement) */
     iqgpu_agc_state entry; int have_entry;       /* the AGC state at first_frame, from the walk */
+    /* --seamless-dc */
+    iqgpu_dc_row *dc_rows; long long n_dc_rows;  /* pass 1: one row per call of this shard's range (planned count with --dry-placement) */
+    iqgpu_dc_state dc_entry;                     /* the blocker's state in front of this shard's preroll, from the walk */
     double measure_seconds;
     int barriers;                     /* how many of the two rendezvous of the passes this thread has been through */
     int rc;
@@ -277,6 +290,61 @@ static void *run_shard(void *arg)
         CK(iqgpu_chain_seek_agc(chain, (uint64_t)sh->first_frame, pre, np, &sh->entry));
         free(pre); pre = NULL;
     }
+    if (o->seamless_dc) {
+        /* pass 1: the map of every call pass 2 will make of this range.  The last shard measures nothing: nobody starts behind it */
+        const size_t np = (size_t)sh->preroll_frames;
+        const double t_m = now_s();
+        if (sh->shard < o->shards - 1) {
+            const size_t cap = (size_t)((sh->frames + (long long)chunk - 1) / (long long)chunk);
+            sh->dc_rows = (iqgpu_dc_row *)malloc((cap ? cap : 1) * sizeof(iqgpu_dc_row));
+            if (!sh->dc_rows) { snprintf(sh->err, sizeof(sh->err), "out of memory for a table of %zu rows", cap); sh->rc = -1; goto done; }
+            for (long long at = 0; at < sh->frames; at += (long long)chunk) {
+                size_t n = chunk;
+                if ((long long)n > sh->frames - at) n = (size_t)(sh->frames - at);
+                if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame + at, n, h_in[0], sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
+                CK(iqgpu_chain_dc_measure(chain, (uint64_t)(sh->first_frame + at), h_in[0], n, &sh->dc_rows[sh->n_dc_rows]));
+                sh->n_dc_rows++;
+            }
+        }
+        sh->measure_seconds = now_s() - t_m;
+        /* the walk: one thread, ONE table of all rows in stream order (row k = call k of the single stream), the state in front of
+         * every call; every shard then enters its preroll with the state in front of the preroll's first call */
+        pthread_barrier_wait(&g_pass); sh->barriers = 1;
+        if (sh->shard == 0) {
+            int ok = 1;
+            long long total = 0;
+            for (int q = 0; q < o->shards; q++) { if (g_shards[q].rc) ok = 0; total += g_shards[q].n_dc_rows; }
+            iqgpu_dc_row *all = (iqgpu_dc_row *)malloc((size_t)(total ? total : 1) * sizeof(iqgpu_dc_row));
+            iqgpu_dc_state *before = (iqgpu_dc_state *)malloc((size_t)(total ? total : 1) * sizeof(iqgpu_dc_state));
+            iqgpu_dc_state st = {0.0, 0.0};
+            if (ok && (!all || !before)) { snprintf(sh->err, sizeof(sh->err), "out of memory for the walk over %lld rows", total); sh->rc = -1; ok = 0; }
+            if (ok) {
+                long long k = 0;
+                for (int q = 0; q < o->shards; q++) { if (g_shards[q].n_dc_rows) memcpy(all + k, g_shards[q].dc_rows, (size_t)g_shards[q].n_dc_rows * sizeof(iqgpu_dc_row)); k += g_shards[q].n_dc_rows; }
+                if (iqgpu_chain_dc_advance(chain, &st, all, (size_t)total, before) != IQGPU_OK) {
+                    snprintf(sh->err, sizeof(sh->err), "iqgpu_chain_dc_advance: %s", iqgpu_last_error()); sh->rc = -1; ok = 0;
+                }
+            }
+            for (int q = 1; q < o->shards && ok; q++) {
+                const long long k = (g_shards[q].first_frame - g_shards[q].preroll_frames) / (long long)chunk;
+                /* (k == total: a preroll of no frames in front of the last shard -- a chain without filter memory; the state behind the last row) */
+                if (k < 0 || k > total) { snprintf(sh->err, sizeof(sh->err), "the walk holds no state in front of call %lld", k); sh->rc = -1; ok = 0; break; }
+                g_shards[q].dc_entry = k < total ? before[k] : st;
+            }
+            free(all); free(before);
+            g_walk_ok = ok;
+        }
+        pthread_barrier_wait(&g_pass); sh->barriers = 2;
+        if (!g_walk_ok) { if (!sh->rc) { snprintf(sh->err, sizeof(sh->err), "the measure pass or the walk of another shard failed"); sh->rc = -1; } goto done; }
+        /* pass 2: the chain at the start of the range, behind a preroll of whole calls entered with the walked state */
+        if (sh->first_frame > 0) {
+            pre = malloc(np ? np * ibps : 1);
+            if (!pre) { snprintf(sh->err, sizeof(sh->err), "out of memory for a preroll of %zu frames", np); sh->rc = -1; goto done; }
+            if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame - sh->preroll_frames, np, pre, sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
+            CK(iqgpu_chain_seek_dc(chain, (uint64_t)sh->first_frame, pre, np, chunk, &sh->dc_entry));
+            free(pre); pre = NULL;
+        }
+    }
     if (o->seamless && sh->first_frame > 0) {
         /* the frames in front of this shard's start, read like any other range of the stream, warm the chain's histories up; the
          * chain then stands at first_frame of the ONE stream (iqgpu_chain_seek) */
@@ -318,7 +386,7 @@ static void *run_shard(void *arg)
                 }
             } else if (o->have_hash) {
                 /* (buffer b is free: chunk i - 2, its last user, retired in the iteration before this one) */
-                if (o->seamless || o->seamless_agc) hash_fill(h_in[b], d.in_format, ibps, o->hash_seed, sh->first_frame + done_in, n);
+                if (o->seamless || o->seamless_agc || o->seamless_dc) hash_fill(h_in[b], d.in_format, ibps, o->hash_seed, sh->first_frame + done_in, n);
                 else hash_fill(h_in[b], d.in_format, ibps, o->hash_seed + (uint64_t)sh->shard, done_in, n);
             }
             CK(iqgpu_memcpy_h2d_async(d_in[b], h_in[b], n * ibps, s_in));
@@ -352,7 +420,7 @@ static void *run_shard(void *arg)
     }
 done:
     /* (a shard that fails early still keeps the rendezvous of the two passes: the others wait there) */
-    while (o->seamless_agc && !o->dry && sh->barriers < 2) { pthread_barrier_wait(&g_pass); sh->barriers++; }
+    while ((o->seamless_agc || o->seamless_dc) && !o->dry && sh->barriers < 2) { pthread_barrier_wait(&g_pass); sh->barriers++; }
     free(pre);
     if (chain) iqgpu_chain_synchronize(chain);
     for (int b = 0; b < NBUF; b++) {
@@ -384,6 +452,7 @@ static void usage(void)
             "          [--chunk-frames N (default 4194304)] [--shards N] [--devices N] [--device D] [--synthetic FRAMES [--synthetic-hash SEED]]\n"
             "          [--seamless (with --shards: the shards continue ONE stream -- the stitched output is what --shards 1 writes)]\n"
             "          [--seamless-agc (--seamless for chains with the digital output AGC: a measure pass, one walk, then the ordinary pass)]\n"
+            "          [--seamless-dc (the exact --seamless for --dc-block chains without an AGC: a measure pass over the input, one walk, then the ordinary pass)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
             "          [--dry-placement (plan the shards, bind every shard thread, size its buffers, report as JSON: no GPU call)]\n");
 }
@@ -431,7 +500,7 @@ int main(int argc, char **argv)
             o.desc.agc_profile = !strcasecmp(v, "dx") ? IQGPU_AGC_DX : !strcasecmp(v, "local") ? IQGPU_AGC_LOCAL : !strcasecmp(v, "digital") ? IQGPU_AGC_DIGITAL : -1; }
         else if (!strcmp(a, "--agc-target")) o.desc.agc_target = (float)atof(NEXT);
         else if (!strcmp(a, "--chunk-frames")) o.chunk_frames = (size_t)atoll(NEXT);
-        else if (!strcmp(a, "--shards")) o.shards = atoi(NEXT);
+        else if (!strcmp(a, "--shards")) { o.shards = atoi(NEXT); o.have_shards = 1; }
         else if (!strcmp(a, "--devices")) o.devices = atoi(NEXT);
         else if (!strcmp(a, "--device")) o.device0 = atoi(NEXT);
         else if (!strcmp(a, "--synthetic")) o.synthetic_frames = atoll(NEXT);
@@ -440,6 +509,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--dry-placement")) o.dry = 1;
         else if (!strcmp(a, "--seamless")) o.seamless = 1;
         else if (!strcmp(a, "--seamless-agc")) o.seamless_agc = 1;
+        else if (!strcmp(a, "--seamless-dc")) o.seamless_dc = 1;
         else if (!strcmp(a, "--debug")) {              /* --debug name=value -> iqgpu_debug_set (the library reads no environment) */
             char kv[512]; snprintf(kv, sizeof(kv), "%s", NEXT);
             char *eq = strchr(kv, '=');
@@ -456,6 +526,17 @@ int main(int argc, char **argv)
     o.desc.input_rate_hz = in_rate; o.desc.target_rate_hz = o.desc.no_resample ? in_rate : out_rate;
     if (o.shards < 1) o.shards = 1;
     if (o.devices < 1) o.devices = 1;
+    if (o.seamless_dc) {
+        /* options that do not go together: exit status 2, as for every other misuse of the command line.  A chain the recipe does not
+         * cover -- what the library would refuse at its first call -- : exit status 1, before anything is planned */
+        if (o.seamless || o.seamless_agc) { fprintf(stderr, "--seamless-dc excludes --seamless and --seamless-agc\n"); return 2; }
+        if (!o.have_shards) { fprintf(stderr, "--seamless-dc needs --shards N\n"); return 2; }
+        if (o.desc.agc_enable) { fprintf(stderr, "--seamless-dc: a chain with the output AGC is not covered (its measure route may cut a call into other segments "
+                                                 "than its process route)%s\n", o.desc.agc_profile == IQGPU_AGC_DIGITAL ? "; --seamless-agc shards it to the DC bound" : ""); return 1; }
+        if (!o.desc.dc_block_enable) { fprintf(stderr, "--seamless-dc: the chain has no DC blocker: give --dc-block, or use --seamless\n"); return 1; }
+        if (o.synthetic_frames > 0 && !o.have_hash) { fprintf(stderr, "--seamless-dc needs a stream it can read twice: an input file, or --synthetic with --synthetic-hash\n"); return 2; }
+        if (o.chunk_frames == 0) { fprintf(stderr, "--seamless-dc: --chunk-frames 0\n"); return 2; }
+    }
 
     const size_t ibps = iqgpu_get_bytes_per_sample(o.desc.in_format), obps = iqgpu_get_bytes_per_sample(o.desc.out_format);
     long long total_frames = o.synthetic_frames;
@@ -532,7 +613,39 @@ int main(int argc, char **argv)
         g_shards = sh;
         if (!o.dry && pthread_barrier_init(&g_pass, NULL, (unsigned)o.shards) != 0) { fprintf(stderr, "pthread_barrier_init failed\n"); return 1; }
     }
-    for (int s = 0; s < o.shards && !o.seamless && !o.seamless_agc; s++) {
+    if (o.seamless_dc) {
+        /* the preroll is the filters' memory alone -- the description with the blocker off -- in whole calls; placement does not depend
+         * on the blocker */
+        iqgpu_chain_desc nd = o.desc;
+        nd.dc_block_enable = 0;
+        if (iqgpu_design_preroll_frames(&nd, &preroll) != IQGPU_OK) { fprintf(stderr, "--seamless-dc: %s\n", iqgpu_last_error()); return 1; }
+        const long long cf = (long long)o.chunk_frames;
+        const long long pre_calls = ((long long)preroll + cf - 1) / cf * cf;
+        long long grid = 4096;
+        { long long x = grid, y = cf; while (y) { const long long t = x % y; x = y; y = t; } grid = grid / x * cf; }
+        for (int s = 0; s < o.shards; s++) {
+            const long long next = (s == o.shards - 1) ? total_frames : ((long long)(s + 1) * per) / grid * grid;
+            sh[s].opt = &o; sh[s].shard = s;
+            sh[s].first_frame = ((long long)s * per) / grid * grid;
+            sh[s].frames = next - sh[s].first_frame;
+            if (sh[s].frames <= 0) {
+                fprintf(stderr, "--seamless-dc: %lld frames are too few for %d shards on a grid of %lld frames (lcm of 4096 and --chunk-frames): "
+                                "shard %d would be empty\n", total_frames, o.shards, grid, s);
+                return 1;
+            }
+            sh[s].preroll_frames = sh[s].first_frame < pre_calls ? sh[s].first_frame : pre_calls;
+            uint64_t first_out = 0, nout = 0;
+            if (iqgpu_design_out_frames_range(&o.desc, (uint64_t)sh[s].first_frame, (uint64_t)sh[s].frames, &first_out, &nout) != IQGPU_OK) {
+                fprintf(stderr, "%s\n", iqgpu_last_error()); return 1;
+            }
+            sh[s].out_offset_bytes = (long long)first_out * (long long)obps;
+            sh[s].planned_out = (long long)nout;
+            if (o.dry && s < o.shards - 1) sh[s].n_dc_rows = (sh[s].frames + cf - 1) / cf;     /* rows pass 1 will record: one per call */
+        }
+        g_shards = sh;
+        if (!o.dry && pthread_barrier_init(&g_pass, NULL, (unsigned)o.shards) != 0) { fprintf(stderr, "pthread_barrier_init failed\n"); return 1; }
+    }
+    for (int s = 0; s < o.shards && !o.seamless && !o.seamless_agc && !o.seamless_dc; s++) {
         sh[s].opt = &o; sh[s].shard = s;
         sh[s].first_frame = (long long)s * per;
         sh[s].frames = (s == o.shards - 1) ? total_frames - sh[s].first_frame : per;
@@ -564,11 +677,12 @@ int main(int argc, char **argv)
         int distinct = 0;
         for (int s = 0; s < o.shards; s++) { int seen = 0; for (int q = 0; q < s; q++) if (!strcmp(sh[q].bus_id, sh[s].bus_id) && sh[q].device == sh[s].device) seen = 1; if (!seen) distinct++; }
         printf("{\"dry_placement\": true, %s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"distinct_devices\": %d, \"per_shard\": [",
-               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : "", total_frames, frames_out, o.shards, o.devices, distinct);
+               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : o.seamless_dc ? "\"seamless_dc\": true, " : "", total_frames, frames_out, o.shards, o.devices, distinct);
         for (int s = 0; s < o.shards; s++) {
             char pre_kv[96] = "";
             if (o.seamless) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld", sh[s].preroll_frames);
             if (o.seamless_agc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"agc_rows\": %lld", sh[s].preroll_frames, sh[s].agc_rows);
+            if (o.seamless_dc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"dc_rows\": %lld", sh[s].preroll_frames, sh[s].n_dc_rows);
             printf("%s{\"shard\": %d, \"device\": %d, \"pci_bus_id\": \"%s\", \"numa_node\": %d, \"cpus_allowed\": %d, \"first_frame\": %lld, \"frames_in\": %lld, \"planned_out\": %lld, "
                    "\"out_offset_bytes\": %lld, \"pinned_bytes\": %lld, \"hbm_bytes\": %lld%s}", s ? ", " : "", s, sh[s].device, sh[s].bus_id, sh[s].numa_node, sh[s].cpus_allowed,
                    sh[s].first_frame, sh[s].frames, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].pinned_bytes, sh[s].hbm_bytes, pre_kv);
@@ -580,7 +694,7 @@ int main(int argc, char **argv)
     if (!o.quiet) {
         printf("{%s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"seconds\": %.6f, \"msps_end_to_end\": %.3f, \"stream_seconds\": %.6f, \"msps_streaming\": %.3f, "
                "\"h2d_GBs\": %.3f, \"d2h_GBs\": %.3f, \"in_bytes_per_frame\": %zu, \"out_bytes_per_frame\": %zu, \"input\": \"%s\", \"per_shard\": [",
-               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : "", total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
+               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : o.seamless_dc ? "\"seamless_dc\": true, " : "", total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
                stream_s > 0 ? (double)total_frames * (double)ibps / stream_s / 1e9 : 0.0, stream_s > 0 ? (double)frames_out * (double)obps / stream_s / 1e9 : 0.0, ibps, obps,
                o.synthetic_frames <= 0 ? "file" : o.have_hash ? "synthetic-hash" : "synthetic-constant");
         for (int s = 0; s < o.shards; s++) {
@@ -590,12 +704,15 @@ int main(int argc, char **argv)
                 "\"peak_memory\": %.9g, \"current_gain\": %.9g, \"last_strong_peak_time\": %.17g, \"samples_seen\": %llu}", sh[s].preroll_frames, sh[s].measure_seconds,
                 sh[s].agc_rows, sh[s].entry.locked, (double)sh[s].entry.peak_memory, (double)sh[s].entry.current_gain, sh[s].entry.last_strong_peak_time,
                 (unsigned long long)sh[s].entry.samples_seen);
+            if (o.seamless_dc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"measure_seconds\": %.6f, \"dc_rows\": %lld, \"entry\": {\"re\": %.17g, \"im\": %.17g}",
+                sh[s].preroll_frames, sh[s].measure_seconds, sh[s].n_dc_rows, sh[s].dc_entry.re, sh[s].dc_entry.im);
             printf("%s{\"shard\": %d, \"device\": %d, \"numa_node\": %d, \"first_frame\": %lld, \"frames_in\": %lld, \"frames_out\": %lld, \"planned_out\": %lld, \"out_offset_bytes\": %lld, \"seconds\": %.6f%s}",
                    s ? ", " : "", s, sh[s].device, sh[s].numa_node, sh[s].first_frame, sh[s].frames, sh[s].frames_out, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].stream_seconds, pre_kv);
         }
         printf("]}\n");
     }
     for (int s = 0; s < o.shards; s++) if (sh[s].rows) iqgpu_host_free_pinned(sh[s].rows);
+    for (int s = 0; s < o.shards; s++) free(sh[s].dc_rows);
     free(th); free(sh);
     return rc;
 }

@@ -512,6 +512,10 @@ hipError_t launch_dc_prefix(const DcPrefixArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
+// the blocker's state behind a piece of stream whose map is v -> f v + g.  ONE definition: k_dc_scan's state update and k_dc_walk
+// (iqgpu_chain_dc_advance) both call it, so a walked state is the ordinary path's bit for bit
+__device__ inline cd2 dc_map_apply(double f, double gr, double gi, cd2 v) { return cd2{f * v.x + gr, f * v.y + gi}; }
+
 constexpr int kDcScanThreads = 1024;      // one workgroup, 3 segments a thread for a launch of 3 072 runs: 11.7 us (256 threads: 17.8 us; loading the
                                           // aggregates ahead of the folds changes nothing -- the folds' 64-bit index arithmetic and the barriers of the scan do)
 // carry[s] = state before segment s; state <- state after the last sample.  The per-segment maps
@@ -552,6 +556,11 @@ __global__ __launch_bounds__(kDcScanThreads) void k_dc_scan(const DcScanArgs a)
         if (has) { sr[tid] = sr[tid] + sf[tid] * pr; si[tid] = si[tid] + sf[tid] * pi; sf[tid] = sf[tid] * pf; }
         __syncthreads();
     }
+    // the measure pass (iqgpu_chain_dc_measure): the call's whole map and nothing else -- state and carries stay as they are
+    if (a.map) {
+        if (tid == kDcScanThreads - 1) { a.map[0] = cd2{sf[tid], 0.0}; a.map[1] = cd2{sr[tid], si[tid]}; }
+        return;
+    }
     const double v0r = a.state->x, v0i = a.state->y;
     // state before this thread's slice = (inclusive scan of the previous thread) applied to v0
     double vr = v0r, vi = v0i;
@@ -567,12 +576,32 @@ __global__ __launch_bounds__(kDcScanThreads) void k_dc_scan(const DcScanArgs a)
         }
     }
     __syncthreads();
-    if (tid == kDcScanThreads - 1) { a.state->x = sf[tid] * v0r + sr[tid]; a.state->y = sf[tid] * v0i + si[tid]; }
+    if (tid == kDcScanThreads - 1) *a.state = dc_map_apply(sf[tid], sr[tid], si[tid], cd2{v0r, v0i});
 }
 
 hipError_t launch_dc_scan(const DcScanArgs &a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_dc_scan, dim3(1), dim3(kDcScanThreads), 0, s, a);
+    return hipGetLastError();
+}
+
+// iqgpu_chain_dc_advance: *state walked over n per-call maps in order, before[k] = the state in front of map k.  One thread: the
+// walk is a chain of n dependent multiply-adds.
+__global__ __launch_bounds__(64) void k_dc_walk(const DcWalkArgs a)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    cd2 v = *a.state;
+    for (int64_t k = 0; k < a.n; ++k) {
+        if (a.before) a.before[k] = v;
+        const DcMapRow r = a.rows[k];
+        v = dc_map_apply(r.f, r.g_re, r.g_im, v);
+    }
+    *a.state = v;
+}
+
+hipError_t launch_dc_walk(const DcWalkArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_dc_walk, dim3(1), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

@@ -325,8 +325,19 @@ struct DcScanArgs {
     cd2       *state;         // in: state before sample 0; out: state after the last sample
     DcGeom     geom;
     double     logc;
+    cd2       *map;           // not NULL (iqgpu_chain_dc_measure): the call's map v -> F v + G goes here, map[0] = {F, 0}, map[1] = G,
+                              // and neither state nor carry is read or written
 };
 hipError_t launch_dc_scan(const DcScanArgs &a, hipStream_t s);
+
+// one CALL's map of the blocker's state, v_after = f v_before + g (iqgpu_dc_row's layout), and the walk over a table of them
+struct DcMapRow { double f, g_re, g_im; uint64_t frames; };
+struct DcWalkArgs {
+    const DcMapRow *rows; int64_t n;
+    cd2 *state;               // in: the state in front of rows[0]; out: behind rows[n-1]
+    cd2 *before;              // [n] or NULL: the state in front of every row
+};
+hipError_t launch_dc_walk(const DcWalkArgs &a, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // k_fir: time-domain FIR over the cf32 filter-input buffer, [post NCO], pack

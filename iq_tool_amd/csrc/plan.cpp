@@ -99,7 +99,7 @@ StreamAt stream_at(const iqgpu_chain *c, uint64_t frames)
 //                       resampler outputs behind it: n outputs span ceil(n step / 2^24) + 1 groups of 2^S frames
 //   dc blocker          ceil(ln(1e6) / alpha) frames in front of all that: the state error decays as (1 - alpha)^n and reaches the
 //                       output as alpha * e with |e| <= max|x| / alpha -- 1e-6 of full scale after that many frames (iqgpu.h)
-uint64_t seek_preroll_frames(const iqgpu_chain *c)
+uint64_t seek_preroll_frames(const iqgpu_chain *c, bool with_dc)
 {
     uint64_t n = 0;
     if (c->decim) {
@@ -115,7 +115,7 @@ uint64_t seek_preroll_frames(const iqgpu_chain *c)
         if (c->decim) f = (((f * (uint64_t)c->rp.step + (((uint64_t)1 << 24) - 1)) >> 24) + 1) << c->S;
         n += f;
     }
-    if (c->dc) n += (uint64_t)std::ceil(std::log(1e6) / (double)c->dc_alpha);
+    if (c->dc && with_dc) n += (uint64_t)std::ceil(std::log(1e6) / (double)c->dc_alpha);
     return n;
 }
 

@@ -333,6 +333,42 @@ int Call::stage_late_resampler()
     return IQGPU_OK;
 }
 
+// what every call starts from: the plan at the chain's position and where the last stage writes without an AGC behind it
+static Call begin_call(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, void *d_out, const CallOpts &o)
+{
+    Call k{};
+    k.c = c; k.d_raw_in = d_raw_in; k.frames_in = frames_in; k.d_out = d_out; k.o = o;
+    k.p = plan_call(c, frames_in);
+    k.filt = c->fp.enabled;
+    k.L1 = k.filt ? c->fp.taps.size() - 1 : 0;
+    k.fpending0 = c->fpending;
+    k.fin_out = d_out; k.fin_fmt = c->desc.out_format;
+    return k;
+}
+
+// iqgpu_chain_dc_measure: the DC blocker's map of ONE call -- the call an ordinary process of frames_in frames at stream position `at`
+// would be, planned by the code that plans it (begin_call, plan_geometry, dc_geom), of which only k_dc_prefix and the scan are
+// launched; the scan writes the map to d_map and leaves the chain's DC state and carries alone.  The chain's position is put back.
+int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, cd2 *d_map)
+{
+    const StreamPos was{c->rem, c->phi, c->fpending};
+    c->rem = at.rem; c->phi = at.phi; c->fpending = at.fpending;
+    Call k = begin_call(c, d_raw_in, frames_in, nullptr, CallOpts());
+    k.plan_geometry();
+    const DcGeom dg = k.dc_geom();
+    c->rem = was.rem; c->phi = was.phi; c->fpending = was.fpending;
+    int rc = c->dc_agg.ensure((size_t)dg.n_seg * sizeof(cf2)); if (rc) return rc;
+    DcPrefixArgs pa{};
+    pa.raw = d_raw_in; pa.in_fmt = c->desc.in_format; pa.gain = c->desc.gain;
+    pa.raw_aligned = k.raw_aligned();
+    pa.c = c->dc_c; pa.logc = c->dc_logc; pa.geom = dg; pa.agg = (cf2 *)c->dc_agg.p;
+    HIP_TRY(launch_dc_prefix(pa, c->stream));
+    DcScanArgs sa{};
+    sa.agg = (const cf2 *)c->dc_agg.p; sa.geom = dg; sa.logc = c->dc_logc; sa.map = d_map;
+    HIP_TRY(launch_dc_scan(sa, c->stream));
+    return IQGPU_OK;
+}
+
 static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
                        void *d_out, size_t out_capacity_bytes, size_t *frames_out, const CallOpts &o, bool past_lock)
 {   // past_lock: the part of an ordinary call behind the AGC's lock, on a chain whose last kernel applies the gain itself
@@ -347,18 +383,12 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     // a fused launch of an earlier call may still owe its fallback: before anything of this call is queued behind it
     { const int prc = agc_resolve_pending(c); if (prc) return prc; }
 
-    Call k{};
-    k.c = c; k.d_raw_in = d_raw_in; k.frames_in = frames_in; k.d_out = d_out; k.o = o;
-    k.p = plan_call(c, frames_in);
+    Call k = begin_call(c, d_raw_in, frames_in, d_out, o);
     const size_t obps = bytes_per_frame(c->desc.out_format);
     if (!bypass && (size_t)k.p.n_emit * obps > out_capacity_bytes)
         return fail(IQGPU_ECAPACITY, "output buffer too small: need %zu bytes, have %zu", (size_t)k.p.n_emit * obps, out_capacity_bytes);
-    k.filt = c->fp.enabled;
-    k.L1 = k.filt ? c->fp.taps.size() - 1 : 0;
-    k.fpending0 = c->fpending;
     // with the AGC on, the last stage leaves cf32 in abuf and k_agc_apply packs -- unless the call is past the lock
     // on a chain whose front kernel applies the gain itself (fused: packed output straight to the caller)
-    k.fin_out = d_out; k.fin_fmt = c->desc.out_format;
     // (the measure pass on k_front_s1<.., AGC>: the fused front launch as it is, against a scratch state and with no verdict -- stage_front)
     const bool agc_fused = past_lock || o.agc == AgcMode::MeasureS1;
     k.agc_fused = agc_fused;

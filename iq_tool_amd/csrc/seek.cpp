@@ -1,5 +1,5 @@
 // seek.cpp -- seamless range sharding: a chain started mid-stream, the AGC measure pass (both: modes of process.cpp's call; its pipelined
-// form is in pipeline.cpp), the AGC walk
+// form is in pipeline.cpp), the AGC walk; the DC blocker's measure pass, walk and seek
 #include "chain.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -18,11 +18,24 @@ int agc_two_pass_check(const iqgpu_chain *c, const char *who)
     return IQGPU_OK;
 }
 
-// agc_variant: iqgpu_chain_seek_agc -- the preroll with the AGC out of the way, then *entry (or the fresh state) installed
-static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, bool on_device,
-                     bool agc_variant = false, const iqgpu_agc_state *entry = nullptr)
+// what the exact two-pass calls of DC-blocker chains ask of a chain
+static int dc_two_pass_check(const iqgpu_chain *c, const char *who)
 {
-    const char *who = agc_variant ? "iqgpu_chain_seek_agc" : "iqgpu_chain_seek";
+    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
+    if (!c->dc) return fail(IQGPU_EINVAL, "%s: the chain has no DC blocker", who);
+    if (c->agc) return fail(IQGPU_EUNSUPPORTED, "%s: a chain with the output AGC -- its measure route may cut a call into other segments than "
+        "the process route, so the two exact recipes do not combine yet", who);
+    return IQGPU_OK;
+}
+
+// agc_variant: iqgpu_chain_seek_agc -- the preroll with the AGC out of the way, then *entry (or the fresh state) installed
+// dc_variant: iqgpu_chain_seek_dc -- no warm-up of the DC blocker asked for: *dc_at (or zero) is its state in front of the preroll,
+// which runs in calls of call_frames (0: one call)
+struct SeekDc { bool on = false; const iqgpu_dc_state *at = nullptr; size_t call_frames = 0; };
+static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, bool on_device,
+                     bool agc_variant = false, const iqgpu_agc_state *entry = nullptr, const SeekDc &dcv = SeekDc())
+{
+    const char *who = dcv.on ? "iqgpu_chain_seek_dc" : agc_variant ? "iqgpu_chain_seek_agc" : "iqgpu_chain_seek";
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
     // what iqgpu_chain_reset does comes first: batches in flight and a pending verdict resolved, histories and dc state zeroed,
     // the poison cleared -- a refused argument below leaves the chain reset
@@ -32,6 +45,14 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         rc = agc_two_pass_check(c, who); if (rc) return rc;
         if (entry && (entry->locked != 0 && entry->locked != 1)) return fail(IQGPU_EINVAL, "%s: entry state with locked = %d", who, entry->locked);
     }
+    cd2 dc_at{0.0, 0.0};
+    if (dcv.on) {
+        rc = dc_two_pass_check(c, who); if (rc) return rc;
+        if (dcv.at) { dc_at.x = dcv.at->re; dc_at.y = dcv.at->im; }
+        if (!std::isfinite(dc_at.x) || !std::isfinite(dc_at.y)) return fail(IQGPU_EINVAL, "%s: the state in front of the preroll is not finite", who);
+        if (dcv.call_frames && preroll_frames % dcv.call_frames != 0) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames is not a whole number "
+            "of calls of %zu frames", who, preroll_frames, dcv.call_frames);
+    }
     if (first_frame > kMaxStreamFrames) return fail(IQGPU_EINVAL, "%s: frame %llu is beyond 2^39 frames", who,
         (unsigned long long)first_frame);
     if ((uint64_t)preroll_frames > first_frame) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames would start in front of "
@@ -39,11 +60,18 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
     if (first_frame > 0) {
         if (c->agc && !agc_variant) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
             "not on a bounded warm-up");
-        const uint64_t memory = seek_preroll_frames(c), need = first_frame < memory ? first_frame : memory;
+        const uint64_t memory = seek_preroll_frames(c, !dcv.on), need = first_frame < memory ? first_frame : memory;
         if ((uint64_t)preroll_frames < need) return fail(IQGPU_EINVAL, "%s: preroll of %zu frames is shorter than the %llu "
             "this chain needs at frame %llu", who, preroll_frames, (unsigned long long)need, (unsigned long long)first_frame);
         if (preroll_frames && !preroll) return fail(IQGPU_EINVAL, "%s: NULL preroll", who);
-
+    }
+    if (dcv.on) {
+        // the blocker's state in front of the preroll (at frame 0: of the stream), where the reset has left zero -- behind every
+        // refusal, so that a refused call leaves the chain reset
+        HIP_TRY(hipMemcpyAsync(c->d_dc_state, &dc_at, sizeof(cd2), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (first_frame > 0) {
         const StreamAt from = stream_at(c, first_frame - (uint64_t)preroll_frames);
         if (c->fp.enabled) {
             // [L-1 history][pending]: zeros stand for the samples in front of the warm-up
@@ -54,7 +82,19 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         c->rem = from.pos.rem; c->phi = from.pos.phi; c->fpending = from.pos.fpending;
         c->nco_theta = from.nco_theta; c->pnco_theta = from.pnco_theta;
 
-        if (preroll_frames) {
+        if (dcv.on) {
+            // the preroll runs in the single stream's own calls -- every one staged like a call of iqgpu_chain_process -- from the
+            // single stream's own state
+            const size_t obps = bytes_per_frame(c->desc.out_format), ibps = bytes_per_frame(c->desc.in_format);
+            const size_t per = dcv.call_frames ? dcv.call_frames : preroll_frames;
+            for (size_t at = 0; at < preroll_frames; at += per) {
+                const void *src = (const char *)preroll + at * ibps, *d_in = src;
+                if (!on_device) { rc = stage_host_input(c, src, per, &d_in); if (rc) return rc; }
+                size_t dropped = 0;
+                rc = c->seek_sink.ensure((size_t)plan_call(c, per).n_emit * obps + 16); if (rc) return rc;
+                rc = process_device_impl(c, d_in, per, c->seek_sink.p, c->seek_sink.cap, &dropped); if (rc) return rc;
+            }
+        } else if (preroll_frames) {
             const size_t obps = bytes_per_frame(c->desc.out_format);
             const void *d_in = preroll;
             if (!on_device) { rc = stage_host_input(c, preroll, preroll_frames, &d_in); if (rc) return rc; }
@@ -112,6 +152,89 @@ extern "C" int iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame,
                                            const iqgpu_agc_state *entry)
 {
     return seek_impl(c, first_frame, d_preroll, preroll_frames, true, true, entry);
+}
+
+extern "C" int iqgpu_chain_seek_dc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
+                                   const iqgpu_dc_state *at_preroll_start)
+{
+    return seek_impl(c, first_frame, preroll, preroll_frames, false, false, nullptr, SeekDc{true, at_preroll_start, call_frames});
+}
+extern "C" int iqgpu_chain_seek_dc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
+                                          size_t call_frames, const iqgpu_dc_state *at_preroll_start)
+{
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, true, false, nullptr, SeekDc{true, at_preroll_start, call_frames});
+}
+
+// ------------------------------------------------------------------------------------------------
+// exact seamless sharding of DC-blocker chains: the map of a call (k_dc_prefix + k_dc_scan's map output), the walk over the maps
+// ------------------------------------------------------------------------------------------------
+static int dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const void *in, size_t frames_in, iqgpu_dc_row *row, bool on_device)
+{
+    const char *who = "iqgpu_chain_dc_measure";
+    int rc = dc_two_pass_check(c, who); if (rc) return rc;
+    if (!row) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
+    if (first_frame > kMaxStreamFrames || (uint64_t)frames_in > kMaxStreamFrames - first_frame) return fail(IQGPU_EINVAL, "%s: stream position "
+        "%llu + %zu frames is beyond 2^39 frames", who, (unsigned long long)first_frame, frames_in);
+    row->f = 1.0; row->g_re = 0.0; row->g_im = 0.0; row->frames = 0;             // (no frames: the identity)
+    if (frames_in == 0) return IQGPU_OK;
+    if (!in) return fail(IQGPU_EINVAL, "%s: NULL buffer", who);
+    if (c->poisoned) return fail(IQGPU_EHIP, "an earlier call failed half way through: the stream state is undefined until iqgpu_chain_reset()");
+    HIP_TRY(hipSetDevice(c->device));
+    rc = pipe_advance(c, c->pipe_seq); if (rc) return rc;         // batches submitted earlier come first (same stream)
+    rc = c->dc_walk.ensure(64); if (rc) return rc;
+    const void *d_in = in;
+    if (!on_device) { rc = stage_host_input(c, in, frames_in, &d_in); if (rc) return rc; }
+    rc = dc_measure_call(c, stream_at(c, first_frame).pos, d_in, frames_in, (cd2 *)c->dc_walk.p); if (rc) return rc;
+    cd2 m[2];
+    HIP_TRY(hipMemcpyAsync(m, c->dc_walk.p, sizeof(m), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    row->f = m[0].x; row->g_re = m[1].x; row->g_im = m[1].y; row->frames = (uint64_t)frames_in;
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_chain_dc_measure(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, iqgpu_dc_row *row)
+{
+    return dc_measure_impl(c, first_frame, raw_in, frames_in, row, false);
+}
+extern "C" int iqgpu_chain_dc_measure_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, iqgpu_dc_row *row)
+{
+    return dc_measure_impl(c, first_frame, d_raw_in, frames_in, row, true);
+}
+
+// One definition of the walk: k_dc_walk applies the helper behind k_dc_scan's state update, in the translation unit of k_dc_scan, a
+// batch of 2^16 rows per launch from a scratch copy of *st
+extern "C" int iqgpu_chain_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
+{
+    static_assert(sizeof(iqgpu_dc_row) == sizeof(DcMapRow) && sizeof(DcMapRow) == 32 && sizeof(iqgpu_dc_state) == sizeof(cd2), "DC row layout");
+    const char *who = "iqgpu_chain_dc_advance";
+    int rc = dc_two_pass_check(c, who); if (rc) return rc;
+    if (!st || (n && !rows)) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
+    if (!std::isfinite(st->re) || !std::isfinite(st->im)) return fail(IQGPU_EINVAL, "%s: the state is not finite", who);
+    for (size_t i = 0; i < n; ++i)
+        if (!(rows[i].f > 0.0 && rows[i].f <= 1.0) || !std::isfinite(rows[i].g_re) || !std::isfinite(rows[i].g_im))
+            return fail(IQGPU_EINVAL, "%s: row %zu is not a row of iqgpu_chain_dc_measure (f %g, g %g %+gi)", who, i, rows[i].f, rows[i].g_re,
+                rows[i].g_im);
+    if (n == 0) return IQGPU_OK;
+    HIP_TRY(hipSetDevice(c->device));
+    constexpr size_t kBatch = (size_t)1 << 16;
+    const size_t nb_max = n < kBatch ? n : kBatch;
+    // [state][rows x nb_max][before x nb_max]
+    rc = c->dc_walk.ensure(64 + nb_max * (sizeof(DcMapRow) + sizeof(cd2))); if (rc) return rc;
+    cd2 *d_st = (cd2 *)c->dc_walk.p;
+    DcMapRow *d_rows = (DcMapRow *)((char *)c->dc_walk.p + 64);
+    cd2 *d_before = (cd2 *)(d_rows + nb_max);
+    HIP_TRY(hipMemcpyAsync(d_st, st, sizeof(cd2), hipMemcpyHostToDevice, c->stream));
+    for (size_t done = 0; done < n; done += kBatch) {
+        const size_t nb = n - done < kBatch ? n - done : kBatch;
+        HIP_TRY(hipMemcpyAsync(d_rows, rows + done, nb * sizeof(DcMapRow), hipMemcpyHostToDevice, c->stream));
+        DcWalkArgs a{};
+        a.rows = d_rows; a.n = (int64_t)nb; a.state = d_st; a.before = before ? d_before : nullptr;
+        HIP_TRY(launch_dc_walk(a, c->stream));
+        if (before) HIP_TRY(hipMemcpyAsync(before + done, d_before, nb * sizeof(cd2), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    HIP_TRY(hipMemcpy(st, d_st, sizeof(cd2), hipMemcpyDeviceToHost));
+    return IQGPU_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
