@@ -63,6 +63,7 @@ enum {
     IQGPU_EUNSUPPORTED = -10/* the placement calls: a *_VISIBLE_DEVICES list that is not plain indices                */
                             /* iqgpu_chain_seek and the two range-design calls: a chain with the output AGC              */
                             /* the AGC two-pass calls (measure*, agc_advance, seek_agc*): profile dx / local, CLOCK_WALL */
+                            /* iqgpu_chain_save_state: a chain on IQGPU_AGC_CLOCK_WALL                                   */
 };
 
 typedef struct iqgpu_chain iqgpu_chain; /* opaque, like resampler_t (include/resampler.h:25-26) */
@@ -367,6 +368,57 @@ int    iqgpu_chain_seek_dc(iqgpu_chain *c, uint64_t first_frame, const void *pre
                            const iqgpu_dc_state *at_preroll_start);
 int    iqgpu_chain_seek_dc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames, size_t call_frames,
                                   const iqgpu_dc_state *at_preroll_start);
+/* ---- checkpoint / resume: everything a chain carries from call to call, in a caller-owned blob (additive, still ABI v9) ----
+ * The seek calls above rebuild the state at a stream position from a closed form and a preroll, and refuse what has no such form.
+ * These two calls need none: iqgpu_chain_save_state copies the state out between two calls, iqgpu_chain_load_state puts it into a
+ * chain of the same description -- in this process or another, on this device or another -- and that chain continues the stream
+ * byte for byte: the same kernels on the same state in the same calls.  They cover every chain the library builds: the output AGC
+ * in all three profiles, the DC blocker with the AGC, factors moved by the I/Q optimiser.
+ * What is carried: the stream position (open decimation group, resampler phase, both NCO phases, pending FFT-block samples) and
+ * the two frame counters of iqgpu_chain_tell; the half-band / polyphase history of the front kernel and, behind k_cascade, of its
+ * last stage; the user filter's [L-1 history][pending] buffer front; the history of the r >= 1 resampler; the DC blocker's state;
+ * the AGC state with the host's mirrors of it and, for dx / local, the warm-up window and the position of its chunk grid; the I/Q
+ * correction factors in force.  Not carried: the description itself (the loading chain is created from it as usual), the stream
+ * and device the chain runs on, profiling, the I/Q probe, batches in flight (save runs them to their end first).
+ * The blob: a 64-byte header (magic, format_version, total size, fingerprint, the two counters, a 64-bit checksum over all the
+ * rest), the host-side words, then the device buffers as logical contents -- which buffer of a ping-pong pair is current is not
+ * stored.  Its size is FIXED per description: buffers whose live length varies are stored at their maximum (the filter front at
+ * L-1 + block) with the unused tail zeroed, so iqgpu_design_state_size needs no device and equals *bytes of every save, and the
+ * blob is a function of the state alone: the same state gives the same bytes.  Little-endian, as the host is.
+ * The fingerprint covers everything the layout and the meaning of the contents depend on: the description's fields that shape the
+ * design and what the design derived from them (ratio bits, half-band plan, phase step, NCO step, filter taps and block, history
+ * sizes, AGC chunk, target and profile, formats, gain, block_samples) and the chain's snapshot of the diagnostic switches, which
+ * decides the routing and with it the history layouts.  It does not cover the I/Q factors, device_ordinal, the stream or profiling.
+ * Refused: iqgpu_chain_save_state on a chain with IQGPU_AGC_CLOCK_WALL is IQGPU_EUNSUPPORTED (a monotonic clock reading means
+ * nothing in another process: the policy of the two-pass calls); on a poisoned chain IQGPU_EHIP; with cap below the blob's size
+ * IQGPU_ECAPACITY, *bytes set to the size needed (blob may then be NULL with cap 0: a size query).  iqgpu_chain_load_state checks
+ * everything BEFORE it touches the chain -- NULL, size, magic, format_version, checksum, fingerprint against this chain, the range of
+ * the position words -- and answers IQGPU_EINVAL with a message that names the mismatch; a refused load leaves the chain exactly as it
+ * was (unlike a refused seek, which leaves it reset: here the validation is total).
+ * iqgpu_chain_save_state first runs every batch already submitted and resolves a pending AGC verdict, as iqgpu_chain_get_agc_state
+ * does, then copies; it changes nothing: a chain that saved continues exactly like one that did not, and the tickets in flight are
+ * collected as usual.  iqgpu_chain_load_state then does what iqgpu_chain_reset does (batches in flight and a pending verdict
+ * resolved, the poison cleared), installs the state and returns with the chain's stream idle; per-call scratch is left as after a
+ * reset.  A stage thread checkpoints between calls; with batches in flight it collects the tickets it still wants first or after.
+ * iqgpu_chain_tell: input frames consumed and output frames emitted since the last reset -- after a seek: first_frame and the index
+ * of the stream's output frame there -- behind every batch already submitted (what submit() has promised, like
+ * iqgpu_chain_next_out_frames).  No device call.
+ * iqgpu_state_inspect: magic, version, size and checksum of a blob, and the header's figures; no device, no chain. */
+typedef struct {
+    uint32_t format_version;            /* of the blob layout                                     */
+    uint32_t reserved;
+    uint64_t bytes;                     /* total blob size                                        */
+    uint64_t fingerprint;               /* of everything the layout and contents depend on        */
+    uint64_t frames_in;                 /* input frames consumed since the last reset / seek base */
+    uint64_t frames_out;                /* output frames emitted since then                       */
+} iqgpu_state_info;
+#define IQGPU_STATE_FORMAT_VERSION 1
+/* size of the blob of a chain of this description; no device; same validation and error codes as iqgpu_design_probe */
+int    iqgpu_design_state_size(const iqgpu_chain_desc *d, size_t *bytes);
+int    iqgpu_state_inspect(const void *blob, size_t bytes, iqgpu_state_info *info);
+int    iqgpu_chain_tell(iqgpu_chain *c, uint64_t *frames_in, uint64_t *frames_out);
+int    iqgpu_chain_save_state(iqgpu_chain *c, void *blob, size_t cap, size_t *bytes);
+int    iqgpu_chain_load_state(iqgpu_chain *c, const void *blob, size_t bytes);
 /* what the I/Q optimiser thread publishes (src/iq_correct.c:141-152 reads them once per chunk) */
 int    iqgpu_chain_set_iq_factors(iqgpu_chain *c, float mag, float phase);
 /* synchronises the chain's stream and reports the AGC state (agc.c keeps it in AppResources) */

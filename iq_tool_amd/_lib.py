@@ -57,6 +57,12 @@ class DcRow(C.Structure):
     _fields_ = [("f", C.c_double), ("g_re", C.c_double), ("g_im", C.c_double), ("frames", C.c_uint64)]
 
 
+class StateInfo(C.Structure):
+    """iqgpu_state_info: the header figures of a saved chain state (iqgpu_state_inspect)"""
+    _fields_ = [("format_version", C.c_uint32), ("reserved", C.c_uint32), ("bytes", C.c_uint64), ("fingerprint", C.c_uint64),
+                ("frames_in", C.c_uint64), ("frames_out", C.c_uint64)]
+
+
 class ChainInfo(C.Structure):
     _fields_ = [("ratio", C.c_float), ("interp", C.c_int), ("num_halfband_stages", C.c_int),
                 ("stage_m", C.c_int * 16), ("rate_arb", C.c_float), ("arb_step", C.c_uint32),
@@ -139,6 +145,11 @@ SYMBOLS = [
     ("iqgpu_chain_dc_advance", C.c_int, [_vp, C.POINTER(DcState), _vp, _sz, _vp]),
     ("iqgpu_chain_seek_dc", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
     ("iqgpu_chain_seek_dc_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
+    ("iqgpu_design_state_size", C.c_int, [C.POINTER(ChainDesc), C.POINTER(_sz)]),
+    ("iqgpu_state_inspect", C.c_int, [_vp, _sz, C.POINTER(StateInfo)]),
+    ("iqgpu_chain_tell", C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("iqgpu_chain_save_state", C.c_int, [_vp, _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_chain_load_state", C.c_int, [_vp, _vp, _sz]),
     ("iqgpu_chain_set_iq_factors", C.c_int, [_vp, C.c_float, C.c_float]),
     ("iqgpu_chain_max_out_frames", _sz, [_vp, _sz]),
     ("iqgpu_chain_next_out_frames", _sz, [_vp, _sz]),

@@ -8,7 +8,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (BYTES_PER_FRAME, FILTER, FILTER_IMPL, FMT, AgcState, ChainDesc, ChainInfo, DcState, FilterReq,
-                   IqgpuError, Profile, check)
+                   IqgpuError, Profile, StateInfo, check)
 
 AGC_PROFILE = {"off": 0, "dx": 1, "local": 2, "digital": 3}
 # iqgpu_agc_chunk as a numpy record: what Chain.measure returns and Chain.agc_advance takes
@@ -95,6 +95,24 @@ def design_out_frames_range(first_frame, frames_in, **kw):
     first, n = C.c_uint64(0), C.c_uint64(0)
     check(_lib.load().iqgpu_design_out_frames_range(C.byref(d), int(first_frame), int(frames_in), C.byref(first), C.byref(n)))
     return int(first.value), int(n.value)
+
+
+def design_state_size(**kw):
+    """bytes of the blob Chain.save_state() returns for a chain of this description (iqgpu_design_state_size; no device needed)"""
+    d = make_desc(**kw)
+    n = C.c_size_t(0)
+    check(_lib.load().iqgpu_design_state_size(C.byref(d), C.byref(n)))
+    return int(n.value)
+
+
+def state_inspect(blob):
+    """validates a saved state's magic, version, size and checksum (iqgpu_state_inspect; no device needed) and returns its header
+    figures: dict(format_version, bytes, fingerprint, frames_in, frames_out).  Raises IqgpuError (EINVAL) on anything else."""
+    blob = bytes(blob) if blob is not None else None
+    info = StateInfo()
+    check(_lib.load().iqgpu_state_inspect(blob, len(blob) if blob is not None else 0, C.byref(info)))
+    return dict(format_version=int(info.format_version), bytes=int(info.bytes), fingerprint=int(info.fingerprint),
+                frames_in=int(info.frames_in), frames_out=int(info.frames_out))
 
 
 def bind_thread_to_device(ordinal):
@@ -373,6 +391,34 @@ class Chain:
             st[...] = state
         check(self._lib.iqgpu_chain_seek_dc_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames), int(call_frames),
                                                    st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
+
+    # ---- checkpoint / resume (include/iqgpu.h): the whole carried state in a blob, into a chain of the same description ----
+    def tell(self):
+        """(frames_in, frames_out) since the last reset -- after a seek: of the stream -- behind every batch already submitted"""
+        fi, fo = C.c_uint64(0), C.c_uint64(0)
+        check(self._lib.iqgpu_chain_tell(self._h, C.byref(fi), C.byref(fo)))
+        return int(fi.value), int(fo.value)
+
+    def state_size(self):
+        """bytes of this chain's saved state: fixed per description (a size query of iqgpu_chain_save_state)"""
+        n = C.c_size_t(0)
+        rc = self._lib.iqgpu_chain_save_state(self._h, None, 0, C.byref(n))
+        if rc != -8:                # IQGPU_ECAPACITY is the answer of a size query
+            check(rc)
+        return int(n.value)
+
+    def save_state(self):
+        """everything the chain carries from call to call, as bytes; the chain itself continues as if it had not been asked"""
+        buf = C.create_string_buffer(self.state_size())
+        n = C.c_size_t(0)
+        check(self._lib.iqgpu_chain_save_state(self._h, buf, len(buf), C.byref(n)))
+        return buf.raw[:n.value]
+
+    def load_state(self, blob):
+        """puts a save_state() blob of a chain of the same description into this chain: it continues that chain's stream byte for
+        byte.  A refused blob (IqgpuError, EINVAL) leaves this chain exactly as it was."""
+        blob = bytes(blob)
+        check(self._lib.iqgpu_chain_load_state(self._h, blob, len(blob)))
 
     def agc_state_raw(self):
         """the chain's AGC state as an AgcState structure: every field with its bits (synchronises)"""

@@ -184,7 +184,7 @@ static void free_device_state(iqgpu_chain *c)
 
 // the eight words behind d_agc_flag as a chain starts (and restarts, iqgpu_chain_reset) with them; static storage: the reset's
 // asynchronous copy reads it after the call has returned
-static const int32_t kAgcFlagInit[8] = {0, 0, 0, -1, 0, 0, 0, 0};
+const int32_t kAgcFlagInit[8] = {0, 0, 0, -1, 0, 0, 0, 0};
 
 template <typename T>
 static int upload(T **dst, const T *src, size_t n)
@@ -673,7 +673,7 @@ extern "C" int iqgpu_chain_reset(iqgpu_chain *c)
     { const int rc = agc_resolve_pending(c); if (rc && !c->poisoned) return rc; }        // ... and what their last fused launch owes
     c->pend.valid = false;
     c->poisoned = false;
-    c->rem = 0; c->phi = 0; c->nco_theta = 0; c->pnco_theta = 0;
+    c->rem = 0; c->phi = 0; c->nco_theta = 0; c->pnco_theta = 0; c->total_in = 0; c->total_out = 0;
     c->agc_locked_host = false; c->agc_seen_host = 0; c->agc_peak_clean = false; c->agc_rms_pos = 0;
     HIP_TRY(hipMemsetAsync(c->d_dc_state, 0, sizeof(cd2), c->stream));
     if (c->agc) { // agc_reset, src/agc.c:224-238

@@ -7,6 +7,8 @@
 //                  iqgpu_chain_dc_measure / _dc_advance
 //   agc_host.cpp   host side of the output AGC: chunk map, fused / unfused split, verifier + fallback launches
 //   pipeline.cpp   iqgpu_chain_submit / _measure_submit / _collect (pinned host buffers, three stages moved along by the host)
+//   state.cpp      checkpoint / resume: iqgpu_chain_tell, iqgpu_chain_save_state / _load_state, iqgpu_design_state_size (the blob's
+//                  header, checksum and iqgpu_state_inspect: state_blob.cpp, which includes nothing of HIP)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -140,6 +142,9 @@ struct iqgpu_chain {
     uint32_t nco_theta = 0;      // pre-NCO phase of the next input sample
     uint32_t pnco_theta = 0;     // post-NCO phase of the next output sample
     uint64_t fpending = 0;       // FFT-mode filter input samples not yet emitted
+    // input frames consumed and output frames emitted since the last reset (a seek: since frame 0 of the stream it seeks in);
+    // iqgpu_chain_tell, the header of a saved state
+    uint64_t total_in = 0, total_out = 0;
     // device state
     hipStream_t own_stream = nullptr, stream = nullptr;
     cf2 *d_nco_tab = nullptr; float *d_arb = nullptr; float *d_hb = nullptr; cf2 *d_ftaps = nullptr;
@@ -217,7 +222,7 @@ struct iqgpu_chain {
     uint64_t pipe_launched = 0;   // tickets whose kernels have been queued (<= pipe_seq)
     uint64_t pipe_copied = 0;     // tickets whose D2H copy has been queued (<= pipe_launched)
     // stream position behind the last ticket (valid while pipe_launched < pipe_seq)
-    int pipe_rem = 0; uint64_t pipe_phi = 0, pipe_fpending = 0;
+    int pipe_rem = 0; uint64_t pipe_phi = 0, pipe_fpending = 0, pipe_total_in = 0, pipe_total_out = 0;
     // I/Q optimiser probe: first 1024 pre-processed samples of a call (device -> pinned host), src/pipeline.c:468-476
     // (the optimiser runs on ITS OWN thread beside the stage thread: aux_mu guards the factors and the probe state;
     //  a block in flight or not yet read is never overwritten -- the optimiser takes at most two a second)
@@ -240,6 +245,8 @@ struct iqgpu_chain {
 
 // ---- create-time design (abi.cpp): validation, ratio, operator constants, plans, launch geometry; touches no device ----
 int design_chain(iqgpu_chain *c, const iqgpu_chain_desc *d);
+// the eight words behind d_agc_flag as a chain starts (and restarts: iqgpu_chain_reset, iqgpu_chain_load_state) with them (abi.cpp)
+extern const int32_t kAgcFlagInit[8];
 
 // ------------------------------------------------------------------------------------------------
 // stream-position arithmetic (closed forms; SPEC B.6)

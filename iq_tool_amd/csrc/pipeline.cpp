@@ -112,9 +112,9 @@ static int pipe_submit(iqgpu_chain *c, const char *who, bool measure, const void
     // stream position behind the tickets already handed out -- pipe_advance below never moves that position), the capacity
     // check, and both device buffers.  Only then is anything queued, and the look-ahead position moves together with the
     // ticket at the very end: a refused submit leaves the handle exactly as it was.
-    StreamPos at;
-    if (c->pipe_launched == c->pipe_seq) { at.rem = c->rem; at.phi = c->phi; at.fpending = c->fpending; }
-    else { at.rem = c->pipe_rem; at.phi = c->pipe_phi; at.fpending = c->pipe_fpending; }
+    StreamPos at; uint64_t at_in, at_out;
+    if (c->pipe_launched == c->pipe_seq) { at.rem = c->rem; at.phi = c->phi; at.fpending = c->fpending; at_in = c->total_in; at_out = c->total_out; }
+    else { at.rem = c->pipe_rem; at.phi = c->pipe_phi; at.fpending = c->pipe_fpending; at_in = c->pipe_total_in; at_out = c->pipe_total_out; }
     const CallPlan plan = plan_call_at(c, at, frames_in);
     const size_t n_emit = (size_t)plan.n_emit;
     if (!measure && n_emit * obps > out_capacity_bytes)
@@ -142,6 +142,7 @@ static int pipe_submit(iqgpu_chain *c, const char *who, bool measure, const void
     if (frames_in) { c->pipe_rem = plan.rem_next; c->pipe_phi = plan.phi_next; c->pipe_fpending = c->fp.enabled ? plan.fpending_next
         : at.fpending; }
     else { c->pipe_rem = at.rem; c->pipe_phi = at.phi; c->pipe_fpending = at.fpending; }
+    c->pipe_total_in = at_in + (uint64_t)frames_in; c->pipe_total_out = at_out + (frames_in ? (uint64_t)n_emit : 0);
     ps.frames_in = frames_in; ps.n_emit = n_emit; ps.out = out;
     ps.measure = measure; ps.rows = rows; ps.n_rows = frames_in ? n_rows : 0;
     { std::lock_guard<std::mutex> g(c->aux_mu); ps.iq_mag = c->iq_mag; ps.iq_phase = c->iq_phase; }

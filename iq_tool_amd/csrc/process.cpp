@@ -451,6 +451,7 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     c->pnco_theta += (uint32_t)(uint64_t)k.p.n_emit * c->nco_dtheta;
     c->rem = k.p.rem_next;
     c->phi = k.p.phi_next;
+    c->total_in += (uint64_t)frames_in; c->total_out += (uint64_t)k.p.n_emit;
     *frames_out = (size_t)k.p.n_emit;
     return IQGPU_OK;
 }

@@ -116,6 +116,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             c->poisoned = true;
             return fail(IQGPU_EINVAL, "internal: the position behind the preroll is not the closed form at frame %llu", (unsigned long long)first_frame);
         }
+        c->total_in = first_frame; c->total_out = to.n_out;       // (iqgpu_chain_tell: of the stream, not of the preroll)
     }
     if (agc_variant && entry) {
         // The AGC state of the stream at first_frame, everywhere the chain keeps it: the device state the kernels read, and the host's
