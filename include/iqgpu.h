@@ -458,8 +458,17 @@ float iqgpu_iq_optimizer_metric(iqgpu_iq_optimizer *o, const float *block_re_im_
 int   iqgpu_iq_optimizer_run(iqgpu_iq_optimizer *o, const float *block_re_im_1024, double now_sec, int *updated);
 int   iqgpu_iq_optimizer_touch(iqgpu_iq_optimizer *o, double now_sec); /* restart the interval (iq_correct.c:294-297) */
 /* The block the reference hands over: the first 1024 samples of a chunk AFTER unpack / dc block / iq correct / pre NCO
- * (src/pipeline.c:468-476).  With the probe enabled every process call of >= 1024 frames leaves that block of its
- * first chunk in a pinned host buffer; read() waits for it.  *valid = 0 until one exists. */
+ * (src/pipeline.c:468-476; a shift behind the resampler is not part of it).  With the probe enabled a call leaves that block of
+ * its first chunk in a pinned host buffer; read() waits for it.  *valid = 0 while there is none.  Which call:
+ *   1. The block is the head of the first ORDINARY stream call of at least 1024 frames since the previous read --
+ *      iqgpu_chain_process, _process_device, a batch of _submit -- with the I/Q factors that call applies (a submitted batch:
+ *      those at its submit).  While a block is staged and unread no later call replaces it; once read it is returned by every
+ *      read until a later call has left the next one.  The block is the head of the whole call, however the library cuts it.
+ *   2. Calls that are no chunk of the running stream neither leave a block nor occupy the slot: the preroll inside
+ *      iqgpu_chain_seek*, _seek_agc*, _seek_dc*, and iqgpu_chain_measure, _measure_device, _measure_submit, _dc_measure*.
+ *   3. iqgpu_chain_reset, every iqgpu_chain_seek* and iqgpu_chain_load_state drop a staged or held block (it belongs to the
+ *      stream position the chain leaves): *valid = 0 until the next call of rule 1.
+ *   4. A call shorter than 1024 frames leaves the slot as it is. */
 int   iqgpu_chain_enable_iq_probe(iqgpu_chain *c, int enable);
 int   iqgpu_chain_read_iq_probe(iqgpu_chain *c, float *block_re_im_1024, int *valid);
 /* the optimiser thread's loop body: read the probe, run, publish with iqgpu_chain_set_iq_factors */

@@ -440,8 +440,9 @@ class Chain:
         check(self._lib.iqgpu_chain_enable_iq_probe(self._h, int(on)))
 
     def read_iq_probe(self):
-        """the block the reference hands its optimiser (src/pipeline.c:468-476): first 1024 pre-processed
-        samples of the most recent call of >= 1024 frames, or None"""
+        """the block the reference hands its optimiser (src/pipeline.c:468-476): first 1024 pre-processed samples of the first
+        ordinary call (process, process_device, submit) of >= 1024 frames since the previous read -- then that block until a later
+        call has left the next one -- or None: none yet, or dropped by reset / seek* / load_state (the rules in include/iqgpu.h)"""
         blk = np.empty(1024, np.complex64)
         valid = C.c_int(0)
         check(self._lib.iqgpu_chain_read_iq_probe(self._h, blk.ctypes.data_as(C.c_void_p), C.byref(valid)))

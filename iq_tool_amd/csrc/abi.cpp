@@ -628,19 +628,34 @@ extern "C" int iqgpu_chain_read_iq_probe(iqgpu_chain *c, float *block_re_im_1024
     if (!c || !block_re_im_1024 || !valid) return fail(IQGPU_EINVAL, "iqgpu_chain_read_iq_probe: NULL argument");
     *valid = 0;
     if (!c->h_probe) return fail(IQGPU_EINVAL, "the probe is not enabled (iqgpu_chain_enable_iq_probe)");
-    bool pending;
-    { std::lock_guard<std::mutex> g(c->aux_mu); pending = c->probe_pending; }
+    bool pending; uint64_t gen;
+    { std::lock_guard<std::mutex> g(c->aux_mu); pending = c->probe_pending; gen = c->probe_gen; }
     if (pending) {
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipEventSynchronize(c->probe_done));          // recorded behind the copy into h_probe
         std::lock_guard<std::mutex> g(c->aux_mu);
-        memcpy(c->probe_last, c->h_probe, 1024 * sizeof(cf2));
-        c->probe_pending = false; c->probe_valid = true;       // the stage thread may stage the next block now
+        if (c->probe_gen == gen) {                             // (else: dropped while this thread waited -- probe_drop)
+            memcpy(c->probe_last, c->h_probe, 1024 * sizeof(cf2));
+            c->probe_pending = false; c->probe_valid = true;   // the stage thread may stage the next block now
+        }
     }
     std::lock_guard<std::mutex> g(c->aux_mu);
     if (!c->probe_valid) return IQGPU_OK;
     memcpy(block_re_im_1024, c->probe_last, 1024 * sizeof(cf2));
     *valid = 1;
+    return IQGPU_OK;
+}
+
+// reset, every seek and load_state leave the stream the block was taken from: nothing staged, nothing held, until the next ordinary
+// call of at least 1024 frames.  The caller has queued the batches in flight; a staged copy is waited for, so that it cannot land in
+// h_probe behind a block of the new stream.
+int probe_drop(iqgpu_chain *c)
+{
+    bool pending;
+    { std::lock_guard<std::mutex> g(c->aux_mu); pending = c->probe_pending; }
+    const hipError_t e = pending ? hipEventSynchronize(c->probe_done) : hipSuccess;
+    { std::lock_guard<std::mutex> g(c->aux_mu); c->probe_pending = false; c->probe_valid = false; ++c->probe_gen; }   // (whatever the wait said)
+    if (e != hipSuccess) return fail(IQGPU_EHIP, "hipEventSynchronize(probe_done) failed: %s", hipGetErrorString(e));
     return IQGPU_OK;
 }
 
@@ -671,6 +686,7 @@ extern "C" int iqgpu_chain_reset(iqgpu_chain *c)
     // pre_processor_reset (dc state, NCO phase, filter), resampler_reset, post_processor_reset
     { const int rc = pipe_advance(c, c->pipe_seq); if (rc && !c->poisoned) return rc; }   // batches in flight come first (same stream)
     { const int rc = agc_resolve_pending(c); if (rc && !c->poisoned) return rc; }        // ... and what their last fused launch owes
+    { const int rc = probe_drop(c); if (rc && !c->poisoned) return rc; }                 // the I/Q probe's block is of the stream that ends here
     c->pend.valid = false;
     c->poisoned = false;
     c->rem = 0; c->phi = 0; c->nco_theta = 0; c->pnco_theta = 0; c->total_in = 0; c->total_out = 0;

@@ -228,6 +228,7 @@ struct iqgpu_chain {
     //  a block in flight or not yet read is never overwritten -- the optimiser takes at most two a second)
     std::mutex aux_mu;
     bool probe_on = false, probe_pending = false, probe_valid = false;
+    uint64_t probe_gen = 0;       // counts probe_drop calls: a reader that waited for a copy meanwhile dropped does not publish it
     cf2 *d_probe = nullptr; cf2 *h_probe = nullptr; hipEvent_t probe_done = nullptr;
     cf2 probe_last[1024];
     char front_kernel[48] = "";   // which front kernel the last call launched (iqgpu_chain_front_kernel)
@@ -308,6 +309,10 @@ struct CallOpts {                 // what an entry point asks of ONE call (proce
     bool host_verdict = false;    // the host-ordered entry points: the verdict of a fused launch on the host (iqgpu_chain::h_agc_verdict)
     bool iq_fixed = false; float iq_mag = 0.0f, iq_phase = 0.0f;   // a pipelined batch: the correction factors as of its submit()
     AgcRow *rows = nullptr;       // Measure / MeasureS1: where the rows go on the device (a pipelined batch: its slot's table; nullptr: agc_rows)
+    // the I/Q probe takes the head of ORDINARY stream calls only (iqgpu.h, iqgpu_chain_enable_iq_probe): the preroll of a seek, a
+    // measuring call and every piece but the first of a call process_device_impl cuts in pieces stay out of it and leave the slot alone
+    bool no_probe = false;
+    size_t probe_span = 0;        // the first piece of such a cut call: frames of the WHOLE call, which the 1024-frame rule counts (0: frames_in)
 };
 
 struct Call {
@@ -404,5 +409,8 @@ int agc_resolve_pending(iqgpu_chain *c, bool *ran = nullptr);                   
 // seek.cpp: what the two-pass calls ask of a chain (the digital output AGC on the sample clock), and the route of its measure pass
 int agc_two_pass_check(const iqgpu_chain *c, const char *who);
 AgcMode measure_route(const iqgpu_chain *c);
+// abi.cpp: empties the I/Q probe's slot -- a block staged or held belongs to the stream the chain is leaving (reset, seek, load_state).
+// Called behind the batches in flight; waits for a staged copy, so that it cannot land in the pinned buffer later
+int probe_drop(iqgpu_chain *c);
 int pipe_advance(iqgpu_chain *c, uint64_t upto);   // pipeline.cpp: queues the kernels of every submitted batch up to ticket `upto`
 int pipe_drain(iqgpu_chain *c, uint64_t upto);     // ... and their D2H copies

@@ -56,7 +56,7 @@ int pipe_advance(iqgpu_chain *c, uint64_t upto)
             if (ps.measure) {
                 // a batch of the measure pass: iqgpu_chain_measure's call (seek.cpp) with the rows into the slot's own table.  It reads
                 // and writes no AGC state and leaves no verdict; the position and the histories advance as for any batch
-                o.agc = measure_route(c); o.rows = (AgcRow *)ps.d_rows.p;
+                o.agc = measure_route(c); o.rows = (AgcRow *)ps.d_rows.p; o.no_probe = true;
                 rc = process_device_impl(c, ps.d_in.p, ps.frames_in, nullptr, 0, &produced, o);
             } else rc = process_device_impl(c, ps.d_in.p, ps.frames_in, ps.d_out.p, ps.d_out.cap, &produced, o);
             if (!rc && produced != ps.n_emit) rc = fail(IQGPU_EHIP, "internal: batch produced %zu frames, planned %zu", produced,

@@ -419,10 +419,11 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     // the handle is poisoned and every later call fails until iqgpu_chain_reset()
     int rc;
     if ((rc = k.prepare_buffers()) != IQGPU_OK) return rc;
+    // the I/Q probe: the head of an ordinary stream call of at least 1024 frames, while the slot is free (CallOpts::no_probe, probe_span)
     bool want_probe = false;
-    {
+    if (!o.no_probe) {
         std::lock_guard<std::mutex> g(c->aux_mu);
-        want_probe = c->probe_on && frames_in >= 1024 && !c->probe_pending;
+        want_probe = c->probe_on && (o.probe_span ? o.probe_span : frames_in) >= 1024 && !c->probe_pending;
     }
     if (want_probe) {
         // before k_dc_scan moves the dc state to the end of this call
@@ -476,15 +477,20 @@ int process_device_impl(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
         return fail(IQGPU_ECAPACITY, "output buffer too small: need %zu bytes, have %zu", (size_t)plan_call(c, frames_in).n_emit * obps,
             out_capacity_bytes);
     size_t n1 = 0, n2 = 0;
+    // (the I/Q probe's block is the head of the WHOLE call: the first piece stages it, counting the call's frames -- the kernel reads
+    //  the 1024 frames at d_raw_in, whichever piece they fall into -- and the piece behind it stays out)
+    CallOpts o1 = o, o2 = o;
+    o1.probe_span = frames_in;
+    if (head > 0) o2.no_probe = true;
     if (head > 0) {
-        const int rc = process_one(c, d_raw_in, head, d_out, out_capacity_bytes, &n1, o, false);
+        const int rc = process_one(c, d_raw_in, head, d_out, out_capacity_bytes, &n1, o1, false);
         if (rc) return rc;
         c->agc_seen_host += n1;
         if (locks) c->agc_locked_host = true;
     }
     if (head < frames_in) {
         const int rc = process_one(c, (const char *)d_raw_in + head * ibps, frames_in - head, (char *)d_out + n1 * obps,
-                                   out_capacity_bytes - n1 * obps, &n2, o, true);
+                                   out_capacity_bytes - n1 * obps, &n2, o2, true);
         if (rc) return rc;
         c->agc_seen_host += n2;
     }

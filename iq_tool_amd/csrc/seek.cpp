@@ -81,6 +81,9 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         }
         c->rem = from.pos.rem; c->phi = from.pos.phi; c->fpending = from.pos.fpending;
         c->nco_theta = from.nco_theta; c->pnco_theta = from.pnco_theta;
+        // (the preroll lies in front of the range the caller asked for: the I/Q probe takes no block from it and keeps its slot free
+        //  for the head of the first call behind the seek)
+        CallOpts preroll_call; preroll_call.no_probe = true;
 
         if (dcv.on) {
             // the preroll runs in the single stream's own calls -- every one staged like a call of iqgpu_chain_process -- from the
@@ -92,7 +95,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
                 if (!on_device) { rc = stage_host_input(c, src, per, &d_in); if (rc) return rc; }
                 size_t dropped = 0;
                 rc = c->seek_sink.ensure((size_t)plan_call(c, per).n_emit * obps + 16); if (rc) return rc;
-                rc = process_device_impl(c, d_in, per, c->seek_sink.p, c->seek_sink.cap, &dropped); if (rc) return rc;
+                rc = process_device_impl(c, d_in, per, c->seek_sink.p, c->seek_sink.cap, &dropped, preroll_call); if (rc) return rc;
             }
         } else if (preroll_frames) {
             const size_t obps = bytes_per_frame(c->desc.out_format);
@@ -101,10 +104,11 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             size_t dropped = 0;
             if (agc_variant) {
                 // nothing of the preroll is kept and the AGC must not see it: the unfused route into abuf, no AGC kernel behind it
-                rc = process_device_impl(c, d_in, preroll_frames, nullptr, 0, &dropped, CallOpts{AgcMode::Drop});
+                CallOpts drop = preroll_call; drop.agc = AgcMode::Drop;
+                rc = process_device_impl(c, d_in, preroll_frames, nullptr, 0, &dropped, drop);
             } else {
                 rc = c->seek_sink.ensure((size_t)plan_call(c, preroll_frames).n_emit * obps + 16); if (rc) return rc;
-                rc = process_device_impl(c, d_in, preroll_frames, c->seek_sink.p, c->seek_sink.cap, &dropped);
+                rc = process_device_impl(c, d_in, preroll_frames, c->seek_sink.p, c->seek_sink.cap, &dropped, preroll_call);
             }
             if (rc) return rc;
         }
@@ -267,7 +271,8 @@ static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_
     const void *d_in = in;
     if (!on_device) { rc = stage_host_input(c, in, frames_in, &d_in); if (rc) return rc; }
     size_t dropped = 0;
-    rc = process_device_impl(c, d_in, frames_in, nullptr, 0, &dropped, CallOpts{measure_route(c)});
+    CallOpts mo; mo.agc = measure_route(c); mo.no_probe = true;      // (a pass whose output nobody keeps: nothing for the I/Q optimiser)
+    rc = process_device_impl(c, d_in, frames_in, nullptr, 0, &dropped, mo);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(rows, c->agc_rows.p, n * sizeof(AgcRow), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

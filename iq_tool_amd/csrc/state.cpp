@@ -211,6 +211,7 @@ extern "C" int iqgpu_chain_load_state(iqgpu_chain *c, const void *blob, size_t b
     { const int prc = agc_resolve_pending(c); if (prc && !c->poisoned) return prc; }
     const size_t front = l.n_fbuf ? c->fp.taps.size() - 1 + (size_t)w.fpending : 0;
     if (l.n_fbuf) { rc = c->fbuf[c->fcur].ensure((front + 1) * sizeof(cf2)); if (rc) { c->poisoned = true; return rc; } }
+    { const int prc = probe_drop(c); if (prc && !c->poisoned) return prc; }              // the I/Q probe's block is of the stream this chain leaves
     // from here on a failure leaves the device state half installed: the handle is poisoned, as by a failed call
 #define LOAD_TRY(expr)                                                                                                  \
     do {                                                                                                                \
