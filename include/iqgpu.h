@@ -368,6 +368,71 @@ int    iqgpu_chain_seek_dc(iqgpu_chain *c, uint64_t first_frame, const void *pre
                            const iqgpu_dc_state *at_preroll_start);
 int    iqgpu_chain_seek_dc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames, size_t call_frames,
                                   const iqgpu_dc_state *at_preroll_start);
+/* ---- EXACT seamless range sharding of chains with the DC blocker AND the digital output AGC (additive, still ABI v9) ----
+ * The two exact recipes above refuse each other's chains: iqgpu_chain_dc_measure* / _dc_advance / _seek_dc* answer
+ * IQGPU_EUNSUPPORTED on a chain with the AGC, and iqgpu_chain_seek_agc meets a chain with the blocker only to the 1e-6 warm-up bound,
+ * so that the AGC's decisions ride on a stream that is not bit-equal.  The calls below are the third recipe, for chains with
+ * dc_block_enable and agc_enable / IQGPU_AGC_DIGITAL / IQGPU_AGC_CLOCK_SAMPLES (the shape of the reference's hd-radio-isolate preset).
+ * What stood in the way: past the AGC's lock the library applies the gain in the chain's last kernel, and the call that holds the
+ * locking chunk is CUT into two pieces -- the unfused head up to that chunk, the fused rest -- each planned on its own, so the
+ * blocker's state is rounded once per piece, over that piece's segments.  The cut is a closed form of the stream position and the
+ * call grid, not of any AGC value: the stream locks on the first non-empty chunk that starts after 2 s of output, and with calls on a
+ * grid of multiples of agc_chunk_frames every chunk starts on such a multiple from frame 0.  So a chain can be told how the single
+ * stream cuts the call at any position without knowing its AGC state, and these calls plan every call through the one function
+ * that cuts the ordinary call.
+ * A SHADOW call is the ordinary call at its position with nothing kept: the same pieces, each with the ordinary piece's plan and
+ * segments and the same DC-state update, histories and position; the gain of a scratch state (1.0) where the ordinary piece
+ * applies the gain in its front kernel, the cf32 output of the same filter launch where it applies it in the filter's epilogue; no
+ * verdict, no fallback, nothing to the caller; the chain's AGC state neither read nor written; the host's mirrors of "locked" and
+ * "frames seen", from which the next call's cut follows, advanced as the ordinary call advances them.
+ * Contract: the union of the two above.  The single stream is processed on a grid of C frames; C and every cut are multiples of
+ * agc_chunk_frames and of 4096; the preroll of a range is the ceil(P_fir / C) grid calls in front of its cut (all of [0, cut) when
+ * that is less), with P_fir = iqgpu_design_preroll_frames of the description with dc_block_enable = 0 and agc_enable = 0.
+ * Recipe:
+ *   1. DC measure (all ranges but the last, in parallel): iqgpu_chain_dcagc_dc_measure for every grid call, in order.  A call yields
+ *      ONE ROW PER PIECE (1 or 2: two for the call the single stream cuts); keep all rows and note the first row index of every call.
+ *      The two maps of a cut call must not be merged: the single stream rounds its state behind each piece.
+ *   2. DC walk (any one chain): st = {0, 0}; one iqgpu_chain_dcagc_dc_advance over all rows with before[]: the state in front of
+ *      grid call k is before[first_row[k]].
+ *   3. AGC measure (all ranges but the last, in parallel): iqgpu_chain_dcagc_seek(c, cut, preroll, n C, C, &dc_before, NULL) with
+ *      dc_before the walked state in front of the first preroll call, then iqgpu_chain_dcagc_measure over the range on the grid;
+ *      keep the rows in order.  (No pipelined form: iqgpu_chain_measure_submit makes no shadow calls; pass 3 is synchronous.)
+ *   4. AGC walk, as above: iqgpu_chain_agc_initial_state, iqgpu_chain_agc_advance per range, entry[s] in front of range s.
+ *   5. Process (all ranges in parallel): iqgpu_chain_dcagc_seek(..., &dc_before, &entry[s]), then the ordinary process /
+ *      process_device / submit loop over the range on the grid.
+ * The stitched bytes, the DC state and the AGC state equal the single stream's bit for bit.  With the _device variants give every
+ * call the alignment (mod 16 bytes) the single stream's call has, as for iqgpu_chain_seek_dc_device.  Cost: pass 1 reads the input
+ * once (k_dc_prefix and the scan), pass 3 is one process pass without the copy of the output, pass 5 is the process pass.
+ * The I/Q correction factors are whatever the caller sets, the same on every chain; factors moved by the optimiser are a function
+ * of wall time and outside this contract.
+ * Errors.  IQGPU_EINVAL: a chain without the blocker or without the AGC; a NULL argument; a position beyond 2^39 frames; first_frame,
+ * call_frames or a preroll that is not a multiple of agc_chunk_frames; a preroll shorter than min(first_frame, P_fir) or not whole
+ * calls; a DC state that is not finite; agc_entry->locked outside {0, 1}; cap < 2 (dcagc_dc_measure); a row iqgpu_chain_dc_advance
+ * refuses.  IQGPU_ECAPACITY: cap below ceil(frames_in / agc_chunk_frames) (dcagc_measure, as iqgpu_chain_measure).
+ * IQGPU_EUNSUPPORTED: the AGC profiles dx / local and IQGPU_AGC_CLOCK_WALL.  A refused seek leaves the chain reset; a refused
+ * measure leaves the handle as it was. */
+/* The maps of the call iqgpu_chain_process[_device] would make of these frames at first_frame (a multiple of agc_chunk_frames): one
+ * row per piece, in order, rows[i].frames the piece's length; cap >= 2.  Every piece is planned as the ordinary piece (routing,
+ * segments, its own start address' alignment); only k_dc_prefix and the scan are launched.  Leaves the handle exactly as it was. */
+int    iqgpu_chain_dcagc_dc_measure(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, iqgpu_dc_row *rows,
+                                    size_t cap, size_t *n_rows);
+int    iqgpu_chain_dcagc_dc_measure_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, iqgpu_dc_row *rows,
+                                           size_t cap, size_t *n_rows);
+/* iqgpu_chain_dc_advance's walk (same kernel, one definition) for these chains */
+int    iqgpu_chain_dcagc_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before);
+/* The chain at first_frame: reset; *dc_at_preroll_start (NULL: zero) as the blocker's state in front of the preroll; the host's lock /
+ * seen mirrors at their closed form at first_frame - preroll_frames; the preroll as SHADOW calls of call_frames frames (0: one
+ * call); then *agc_entry (NULL: the fresh state, for a measuring chain) installed as iqgpu_chain_seek_agc installs it. */
+int    iqgpu_chain_dcagc_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
+                              const iqgpu_dc_state *dc_at_preroll_start, const iqgpu_agc_state *agc_entry);
+int    iqgpu_chain_dcagc_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames, size_t call_frames,
+                                     const iqgpu_dc_state *dc_at_preroll_start, const iqgpu_agc_state *agc_entry);
+/* The AGC rows of the ordinary call at the chain's position, as a SHADOW call: consumes the frames like iqgpu_chain_process (position,
+ * histories, DC state, lock / seen mirrors), emits nothing, leaves the AGC state alone; one row per chunk of the call, the rows of
+ * a cut call joined in chunk order, every peak2 exact.  Returns with the stream idle. */
+int    iqgpu_chain_dcagc_measure(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows);
+int    iqgpu_chain_dcagc_measure_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap,
+                                        size_t *n_rows);
 /* ---- checkpoint / resume: everything a chain carries from call to call, in a caller-owned blob (additive, still ABI v9) ----
  * The seek calls above rebuild the state at a stream position from a closed form and a preroll, and refuse what has no such form.
  * These two calls need none: iqgpu_chain_save_state copies the state out between two calls, iqgpu_chain_load_state puts it into a
@@ -465,8 +530,9 @@ int   iqgpu_iq_optimizer_touch(iqgpu_iq_optimizer *o, double now_sec); /* restar
  *      those at its submit).  While a block is staged and unread no later call replaces it; once read it is returned by every
  *      read until a later call has left the next one.  The block is the head of the whole call, however the library cuts it.
  *   2. Calls that are no chunk of the running stream neither leave a block nor occupy the slot: the preroll inside
- *      iqgpu_chain_seek*, _seek_agc*, _seek_dc*, and iqgpu_chain_measure, _measure_device, _measure_submit, _dc_measure*.
- *   3. iqgpu_chain_reset, every iqgpu_chain_seek* and iqgpu_chain_load_state drop a staged or held block (it belongs to the
+ *      iqgpu_chain_seek*, _seek_agc*, _seek_dc*, _dcagc_seek*, and iqgpu_chain_measure, _measure_device, _measure_submit,
+ *      _dc_measure*, _dcagc_dc_measure*, _dcagc_measure* (shadow calls leave no block).
+ *   3. iqgpu_chain_reset, every iqgpu_chain_seek* (iqgpu_chain_dcagc_seek* too) and iqgpu_chain_load_state drop a staged or held block (it belongs to the
  *      stream position the chain leaves): *valid = 0 until the next call of rule 1.
  *   4. A call shorter than 1024 frames leaves the slot as it is. */
 int   iqgpu_chain_enable_iq_probe(iqgpu_chain *c, int enable);

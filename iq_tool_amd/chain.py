@@ -392,6 +392,82 @@ class Chain:
         check(self._lib.iqgpu_chain_seek_dc_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames), int(call_frames),
                                                    st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
 
+    # ---- exact seamless sharding of chains with the DC blocker AND the digital AGC (include/iqgpu.h, iqgpu_chain_dcagc_*) ----
+    def dcagc_dc_measure(self, first_frame, raw):
+        """the DC maps of the call process(raw) would be at stream frame first_frame: DC_ROW records, ONE PER PIECE (two for the
+        call the stream cuts at the AGC's lock), in order; the chain itself stays exactly as it was"""
+        raw = np.ascontiguousarray(raw)
+        n = raw.nbytes // self.in_bytes
+        rows = np.zeros(2, DC_ROW)
+        got = C.c_size_t(0)
+        check(self._lib.iqgpu_chain_dcagc_dc_measure(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n,
+                                                     rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
+        return rows[:got.value]
+
+    def dcagc_dc_measure_device(self, first_frame, d_in, frames_in):
+        """dcagc_dc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
+        rows = np.zeros(2, DC_ROW)
+        got = C.c_size_t(0)
+        check(self._lib.iqgpu_chain_dcagc_dc_measure_device(self._h, int(first_frame), C.c_void_p(d_in), int(frames_in),
+                                                            rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
+        return rows[:got.value]
+
+    def dcagc_dc_advance(self, state, rows):
+        """dc_advance() for these chains: (state behind the last row, before) with before[k] the state in front of row k"""
+        rows = np.ascontiguousarray(rows, DC_ROW).reshape(-1)
+        st = np.zeros((), DC_STATE)
+        if state is not None:
+            st[...] = state
+        before = np.zeros(rows.size, DC_STATE)
+        check(self._lib.iqgpu_chain_dcagc_dc_advance(self._h, st.ctypes.data_as(C.POINTER(DcState)),
+                                                     rows.ctypes.data_as(C.c_void_p) if rows.size else None, rows.size,
+                                                     before.ctypes.data_as(C.c_void_p) if rows.size else None))
+        return st, before
+
+    def dcagc_seek(self, first_frame, preroll_raw=None, call_frames=0, dc_state=None, entry=None):
+        """puts the chain at first_frame, exact in both states: `dc_state` (a DC_STATE record from dcagc_dc_advance; None: zero) is
+        the blocker's state in front of the preroll, which runs as shadow calls of call_frames (0: one call); then the chain carries
+        `entry` (an AgcState from agc_advance; None: the fresh state, for a measuring chain)"""
+        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
+        n = raw.nbytes // self.in_bytes
+        st = None
+        if dc_state is not None:
+            st = np.zeros((), DC_STATE)
+            st[...] = dc_state
+        check(self._lib.iqgpu_chain_dcagc_seek(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n, int(call_frames),
+                                               st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None,
+                                               C.byref(entry) if entry is not None else None))
+
+    def dcagc_seek_device(self, first_frame, d_preroll, preroll_frames, call_frames=0, dc_state=None, entry=None):
+        st = None
+        if dc_state is not None:
+            st = np.zeros((), DC_STATE)
+            st[...] = dc_state
+        check(self._lib.iqgpu_chain_dcagc_seek_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames), int(call_frames),
+                                                      st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None,
+                                                      C.byref(entry) if entry is not None else None))
+
+    def dcagc_measure(self, raw):
+        """the AGC_ROW records of the call process(raw) would be at the chain's position, as a shadow call: consumes raw like
+        process() (position, histories, DC state), emits nothing, leaves the AGC state alone"""
+        raw = np.ascontiguousarray(raw)
+        n = raw.nbytes // self.in_bytes
+        chunk = int(self.desc.agc_chunk_frames) or 16384
+        rows = np.zeros(-(-n // chunk), AGC_ROW)
+        got = C.c_size_t(0)
+        check(self._lib.iqgpu_chain_dcagc_measure(self._h, raw.ctypes.data_as(C.c_void_p) if n else None, n,
+                                                  rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
+        return rows[:got.value]
+
+    def dcagc_measure_device(self, d_in, frames_in):
+        """dcagc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
+        chunk = int(self.desc.agc_chunk_frames) or 16384
+        rows = np.zeros(-(-int(frames_in) // chunk), AGC_ROW)
+        got = C.c_size_t(0)
+        check(self._lib.iqgpu_chain_dcagc_measure_device(self._h, C.c_void_p(d_in), int(frames_in), rows.ctypes.data_as(C.c_void_p),
+                                                         rows.size, C.byref(got)))
+        return rows[:got.value]
+
     # ---- checkpoint / resume (include/iqgpu.h): the whole carried state in a blob, into a chain of the same description ----
     def tell(self):
         """(frames_in, frames_out) since the last reset -- after a seek: of the stream -- behind every batch already submitted"""

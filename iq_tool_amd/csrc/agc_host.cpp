@@ -221,26 +221,51 @@ int agc_resolve_pending(iqgpu_chain *c, bool *ran)
 // while the stream has not locked.  agc_apply locks on the first chunk that STARTS after AGC_DIGITAL_LOCK_TIME of
 // output (src/agc.c:151-155: elapsed = samples_seen / rate before this chunk is counted), a closed form of the
 // stream position; sets *locks when that chunk lies in this call.
-size_t agc_unfused_head(const iqgpu_chain *c, size_t frames_in, bool *locks)
+static size_t agc_unfused_head(const iqgpu_chain *c, bool locked, uint64_t seen0, const StreamPos &at, size_t frames_in, bool *locks)
 {
     *locks = false;
-    if (c->agc_locked_host) return 0;
+    if (locked) return 0;
     AgcGeom g{};
     g.frames_in = (int64_t)frames_in; g.chunk_frames = c->agc_chunk;
-    g.n_chunks = (int)(((int64_t)frames_in + c->agc_chunk - 1) / c->agc_chunk);
-    g.mode = 1; g.rem = c->rem; g.S = c->S; g.phi = c->phi; g.step = c->rp.step;
-    if (c->fp.enabled && c->fp.block) { g.block = c->fp.block; g.fpending = c->fpending; }     // (a filter behind the resampler emits whole blocks)
-    int64_t lo = 0, hi = g.n_chunks;                        // first chunk whose start time exceeds the lock time
+    const int64_t n_chunks = ((int64_t)frames_in + c->agc_chunk - 1) / c->agc_chunk;      // (agc_out_end does not read g.n_chunks)
+    g.mode = 1; g.rem = at.rem; g.S = c->S; g.phi = at.phi; g.step = c->rp.step;
+    if (c->fp.enabled && c->fp.block) { g.block = c->fp.block; g.fpending = at.fpending; }     // (a filter behind the resampler emits whole blocks)
+    int64_t lo = 0, hi = n_chunks;                        // first chunk whose start time exceeds the lock time
     while (lo < hi) {
         const int64_t mid = (lo + hi) / 2;
-        const uint64_t seen = c->agc_seen_host + (uint64_t)agc_out_end(g, mid - 1);
+        const uint64_t seen = seen0 + (uint64_t)agc_out_end(g, mid - 1);
         if ((double)seen / c->target_rate > (double)2.0f) hi = mid; else lo = mid + 1;
     }
     // (empty chunks never reach agc_apply; a decimating chain with chunks of at least a tile has none but a possible
     //  first one, which the search passes over because its successor starts at the same time)
-    while (lo < g.n_chunks && agc_out_end(g, lo) == agc_out_end(g, lo - 1)) ++lo;
-    if (lo >= g.n_chunks) return frames_in;
+    while (lo < n_chunks && agc_out_end(g, lo) == agc_out_end(g, lo - 1)) ++lo;
+    if (lo >= n_chunks) return frames_in;
     *locks = true;
     const int64_t head = (lo + 1) * c->agc_chunk;
     return head < (int64_t)frames_in ? (size_t)head : frames_in;
+}
+
+size_t agc_call_cut(const iqgpu_chain *c, bool locked, uint64_t seen, const StreamPos &at, size_t frames_in, bool *locks)
+{
+    size_t head = agc_unfused_head(c, locked, seen, at, frames_in, locks);
+    // with a user filter between the resampler and the AGC the call that holds the lock stays whole: cutting it at the locking chunk
+    // would move the filter's overlap-save windows on the stream (other roundings: the bytes of the unfused path would be missed by a
+    // code here and there); the fused epilogue starts with the next call
+    if (c->agc_fusable_filter && head > 0 && head < frames_in) head = frames_in;
+    return head;
+}
+
+// The mirrors as the ordinary path leaves them in front of frame `frames`.  seen: the outputs in front of it.  locked: every chunk of
+// a stream whose calls lie on the chunk grid starts on a multiple of agc_chunk_frames from frame 0, so the chunk that locks is the one
+// a single call [0, frames) would find -- and the mirror is up once the call that holds it has run.  (frames on the CALL grid: a
+// filter chain keeps the locking call whole, so its mirror changes at call boundaries only.)
+void agc_mirrors_at(const iqgpu_chain *c, uint64_t frames, bool *locked, uint64_t *seen)
+{
+    *seen = stream_at(c, frames).n_out;
+    *locked = false;
+    // (chains that never cut a call never move the lock mirror -- and have no decimating chunk map to search)
+    if (frames == 0 || !(c->agc_fusable || c->agc_fusable_filter)) return;
+    bool locks = false;
+    (void)agc_unfused_head(c, false, 0, stream_at(c, 0).pos, (size_t)frames, &locks);
+    *locked = locks;
 }

@@ -4,7 +4,7 @@
 //   plan.cpp       stream-position arithmetic (plan_call), per-call run geometry of the wave kernels (Call::plan_geometry)
 //   process.cpp    one process() call: buffers, the stages in stream order, iqgpu_chain_process[_device]
 //   seek.cpp       seamless range sharding: iqgpu_chain_seek[_agc | _dc], iqgpu_chain_measure, iqgpu_chain_agc_initial_state / _advance,
-//                  iqgpu_chain_dc_measure / _dc_advance
+//                  iqgpu_chain_dc_measure / _dc_advance, iqgpu_chain_dcagc_*
 //   agc_host.cpp   host side of the output AGC: chunk map, fused / unfused split, verifier + fallback launches
 //   pipeline.cpp   iqgpu_chain_submit / _measure_submit / _collect (pinned host buffers, three stages moved along by the host)
 //   state.cpp      checkpoint / resume: iqgpu_chain_tell, iqgpu_chain_save_state / _load_state, iqgpu_design_state_size (the blob's
@@ -303,12 +303,21 @@ struct KernelTimer {
 // MeasureS1: the other route of the measure pass, for agc_fusable chains: k_front_s1<.., AGC> -- their fallback kernel, which
 // reduces the exact peak in front of the gain in its epilogue -- as it is, with the packed output into seek_sink and a scratch AGC
 // state (agc_scratch); the rows are then put together from its peak array.  Half the traffic of Measure, a slower kernel.
-enum class AgcMode { Ordinary, Measure, Drop, MeasureS1 };
+// Shadow: exact sharding of chains with the DC blocker AND the AGC (iqgpu_chain_dcagc_*, seek.cpp).  The call is cut into the pieces
+// of the ORDINARY call at its position (agc_call_cut) and every piece is planned as the ordinary piece is -- same plan_geometry, same
+// dc_geom, agc_fused in the plan -- so the DC state, the histories and the position advance exactly as in the ordinary call, and so do
+// the host's lock / seen mirrors.  Behind the arithmetic nothing is kept: an unfused piece leaves cf32 in abuf and k_agc_measure reads
+// it (as Measure); a piece fused into the front kernel runs that launch against the scratch state with its packed output into
+// seek_sink, no verdict and no fallback, and its rows come from the kernel's exact peak array (as MeasureS1, but on the ordinary
+// call's plan); a piece whose gain the ordinary call applies in the FILTER's epilogue runs the same filter launch with the cf32
+// epilogue -- the ordinary call's own fallback launch: same windows, same history move -- because the fused epilogue keeps float
+// peaks, good for the verifier's margin test and not for a row.  The rows of a cut call are joined in chunk order.
+enum class AgcMode { Ordinary, Measure, Drop, MeasureS1, Shadow };
 struct CallOpts {                 // what an entry point asks of ONE call (process_device_impl).  The default: an ordinary call
     AgcMode agc = AgcMode::Ordinary;
     bool host_verdict = false;    // the host-ordered entry points: the verdict of a fused launch on the host (iqgpu_chain::h_agc_verdict)
     bool iq_fixed = false; float iq_mag = 0.0f, iq_phase = 0.0f;   // a pipelined batch: the correction factors as of its submit()
-    AgcRow *rows = nullptr;       // Measure / MeasureS1: where the rows go on the device (a pipelined batch: its slot's table; nullptr: agc_rows)
+    AgcRow *rows = nullptr;       // Measure / MeasureS1 / Shadow: where the rows go on the device (a pipelined batch: its slot's table; nullptr: agc_rows)
     // the I/Q probe takes the head of ORDINARY stream calls only (iqgpu.h, iqgpu_chain_enable_iq_probe): the preroll of a seek, a
     // measuring call and every piece but the first of a call process_device_impl cuts in pieces stay out of it and leave the slot alone
     bool no_probe = false;
@@ -334,6 +343,8 @@ struct Call {
     float iq_mag = 0.0f, iq_phase = 0.0f;    // the correction factors this call applies (snapshot under aux_mu)
     bool agc_fused = false;                  // this call: gain applied in the front kernel -- or, with a filter behind it, in the filter's epilogue -- and verified behind it (AgcMode::MeasureS1: that front kernel, no verdict)
     bool front_fused() const { return agc_fused && !filt; }
+    // a fused front launch whose output nobody keeps: the scratch AGC state, no verdict, the rows from its peak array
+    bool no_verdict() const { return o.agc == AgcMode::MeasureS1 || o.agc == AgcMode::Shadow; }
     bool verdict_on_host() const { return o.host_verdict && c->h_agc_verdict != nullptr; }   // the fallback behind a fused launch waits for the host
     FrontArgs cplan;                         // run geometry of the wave-autonomous kernel that sees the raw input
     cf2 *fcur = nullptr, *icur = nullptr;    // filter-input / k_interp-input buffers of this call
@@ -374,7 +385,7 @@ struct Call {
     // the fused-AGC fields of a front launch (the measure pass on that kernel: the gain of a scratch state), and its peak array zeroed
     hipError_t wire_fused_agc(FrontArgs &a)
     {
-        a.agc_fused = 1; a.agc_state = o.agc == AgcMode::MeasureS1 ? (const AgcState *)c->agc_scratch.p : c->d_agc_state;
+        a.agc_fused = 1; a.agc_state = no_verdict() ? (const AgcState *)c->agc_scratch.p : c->d_agc_state;
         a.agc_peak2 = (unsigned long long *)c->agc_peak.p; a.agc_chunk_frames = c->agc_chunk; a.agc_shift = c->S; a.agc_rem = c->rem;
         return clean_agc_peaks();
     }
@@ -401,8 +412,14 @@ int process_device_impl(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, 
                         size_t *frames_out, const CallOpts &o = CallOpts());              // process.cpp
 int stage_host_input(iqgpu_chain *c, const void *in, size_t frames, const void **d_in);   // process.cpp: host frames into stage_in, *d_in
 // process.cpp: the DC blocker's map of the call process_device_impl would make of these frames at stream position `at`, into d_map[0 .. 2)
-int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, cd2 *d_map);
-size_t agc_unfused_head(const iqgpu_chain *c, size_t frames_in, bool *locks);             // agc_host.cpp
+// (past_lock: the piece of an AGC chain's call behind the lock, planned with the gain in its last kernel -- iqgpu_chain_dcagc_dc_measure)
+int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, cd2 *d_map, bool past_lock = false);
+// agc_host.cpp: ONE definition of how a call of a chain with the digital AGC is cut -- the frames of its unfused head (0: none,
+// frames_in: the whole call); the rest runs with the gain fused into its last kernel.  A function of the lock / seen mirrors, the
+// stream position and the call's length alone; *locks: the locking chunk lies in this call
+size_t agc_call_cut(const iqgpu_chain *c, bool locked, uint64_t seen, const StreamPos &at, size_t frames_in, bool *locks);
+// ... and the mirrors in front of stream frame `frames` of a stream processed on a grid of multiples of agc_chunk_frames (closed form)
+void agc_mirrors_at(const iqgpu_chain *c, uint64_t frames, bool *locked, uint64_t *seen);
 // behind a fused launch whose fallback waits for the verdict on the host: waits for the word, launches the fallback when it is set
 // (*ran = true then).  No-op without a pending verdict.
 int agc_resolve_pending(iqgpu_chain *c, bool *ran = nullptr);                             // agc_host.cpp

@@ -41,6 +41,15 @@
  * preroll is the filters' memory rounded up to whole chunks, with NO warm-up of the blocker, entered with the walked state -- and runs
  * the usual chunk loop.  The stitched file is the file --shards 1 writes, byte for byte.
  *
+ * --shards N --seamless-dc-agc is the exact --seamless for chains with the DC blocker AND the digital output AGC (--dc-block
+ * --agc-profile digital), in the five steps of iqgpu.h's block on such chains.  Shard starts lie on lcm(4096, --chunk-frames), and
+ * --chunk-frames is a multiple of the AGC chunk.  Step 1: shards 0 .. N-2 measure the DC maps of every call of their range
+ * (iqgpu_chain_dcagc_dc_measure: one row per piece, two for the call the stream cuts at the AGC's lock).  Step 2: one walk over all
+ * rows; the state in front of a call is the one in front of its first row.  Step 3: the same shards put their chain at their start
+ * with the walked DC state and no AGC entry (iqgpu_chain_dcagc_seek) and measure the AGC rows of their range in shadow calls
+ * (iqgpu_chain_dcagc_measure, synchronous).  Step 4: the AGC walk.  Step 5: every shard seeks with both states and runs the usual
+ * chunk loop.  The stitched file is the file --shards 1 writes, byte for byte.
+ *
  * --synthetic FRAMES [--synthetic-hash SEED]: no input file.  Without a seed one constant pinned buffer is sent again and again
  * (the PCIe-inclusive rate of the path, nothing else); with one, shard s is the stream frame n -> splitmix64((SEED + s) * K + n)
  * of its own (iq_tool_amd/synth.py hash_stream restates it): configs[4] at its real size -- 8 x 2.5 G frames -- without 80 GB of
@@ -77,6 +86,7 @@ typedef struct {
     int seamless;                     /* --seamless: the shards continue ONE stream (iqgpu_chain_seek behind a preroll) */
     int seamless_agc;                 /* --seamless-agc: --seamless for digital-AGC chains, in two passes (measure, walk, process) */
     int seamless_dc;                  /* --seamless-dc: the exact --seamless for DC-blocker chains, in three passes (measure, walk, process) */
+    int seamless_dc_agc;              /* --seamless-dc-agc: exact for chains with the DC blocker and the digital AGC, in five steps */
     int have_shards;                  /* --shards was given */
     int dry;                          /* --dry-placement: plan, bind, size the buffers, report -- no GPU call */
     int quiet;
@@ -99,8 +109,10 @@ typedef struct {
     /* --seamless-dc */
     iqgpu_dc_row *dc_rows; long long n_dc_rows;  /* pass 1: one row per call of this shard's range (planned count with --dry-placement) */
     iqgpu_dc_state dc_entry;                     /* the blocker's state in front of this shard's preroll, from the walk */
+    /* --seamless-dc-agc: both of the above, and how many rows every call of the range gave (1 or 2) */
+    unsigned char *dc_call_rows; long long n_dc_calls;
     double measure_seconds;
-    int barriers;                     /* how many of the two rendezvous of the passes this thread has been through */
+    int barriers;                     /* how many of the rendezvous of the passes (two; --seamless-dc-agc: four) this thread has been through */
     int rc;
     char err[256];
 } Shard;
@@ -345,6 +357,103 @@ static void *run_shard(void *arg)
             free(pre); pre = NULL;
         }
     }
+    if (o->seamless_dc_agc) {
+        const size_t np = (size_t)sh->preroll_frames;
+        const size_t agc_chunk = d.agc_chunk_frames ? d.agc_chunk_frames : 16384;
+        const size_t calls = (size_t)((sh->frames + (long long)chunk - 1) / (long long)chunk);
+        const int measures = sh->shard < o->shards - 1;     /* the last shard measures nothing: nobody starts behind it */
+        const double t_m = now_s();
+        /* step 1: the DC maps of every call step 5 will make of this range, one row per piece */
+        if (measures) {
+            sh->dc_rows = (iqgpu_dc_row *)malloc((2 * calls + 1) * sizeof(iqgpu_dc_row));
+            sh->dc_call_rows = (unsigned char *)malloc(calls + 1);
+            if (!sh->dc_rows || !sh->dc_call_rows) { snprintf(sh->err, sizeof(sh->err), "out of memory for a table of %zu rows", 2 * calls); sh->rc = -1; goto done; }
+            for (long long at = 0; at < sh->frames; at += (long long)chunk) {
+                size_t n = chunk, got = 0;
+                if ((long long)n > sh->frames - at) n = (size_t)(sh->frames - at);
+                if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame + at, n, h_in[0], sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
+                CK(iqgpu_chain_dcagc_dc_measure(chain, (uint64_t)(sh->first_frame + at), h_in[0], n, &sh->dc_rows[sh->n_dc_rows], 2, &got));
+                sh->dc_call_rows[sh->n_dc_calls++] = (unsigned char)got;
+                sh->n_dc_rows += (long long)got;
+            }
+        }
+        /* step 2: one thread walks ALL rows in stream order; the state in front of grid call k stands in front of its first row */
+        pthread_barrier_wait(&g_pass); sh->barriers = 1;
+        if (sh->shard == 0) {
+            int ok = 1;
+            long long total = 0, total_calls = 0;
+            for (int q = 0; q < o->shards; q++) { if (g_shards[q].rc) ok = 0; total += g_shards[q].n_dc_rows; total_calls += g_shards[q].n_dc_calls; }
+            iqgpu_dc_row *all = (iqgpu_dc_row *)malloc((size_t)(total ? total : 1) * sizeof(iqgpu_dc_row));
+            iqgpu_dc_state *before = (iqgpu_dc_state *)malloc((size_t)(total ? total : 1) * sizeof(iqgpu_dc_state));
+            long long *first_row = (long long *)malloc((size_t)(total_calls + 1) * sizeof(long long));
+            iqgpu_dc_state st = {0.0, 0.0};
+            if (ok && (!all || !before || !first_row)) { snprintf(sh->err, sizeof(sh->err), "out of memory for the walk over %lld rows", total); sh->rc = -1; ok = 0; }
+            if (ok) {
+                long long k = 0, call = 0;
+                for (int q = 0; q < o->shards; q++) {
+                    if (g_shards[q].n_dc_rows) memcpy(all + k, g_shards[q].dc_rows, (size_t)g_shards[q].n_dc_rows * sizeof(iqgpu_dc_row));
+                    long long r = k;
+                    for (long long j = 0; j < g_shards[q].n_dc_calls; j++) { first_row[call++] = r; r += g_shards[q].dc_call_rows[j]; }
+                    k += g_shards[q].n_dc_rows;
+                }
+                first_row[call] = k;
+                if (iqgpu_chain_dcagc_dc_advance(chain, &st, all, (size_t)total, before) != IQGPU_OK) {
+                    snprintf(sh->err, sizeof(sh->err), "iqgpu_chain_dcagc_dc_advance: %s", iqgpu_last_error()); sh->rc = -1; ok = 0;
+                }
+            }
+            for (int q = 1; q < o->shards && ok; q++) {
+                const long long k = (g_shards[q].first_frame - g_shards[q].preroll_frames) / (long long)chunk;
+                if (k < 0 || k > total_calls) { snprintf(sh->err, sizeof(sh->err), "the walk holds no state in front of call %lld", k); sh->rc = -1; ok = 0; break; }
+                g_shards[q].dc_entry = first_row[k] < total ? before[first_row[k]] : st;
+            }
+            free(all); free(before); free(first_row);
+            g_walk_ok = ok;
+        }
+        pthread_barrier_wait(&g_pass); sh->barriers = 2;
+        if (!g_walk_ok) { if (!sh->rc) { snprintf(sh->err, sizeof(sh->err), "the DC measure pass or the walk of another shard failed"); sh->rc = -1; } goto done; }
+        /* step 3: the chain at the start of the range -- the preroll as shadow calls from the walked DC state, no AGC entry -- and the
+         * AGC rows of every call of the range, as shadow calls (synchronous: the pipelined measure makes no shadow calls) */
+        if (np) {
+            pre = malloc(np * ibps);
+            if (!pre) { snprintf(sh->err, sizeof(sh->err), "out of memory for a preroll of %zu frames", np); sh->rc = -1; goto done; }
+            if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame - sh->preroll_frames, np, pre, sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
+        }
+        if (measures) {
+            const size_t cap = calls * ((chunk + agc_chunk - 1) / agc_chunk) + 1;
+            void *table = NULL;
+            if (iqgpu_host_malloc_pinned(cap * sizeof(iqgpu_agc_chunk), &table) != IQGPU_OK) { snprintf(sh->err, sizeof(sh->err), "out of memory for a table of %zu rows", cap); sh->rc = -1; goto done; }
+            sh->rows = (iqgpu_agc_chunk *)table;
+            CK(iqgpu_chain_dcagc_seek(chain, (uint64_t)sh->first_frame, pre, np, chunk, &sh->dc_entry, NULL));
+            for (long long at = 0; at < sh->frames; at += (long long)chunk) {
+                size_t n = chunk, got = 0;
+                if ((long long)n > sh->frames - at) n = (size_t)(sh->frames - at);
+                if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame + at, n, h_in[0], sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
+                CK(iqgpu_chain_dcagc_measure(chain, h_in[0], n, sh->rows + sh->agc_rows, cap - (size_t)sh->agc_rows, &got));
+                sh->agc_rows += (long long)got;
+            }
+        }
+        sh->measure_seconds = now_s() - t_m;
+        /* step 4: the AGC walk, the tables in shard order */
+        pthread_barrier_wait(&g_pass); sh->barriers = 3;
+        if (sh->shard == 0) {
+            int ok = 1;
+            iqgpu_agc_state st;
+            for (int q = 0; q < o->shards; q++) if (g_shards[q].rc) ok = 0;
+            if (ok && iqgpu_chain_agc_initial_state(chain, &st) != IQGPU_OK) ok = 0;
+            for (int q = 0; q < o->shards && ok; q++) {
+                g_shards[q].entry = st; g_shards[q].have_entry = 1;
+                if (q < o->shards - 1 && iqgpu_chain_agc_advance(chain, &st, g_shards[q].rows, (size_t)g_shards[q].agc_rows, NULL) != IQGPU_OK) {
+                    snprintf(sh->err, sizeof(sh->err), "iqgpu_chain_agc_advance: %s", iqgpu_last_error()); sh->rc = -1; ok = 0;
+                }
+            }
+            g_walk_ok = ok;
+        }
+        pthread_barrier_wait(&g_pass); sh->barriers = 4;
+        if (!g_walk_ok) { if (!sh->rc) { snprintf(sh->err, sizeof(sh->err), "the AGC measure pass or the walk of another shard failed"); sh->rc = -1; } goto done; }
+        /* step 5: the same position again, now with both states of the stream there */
+        CK(iqgpu_chain_dcagc_seek(chain, (uint64_t)sh->first_frame, pre, np, chunk, &sh->dc_entry, &sh->entry));
+        free(pre); pre = NULL;
+    }
     if (o->seamless && sh->first_frame > 0) {
         /* the frames in front of this shard's start, read like any other range of the stream, warm the chain's histories up; the
          * chain then stands at first_frame of the ONE stream (iqgpu_chain_seek) */
@@ -386,7 +495,7 @@ static void *run_shard(void *arg)
                 }
             } else if (o->have_hash) {
                 /* (buffer b is free: chunk i - 2, its last user, retired in the iteration before this one) */
-                if (o->seamless || o->seamless_agc || o->seamless_dc) hash_fill(h_in[b], d.in_format, ibps, o->hash_seed, sh->first_frame + done_in, n);
+                if (o->seamless || o->seamless_agc || o->seamless_dc || o->seamless_dc_agc) hash_fill(h_in[b], d.in_format, ibps, o->hash_seed, sh->first_frame + done_in, n);
                 else hash_fill(h_in[b], d.in_format, ibps, o->hash_seed + (uint64_t)sh->shard, done_in, n);
             }
             CK(iqgpu_memcpy_h2d_async(d_in[b], h_in[b], n * ibps, s_in));
@@ -420,7 +529,7 @@ static void *run_shard(void *arg)
     }
 done:
     /* (a shard that fails early still keeps the rendezvous of the two passes: the others wait there) */
-    while ((o->seamless_agc || o->seamless_dc) && !o->dry && sh->barriers < 2) { pthread_barrier_wait(&g_pass); sh->barriers++; }
+    while ((o->seamless_agc || o->seamless_dc || o->seamless_dc_agc) && !o->dry && sh->barriers < (o->seamless_dc_agc ? 4 : 2)) { pthread_barrier_wait(&g_pass); sh->barriers++; }
     free(pre);
     if (chain) iqgpu_chain_synchronize(chain);
     for (int b = 0; b < NBUF; b++) {
@@ -453,6 +562,7 @@ static void usage(void)
             "          [--seamless (with --shards: the shards continue ONE stream -- the stitched output is what --shards 1 writes)]\n"
             "          [--seamless-agc (--seamless for chains with the digital output AGC: a measure pass, one walk, then the ordinary pass)]\n"
             "          [--seamless-dc (the exact --seamless for --dc-block chains without an AGC: a measure pass over the input, one walk, then the ordinary pass)]\n"
+            "          [--seamless-dc-agc (the exact --seamless for --dc-block chains with the digital AGC: DC measure, walk, shadow AGC measure, walk, then the ordinary pass)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
             "          [--dry-placement (plan the shards, bind every shard thread, size its buffers, report as JSON: no GPU call)]\n");
 }
@@ -510,6 +620,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--seamless")) o.seamless = 1;
         else if (!strcmp(a, "--seamless-agc")) o.seamless_agc = 1;
         else if (!strcmp(a, "--seamless-dc")) o.seamless_dc = 1;
+        else if (!strcmp(a, "--seamless-dc-agc")) o.seamless_dc_agc = 1;
         else if (!strcmp(a, "--debug")) {              /* --debug name=value -> iqgpu_debug_set (the library reads no environment) */
             char kv[512]; snprintf(kv, sizeof(kv), "%s", NEXT);
             char *eq = strchr(kv, '=');
@@ -526,6 +637,20 @@ int main(int argc, char **argv)
     o.desc.input_rate_hz = in_rate; o.desc.target_rate_hz = o.desc.no_resample ? in_rate : out_rate;
     if (o.shards < 1) o.shards = 1;
     if (o.devices < 1) o.devices = 1;
+    if (o.seamless_dc_agc) {
+        if (o.seamless || o.seamless_agc || o.seamless_dc) { fprintf(stderr, "--seamless-dc-agc excludes --seamless, --seamless-agc and --seamless-dc\n"); return 2; }
+        if (!o.have_shards) { fprintf(stderr, "--seamless-dc-agc needs --shards N\n"); return 2; }
+        if (!o.desc.dc_block_enable) { fprintf(stderr, "--seamless-dc-agc: the chain has no DC blocker: give --dc-block, or use --seamless-agc\n"); return 1; }
+        if (!o.desc.agc_enable) { fprintf(stderr, "--seamless-dc-agc: the chain has no output AGC (use --seamless-dc)\n"); return 1; }
+        if (o.desc.agc_profile != IQGPU_AGC_DIGITAL) {
+            fprintf(stderr, "--seamless-dc-agc: the AGC profiles dx / local carry a per-sample loop state that no table of per-chunk figures reproduces exactly; "
+                            "only the digital profile is sharded seamlessly\n");
+            return 1;
+        }
+        if (o.synthetic_frames > 0 && !o.have_hash) { fprintf(stderr, "--seamless-dc-agc needs a stream it can read twice: an input file, or --synthetic with --synthetic-hash\n"); return 2; }
+        const size_t agc_chunk = o.desc.agc_chunk_frames ? o.desc.agc_chunk_frames : 16384;
+        if (o.chunk_frames == 0 || o.chunk_frames % agc_chunk) { fprintf(stderr, "--seamless-dc-agc: --chunk-frames has to be a multiple of the AGC chunk (%zu frames)\n", agc_chunk); return 2; }
+    }
     if (o.seamless_dc) {
         /* options that do not go together: exit status 2, as for every other misuse of the command line.  A chain the recipe does not
          * cover -- what the library would refuse at its first call -- : exit status 1, before anything is planned */
@@ -645,7 +770,42 @@ int main(int argc, char **argv)
         g_shards = sh;
         if (!o.dry && pthread_barrier_init(&g_pass, NULL, (unsigned)o.shards) != 0) { fprintf(stderr, "pthread_barrier_init failed\n"); return 1; }
     }
-    for (int s = 0; s < o.shards && !o.seamless && !o.seamless_agc && !o.seamless_dc; s++) {
+    if (o.seamless_dc_agc) {
+        /* the preroll is the filters' memory alone -- the description with the blocker and the AGC off -- in whole calls; placement
+         * depends on neither */
+        iqgpu_chain_desc nd = o.desc;
+        nd.dc_block_enable = 0; nd.agc_enable = 0;
+        if (iqgpu_design_preroll_frames(&nd, &preroll) != IQGPU_OK) { fprintf(stderr, "--seamless-dc-agc: %s\n", iqgpu_last_error()); return 1; }
+        const long long cf = (long long)o.chunk_frames, agc_chunk = o.desc.agc_chunk_frames ? (long long)o.desc.agc_chunk_frames : 16384;
+        const long long pre_calls = ((long long)preroll + cf - 1) / cf * cf;
+        long long grid = 4096;
+        { long long x = grid, y = cf; while (y) { const long long t = x % y; x = y; y = t; } grid = grid / x * cf; }
+        for (int s = 0; s < o.shards; s++) {
+            const long long next = (s == o.shards - 1) ? total_frames : ((long long)(s + 1) * per) / grid * grid;
+            sh[s].opt = &o; sh[s].shard = s;
+            sh[s].first_frame = ((long long)s * per) / grid * grid;
+            sh[s].frames = next - sh[s].first_frame;
+            if (sh[s].frames <= 0) {
+                fprintf(stderr, "--seamless-dc-agc: %lld frames are too few for %d shards on a grid of %lld frames (lcm of 4096 and --chunk-frames): "
+                                "shard %d would be empty\n", total_frames, o.shards, grid, s);
+                return 1;
+            }
+            sh[s].preroll_frames = sh[s].first_frame < pre_calls ? sh[s].first_frame : pre_calls;
+            uint64_t first_out = 0, nout = 0;
+            if (iqgpu_design_out_frames_range(&nd, (uint64_t)sh[s].first_frame, (uint64_t)sh[s].frames, &first_out, &nout) != IQGPU_OK) {
+                fprintf(stderr, "%s\n", iqgpu_last_error()); return 1;
+            }
+            sh[s].out_offset_bytes = (long long)first_out * (long long)obps;
+            sh[s].planned_out = (long long)nout;
+            if (o.dry && s < o.shards - 1) {        /* what the measuring steps will record at least: one DC row per call (two for a cut one), one AGC row per chunk */
+                sh[s].n_dc_rows = (sh[s].frames + cf - 1) / cf;
+                sh[s].agc_rows = (sh[s].frames + agc_chunk - 1) / agc_chunk;
+            }
+        }
+        g_shards = sh;
+        if (!o.dry && pthread_barrier_init(&g_pass, NULL, (unsigned)o.shards) != 0) { fprintf(stderr, "pthread_barrier_init failed\n"); return 1; }
+    }
+    for (int s = 0; s < o.shards && !o.seamless && !o.seamless_agc && !o.seamless_dc && !o.seamless_dc_agc; s++) {
         sh[s].opt = &o; sh[s].shard = s;
         sh[s].first_frame = (long long)s * per;
         sh[s].frames = (s == o.shards - 1) ? total_frames - sh[s].first_frame : per;
@@ -677,12 +837,13 @@ int main(int argc, char **argv)
         int distinct = 0;
         for (int s = 0; s < o.shards; s++) { int seen = 0; for (int q = 0; q < s; q++) if (!strcmp(sh[q].bus_id, sh[s].bus_id) && sh[q].device == sh[s].device) seen = 1; if (!seen) distinct++; }
         printf("{\"dry_placement\": true, %s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"distinct_devices\": %d, \"per_shard\": [",
-               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : o.seamless_dc ? "\"seamless_dc\": true, " : "", total_frames, frames_out, o.shards, o.devices, distinct);
+               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : o.seamless_dc ? "\"seamless_dc\": true, " : o.seamless_dc_agc ? "\"seamless_dc_agc\": true, " : "", total_frames, frames_out, o.shards, o.devices, distinct);
         for (int s = 0; s < o.shards; s++) {
-            char pre_kv[96] = "";
+            char pre_kv[160] = "";
             if (o.seamless) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld", sh[s].preroll_frames);
             if (o.seamless_agc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"agc_rows\": %lld", sh[s].preroll_frames, sh[s].agc_rows);
             if (o.seamless_dc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"dc_rows\": %lld", sh[s].preroll_frames, sh[s].n_dc_rows);
+            if (o.seamless_dc_agc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"dc_rows\": %lld, \"agc_rows\": %lld", sh[s].preroll_frames, sh[s].n_dc_rows, sh[s].agc_rows);
             printf("%s{\"shard\": %d, \"device\": %d, \"pci_bus_id\": \"%s\", \"numa_node\": %d, \"cpus_allowed\": %d, \"first_frame\": %lld, \"frames_in\": %lld, \"planned_out\": %lld, "
                    "\"out_offset_bytes\": %lld, \"pinned_bytes\": %lld, \"hbm_bytes\": %lld%s}", s ? ", " : "", s, sh[s].device, sh[s].bus_id, sh[s].numa_node, sh[s].cpus_allowed,
                    sh[s].first_frame, sh[s].frames, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].pinned_bytes, sh[s].hbm_bytes, pre_kv);
@@ -694,7 +855,7 @@ int main(int argc, char **argv)
     if (!o.quiet) {
         printf("{%s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"seconds\": %.6f, \"msps_end_to_end\": %.3f, \"stream_seconds\": %.6f, \"msps_streaming\": %.3f, "
                "\"h2d_GBs\": %.3f, \"d2h_GBs\": %.3f, \"in_bytes_per_frame\": %zu, \"out_bytes_per_frame\": %zu, \"input\": \"%s\", \"per_shard\": [",
-               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : o.seamless_dc ? "\"seamless_dc\": true, " : "", total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
+               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : o.seamless_dc ? "\"seamless_dc\": true, " : o.seamless_dc_agc ? "\"seamless_dc_agc\": true, " : "", total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
                stream_s > 0 ? (double)total_frames * (double)ibps / stream_s / 1e9 : 0.0, stream_s > 0 ? (double)frames_out * (double)obps / stream_s / 1e9 : 0.0, ibps, obps,
                o.synthetic_frames <= 0 ? "file" : o.have_hash ? "synthetic-hash" : "synthetic-constant");
         for (int s = 0; s < o.shards; s++) {
@@ -706,13 +867,17 @@ int main(int argc, char **argv)
                 (unsigned long long)sh[s].entry.samples_seen);
             if (o.seamless_dc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"measure_seconds\": %.6f, \"dc_rows\": %lld, \"entry\": {\"re\": %.17g, \"im\": %.17g}",
                 sh[s].preroll_frames, sh[s].measure_seconds, sh[s].n_dc_rows, sh[s].dc_entry.re, sh[s].dc_entry.im);
+            if (o.seamless_dc_agc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"measure_seconds\": %.6f, \"dc_rows\": %lld, \"agc_rows\": %lld, "
+                "\"dc_entry\": {\"re\": %.17g, \"im\": %.17g}, \"entry\": {\"locked\": %d, \"current_gain\": %.9g, \"samples_seen\": %llu}", sh[s].preroll_frames,
+                sh[s].measure_seconds, sh[s].n_dc_rows, sh[s].agc_rows, sh[s].dc_entry.re, sh[s].dc_entry.im, sh[s].entry.locked, (double)sh[s].entry.current_gain,
+                (unsigned long long)sh[s].entry.samples_seen);
             printf("%s{\"shard\": %d, \"device\": %d, \"numa_node\": %d, \"first_frame\": %lld, \"frames_in\": %lld, \"frames_out\": %lld, \"planned_out\": %lld, \"out_offset_bytes\": %lld, \"seconds\": %.6f%s}",
                    s ? ", " : "", s, sh[s].device, sh[s].numa_node, sh[s].first_frame, sh[s].frames, sh[s].frames_out, sh[s].planned_out, sh[s].out_offset_bytes, sh[s].stream_seconds, pre_kv);
         }
         printf("]}\n");
     }
     for (int s = 0; s < o.shards; s++) if (sh[s].rows) iqgpu_host_free_pinned(sh[s].rows);
-    for (int s = 0; s < o.shards; s++) free(sh[s].dc_rows);
+    for (int s = 0; s < o.shards; s++) { free(sh[s].dc_rows); free(sh[s].dc_call_rows); }
     free(th); free(sh);
     return rc;
 }

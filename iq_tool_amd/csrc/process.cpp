@@ -108,8 +108,9 @@ int Call::stage_front()
         snprintf(c->front_kernel, sizeof(c->front_kernel), "k_p0fft16");
         return IQGPU_OK;
     }
-    // (the measure pass on k_front_s1<.., AGC>: the gain of a scratch state, no verdict -- only the kernel's peak array is wanted)
-    const bool measure_s1 = o.agc == AgcMode::MeasureS1;
+    // (the measure pass on k_front_s1<.., AGC>, a fused piece of a shadow call: the gain of a scratch state, no verdict -- only the
+    //  kernel's peak array is wanted)
+    const bool measure_s1 = no_verdict();
     FrontArgs a{};
     a.dbg = c->sw.dbg;
     a.raw = d_raw_in;
@@ -349,11 +350,15 @@ static Call begin_call(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, v
 // iqgpu_chain_dc_measure: the DC blocker's map of ONE call -- the call an ordinary process of frames_in frames at stream position `at`
 // would be, planned by the code that plans it (begin_call, plan_geometry, dc_geom), of which only k_dc_prefix and the scan are
 // launched; the scan writes the map to d_map and leaves the chain's DC state and carries alone.  The chain's position is put back.
-int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, cd2 *d_map)
+// (a chain with the AGC: the piece in front of the lock leaves cf32 for the AGC kernels, the piece behind it -- past_lock -- has the
+//  gain in its last kernel; both enter the plan as in process_one)
+int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, cd2 *d_map, bool past_lock)
 {
     const StreamPos was{c->rem, c->phi, c->fpending};
     c->rem = at.rem; c->phi = at.phi; c->fpending = at.fpending;
     Call k = begin_call(c, d_raw_in, frames_in, nullptr, CallOpts());
+    k.agc_fused = past_lock;
+    if (c->agc && !past_lock) k.fin_fmt = IQGPU_FMT_CF32;
     k.plan_geometry();
     const DcGeom dg = k.dc_geom();
     c->rem = was.rem; c->phi = was.phi; c->fpending = was.fpending;
@@ -390,18 +395,23 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     // with the AGC on, the last stage leaves cf32 in abuf and k_agc_apply packs -- unless the call is past the lock
     // on a chain whose front kernel applies the gain itself (fused: packed output straight to the caller)
     // (the measure pass on k_front_s1<.., AGC>: the fused front launch as it is, against a scratch state and with no verdict -- stage_front)
-    const bool agc_fused = past_lock || o.agc == AgcMode::MeasureS1;
+    // (a shadow call, chain.hpp: the piece behind a filter keeps the filter's cf32 epilogue -- the plan of a chain with a filter does
+    //  not read agc_fused -- and is measured like a piece in front of the lock)
+    const bool shadow = o.agc == AgcMode::Shadow;
+    const bool agc_fused = (past_lock && !(shadow && c->fp.enabled)) || o.agc == AgcMode::MeasureS1;
+    const bool scratch_fused = o.agc == AgcMode::MeasureS1 || (shadow && agc_fused);      // the fused front launch against the scratch state
+    const bool measure_unfused = o.agc == AgcMode::Measure || (shadow && !agc_fused);    // k_agc_measure over abuf
     k.agc_fused = agc_fused;
     if (c->agc && !agc_fused) {
         // (dx / local: the AGC's input of earlier calls stands in front of this call's, see stage_agc)
         const size_t lead = c->agc_rms_alpha > 0.0f ? (size_t)c->agc_rms_warm : 0;
         int rc = c->abuf.ensure((lead + (size_t)k.p.n_emit + 1) * sizeof(cf2)); if (rc) return rc;
         k.fin_out = (cf2 *)c->abuf.p + lead; k.fin_fmt = IQGPU_FMT_CF32;
-        if (o.agc == AgcMode::Measure && !o.rows) {
+        if (measure_unfused && !o.rows) {
             rc = c->agc_rows.ensure((((size_t)frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk) * sizeof(AgcRow)); if (rc) return rc;
         }
     }
-    if (o.agc == AgcMode::MeasureS1) {
+    if (scratch_fused) {
         // the packed output nobody keeps, the scratch state (the fresh one: gain 1) and the table
         int rc = c->seek_sink.ensure((size_t)k.p.n_emit * obps + 16); if (rc) return rc;
         k.fin_out = c->seek_sink.p;
@@ -444,8 +454,8 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     if (k.filt && (rc = k.stage_filter()) != IQGPU_OK) { c->poisoned = true; return rc; }
     if (c->late && (rc = k.stage_late_resampler()) != IQGPU_OK) { c->poisoned = true; return rc; }
     if (c->agc && !agc_fused && o.agc != AgcMode::Drop &&
-        (rc = o.agc == AgcMode::Measure ? k.stage_agc_measure() : k.stage_agc()) != IQGPU_OK) { c->poisoned = true; return rc; }
-    if (o.agc == AgcMode::MeasureS1 && (rc = k.stage_agc_rows_from_peaks()) != IQGPU_OK) { c->poisoned = true; return rc; }
+        (rc = measure_unfused ? k.stage_agc_measure() : k.stage_agc()) != IQGPU_OK) { c->poisoned = true; return rc; }
+    if (scratch_fused && (rc = k.stage_agc_rows_from_peaks()) != IQGPU_OK) { c->poisoned = true; return rc; }
 
     // ---- advance the stream position ----
     c->nco_theta += (uint32_t)frames_in * c->nco_dtheta;
@@ -460,20 +470,18 @@ static int process_one(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
 int process_device_impl(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
                                void *d_out, size_t out_capacity_bytes, size_t *frames_out, const CallOpts &o)
 {
-    // (a measuring or seeking call keeps the AGC out: the whole call in one piece, process_one)
-    if (!(c->agc_fusable || c->agc_fusable_filter) || frames_in == 0 || o.agc != AgcMode::Ordinary)
+    // (a measuring or seeking call keeps the AGC out: the whole call in one piece, process_one -- but for a shadow call, which is cut
+    //  as the ordinary call at its position is)
+    const bool shadow = o.agc == AgcMode::Shadow;
+    if (!(c->agc_fusable || c->agc_fusable_filter) || frames_in == 0 || (o.agc != AgcMode::Ordinary && !shadow))
         return process_one(c, d_raw_in, frames_in, d_out, out_capacity_bytes, frames_out, o, false);
     // output AGC on the specialised front kernel: the scanning phase (and the chunk that locks) through the unfused
     // kernels, everything behind it fused
     *frames_out = 0;
     bool locks = false;
-    size_t head = agc_unfused_head(c, frames_in, &locks);
-    // with a user filter between the resampler and the AGC the call that holds the lock stays whole: cutting it at the locking chunk
-    // would move the filter's overlap-save windows on the stream (other roundings: the bytes of the unfused path would be missed by a
-    // code here and there); the fused epilogue starts with the next call
-    if (c->agc_fusable_filter && head > 0 && head < frames_in) head = frames_in;
+    const size_t head = agc_call_cut(c, c->agc_locked_host, c->agc_seen_host, StreamPos{c->rem, c->phi, c->fpending}, frames_in, &locks);
     const size_t ibps = bytes_per_frame(c->desc.in_format), obps = bytes_per_frame(c->desc.out_format);
-    if ((size_t)plan_call(c, frames_in).n_emit * obps > out_capacity_bytes)
+    if (!shadow && (size_t)plan_call(c, frames_in).n_emit * obps > out_capacity_bytes)
         return fail(IQGPU_ECAPACITY, "output buffer too small: need %zu bytes, have %zu", (size_t)plan_call(c, frames_in).n_emit * obps,
             out_capacity_bytes);
     size_t n1 = 0, n2 = 0;
@@ -482,6 +490,15 @@ int process_device_impl(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
     CallOpts o1 = o, o2 = o;
     o1.probe_span = frames_in;
     if (head > 0) o2.no_probe = true;
+    if (shadow) {
+        // the rows of the call in chunk order: the head is a whole number of chunks, the second piece's rows stand behind them
+        if (!o.rows) {
+            const int rc = c->agc_rows.ensure((((size_t)frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk) * sizeof(AgcRow));
+            if (rc) return rc;
+            o1.rows = (AgcRow *)c->agc_rows.p;
+        }
+        o2.rows = o1.rows + head / (size_t)c->agc_chunk;
+    }
     if (head > 0) {
         const int rc = process_one(c, d_raw_in, head, d_out, out_capacity_bytes, &n1, o1, false);
         if (rc) return rc;
@@ -489,8 +506,8 @@ int process_device_impl(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
         if (locks) c->agc_locked_host = true;
     }
     if (head < frames_in) {
-        const int rc = process_one(c, (const char *)d_raw_in + head * ibps, frames_in - head, (char *)d_out + n1 * obps,
-                                   out_capacity_bytes - n1 * obps, &n2, o2, true);
+        const int rc = process_one(c, (const char *)d_raw_in + head * ibps, frames_in - head, shadow ? nullptr : (char *)d_out + n1 * obps,
+                                   shadow ? 0 : out_capacity_bytes - n1 * obps, &n2, o2, true);
         if (rc) return rc;
         c->agc_seen_host += n2;
     }

@@ -28,30 +28,43 @@ static int dc_two_pass_check(const iqgpu_chain *c, const char *who)
     return IQGPU_OK;
 }
 
+// what the exact calls of chains with the DC blocker AND the digital AGC ask of a chain (iqgpu_chain_dcagc_*)
+static int dcagc_check(const iqgpu_chain *c, const char *who)
+{
+    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
+    if (!c->dc) return fail(IQGPU_EINVAL, "%s: the chain has no DC blocker", who);
+    return agc_two_pass_check(c, who);
+}
+
 // agc_variant: iqgpu_chain_seek_agc -- the preroll with the AGC out of the way, then *entry (or the fresh state) installed
 // dc_variant: iqgpu_chain_seek_dc -- no warm-up of the DC blocker asked for: *dc_at (or zero) is its state in front of the preroll,
 // which runs in calls of call_frames (0: one call)
-struct SeekDc { bool on = false; const iqgpu_dc_state *at = nullptr; size_t call_frames = 0; };
+// agc: iqgpu_chain_dcagc_seek -- both at once: the preroll as SHADOW calls (chain.hpp, AgcMode) from the host mirrors' closed form
+struct SeekDc { bool on = false; const iqgpu_dc_state *at = nullptr; size_t call_frames = 0; bool agc = false; };
 static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, bool on_device,
                      bool agc_variant = false, const iqgpu_agc_state *entry = nullptr, const SeekDc &dcv = SeekDc())
 {
-    const char *who = dcv.on ? "iqgpu_chain_seek_dc" : agc_variant ? "iqgpu_chain_seek_agc" : "iqgpu_chain_seek";
+    const char *who = dcv.agc ? "iqgpu_chain_dcagc_seek" : dcv.on ? "iqgpu_chain_seek_dc" : agc_variant ? "iqgpu_chain_seek_agc" : "iqgpu_chain_seek";
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
     // what iqgpu_chain_reset does comes first: batches in flight and a pending verdict resolved, histories and dc state zeroed,
     // the poison cleared -- a refused argument below leaves the chain reset
     int rc = iqgpu_chain_reset(c); if (rc) return rc;
     c->fpending = 0;                                          // (reset keeps the FFT remainder queued: a seek starts a stream)
     if (agc_variant) {
-        rc = agc_two_pass_check(c, who); if (rc) return rc;
+        rc = dcv.agc ? dcagc_check(c, who) : agc_two_pass_check(c, who); if (rc) return rc;
         if (entry && (entry->locked != 0 && entry->locked != 1)) return fail(IQGPU_EINVAL, "%s: entry state with locked = %d", who, entry->locked);
     }
     cd2 dc_at{0.0, 0.0};
     if (dcv.on) {
-        rc = dc_two_pass_check(c, who); if (rc) return rc;
+        if (!dcv.agc) { rc = dc_two_pass_check(c, who); if (rc) return rc; }
         if (dcv.at) { dc_at.x = dcv.at->re; dc_at.y = dcv.at->im; }
         if (!std::isfinite(dc_at.x) || !std::isfinite(dc_at.y)) return fail(IQGPU_EINVAL, "%s: the state in front of the preroll is not finite", who);
         if (dcv.call_frames && preroll_frames % dcv.call_frames != 0) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames is not a whole number "
             "of calls of %zu frames", who, preroll_frames, dcv.call_frames);
+        // (the cut of a call is a closed form of the position only on the chunk grid)
+        if (dcv.agc && (first_frame % (uint64_t)c->agc_chunk || dcv.call_frames % (size_t)c->agc_chunk || preroll_frames % (size_t)c->agc_chunk))
+            return fail(IQGPU_EINVAL, "%s: first_frame %llu, call_frames %zu and the preroll of %zu frames have to be multiples of "
+                "agc_chunk_frames = %lld", who, (unsigned long long)first_frame, dcv.call_frames, preroll_frames, (long long)c->agc_chunk);
     }
     if (first_frame > kMaxStreamFrames) return fail(IQGPU_EINVAL, "%s: frame %llu is beyond 2^39 frames", who,
         (unsigned long long)first_frame);
@@ -84,6 +97,11 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         // (the preroll lies in front of the range the caller asked for: the I/Q probe takes no block from it and keeps its slot free
         //  for the head of the first call behind the seek)
         CallOpts preroll_call; preroll_call.no_probe = true;
+        if (dcv.agc) {
+            // shadow calls: cut as the single stream's calls are, from the mirrors the single stream has in front of the preroll
+            preroll_call.agc = AgcMode::Shadow;
+            agc_mirrors_at(c, first_frame - (uint64_t)preroll_frames, &c->agc_locked_host, &c->agc_seen_host);
+        }
 
         if (dcv.on) {
             // the preroll runs in the single stream's own calls -- every one staged like a call of iqgpu_chain_process -- from the
@@ -94,8 +112,12 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
                 const void *src = (const char *)preroll + at * ibps, *d_in = src;
                 if (!on_device) { rc = stage_host_input(c, src, per, &d_in); if (rc) return rc; }
                 size_t dropped = 0;
-                rc = c->seek_sink.ensure((size_t)plan_call(c, per).n_emit * obps + 16); if (rc) return rc;
-                rc = process_device_impl(c, d_in, per, c->seek_sink.p, c->seek_sink.cap, &dropped, preroll_call); if (rc) return rc;
+                if (dcv.agc) rc = process_device_impl(c, d_in, per, nullptr, 0, &dropped, preroll_call);
+                else {
+                    rc = c->seek_sink.ensure((size_t)plan_call(c, per).n_emit * obps + 16); if (rc) return rc;
+                    rc = process_device_impl(c, d_in, per, c->seek_sink.p, c->seek_sink.cap, &dropped, preroll_call);
+                }
+                if (rc) return rc;
             }
         } else if (preroll_frames) {
             const size_t obps = bytes_per_frame(c->desc.out_format);
@@ -121,6 +143,9 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             return fail(IQGPU_EINVAL, "internal: the position behind the preroll is not the closed form at frame %llu", (unsigned long long)first_frame);
         }
         c->total_in = first_frame; c->total_out = to.n_out;       // (iqgpu_chain_tell: of the stream, not of the preroll)
+        // (the mirrors the shadow calls have walked forward: the closed form at first_frame -- stated, so that a chain which never cuts
+        //  a call, and so never moves them, carries them too)
+        if (dcv.agc) agc_mirrors_at(c, first_frame, &c->agc_locked_host, &c->agc_seen_host);
     }
     if (agc_variant && entry) {
         // The AGC state of the stream at first_frame, everywhere the chain keeps it: the device state the kernels read, and the host's
@@ -170,6 +195,17 @@ extern "C" int iqgpu_chain_seek_dc_device(iqgpu_chain *c, uint64_t first_frame, 
     return seek_impl(c, first_frame, d_preroll, preroll_frames, true, false, nullptr, SeekDc{true, at_preroll_start, call_frames});
 }
 
+extern "C" int iqgpu_chain_dcagc_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
+                                      const iqgpu_dc_state *dc_at_preroll_start, const iqgpu_agc_state *agc_entry)
+{
+    return seek_impl(c, first_frame, preroll, preroll_frames, false, true, agc_entry, SeekDc{true, dc_at_preroll_start, call_frames, true});
+}
+extern "C" int iqgpu_chain_dcagc_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
+                                             size_t call_frames, const iqgpu_dc_state *dc_at_preroll_start, const iqgpu_agc_state *agc_entry)
+{
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, true, true, agc_entry, SeekDc{true, dc_at_preroll_start, call_frames, true});
+}
+
 // ------------------------------------------------------------------------------------------------
 // exact seamless sharding of DC-blocker chains: the map of a call (k_dc_prefix + k_dc_scan's map output), the walk over the maps
 // ------------------------------------------------------------------------------------------------
@@ -208,11 +244,11 @@ extern "C" int iqgpu_chain_dc_measure_device(iqgpu_chain *c, uint64_t first_fram
 
 // One definition of the walk: k_dc_walk applies the helper behind k_dc_scan's state update, in the translation unit of k_dc_scan, a
 // batch of 2^16 rows per launch from a scratch copy of *st
-extern "C" int iqgpu_chain_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
+static int dc_advance_impl(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before, bool dcagc)
 {
     static_assert(sizeof(iqgpu_dc_row) == sizeof(DcMapRow) && sizeof(DcMapRow) == 32 && sizeof(iqgpu_dc_state) == sizeof(cd2), "DC row layout");
-    const char *who = "iqgpu_chain_dc_advance";
-    int rc = dc_two_pass_check(c, who); if (rc) return rc;
+    const char *who = dcagc ? "iqgpu_chain_dcagc_dc_advance" : "iqgpu_chain_dc_advance";
+    int rc = dcagc ? dcagc_check(c, who) : dc_two_pass_check(c, who); if (rc) return rc;
     if (!st || (n && !rows)) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     if (!std::isfinite(st->re) || !std::isfinite(st->im)) return fail(IQGPU_EINVAL, "%s: the state is not finite", who);
     for (size_t i = 0; i < n; ++i)
@@ -242,6 +278,75 @@ extern "C" int iqgpu_chain_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const 
     return IQGPU_OK;
 }
 
+extern "C" int iqgpu_chain_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
+{
+    return dc_advance_impl(c, st, rows, n, before, false);
+}
+extern "C" int iqgpu_chain_dcagc_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
+{
+    return dc_advance_impl(c, st, rows, n, before, true);
+}
+
+// iqgpu_chain_dcagc_dc_measure: the maps of the ordinary call at first_frame, ONE ROW PER PIECE -- the call is cut as
+// process_device_impl cuts it there (agc_call_cut with the mirrors' closed form at first_frame), and the single stream rounds its
+// state behind each piece, so the two maps of a cut call are not merged
+static int dcagc_dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const void *in, size_t frames_in, iqgpu_dc_row *rows, size_t cap,
+                                 size_t *n_rows, bool on_device)
+{
+    const char *who = "iqgpu_chain_dcagc_dc_measure";
+    int rc = dcagc_check(c, who); if (rc) return rc;
+    if (!rows || !n_rows) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
+    *n_rows = 0;
+    if (cap < 2) return fail(IQGPU_EINVAL, "%s: the table holds %zu rows, a call can be two pieces", who, cap);
+    if (first_frame > kMaxStreamFrames || (uint64_t)frames_in > kMaxStreamFrames - first_frame) return fail(IQGPU_EINVAL, "%s: stream position "
+        "%llu + %zu frames is beyond 2^39 frames", who, (unsigned long long)first_frame, frames_in);
+    if (first_frame % (uint64_t)c->agc_chunk) return fail(IQGPU_EINVAL, "%s: first_frame %llu is not a multiple of agc_chunk_frames = %lld",
+        who, (unsigned long long)first_frame, (long long)c->agc_chunk);
+    if (frames_in == 0) return IQGPU_OK;
+    if (!in) return fail(IQGPU_EINVAL, "%s: NULL buffer", who);
+    if (c->poisoned) return fail(IQGPU_EHIP, "an earlier call failed half way through: the stream state is undefined until iqgpu_chain_reset()");
+    HIP_TRY(hipSetDevice(c->device));
+    rc = pipe_advance(c, c->pipe_seq); if (rc) return rc;         // batches submitted earlier come first (same stream)
+    rc = c->dc_walk.ensure(64); if (rc) return rc;
+    const void *d_in = in;
+    if (!on_device) { rc = stage_host_input(c, in, frames_in, &d_in); if (rc) return rc; }
+    // the pieces: [0, head) in front of the lock, [head, frames_in) behind it; a chain that never cuts runs the call whole, unfused
+    size_t head = frames_in;
+    if (c->agc_fusable || c->agc_fusable_filter) {
+        bool locked = false, locks = false; uint64_t seen = 0;
+        agc_mirrors_at(c, first_frame, &locked, &seen);
+        head = agc_call_cut(c, locked, seen, stream_at(c, first_frame).pos, frames_in, &locks);
+    }
+    const size_t ibps = bytes_per_frame(c->desc.in_format);
+    const size_t len[2] = {head, frames_in - head};
+    size_t n = 0;
+    for (int k = 0; k < 2; ++k) {
+        if (len[k] == 0) continue;
+        const size_t off = k ? head : 0;
+        rc = dc_measure_call(c, stream_at(c, first_frame + off).pos, (const char *)d_in + off * ibps, len[k], (cd2 *)c->dc_walk.p + 2 * n, k == 1);
+        if (rc) return rc;
+        rows[n].frames = (uint64_t)len[k];
+        ++n;
+    }
+    cd2 m[4];
+    HIP_TRY(hipMemcpyAsync(m, c->dc_walk.p, sizeof(cd2) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < n; ++i) { rows[i].f = m[2 * i].x; rows[i].g_re = m[2 * i + 1].x; rows[i].g_im = m[2 * i + 1].y; }
+    *n_rows = n;
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_chain_dcagc_dc_measure(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, iqgpu_dc_row *rows,
+                                            size_t cap, size_t *n_rows)
+{
+    return dcagc_dc_measure_impl(c, first_frame, raw_in, frames_in, rows, cap, n_rows, false);
+}
+extern "C" int iqgpu_chain_dcagc_dc_measure_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in,
+                                                   iqgpu_dc_row *rows, size_t cap, size_t *n_rows)
+{
+    return dcagc_dc_measure_impl(c, first_frame, d_raw_in, frames_in, rows, cap, n_rows, true);
+}
+
 // ------------------------------------------------------------------------------------------------
 // seamless sharding of digital-AGC chains (ABI v8): the measure pass, and the walk over its tables
 // ------------------------------------------------------------------------------------------------
@@ -255,23 +360,26 @@ AgcMode measure_route(const iqgpu_chain *c)
     return s1 ? AgcMode::MeasureS1 : AgcMode::Measure;
 }
 
-static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows, bool on_device)
+// (shadow: iqgpu_chain_dcagc_measure -- the call cut and planned as the ordinary call at the chain's position, chain.hpp AgcMode::Shadow)
+static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows, bool on_device,
+                        bool shadow = false)
 {
     static_assert(sizeof(iqgpu_agc_chunk) == sizeof(AgcRow) && sizeof(AgcRow) == 16, "AGC row layout");
-    int rc = agc_two_pass_check(c, "iqgpu_chain_measure"); if (rc) return rc;
-    if (!n_rows) return fail(IQGPU_EINVAL, "iqgpu_chain_measure: NULL argument");
+    const char *who = shadow ? "iqgpu_chain_dcagc_measure" : "iqgpu_chain_measure";
+    int rc = shadow ? dcagc_check(c, who) : agc_two_pass_check(c, who); if (rc) return rc;
+    if (!n_rows) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     *n_rows = 0;
     if (frames_in == 0) return IQGPU_OK;
-    if (!in || !rows) return fail(IQGPU_EINVAL, "iqgpu_chain_measure: NULL buffer");
+    if (!in || !rows) return fail(IQGPU_EINVAL, "%s: NULL buffer", who);
     const size_t n = (frames_in + (size_t)c->agc_chunk - 1) / (size_t)c->agc_chunk;
-    if (cap < n) return fail(IQGPU_ECAPACITY, "iqgpu_chain_measure: %zu frames are %zu chunks, the table holds %zu rows", frames_in, n, cap);
+    if (cap < n) return fail(IQGPU_ECAPACITY, "%s: %zu frames are %zu chunks, the table holds %zu rows", who, frames_in, n, cap);
     HIP_TRY(hipSetDevice(c->device));
     rc = pipe_advance(c, c->pipe_seq); if (rc) return rc;         // batches submitted earlier come first (same stream)
     rc = agc_resolve_pending(c); if (rc) return rc;
     const void *d_in = in;
     if (!on_device) { rc = stage_host_input(c, in, frames_in, &d_in); if (rc) return rc; }
     size_t dropped = 0;
-    CallOpts mo; mo.agc = measure_route(c); mo.no_probe = true;      // (a pass whose output nobody keeps: nothing for the I/Q optimiser)
+    CallOpts mo; mo.agc = shadow ? AgcMode::Shadow : measure_route(c); mo.no_probe = true;      // (a pass whose output nobody keeps: nothing for the I/Q optimiser)
     rc = process_device_impl(c, d_in, frames_in, nullptr, 0, &dropped, mo);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(rows, c->agc_rows.p, n * sizeof(AgcRow), hipMemcpyDeviceToHost, c->stream));
@@ -288,6 +396,16 @@ extern "C" int iqgpu_chain_measure_device(iqgpu_chain *c, const void *d_raw_in, 
                                           size_t *n_rows)
 {
     return measure_impl(c, d_raw_in, frames_in, rows, cap, n_rows, true);
+}
+
+extern "C" int iqgpu_chain_dcagc_measure(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows)
+{
+    return measure_impl(c, raw_in, frames_in, rows, cap, n_rows, false, true);
+}
+extern "C" int iqgpu_chain_dcagc_measure_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap,
+                                                size_t *n_rows)
+{
+    return measure_impl(c, d_raw_in, frames_in, rows, cap, n_rows, true, true);
 }
 
 extern "C" int iqgpu_chain_agc_initial_state(const iqgpu_chain *c, iqgpu_agc_state *st)
