@@ -64,6 +64,7 @@ enum {
                             /* iqgpu_chain_seek and the two range-design calls: a chain with the output AGC              */
                             /* the AGC two-pass calls (measure*, agc_advance, seek_agc*): profile dx / local, CLOCK_WALL */
                             /* iqgpu_chain_save_state: a chain on IQGPU_AGC_CLOCK_WALL                                   */
+                            /* iqgpu_chain_seek_rms* / iqgpu_design_preroll_frames_rms: profile digital, the DC blocker  */
 };
 
 typedef struct iqgpu_chain iqgpu_chain; /* opaque, like resampler_t (include/resampler.h:25-26) */
@@ -433,6 +434,57 @@ int    iqgpu_chain_dcagc_seek_device(iqgpu_chain *c, uint64_t first_frame, const
 int    iqgpu_chain_dcagc_measure(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows);
 int    iqgpu_chain_dcagc_measure_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap,
                                         size_t *n_rows);
+/* ---- seamless range sharding of chains with the DX / LOCAL output AGC: a bounded window and a seam certificate (additive, still ABI v9) ----
+ * Every seek above refuses the profiles dx / local, and keeps doing so: agc_crcf's per-sample loop has no closed form and no table of
+ * per-chunk figures carries its state.  What the library's own kernels make of it does have a bounded window (agc.hip).  The output
+ * is cut into chunks on a grid that belongs to the STREAM (chunk k = output frames [k C, (k+1) C), C = max(256, warm / 16), warm =
+ * 26 / alpha: 2600 / 256 for local, 260 000 / 16 250 for dx), and every chunk runs a trajectory of its own: it starts warm samples
+ * ahead of k C from a guess made of 256 samples of that window alone -- within warm samples of the reset: at the reset, from the reset
+ * state -- and is ACCEPTED when it arrives within 2e-6 of where the chunk before it left.  What the single stream emits for an
+ * accepted chunk, and the state it carries through and behind it, is that trajectory bit for bit, under any split into calls.  So
+ * the state in front of output frame `cut` is a function of the warm + C pre-AGC samples in front of it at most: iqgpu_chain_seek_rms
+ * re-runs the trajectory of chunk (cut - 1) / C -- one definition of its start and of the per-sample step with the streaming
+ * kernel -- over the samples its preroll has produced, and the chain continues the single stream byte for byte.
+ * The exception is a chunk whose speculation was REJECTED: the loop freezes its gain while the smoothed output energy is <= 1e-6, so
+ * through a silent stretch the state is a value from arbitrarily far back, which no bounded window knows; the single stream then
+ * re-runs that chunk from its predecessor's end, and a seek into it lands on the speculated state instead.  That cannot be known
+ * from the window -- but it shows at the seam, at no cost:
+ * THE SEAM CERTIFICATE.  Ranges s = 0 .. N-1 of one stream, each on a chain of its own: range 0 from a fresh chain, range s > 0 behind
+ * iqgpu_chain_seek_rms(first[s]).  Read E[s] = iqgpu_chain_get_agc_state after range s has been processed (and keep its
+ * iqgpu_chain_save_state blob), and S[s+1] = iqgpu_chain_get_agc_state of chain s+1 right after its seek.  If current_gain,
+ * peak_memory and samples_seen of S[s+1] and E[s] are bit-equal, chain s+1 started from the state chain s ended in; when that holds
+ * at every seam in order, E[s] is the single stream's state at every cut (induction from range 0) and the stitched output is the
+ * single stream's byte for byte.  A seam that differs: iqgpu_chain_load_state of chain s's end-of-range blob into chain s+1, process
+ * range s+1 again, take its new end state as E[s+1] and re-check seam s+2 against it.  The output is thus always the single
+ * stream's; the work is parallel wherever the seams certify and sequential only for a range behind a seam that does not.
+ * When a seam does not certify: when the single stream's chunk that holds the last output in front of the cut was rejected -- in
+ * practice a cut inside or just behind a stretch whose AGC output energy stays <= 1e-6 (digital silence, a gap in the capture) for
+ * more than a chunk.  On a capture that carries signal or receiver noise there, every seam certifies.  One more case: a chain with
+ * an FFT user filter.  Its overlap-save windows start at the head of a call's buffer, so the last bits of what the filter emits --
+ * the AGC's input -- follow the cuts of the calls, and the preroll is a call of its own: such a seam certifies where the single
+ * stream made that very call ([first_frame - preroll_frames, first_frame)) and as a rule not elsewhere.  The certificate catches
+ * it like the silent case, and the fallback gives the single stream's bytes.  FIR filters and chains without a filter: any calls.
+ * iqgpu_design_preroll_frames_rms (no device): P_rms = P_fir + E, with P_fir = iqgpu_design_preroll_frames of the description with
+ * agc_enable = 0 and E the input frames that make the chain emit at least n = warm + C outputs wherever they lie in the stream.  With
+ * 2^S the half-band factor, step the 24-bit phase step (iqgpu_chain_info.arb_step), B the FFT block of the user filter and
+ * q = B - 1 (0 without an FFT filter):  no resampler E = n + q;  r < 1 (the filter behind the resampler)
+ * E = ceil((n + q) step / 2^24) * 2^S;  r >= 1 (the filter in front) E = ceil(ceil(n / 2^S) step / 2^24) + q.  (E frames close at
+ * least E / 2^S groups, g groups give at least floor(g 2^24 / step) resampler outputs, a block boundary holds back at most q.)
+ * Validation and error codes of iqgpu_design_probe, then the refusals of iqgpu_chain_seek_rms.
+ * iqgpu_chain_seek_rms[_device]: arguments, reset semantics and preroll rule of iqgpu_chain_seek with P_rms for the preroll:
+ * preroll_frames >= min(first_frame, P_rms), longer is allowed.  The preroll runs through the ordinary kernels with the AGC out of
+ * the way (cf32 kept on the device; the I/Q probe takes no block); then one launch of k_agc_rms_seek leaves gain, peak_memory and
+ * samples_seen at first_frame in the chain's AGC state, and the last warm pre-AGC samples become the warm-up window of the calls to
+ * come.  Returns with the stream idle; first_frame == 0 leaves a fresh chain.  Placement: iqgpu_design_out_frames_range of the
+ * description with agc_enable = 0.  Cuts: any frame (multiples of 4096 keep the input alignment of the single stream's calls); the
+ * calls behind a seek may have any lengths.  Cost: the preroll, plus at most warm + C dependent loop steps on one lane.
+ * Errors.  IQGPU_EINVAL: a chain without the output AGC, a NULL argument, a position beyond 2^39 frames, a preroll shorter than
+ * min(first_frame, P_rms) or longer than first_frame.  IQGPU_EUNSUPPORTED: the digital profile (it has iqgpu_chain_seek_agc); a chain
+ * with the DC blocker (its exact route needs a call grid and a walked state, iqgpu_chain_seek_dc; composing the two is not done
+ * yet).  A refused seek leaves the chain reset. */
+int    iqgpu_design_preroll_frames_rms(const iqgpu_chain_desc *d, uint64_t *frames);
+int    iqgpu_chain_seek_rms(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames);
+int    iqgpu_chain_seek_rms_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames);
 /* ---- checkpoint / resume: everything a chain carries from call to call, in a caller-owned blob (additive, still ABI v9) ----
  * The seek calls above rebuild the state at a stream position from a closed form and a preroll, and refuse what has no such form.
  * These two calls need none: iqgpu_chain_save_state copies the state out between two calls, iqgpu_chain_load_state puts it into a
@@ -530,9 +582,9 @@ int   iqgpu_iq_optimizer_touch(iqgpu_iq_optimizer *o, double now_sec); /* restar
  *      those at its submit).  While a block is staged and unread no later call replaces it; once read it is returned by every
  *      read until a later call has left the next one.  The block is the head of the whole call, however the library cuts it.
  *   2. Calls that are no chunk of the running stream neither leave a block nor occupy the slot: the preroll inside
- *      iqgpu_chain_seek*, _seek_agc*, _seek_dc*, _dcagc_seek*, and iqgpu_chain_measure, _measure_device, _measure_submit,
+ *      iqgpu_chain_seek*, _seek_agc*, _seek_dc*, _dcagc_seek*, _seek_rms*, and iqgpu_chain_measure, _measure_device, _measure_submit,
  *      _dc_measure*, _dcagc_dc_measure*, _dcagc_measure* (shadow calls leave no block).
- *   3. iqgpu_chain_reset, every iqgpu_chain_seek* (iqgpu_chain_dcagc_seek* too) and iqgpu_chain_load_state drop a staged or held block (it belongs to the
+ *   3. iqgpu_chain_reset, every iqgpu_chain_seek* (iqgpu_chain_dcagc_seek* and iqgpu_chain_seek_rms* too) and iqgpu_chain_load_state drop a staged or held block (it belongs to the
  *      stream position the chain leaves): *valid = 0 until the next call of rule 1.
  *   4. A call shorter than 1024 frames leaves the slot as it is. */
 int   iqgpu_chain_enable_iq_probe(iqgpu_chain *c, int enable);

@@ -88,6 +88,16 @@ def design_preroll_frames(**kw):
     return int(n.value)
 
 
+def design_preroll_frames_rms(desc=None, **kw):
+    """P_rms: the preroll Chain.seek_rms asks for on a chain with the dx / local output AGC -- the FIR memory plus the input frames
+    that make the chain emit warm + chunk outputs anywhere in the stream (iqgpu_design_preroll_frames_rms; no device needed).  desc: a
+    ChainDesc, or the description as make_desc keywords"""
+    d = desc if desc is not None else make_desc(**kw)
+    n = C.c_uint64(0)
+    check(_lib.load().iqgpu_design_preroll_frames_rms(C.byref(d), C.byref(n)))
+    return int(n.value)
+
+
 def design_out_frames_range(first_frame, frames_in, **kw):
     """(out_first, frames_out): what ONE stream of this description emits while it consumes input frames
     [first_frame, first_frame + frames_in) -- where a seamless shard's output goes and how long it is (no device needed)"""
@@ -334,6 +344,20 @@ class Chain:
     def seek_agc_device(self, first_frame, d_preroll, preroll_frames, entry=None):
         check(self._lib.iqgpu_chain_seek_agc_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames),
                                                     C.byref(entry) if entry is not None else None))
+
+    # ---- seamless sharding of dx / local AGC chains: a bounded window, certified at the seam (include/iqgpu.h) ----
+    def seek_rms(self, first_frame, preroll_raw=None):
+        """seek() for a chain with the dx / local AGC: preroll_raw holds the input frames that END at first_frame, at least
+        min(first_frame, design_preroll_frames_rms) of them; the AGC loop's state at first_frame is rebuilt from the preroll's own
+        output.  The seam is certified when agc_state_raw() right after this call equals, in gain, peak_memory and samples_seen, the
+        state of the chain that processed the range in front; otherwise load_state() that chain's blob and process the range again"""
+        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
+        n = raw.nbytes // self.in_bytes
+        check(self._lib.iqgpu_chain_seek_rms(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n))
+
+    def seek_rms_device(self, first_frame, d_preroll, preroll_frames):
+        """seek_rms() with the preroll already in device memory of this chain's GPU (a device address as an int)"""
+        check(self._lib.iqgpu_chain_seek_rms_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames)))
 
     # ---- exact seamless sharding of DC-blocker chains: measure, walk, seek with the walked state (include/iqgpu.h) ----
     def dc_state(self):

@@ -571,6 +571,32 @@ __device__ __forceinline__ void rms_run(const AgcRmsArgs &a, int64_t i0, int64_t
     }
 }
 
+// The start of the trajectory of the chunk whose first stream position is abs_s (x[abs_s - pos0] in this call): the state that
+// trajectory has in front of the chunk's first output.  One definition for k_agc_rms_spec and k_agc_rms_seek: a seek that re-runs a
+// chunk's trajectory arrives where the single stream's lane arrived because it runs this, over the same samples.
+__device__ __forceinline__ RmsSt rms_trajectory_start(const AgcRmsArgs &a, int64_t abs_s, float han)
+{
+    RmsSt st;
+    const int64_t a0 = abs_s - a.warm;
+    int64_t i;
+    if (a0 <= 0) { i = -a.pos0; st.g = 1.0f; st.p = 1.0f; }      // from the reset, in the reset state (agc_reset: src/agc.c:227-229)
+    else {
+        i = a0 - a.pos0;                                 // >= -warm = -hist_valid here
+        // (round 5: the power of the first 256 samples, four independent sums -- a guess within a few per cent instead of the
+        //  ~18 % of 32 samples, which is what lets the warm-up end after 26 / alpha samples instead of 40 / alpha)
+        float m4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int k = 0; k < 256; k += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { const cf2 v = a.x[i + k + u]; m4[u] = fmaf(v.x, v.x, fmaf(v.y, v.y, m4[u])); }
+        }
+        float m = ((m4[0] + m4[1]) + (m4[2] + m4[3])) * (1.0f / 256.0f);
+        st.g = m > 1e-20f ? fminf(1.0f / sqrtf(m), 1e6f) : 1.0f;
+        st.p = 1.0f;
+    }
+    rms_run<false>(a, i, abs_s - a.pos0, st, han);
+    return st;
+}
+
 __global__ __launch_bounds__(64) void k_agc_rms_spec(const AgcRmsArgs a)
 {
     const int64_t j = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -580,25 +606,7 @@ __global__ __launch_bounds__(64) void k_agc_rms_spec(const AgcRmsArgs a)
     const int64_t e = (abs_s + a.chunk < a.pos0 + a.n ? abs_s + a.chunk : a.pos0 + a.n) - a.pos0;
     const float han = -0.5f * a.alpha;
     RmsSt st{a.state->gain, a.state->peak_memory};
-    if (abs_s >= a.pos0) {                                   // the chunk begins in this call: a trajectory of its own
-        const int64_t a0 = abs_s - a.warm;
-        int64_t i;
-        if (a0 <= 0) { i = -a.pos0; st.g = 1.0f; st.p = 1.0f; }      // from the reset, in the reset state (agc_reset: src/agc.c:227-229)
-        else {
-            i = a0 - a.pos0;                                 // >= -warm = -hist_valid here
-            // (round 5: the power of the first 256 samples, four independent sums -- a guess within a few per cent instead of the
-            //  ~18 % of 32 samples, which is what lets the warm-up end after 26 / alpha samples instead of 40 / alpha)
-            float m4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int k = 0; k < 256; k += 4) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { const cf2 v = a.x[i + k + u]; m4[u] = fmaf(v.x, v.x, fmaf(v.y, v.y, m4[u])); }
-            }
-            float m = ((m4[0] + m4[1]) + (m4[2] + m4[3])) * (1.0f / 256.0f);
-            st.g = m > 1e-20f ? fminf(1.0f / sqrtf(m), 1e6f) : 1.0f;
-            st.p = 1.0f;
-        }
-        rms_run<false>(a, i, s, st, han);
-    }
+    if (abs_s >= a.pos0) st = rms_trajectory_start(a, abs_s, han);      // the chunk begins in this call: a trajectory of its own
     a.st[4 * j + 0] = st.g; a.st[4 * j + 1] = st.p;
     rms_run<true>(a, s, e, st, han);
     a.st[4 * j + 2] = st.g; a.st[4 * j + 3] = st.p;
@@ -634,6 +642,32 @@ __global__ __launch_bounds__(1024) void k_agc_rms_fix(const AgcRmsArgs a)
         a.state->peak_memory = a.st[4 * (int64_t)a.n_chunks - 1];
         a.state->seen += (uint64_t)a.n;
     }
+}
+
+// iqgpu_chain_seek_rms: the stream state in front of stream position cut = pos0 + n, from the samples x[0 .. n) in front of it alone.
+// One lane re-runs the trajectory of chunk k = (cut - 1) / chunk -- the chunk that holds the last sample in front of the cut -- from
+// its start (rms_trajectory_start: k chunk - warm, or the reset) to the cut, and emits nothing.  Where k_agc_rms_fix accepted that
+// chunk's speculation the single stream's state at the cut IS this trajectory's, under any split into calls: same start, same
+// samples, same rms_step, so the same bits.  The host has checked that x reaches back to the start (pos0 <= k chunk - warm, or
+// pos0 == 0).  The other state words stay as the reset left them, as k_agc_rms_fix leaves them.
+__global__ __launch_bounds__(64) void k_agc_rms_seek(const AgcRmsArgs a)
+{
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const int64_t cut = a.pos0 + a.n;
+    const int64_t abs_s = ((cut - 1) / a.chunk) * a.chunk;
+    const float han = -0.5f * a.alpha;
+    RmsSt st = rms_trajectory_start(a, abs_s, han);
+    rms_run<false>(a, abs_s - a.pos0, a.n, st, han);
+    a.state->gain = st.g;
+    a.state->peak_memory = st.p;
+    a.state->seen = (uint64_t)cut;
+}
+
+hipError_t launch_agc_rms_seek(const AgcRmsArgs &a, hipStream_t s)
+{
+    if (a.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_agc_rms_seek, dim3(1), dim3(64), 0, s, a);
+    return hipGetLastError();
 }
 
 void agc_rms_geometry(float alpha, int64_t pos0, int64_t n, int64_t *chunk, int64_t *warm, int32_t *n_chunks)

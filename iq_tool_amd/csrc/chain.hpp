@@ -276,6 +276,10 @@ StreamAt stream_at(const iqgpu_chain *c, uint64_t frames);
 // the chain's FIR memory in input frames (+ the DC blocker's warm-up): what a seek has to run in front of its position
 // (with_dc = false: without that warm-up -- what iqgpu_chain_seek_dc asks for, which is handed the blocker's state)
 uint64_t seek_preroll_frames(const iqgpu_chain *c, bool with_dc = true);
+// what iqgpu_chain_seek_rms asks for (dx / local): that FIR memory, plus input frames that make the chain emit at least
+// warm + chunk outputs wherever in the stream they lie (the closed form in iqgpu.h)
+uint64_t seek_rms_preroll_frames(const iqgpu_chain *c);
+int rms_seek_check(const iqgpu_chain *c, const char *who);      // an output AGC of profile dx / local, no DC blocker
 
 // ---- profiling (process.cpp): HIP events around every launch while profiling is on ----
 hipEvent_t get_event(iqgpu_chain *c);
@@ -299,7 +303,8 @@ struct KernelTimer {
 // Seamless sharding of digital-AGC chains (ABI v8, seek.cpp).  Other than Ordinary: a call runs the chain's ordinary UNFUSED route
 // -- its last stage leaves cf32 in abuf -- and the AGC itself stays out: no scan, no apply, no pack, the AGC state and its host
 // mirrors untouched, nothing written to the caller's output.  Measure: k_agc_measure then writes one row per chunk into agc_rows
-// (iqgpu_chain_measure); Drop: nothing reads abuf (the preroll of iqgpu_chain_seek_agc).
+// (iqgpu_chain_measure); Drop: nothing reads abuf (the preroll of iqgpu_chain_seek_agc) -- or, dx / local, k_agc_rms_seek reads the
+// call's samples behind abuf's lead of agc_rms_warm samples (the preroll of iqgpu_chain_seek_rms).
 // MeasureS1: the other route of the measure pass, for agc_fusable chains: k_front_s1<.., AGC> -- their fallback kernel, which
 // reduces the exact peak in front of the gain in its epilogue -- as it is, with the packed output into seek_sink and a scratch AGC
 // state (agc_scratch); the rows are then put together from its peak array.  Half the traffic of Measure, a slower kernel.

@@ -41,6 +41,14 @@
  * preroll is the filters' memory rounded up to whole chunks, with NO warm-up of the blocker, entered with the walked state -- and runs
  * the usual chunk loop.  The stitched file is the file --shards 1 writes, byte for byte.
  *
+ * --shards N --seamless-rms is --seamless for chains with the dx / local output AGC (--output-agc, --agc-profile dx|local), whose
+ * loop state the library rebuilds from a bounded window (iqgpu.h): cuts at multiples of 4096 frames, every shard thread reads the
+ * iqgpu_design_preroll_frames_rms frames in front of its start, seeks with iqgpu_chain_seek_rms, processes its range and records its
+ * AGC state right after the seek and behind the range, and a checkpoint behind the range.  After the join the seams are checked in
+ * order: the state a shard started from against the state the shard in front ended in (gain, peak_memory, samples_seen, bit for
+ * bit).  A range behind a seam that does not certify -- a cut in or behind digital silence -- is processed again from the checkpoint
+ * of the range in front, and the next seam is checked against its new end state.  The file is the one --shards 1 writes; the report
+ * says how many seams certified and how many ranges were redone.
  * --shards N --seamless-dc-agc is the exact --seamless for chains with the DC blocker AND the digital output AGC (--dc-block
  * --agc-profile digital), in the five steps of iqgpu.h's block on such chains.  Shard starts lie on lcm(4096, --chunk-frames), and
  * --chunk-frames is a multiple of the AGC chunk.  Step 1: shards 0 .. N-2 measure the DC maps of every call of their range
@@ -87,6 +95,7 @@ typedef struct {
     int seamless_agc;                 /* --seamless-agc: --seamless for digital-AGC chains, in two passes (measure, walk, process) */
     int seamless_dc;                  /* --seamless-dc: the exact --seamless for DC-blocker chains, in three passes (measure, walk, process) */
     int seamless_dc_agc;              /* --seamless-dc-agc: exact for chains with the DC blocker and the digital AGC, in five steps */
+    int seamless_rms;                 /* --seamless-rms: --seamless for dx / local AGC chains: seek from a bounded window, seams certified, ranges redone where not */
     int have_shards;                  /* --shards was given */
     int dry;                          /* --dry-placement: plan, bind, size the buffers, report -- no GPU call */
     int quiet;
@@ -112,6 +121,12 @@ typedef struct {
     /* --seamless-dc-agc: both of the above, and how many rows every call of the range gave (1 or 2) */
     unsigned char *dc_call_rows; long long n_dc_calls;
     double measure_seconds;
+    /* --seamless-rms: the AGC state right after the seek and behind the range, the checkpoint behind the range; redo_blob: this
+     * range again from the checkpoint of the range in front (its seam did not certify) */
+    iqgpu_agc_state rms_seek_state, rms_end_state;
+    void *blob; size_t blob_bytes;
+    const void *redo_blob; size_t redo_bytes;
+    int certified, redone;
     int barriers;                     /* how many of the rendezvous of the passes (two; --seamless-dc-agc: four) this thread has been through */
     int rc;
     char err[256];
@@ -454,6 +469,18 @@ static void *run_shard(void *arg)
         CK(iqgpu_chain_dcagc_seek(chain, (uint64_t)sh->first_frame, pre, np, chunk, &sh->dc_entry, &sh->entry));
         free(pre); pre = NULL;
     }
+    if (o->seamless_rms && sh->redo_blob) {
+        /* the seam in front of this range did not certify: the range again, from where the range in front really ended */
+        CK(iqgpu_chain_load_state(chain, sh->redo_blob, sh->redo_bytes));
+    } else if (o->seamless_rms && sh->first_frame > 0) {
+        const size_t np = (size_t)sh->preroll_frames;
+        pre = malloc(np ? np * ibps : 1);
+        if (!pre) { snprintf(sh->err, sizeof(sh->err), "out of memory for a preroll of %zu frames", np); sh->rc = -1; goto done; }
+        if (read_frames(o, in_fd, d.in_format, ibps, sh->first_frame - sh->preroll_frames, np, pre, sh->err, sizeof(sh->err))) { sh->rc = -1; goto done; }
+        CK(iqgpu_chain_seek_rms(chain, (uint64_t)sh->first_frame, pre, np));
+        CK(iqgpu_chain_get_agc_state(chain, &sh->rms_seek_state));
+        free(pre); pre = NULL;
+    }
     if (o->seamless && sh->first_frame > 0) {
         /* the frames in front of this shard's start, read like any other range of the stream, warm the chain's histories up; the
          * chain then stands at first_frame of the ONE stream (iqgpu_chain_seek) */
@@ -495,7 +522,7 @@ static void *run_shard(void *arg)
                 }
             } else if (o->have_hash) {
                 /* (buffer b is free: chunk i - 2, its last user, retired in the iteration before this one) */
-                if (o->seamless || o->seamless_agc || o->seamless_dc || o->seamless_dc_agc) hash_fill(h_in[b], d.in_format, ibps, o->hash_seed, sh->first_frame + done_in, n);
+                if (o->seamless || o->seamless_agc || o->seamless_dc || o->seamless_dc_agc || o->seamless_rms) hash_fill(h_in[b], d.in_format, ibps, o->hash_seed, sh->first_frame + done_in, n);
                 else hash_fill(h_in[b], d.in_format, ibps, o->hash_seed + (uint64_t)sh->shard, done_in, n);
             }
             CK(iqgpu_memcpy_h2d_async(d_in[b], h_in[b], n * ibps, s_in));
@@ -526,6 +553,16 @@ static void *run_shard(void *arg)
     if (written != sh->planned_out) {
         snprintf(sh->err, sizeof(sh->err), "shard %d produced %lld frames, its place in the output was planned for %lld", sh->shard, written, sh->planned_out);
         sh->rc = -1;
+    }
+    if (o->seamless_rms && !sh->rc) {
+        /* what the seam behind this range is checked against, and what the range behind it restarts from if the check fails */
+        size_t need = 0;
+        CK(iqgpu_chain_get_agc_state(chain, &sh->rms_end_state));
+        (void)iqgpu_chain_save_state(chain, NULL, 0, &need);          /* (a size query: IQGPU_ECAPACITY) */
+        free(sh->blob);
+        sh->blob = malloc(need ? need : 1);
+        if (!sh->blob) { snprintf(sh->err, sizeof(sh->err), "out of memory for a checkpoint of %zu bytes", need); sh->rc = -1; goto done; }
+        CK(iqgpu_chain_save_state(chain, sh->blob, need, &sh->blob_bytes));
     }
 done:
     /* (a shard that fails early still keeps the rendezvous of the two passes: the others wait there) */
@@ -562,6 +599,7 @@ static void usage(void)
             "          [--seamless (with --shards: the shards continue ONE stream -- the stitched output is what --shards 1 writes)]\n"
             "          [--seamless-agc (--seamless for chains with the digital output AGC: a measure pass, one walk, then the ordinary pass)]\n"
             "          [--seamless-dc (the exact --seamless for --dc-block chains without an AGC: a measure pass over the input, one walk, then the ordinary pass)]\n"
+            "          [--seamless-rms (--seamless for chains with the dx / local output AGC: seek from a bounded window, seams certified, a range behind a seam that is not is redone)]\n"
             "          [--seamless-dc-agc (the exact --seamless for --dc-block chains with the digital AGC: DC measure, walk, shadow AGC measure, walk, then the ordinary pass)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
             "          [--dry-placement (plan the shards, bind every shard thread, size its buffers, report as JSON: no GPU call)]\n");
@@ -621,6 +659,7 @@ int main(int argc, char **argv)
         else if (!strcmp(a, "--seamless-agc")) o.seamless_agc = 1;
         else if (!strcmp(a, "--seamless-dc")) o.seamless_dc = 1;
         else if (!strcmp(a, "--seamless-dc-agc")) o.seamless_dc_agc = 1;
+        else if (!strcmp(a, "--seamless-rms")) o.seamless_rms = 1;
         else if (!strcmp(a, "--debug")) {              /* --debug name=value -> iqgpu_debug_set (the library reads no environment) */
             char kv[512]; snprintf(kv, sizeof(kv), "%s", NEXT);
             char *eq = strchr(kv, '=');
@@ -637,6 +676,12 @@ int main(int argc, char **argv)
     o.desc.input_rate_hz = in_rate; o.desc.target_rate_hz = o.desc.no_resample ? in_rate : out_rate;
     if (o.shards < 1) o.shards = 1;
     if (o.devices < 1) o.devices = 1;
+    if (o.seamless_rms) {
+        if (o.seamless || o.seamless_agc || o.seamless_dc || o.seamless_dc_agc) { fprintf(stderr, "--seamless-rms excludes the other --seamless modes\n"); return 2; }
+        if (!o.have_shards) { fprintf(stderr, "--seamless-rms needs --shards N\n"); return 2; }
+        if (o.synthetic_frames > 0 && !o.have_hash) { fprintf(stderr, "--seamless-rms needs a stream it can read twice: an input file, or --synthetic with --synthetic-hash\n"); return 2; }
+        if (o.chunk_frames == 0) { fprintf(stderr, "--seamless-rms: --chunk-frames 0\n"); return 2; }
+    }
     if (o.seamless_dc_agc) {
         if (o.seamless || o.seamless_agc || o.seamless_dc) { fprintf(stderr, "--seamless-dc-agc excludes --seamless, --seamless-agc and --seamless-dc\n"); return 2; }
         if (!o.have_shards) { fprintf(stderr, "--seamless-dc-agc needs --shards N\n"); return 2; }
@@ -693,6 +738,29 @@ int main(int argc, char **argv)
         }
         sh[s].out_offset_bytes = (long long)first_out * (long long)obps;
         sh[s].planned_out = (long long)nout;
+    }
+    if (o.seamless_rms) {
+        /* a chain the seek refuses is refused here, in the library's words; placement does not depend on the AGC */
+        if (iqgpu_design_preroll_frames_rms(&o.desc, &preroll) != IQGPU_OK) { fprintf(stderr, "--seamless-rms: %s\n", iqgpu_last_error()); return 1; }
+        iqgpu_chain_desc na = o.desc;
+        na.agc_enable = 0;
+        for (int s = 0; s < o.shards; s++) {
+            const long long next = (s == o.shards - 1) ? total_frames : ((long long)(s + 1) * per) & ~4095ll;
+            sh[s].opt = &o; sh[s].shard = s;
+            sh[s].first_frame = ((long long)s * per) & ~4095ll;
+            sh[s].frames = next - sh[s].first_frame;
+            if (sh[s].frames <= 0) {
+                fprintf(stderr, "--seamless-rms: %lld frames are too few for %d shards on a grid of 4096 frames: shard %d would be empty\n", total_frames, o.shards, s);
+                return 1;
+            }
+            sh[s].preroll_frames = sh[s].first_frame < (long long)preroll ? sh[s].first_frame : (long long)preroll;
+            uint64_t first_out = 0, nout = 0;
+            if (iqgpu_design_out_frames_range(&na, (uint64_t)sh[s].first_frame, (uint64_t)sh[s].frames, &first_out, &nout) != IQGPU_OK) {
+                fprintf(stderr, "%s\n", iqgpu_last_error()); return 1;
+            }
+            sh[s].out_offset_bytes = (long long)first_out * (long long)obps;
+            sh[s].planned_out = (long long)nout;
+        }
     }
     if (o.seamless_agc) {
         /* what the library would refuse at the first v8 call, before anything is planned (its own words) */
@@ -805,7 +873,7 @@ int main(int argc, char **argv)
         g_shards = sh;
         if (!o.dry && pthread_barrier_init(&g_pass, NULL, (unsigned)o.shards) != 0) { fprintf(stderr, "pthread_barrier_init failed\n"); return 1; }
     }
-    for (int s = 0; s < o.shards && !o.seamless && !o.seamless_agc && !o.seamless_dc && !o.seamless_dc_agc; s++) {
+    for (int s = 0; s < o.shards && !o.seamless && !o.seamless_agc && !o.seamless_dc && !o.seamless_dc_agc && !o.seamless_rms; s++) {
         sh[s].opt = &o; sh[s].shard = s;
         sh[s].first_frame = (long long)s * per;
         sh[s].frames = (s == o.shards - 1) ? total_frames - sh[s].first_frame : per;
@@ -831,16 +899,38 @@ int main(int argc, char **argv)
         frames_out += sh[s].frames_out;
         if (sh[s].stream_seconds > stream_s) stream_s = sh[s].stream_seconds;
     }
+    /* --seamless-rms: the seam certificate (iqgpu.h), in order.  Shard s started from the state shard s-1 ended in, bit for bit: its
+     * bytes are the single stream's, given that shard s-1's are.  Otherwise its range again from shard s-1's checkpoint, in a thread
+     * of its own like the first time, and the seam behind it is checked against the new end state. */
+    int seams_certified = 0, ranges_redone = 0;
+    for (int s = 1; s < o.shards && o.seamless_rms && !o.dry && rc == 0; s++) {
+        const iqgpu_agc_state *e = &sh[s - 1].rms_end_state, *b = &sh[s].rms_seek_state;
+        if (!memcmp(&e->current_gain, &b->current_gain, sizeof(float)) && !memcmp(&e->peak_memory, &b->peak_memory, sizeof(float)) &&
+            e->samples_seen == b->samples_seen) { sh[s].certified = 1; seams_certified++; continue; }
+        sh[s].redo_blob = sh[s - 1].blob; sh[s].redo_bytes = sh[s - 1].blob_bytes; sh[s].redone = 1; ranges_redone++;
+        frames_out -= sh[s].frames_out;
+        sh[s].rc = 0; sh[s].err[0] = 0;
+        pthread_create(&th[s], NULL, run_shard, &sh[s]);
+        pthread_join(th[s], NULL);
+        if (sh[s].rc) { fprintf(stderr, "shard %d failed when its range was redone: %s\n", s, sh[s].err); rc = 1; }
+        frames_out += sh[s].frames_out;
+    }
+    char mode_kv[160] = "";
+    snprintf(mode_kv, sizeof(mode_kv), "%s", o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : o.seamless_dc ? "\"seamless_dc\": true, " :
+             o.seamless_dc_agc ? "\"seamless_dc_agc\": true, " : "");
+    if (o.seamless_rms && o.dry) snprintf(mode_kv, sizeof(mode_kv), "\"seamless_rms\": true, ");
+    else if (o.seamless_rms) snprintf(mode_kv, sizeof(mode_kv), "\"seamless_rms\": true, \"seams\": %d, \"seams_certified\": %d, \"ranges_redone\": %d, ", o.shards - 1,
+                                      seams_certified, ranges_redone);
     const double dt = now_s() - t0;
     if (o.dry) {
         /* one JSON line: the placement as planned; `distinct_devices` is what an N-shard job on N GPUs must show */
         int distinct = 0;
         for (int s = 0; s < o.shards; s++) { int seen = 0; for (int q = 0; q < s; q++) if (!strcmp(sh[q].bus_id, sh[s].bus_id) && sh[q].device == sh[s].device) seen = 1; if (!seen) distinct++; }
         printf("{\"dry_placement\": true, %s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"distinct_devices\": %d, \"per_shard\": [",
-               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : o.seamless_dc ? "\"seamless_dc\": true, " : o.seamless_dc_agc ? "\"seamless_dc_agc\": true, " : "", total_frames, frames_out, o.shards, o.devices, distinct);
+               mode_kv, total_frames, frames_out, o.shards, o.devices, distinct);
         for (int s = 0; s < o.shards; s++) {
             char pre_kv[160] = "";
-            if (o.seamless) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld", sh[s].preroll_frames);
+            if (o.seamless || o.seamless_rms) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld", sh[s].preroll_frames);
             if (o.seamless_agc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"agc_rows\": %lld", sh[s].preroll_frames, sh[s].agc_rows);
             if (o.seamless_dc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"dc_rows\": %lld", sh[s].preroll_frames, sh[s].n_dc_rows);
             if (o.seamless_dc_agc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"dc_rows\": %lld, \"agc_rows\": %lld", sh[s].preroll_frames, sh[s].n_dc_rows, sh[s].agc_rows);
@@ -855,12 +945,15 @@ int main(int argc, char **argv)
     if (!o.quiet) {
         printf("{%s\"frames_in\": %lld, \"frames_out\": %lld, \"shards\": %d, \"devices\": %d, \"seconds\": %.6f, \"msps_end_to_end\": %.3f, \"stream_seconds\": %.6f, \"msps_streaming\": %.3f, "
                "\"h2d_GBs\": %.3f, \"d2h_GBs\": %.3f, \"in_bytes_per_frame\": %zu, \"out_bytes_per_frame\": %zu, \"input\": \"%s\", \"per_shard\": [",
-               o.seamless ? "\"seamless\": true, " : o.seamless_agc ? "\"seamless_agc\": true, " : o.seamless_dc ? "\"seamless_dc\": true, " : o.seamless_dc_agc ? "\"seamless_dc_agc\": true, " : "", total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
+               mode_kv, total_frames, frames_out, o.shards, o.devices, dt, total_frames / dt / 1e6, stream_s, stream_s > 0 ? total_frames / stream_s / 1e6 : 0.0,
                stream_s > 0 ? (double)total_frames * (double)ibps / stream_s / 1e9 : 0.0, stream_s > 0 ? (double)frames_out * (double)obps / stream_s / 1e9 : 0.0, ibps, obps,
                o.synthetic_frames <= 0 ? "file" : o.have_hash ? "synthetic-hash" : "synthetic-constant");
         for (int s = 0; s < o.shards; s++) {
             char pre_kv[512] = "";
             if (o.seamless) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld", sh[s].preroll_frames);
+            if (o.seamless_rms) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"certified\": %s, \"redone\": %s, \"end\": {\"peak_memory\": %.9g, "
+                "\"current_gain\": %.9g, \"samples_seen\": %llu}", sh[s].preroll_frames, sh[s].certified ? "true" : "false", sh[s].redone ? "true" : "false",
+                (double)sh[s].rms_end_state.peak_memory, (double)sh[s].rms_end_state.current_gain, (unsigned long long)sh[s].rms_end_state.samples_seen);
             if (o.seamless_agc) snprintf(pre_kv, sizeof(pre_kv), ", \"preroll_frames\": %lld, \"measure_seconds\": %.6f, \"agc_rows\": %lld, \"entry\": {\"locked\": %d, "
                 "\"peak_memory\": %.9g, \"current_gain\": %.9g, \"last_strong_peak_time\": %.17g, \"samples_seen\": %llu}", sh[s].preroll_frames, sh[s].measure_seconds,
                 sh[s].agc_rows, sh[s].entry.locked, (double)sh[s].entry.peak_memory, (double)sh[s].entry.current_gain, sh[s].entry.last_strong_peak_time,
@@ -877,7 +970,7 @@ int main(int argc, char **argv)
         printf("]}\n");
     }
     for (int s = 0; s < o.shards; s++) if (sh[s].rows) iqgpu_host_free_pinned(sh[s].rows);
-    for (int s = 0; s < o.shards; s++) { free(sh[s].dc_rows); free(sh[s].dc_call_rows); }
+    for (int s = 0; s < o.shards; s++) { free(sh[s].dc_rows); free(sh[s].dc_call_rows); free(sh[s].blob); }
     free(th); free(sh);
     return rc;
 }

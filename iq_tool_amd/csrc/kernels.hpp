@@ -600,6 +600,10 @@ struct AgcRmsArgs {
 };
 void agc_rms_geometry(float alpha, int64_t pos0, int64_t n, int64_t *chunk, int64_t *warm, int32_t *n_chunks);
 hipError_t launch_agc_rms(const AgcRmsArgs &a, hipStream_t s);   // peak, scan, apply
+// k_agc_rms_seek: x[0 .. n) = the samples in front of stream position pos0 + n; leaves the stream's state at that position in *state
+// (gain, peak_memory, seen).  Reads a.x, n, pos0, alpha, state, chunk, warm; x has to reach back to the start of the trajectory of
+// the chunk that holds sample pos0 + n - 1 (pos0 <= its first position - warm, or pos0 == 0)
+hipError_t launch_agc_rms_seek(const AgcRmsArgs &a, hipStream_t s);
 // after a fused launch of the front kernel: all chunks healthy at the unchanged gain -> state advanced, *verify_flag = 0;
 // otherwise state untouched and *verify_flag = 1 (the caller has queued the unfused kernels behind it, run_if = verify_flag)
 hipError_t launch_agc_verify(const AgcArgs &a, hipStream_t s);

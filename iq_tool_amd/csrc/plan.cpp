@@ -119,6 +119,59 @@ uint64_t seek_preroll_frames(const iqgpu_chain *c, bool with_dc)
     return n;
 }
 
+// Input frames E such that ANY E consecutive frames of the stream make the chain emit at least n outputs: plan_call_at's laws read
+// from their worst position.  With B the FFT block of the user filter (0: FIR or none) and q(B) = B - 1 outputs a block boundary can
+// hold back (0 without a block):
+//   a call of E frames at an open group of rem frames closes (rem + E) >> S >= E >> S groups; g groups at phase phi < step give
+//   ceil((g 2^24 - phi) / step) >= floor(g 2^24 / step) resampler outputs; n samples into the block filter with fpending >= 0 pending
+//   leave floor((fpending + n) / B) B >= n - (B - 1).
+//   no resampler          E = n + q
+//   r < 1 (filter behind) E = ceil((n + q) step / 2^24) << S
+//   r >= 1 (filter first) E = ceil(ceil(n / 2^S) step / 2^24) + q        (every resampler output becomes 2^S frames)
+static uint64_t frames_for_outputs(const iqgpu_chain *c, uint64_t n)
+{
+    const uint64_t q = (c->fp.enabled && c->fp.block) ? (uint64_t)c->fp.block - 1 : 0;
+    const uint64_t one = (uint64_t)1 << 24;
+    if (c->late) {
+        const uint64_t m = (n + (((uint64_t)1 << c->ia.S) - 1)) >> c->ia.S;
+        return (m * (uint64_t)c->rp.step + one - 1) / one + q;
+    }
+    if (c->decim) return (((n + q) * (uint64_t)c->rp.step + one - 1) / one) << c->S;
+    return n + q;
+}
+
+uint64_t seek_rms_preroll_frames(const iqgpu_chain *c)
+{
+    int64_t chunk = 0, warm = 0; int32_t nch = 0;
+    agc_rms_geometry(c->agc_rms_alpha, 0, 0, &chunk, &warm, &nch);
+    return seek_preroll_frames(c, false) + frames_for_outputs(c, (uint64_t)(warm + chunk));
+}
+
+// what iqgpu_chain_seek_rms asks of a chain (seek.cpp) and iqgpu_design_preroll_frames_rms of a description
+int rms_seek_check(const iqgpu_chain *c, const char *who)
+{
+    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
+    if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC", who);
+    if (!(c->agc_rms_alpha > 0.0f)) return fail(IQGPU_EUNSUPPORTED, "%s: the digital AGC profile works chunk by chunk and is sharded by "
+        "iqgpu_chain_seek_agc; this call is for the profiles dx / local", who);
+    if (c->dc) return fail(IQGPU_EUNSUPPORTED, "%s: a chain with the DC blocker -- its exact route needs a call grid and a walked state "
+        "(iqgpu_chain_seek_dc); the two are not composed yet", who);
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_design_preroll_frames_rms(const iqgpu_chain_desc *d, uint64_t *frames)
+{
+    if (!d || !frames) return fail(IQGPU_EINVAL, "iqgpu_design_preroll_frames_rms: NULL argument");
+    *frames = 0;
+    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
+    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
+    int rc = design_chain(c, d);
+    if (rc == IQGPU_OK) rc = rms_seek_check(c, "iqgpu_design_preroll_frames_rms");
+    if (rc == IQGPU_OK) *frames = seek_rms_preroll_frames(c);
+    delete c;
+    return rc;
+}
+
 // design of a throw-away chain for the two calls below: create's validation first, then what seamless sharding cannot do
 static int design_for_seek(iqgpu_chain *c, const iqgpu_chain_desc *d)
 {

@@ -41,10 +41,12 @@ static int dcagc_check(const iqgpu_chain *c, const char *who)
 // which runs in calls of call_frames (0: one call)
 // agc: iqgpu_chain_dcagc_seek -- both at once: the preroll as SHADOW calls (chain.hpp, AgcMode) from the host mirrors' closed form
 struct SeekDc { bool on = false; const iqgpu_dc_state *at = nullptr; size_t call_frames = 0; bool agc = false; };
+// rms: iqgpu_chain_seek_rms -- dx / local: the preroll with the AGC out of the way and its cf32 output kept on the device, then the
+// loop's state at first_frame from k_agc_rms_seek over those samples
 static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, bool on_device,
-                     bool agc_variant = false, const iqgpu_agc_state *entry = nullptr, const SeekDc &dcv = SeekDc())
+                     bool agc_variant = false, const iqgpu_agc_state *entry = nullptr, const SeekDc &dcv = SeekDc(), bool rms = false)
 {
-    const char *who = dcv.agc ? "iqgpu_chain_dcagc_seek" : dcv.on ? "iqgpu_chain_seek_dc" : agc_variant ? "iqgpu_chain_seek_agc" : "iqgpu_chain_seek";
+    const char *who = rms ? "iqgpu_chain_seek_rms" : dcv.agc ? "iqgpu_chain_dcagc_seek" : dcv.on ? "iqgpu_chain_seek_dc" : agc_variant ? "iqgpu_chain_seek_agc" : "iqgpu_chain_seek";
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
     // what iqgpu_chain_reset does comes first: batches in flight and a pending verdict resolved, histories and dc state zeroed,
     // the poison cleared -- a refused argument below leaves the chain reset
@@ -54,6 +56,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         rc = dcv.agc ? dcagc_check(c, who) : agc_two_pass_check(c, who); if (rc) return rc;
         if (entry && (entry->locked != 0 && entry->locked != 1)) return fail(IQGPU_EINVAL, "%s: entry state with locked = %d", who, entry->locked);
     }
+    if (rms) { rc = rms_seek_check(c, who); if (rc) return rc; }
     cd2 dc_at{0.0, 0.0};
     if (dcv.on) {
         if (!dcv.agc) { rc = dc_two_pass_check(c, who); if (rc) return rc; }
@@ -71,9 +74,9 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
     if ((uint64_t)preroll_frames > first_frame) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames would start in front of "
         "frame 0 (first_frame %llu)", who, preroll_frames, (unsigned long long)first_frame);
     if (first_frame > 0) {
-        if (c->agc && !agc_variant) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
+        if (c->agc && !agc_variant && !rms) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
             "not on a bounded warm-up");
-        const uint64_t memory = seek_preroll_frames(c, !dcv.on), need = first_frame < memory ? first_frame : memory;
+        const uint64_t memory = rms ? seek_rms_preroll_frames(c) : seek_preroll_frames(c, !dcv.on), need = first_frame < memory ? first_frame : memory;
         if ((uint64_t)preroll_frames < need) return fail(IQGPU_EINVAL, "%s: preroll of %zu frames is shorter than the %llu "
             "this chain needs at frame %llu", who, preroll_frames, (unsigned long long)need, (unsigned long long)first_frame);
         if (preroll_frames && !preroll) return fail(IQGPU_EINVAL, "%s: NULL preroll", who);
@@ -124,8 +127,9 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             const void *d_in = preroll;
             if (!on_device) { rc = stage_host_input(c, preroll, preroll_frames, &d_in); if (rc) return rc; }
             size_t dropped = 0;
-            if (agc_variant) {
+            if (agc_variant || rms) {
                 // nothing of the preroll is kept and the AGC must not see it: the unfused route into abuf, no AGC kernel behind it
+                // (rms: the call's cf32 samples stay in abuf, behind its lead of agc_rms_warm samples, for k_agc_rms_seek below)
                 CallOpts drop = preroll_call; drop.agc = AgcMode::Drop;
                 rc = process_device_impl(c, d_in, preroll_frames, nullptr, 0, &dropped, drop);
             } else {
@@ -146,6 +150,34 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         // (the mirrors the shadow calls have walked forward: the closed form at first_frame -- stated, so that a chain which never cuts
         //  a call, and so never moves them, carries them too)
         if (dcv.agc) agc_mirrors_at(c, first_frame, &c->agc_locked_host, &c->agc_seen_host);
+        if (rms && to.n_out > 0) {
+            // The loop's state at the cut from the samples the preroll has left at abuf + W: stream positions [pos0, cut).  The
+            // trajectory of the chunk that holds sample cut - 1 starts at `start`; the preroll's outputs are the single stream's from
+            // `clean` on (position 0 when it began at frame 0, else the first output behind the frames that refill the FIR memory).
+            const int64_t W = c->agc_rms_warm, cut = (int64_t)to.n_out, pos0 = (int64_t)from.n_out;
+            AgcRmsArgs ra{};
+            int32_t nch = 0;
+            agc_rms_geometry(c->agc_rms_alpha, 0, 0, &ra.chunk, &ra.warm, &nch);
+            const int64_t a0 = (cut - 1) / ra.chunk * ra.chunk - ra.warm, start = a0 > 0 ? a0 : 0;
+            const int64_t clean = (uint64_t)preroll_frames == first_frame ? 0
+                : (int64_t)stream_at(c, first_frame - (uint64_t)preroll_frames + seek_preroll_frames(c, false)).n_out;
+            if (clean > start || pos0 > start || (int64_t)c->abuf.cap < (W + cut - pos0) * (int64_t)sizeof(cf2)) {
+                c->poisoned = true;
+                return fail(IQGPU_EINVAL, "internal: the preroll's outputs [%lld, %lld) (exact from %lld) do not reach back to %lld, where the AGC "
+                    "trajectory in front of frame %llu starts", (long long)pos0, (long long)cut, (long long)clean, (long long)start,
+                    (unsigned long long)first_frame);
+            }
+            ra.x = (const cf2 *)c->abuf.p + W; ra.n = cut - pos0; ra.pos0 = pos0; ra.hist_valid = 0;
+            ra.alpha = c->agc_rms_alpha; ra.state = c->d_agc_state;
+            hipError_t e = launch_agc_rms_seek(ra, c->stream);
+            // the warm-up window of the calls to come: the last W samples in front of the cut (a stream shorter than that: its own
+            // samples, at the end)
+            const int64_t keep = ra.n < W ? ra.n : W;
+            if (e == hipSuccess) e = launch_copy_cf((cf2 *)c->agc_hist.p + (W - keep), ra.x + (ra.n - keep), keep, c->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+            if (e != hipSuccess) { c->poisoned = true; return fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e)); }
+            c->agc_rms_pos = to.n_out;
+        }
     }
     if (agc_variant && entry) {
         // The AGC state of the stream at first_frame, everywhere the chain keeps it: the device state the kernels read, and the host's
@@ -182,6 +214,15 @@ extern "C" int iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame,
                                            const iqgpu_agc_state *entry)
 {
     return seek_impl(c, first_frame, d_preroll, preroll_frames, true, true, entry);
+}
+
+extern "C" int iqgpu_chain_seek_rms(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames)
+{
+    return seek_impl(c, first_frame, preroll, preroll_frames, false, false, nullptr, SeekDc(), true);
+}
+extern "C" int iqgpu_chain_seek_rms_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames)
+{
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, true, false, nullptr, SeekDc(), true);
 }
 
 extern "C" int iqgpu_chain_seek_dc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
