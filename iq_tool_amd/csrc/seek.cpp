@@ -6,10 +6,16 @@
 // iqgpu_chain_seek: the chain at stream frame first_frame -- reset, the closed-form position preroll_frames earlier, and the
 // preroll through the ordinary per-call path with its output dropped (seamless range sharding, iqgpu.h)
 // ------------------------------------------------------------------------------------------------
-// what the v8 / v9 calls ask of a chain: the digital output AGC on the sample clock
-int agc_two_pass_check(const iqgpu_chain *c, const char *who)
+// What the calls of the exact recipes ask of a chain.  kNeedAgc (the v8 / v9 calls): the digital output AGC on the sample clock.
+// kNeedDc (the DC blocker's calls): the blocker -- and, alone, no output AGC.  Both: iqgpu_chain_dcagc_*
+enum : unsigned { kNeedAgc = 1, kNeedDc = 2 };
+static int two_pass_check(const iqgpu_chain *c, const char *who, unsigned needs)
 {
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
+    if ((needs & kNeedDc) && !c->dc) return fail(IQGPU_EINVAL, "%s: the chain has no DC blocker", who);
+    if (needs == kNeedDc && c->agc) return fail(IQGPU_EUNSUPPORTED, "%s: a chain with the output AGC -- its measure route may cut a call into "
+        "other segments than the process route, so the two exact recipes do not combine yet", who);
+    if (!(needs & kNeedAgc)) return IQGPU_OK;
     if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC", who);
     if (c->agc_rms_alpha > 0.0f) return fail(IQGPU_EUNSUPPORTED, "%s: the AGC profiles dx / local carry a per-sample loop state that no "
         "table of per-chunk figures reproduces exactly; only the digital profile is sharded seamlessly", who);
@@ -17,71 +23,77 @@ int agc_two_pass_check(const iqgpu_chain *c, const char *who)
         "position; use IQGPU_AGC_CLOCK_SAMPLES", who);
     return IQGPU_OK;
 }
+int agc_two_pass_check(const iqgpu_chain *c, const char *who) { return two_pass_check(c, who, kNeedAgc); }
 
-// what the exact two-pass calls of DC-blocker chains ask of a chain
-static int dc_two_pass_check(const iqgpu_chain *c, const char *who)
-{
-    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
-    if (!c->dc) return fail(IQGPU_EINVAL, "%s: the chain has no DC blocker", who);
-    if (c->agc) return fail(IQGPU_EUNSUPPORTED, "%s: a chain with the output AGC -- its measure route may cut a call into other segments than "
-        "the process route, so the two exact recipes do not combine yet", who);
-    return IQGPU_OK;
-}
+// Which seek is running, and what it was given beyond the position and the preroll.
+//   Plain  iqgpu_chain_seek: the preroll as ordinary calls, their output into seek_sink
+//   Agc    iqgpu_chain_seek_agc: the preroll with the AGC out of the way, then *agc_entry (or the fresh state) installed
+//   Dc     iqgpu_chain_seek_dc: no warm-up of the DC blocker asked for: *dc_at (or zero) is its state in front of the preroll, which
+//          runs in calls of call_frames (0: one call)
+//   DcAgc  iqgpu_chain_dcagc_seek: both at once: the preroll as SHADOW calls (chain.hpp, AgcMode) from the host mirrors' closed form
+//   Rms    iqgpu_chain_seek_rms: dx / local: the preroll with the AGC out of the way and its cf32 output kept on the device, then the
+//          loop's state at first_frame from k_agc_rms_seek over those samples
+enum class SeekKind { Plain, Agc, Dc, DcAgc, Rms };
+struct SeekRequest {
+    SeekKind kind = SeekKind::Plain;
+    bool on_device = false;                        // the preroll is in device memory
+    const iqgpu_agc_state *agc_entry = nullptr;    // Agc, DcAgc
+    const iqgpu_dc_state *dc_at = nullptr;         // Dc, DcAgc
+    size_t call_frames = 0;                        // Dc, DcAgc
+};
 
-// what the exact calls of chains with the DC blocker AND the digital AGC ask of a chain (iqgpu_chain_dcagc_*)
-static int dcagc_check(const iqgpu_chain *c, const char *who)
+static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, const SeekRequest &rq)
 {
-    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
-    if (!c->dc) return fail(IQGPU_EINVAL, "%s: the chain has no DC blocker", who);
-    return agc_two_pass_check(c, who);
-}
-
-// agc_variant: iqgpu_chain_seek_agc -- the preroll with the AGC out of the way, then *entry (or the fresh state) installed
-// dc_variant: iqgpu_chain_seek_dc -- no warm-up of the DC blocker asked for: *dc_at (or zero) is its state in front of the preroll,
-// which runs in calls of call_frames (0: one call)
-// agc: iqgpu_chain_dcagc_seek -- both at once: the preroll as SHADOW calls (chain.hpp, AgcMode) from the host mirrors' closed form
-struct SeekDc { bool on = false; const iqgpu_dc_state *at = nullptr; size_t call_frames = 0; bool agc = false; };
-// rms: iqgpu_chain_seek_rms -- dx / local: the preroll with the AGC out of the way and its cf32 output kept on the device, then the
-// loop's state at first_frame from k_agc_rms_seek over those samples
-static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, bool on_device,
-                     bool agc_variant = false, const iqgpu_agc_state *entry = nullptr, const SeekDc &dcv = SeekDc(), bool rms = false)
-{
-    const char *who = rms ? "iqgpu_chain_seek_rms" : dcv.agc ? "iqgpu_chain_dcagc_seek" : dcv.on ? "iqgpu_chain_seek_dc" : agc_variant ? "iqgpu_chain_seek_agc" : "iqgpu_chain_seek";
+    // everything that depends on the kind: the entry point's name, what it asks of the chain, and how its preroll runs -- the AGC
+    // stage of the preroll's calls, and whether their output goes to seek_sink (ordinary calls) or nowhere
+    const char *who = "iqgpu_chain_seek";
+    unsigned needs = 0;
+    AgcMode preroll_agc = AgcMode::Ordinary;
+    switch (rq.kind) {
+    case SeekKind::Plain: break;
+    case SeekKind::Agc:   who = "iqgpu_chain_seek_agc";   needs = kNeedAgc;           preroll_agc = AgcMode::Drop;   break;
+    case SeekKind::Dc:    who = "iqgpu_chain_seek_dc";    needs = kNeedDc;                                           break;
+    case SeekKind::DcAgc: who = "iqgpu_chain_dcagc_seek"; needs = kNeedAgc | kNeedDc; preroll_agc = AgcMode::Shadow; break;
+    case SeekKind::Rms:   who = "iqgpu_chain_seek_rms";                               preroll_agc = AgcMode::Drop;   break;
+    }
+    const bool with_agc = needs & kNeedAgc, with_dc = needs & kNeedDc, rms = rq.kind == SeekKind::Rms, shadow = preroll_agc == AgcMode::Shadow;
+    const bool to_sink = preroll_agc == AgcMode::Ordinary;
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
     // what iqgpu_chain_reset does comes first: batches in flight and a pending verdict resolved, histories and dc state zeroed,
     // the poison cleared -- a refused argument below leaves the chain reset
     int rc = iqgpu_chain_reset(c); if (rc) return rc;
     c->fpending = 0;                                          // (reset keeps the FFT remainder queued: a seek starts a stream)
-    if (agc_variant) {
-        rc = dcv.agc ? dcagc_check(c, who) : agc_two_pass_check(c, who); if (rc) return rc;
-        if (entry && (entry->locked != 0 && entry->locked != 1)) return fail(IQGPU_EINVAL, "%s: entry state with locked = %d", who, entry->locked);
+    if (with_agc) {
+        rc = two_pass_check(c, who, needs); if (rc) return rc;
+        const iqgpu_agc_state *e = rq.agc_entry;
+        if (e && (e->locked != 0 && e->locked != 1)) return fail(IQGPU_EINVAL, "%s: entry state with locked = %d", who, e->locked);
     }
     if (rms) { rc = rms_seek_check(c, who); if (rc) return rc; }
     cd2 dc_at{0.0, 0.0};
-    if (dcv.on) {
-        if (!dcv.agc) { rc = dc_two_pass_check(c, who); if (rc) return rc; }
-        if (dcv.at) { dc_at.x = dcv.at->re; dc_at.y = dcv.at->im; }
+    if (with_dc) {
+        if (!with_agc) { rc = two_pass_check(c, who, needs); if (rc) return rc; }
+        if (rq.dc_at) { dc_at.x = rq.dc_at->re; dc_at.y = rq.dc_at->im; }
         if (!std::isfinite(dc_at.x) || !std::isfinite(dc_at.y)) return fail(IQGPU_EINVAL, "%s: the state in front of the preroll is not finite", who);
-        if (dcv.call_frames && preroll_frames % dcv.call_frames != 0) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames is not a whole number "
-            "of calls of %zu frames", who, preroll_frames, dcv.call_frames);
+        if (rq.call_frames && preroll_frames % rq.call_frames != 0) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames is not a whole number "
+            "of calls of %zu frames", who, preroll_frames, rq.call_frames);
         // (the cut of a call is a closed form of the position only on the chunk grid)
-        if (dcv.agc && (first_frame % (uint64_t)c->agc_chunk || dcv.call_frames % (size_t)c->agc_chunk || preroll_frames % (size_t)c->agc_chunk))
+        if (with_agc && (first_frame % (uint64_t)c->agc_chunk || rq.call_frames % (size_t)c->agc_chunk || preroll_frames % (size_t)c->agc_chunk))
             return fail(IQGPU_EINVAL, "%s: first_frame %llu, call_frames %zu and the preroll of %zu frames have to be multiples of "
-                "agc_chunk_frames = %lld", who, (unsigned long long)first_frame, dcv.call_frames, preroll_frames, (long long)c->agc_chunk);
+                "agc_chunk_frames = %lld", who, (unsigned long long)first_frame, rq.call_frames, preroll_frames, (long long)c->agc_chunk);
     }
-    if (first_frame > kMaxStreamFrames) return fail(IQGPU_EINVAL, "%s: frame %llu is beyond 2^39 frames", who,
-        (unsigned long long)first_frame);
+    if (first_frame > kMaxStreamFrames) return fail(IQGPU_EINVAL, "%s: frame %llu is beyond 2^39 frames", who, (unsigned long long)first_frame);
     if ((uint64_t)preroll_frames > first_frame) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames would start in front of "
         "frame 0 (first_frame %llu)", who, preroll_frames, (unsigned long long)first_frame);
     if (first_frame > 0) {
-        if (c->agc && !agc_variant && !rms) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
+        // (Dc never gets here with an AGC: its check above has refused the chain)
+        if (c->agc && !with_agc && !rms) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
             "not on a bounded warm-up");
-        const uint64_t memory = rms ? seek_rms_preroll_frames(c) : seek_preroll_frames(c, !dcv.on), need = first_frame < memory ? first_frame : memory;
+        const uint64_t memory = rms ? seek_rms_preroll_frames(c) : seek_preroll_frames(c, !with_dc), need = first_frame < memory ? first_frame : memory;
         if ((uint64_t)preroll_frames < need) return fail(IQGPU_EINVAL, "%s: preroll of %zu frames is shorter than the %llu "
             "this chain needs at frame %llu", who, preroll_frames, (unsigned long long)need, (unsigned long long)first_frame);
         if (preroll_frames && !preroll) return fail(IQGPU_EINVAL, "%s: NULL preroll", who);
     }
-    if (dcv.on) {
+    if (with_dc) {
         // the blocker's state in front of the preroll (at frame 0: of the stream), where the reset has left zero -- behind every
         // refusal, so that a refused call leaves the chain reset
         HIP_TRY(hipMemcpyAsync(c->d_dc_state, &dc_at, sizeof(cd2), hipMemcpyHostToDevice, c->stream));
@@ -99,43 +111,22 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         c->nco_theta = from.nco_theta; c->pnco_theta = from.pnco_theta;
         // (the preroll lies in front of the range the caller asked for: the I/Q probe takes no block from it and keeps its slot free
         //  for the head of the first call behind the seek)
-        CallOpts preroll_call; preroll_call.no_probe = true;
-        if (dcv.agc) {
-            // shadow calls: cut as the single stream's calls are, from the mirrors the single stream has in front of the preroll
-            preroll_call.agc = AgcMode::Shadow;
-            agc_mirrors_at(c, first_frame - (uint64_t)preroll_frames, &c->agc_locked_host, &c->agc_seen_host);
-        }
+        // Drop: nothing of the preroll is kept and the AGC must not see it: the unfused route into abuf, no AGC kernel behind it
+        // (rms: the call's cf32 samples stay in abuf, behind its lead of agc_rms_warm samples, for k_agc_rms_seek below).
+        // Shadow: cut as the single stream's calls are, from the mirrors the single stream has in front of the preroll
+        CallOpts preroll_call; preroll_call.no_probe = true; preroll_call.agc = preroll_agc;
+        if (shadow) agc_mirrors_at(c, first_frame - (uint64_t)preroll_frames, &c->agc_locked_host, &c->agc_seen_host);
 
-        if (dcv.on) {
-            // the preroll runs in the single stream's own calls -- every one staged like a call of iqgpu_chain_process -- from the
-            // single stream's own state
-            const size_t obps = bytes_per_frame(c->desc.out_format), ibps = bytes_per_frame(c->desc.in_format);
-            const size_t per = dcv.call_frames ? dcv.call_frames : preroll_frames;
-            for (size_t at = 0; at < preroll_frames; at += per) {
-                const void *src = (const char *)preroll + at * ibps, *d_in = src;
-                if (!on_device) { rc = stage_host_input(c, src, per, &d_in); if (rc) return rc; }
-                size_t dropped = 0;
-                if (dcv.agc) rc = process_device_impl(c, d_in, per, nullptr, 0, &dropped, preroll_call);
-                else {
-                    rc = c->seek_sink.ensure((size_t)plan_call(c, per).n_emit * obps + 16); if (rc) return rc;
-                    rc = process_device_impl(c, d_in, per, c->seek_sink.p, c->seek_sink.cap, &dropped, preroll_call);
-                }
-                if (rc) return rc;
-            }
-        } else if (preroll_frames) {
-            const size_t obps = bytes_per_frame(c->desc.out_format);
-            const void *d_in = preroll;
-            if (!on_device) { rc = stage_host_input(c, preroll, preroll_frames, &d_in); if (rc) return rc; }
+        // with call_frames the preroll runs in the single stream's own calls -- every one staged like a call of iqgpu_chain_process --
+        // from the single stream's own state; otherwise in one call.  No frames: no call
+        const size_t obps = bytes_per_frame(c->desc.out_format), ibps = bytes_per_frame(c->desc.in_format);
+        const size_t per = with_dc && rq.call_frames ? rq.call_frames : preroll_frames;
+        for (size_t at = 0; at < preroll_frames; at += per) {
+            const void *src = (const char *)preroll + at * ibps, *d_in = src;
+            if (!rq.on_device) { rc = stage_host_input(c, src, per, &d_in); if (rc) return rc; }
             size_t dropped = 0;
-            if (agc_variant || rms) {
-                // nothing of the preroll is kept and the AGC must not see it: the unfused route into abuf, no AGC kernel behind it
-                // (rms: the call's cf32 samples stay in abuf, behind its lead of agc_rms_warm samples, for k_agc_rms_seek below)
-                CallOpts drop = preroll_call; drop.agc = AgcMode::Drop;
-                rc = process_device_impl(c, d_in, preroll_frames, nullptr, 0, &dropped, drop);
-            } else {
-                rc = c->seek_sink.ensure((size_t)plan_call(c, preroll_frames).n_emit * obps + 16); if (rc) return rc;
-                rc = process_device_impl(c, d_in, preroll_frames, c->seek_sink.p, c->seek_sink.cap, &dropped, preroll_call);
-            }
+            if (to_sink) { rc = c->seek_sink.ensure((size_t)plan_call(c, per).n_emit * obps + 16); if (rc) return rc; }
+            rc = process_device_impl(c, d_in, per, to_sink ? c->seek_sink.p : nullptr, to_sink ? c->seek_sink.cap : 0, &dropped, preroll_call);
             if (rc) return rc;
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -149,7 +140,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         c->total_in = first_frame; c->total_out = to.n_out;       // (iqgpu_chain_tell: of the stream, not of the preroll)
         // (the mirrors the shadow calls have walked forward: the closed form at first_frame -- stated, so that a chain which never cuts
         //  a call, and so never moves them, carries them too)
-        if (dcv.agc) agc_mirrors_at(c, first_frame, &c->agc_locked_host, &c->agc_seen_host);
+        if (shadow) agc_mirrors_at(c, first_frame, &c->agc_locked_host, &c->agc_seen_host);
         if (rms && to.n_out > 0) {
             // The loop's state at the cut from the samples the preroll has left at abuf + W: stream positions [pos0, cut).  The
             // trajectory of the chunk that holds sample cut - 1 starts at `start`; the preroll's outputs are the single stream's from
@@ -179,7 +170,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             c->agc_rms_pos = to.n_out;
         }
     }
-    if (agc_variant && entry) {
+    if (with_agc && rq.agc_entry) {
         // The AGC state of the stream at first_frame, everywhere the chain keeps it: the device state the kernels read, and the host's
         // mirrors of "has the stream locked" and of samples_seen, from which the fused / unfused split of every later call follows
         // (agc_unfused_head).  The reset above has left the rest as on a chain that arrived here by processing: no pending verdict,
@@ -187,7 +178,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         // dirty so that the first fused launch clears it.
         static_assert(sizeof(iqgpu_agc_state) == sizeof(AgcState), "AGC state layout");
         AgcState st;
-        memcpy(&st, entry, sizeof(st));
+        memcpy(&st, rq.agc_entry, sizeof(st));
         st.reserved = 0;
         HIP_TRY(hipMemcpyAsync(c->d_agc_state, &st, sizeof(AgcState), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -199,52 +190,61 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
 
 extern "C" int iqgpu_chain_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames)
 {
-    return seek_impl(c, first_frame, preroll, preroll_frames, false);
+    SeekRequest rq; rq.kind = SeekKind::Plain;
+    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
 }
 extern "C" int iqgpu_chain_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames)
 {
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, true);
+    SeekRequest rq; rq.kind = SeekKind::Plain; rq.on_device = true;
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
 }
-extern "C" int iqgpu_chain_seek_agc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames,
-                                    const iqgpu_agc_state *entry)
+extern "C" int iqgpu_chain_seek_agc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, const iqgpu_agc_state *entry)
 {
-    return seek_impl(c, first_frame, preroll, preroll_frames, false, true, entry);
+    SeekRequest rq; rq.kind = SeekKind::Agc; rq.agc_entry = entry;
+    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
 }
 extern "C" int iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
                                            const iqgpu_agc_state *entry)
 {
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, true, true, entry);
+    SeekRequest rq; rq.kind = SeekKind::Agc; rq.on_device = true; rq.agc_entry = entry;
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
 }
 
 extern "C" int iqgpu_chain_seek_rms(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames)
 {
-    return seek_impl(c, first_frame, preroll, preroll_frames, false, false, nullptr, SeekDc(), true);
+    SeekRequest rq; rq.kind = SeekKind::Rms;
+    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
 }
 extern "C" int iqgpu_chain_seek_rms_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames)
 {
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, true, false, nullptr, SeekDc(), true);
+    SeekRequest rq; rq.kind = SeekKind::Rms; rq.on_device = true;
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
 }
 
 extern "C" int iqgpu_chain_seek_dc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
                                    const iqgpu_dc_state *at_preroll_start)
 {
-    return seek_impl(c, first_frame, preroll, preroll_frames, false, false, nullptr, SeekDc{true, at_preroll_start, call_frames});
+    SeekRequest rq; rq.kind = SeekKind::Dc; rq.dc_at = at_preroll_start; rq.call_frames = call_frames;
+    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
 }
 extern "C" int iqgpu_chain_seek_dc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
                                           size_t call_frames, const iqgpu_dc_state *at_preroll_start)
 {
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, true, false, nullptr, SeekDc{true, at_preroll_start, call_frames});
+    SeekRequest rq; rq.kind = SeekKind::Dc; rq.on_device = true; rq.dc_at = at_preroll_start; rq.call_frames = call_frames;
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
 }
 
 extern "C" int iqgpu_chain_dcagc_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
                                       const iqgpu_dc_state *dc_at_preroll_start, const iqgpu_agc_state *agc_entry)
 {
-    return seek_impl(c, first_frame, preroll, preroll_frames, false, true, agc_entry, SeekDc{true, dc_at_preroll_start, call_frames, true});
+    SeekRequest rq; rq.kind = SeekKind::DcAgc; rq.agc_entry = agc_entry; rq.dc_at = dc_at_preroll_start; rq.call_frames = call_frames;
+    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
 }
 extern "C" int iqgpu_chain_dcagc_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
                                              size_t call_frames, const iqgpu_dc_state *dc_at_preroll_start, const iqgpu_agc_state *agc_entry)
 {
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, true, true, agc_entry, SeekDc{true, dc_at_preroll_start, call_frames, true});
+    SeekRequest rq; rq.kind = SeekKind::DcAgc; rq.on_device = true; rq.agc_entry = agc_entry; rq.dc_at = dc_at_preroll_start; rq.call_frames = call_frames;
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -253,7 +253,7 @@ extern "C" int iqgpu_chain_dcagc_seek_device(iqgpu_chain *c, uint64_t first_fram
 static int dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const void *in, size_t frames_in, iqgpu_dc_row *row, bool on_device)
 {
     const char *who = "iqgpu_chain_dc_measure";
-    int rc = dc_two_pass_check(c, who); if (rc) return rc;
+    int rc = two_pass_check(c, who, kNeedDc); if (rc) return rc;
     if (!row) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     if (first_frame > kMaxStreamFrames || (uint64_t)frames_in > kMaxStreamFrames - first_frame) return fail(IQGPU_EINVAL, "%s: stream position "
         "%llu + %zu frames is beyond 2^39 frames", who, (unsigned long long)first_frame, frames_in);
@@ -289,7 +289,7 @@ static int dc_advance_impl(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_ro
 {
     static_assert(sizeof(iqgpu_dc_row) == sizeof(DcMapRow) && sizeof(DcMapRow) == 32 && sizeof(iqgpu_dc_state) == sizeof(cd2), "DC row layout");
     const char *who = dcagc ? "iqgpu_chain_dcagc_dc_advance" : "iqgpu_chain_dc_advance";
-    int rc = dcagc ? dcagc_check(c, who) : dc_two_pass_check(c, who); if (rc) return rc;
+    int rc = two_pass_check(c, who, dcagc ? kNeedDc | kNeedAgc : kNeedDc); if (rc) return rc;
     if (!st || (n && !rows)) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     if (!std::isfinite(st->re) || !std::isfinite(st->im)) return fail(IQGPU_EINVAL, "%s: the state is not finite", who);
     for (size_t i = 0; i < n; ++i)
@@ -335,7 +335,7 @@ static int dcagc_dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const voi
                                  size_t *n_rows, bool on_device)
 {
     const char *who = "iqgpu_chain_dcagc_dc_measure";
-    int rc = dcagc_check(c, who); if (rc) return rc;
+    int rc = two_pass_check(c, who, kNeedDc | kNeedAgc); if (rc) return rc;
     if (!rows || !n_rows) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     *n_rows = 0;
     if (cap < 2) return fail(IQGPU_EINVAL, "%s: the table holds %zu rows, a call can be two pieces", who, cap);
@@ -407,7 +407,7 @@ static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_
 {
     static_assert(sizeof(iqgpu_agc_chunk) == sizeof(AgcRow) && sizeof(AgcRow) == 16, "AGC row layout");
     const char *who = shadow ? "iqgpu_chain_dcagc_measure" : "iqgpu_chain_measure";
-    int rc = shadow ? dcagc_check(c, who) : agc_two_pass_check(c, who); if (rc) return rc;
+    int rc = two_pass_check(c, who, shadow ? kNeedDc | kNeedAgc : kNeedAgc); if (rc) return rc;
     if (!n_rows) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     *n_rows = 0;
     if (frames_in == 0) return IQGPU_OK;
@@ -464,7 +464,7 @@ extern "C" int iqgpu_chain_agc_initial_state(const iqgpu_chain *c, iqgpu_agc_sta
 // can hold 2^25 rows).  The kernel carries its state from launch to launch exactly as from call to call.
 extern "C" int iqgpu_chain_agc_advance(iqgpu_chain *c, iqgpu_agc_state *st, const iqgpu_agc_chunk *rows, size_t n, float *gains)
 {
-    int rc = agc_two_pass_check(c, "iqgpu_chain_agc_advance"); if (rc) return rc;
+    int rc = two_pass_check(c, "iqgpu_chain_agc_advance", kNeedAgc); if (rc) return rc;
     if (!st || (n && !rows)) return fail(IQGPU_EINVAL, "iqgpu_chain_agc_advance: NULL argument");
     if (n == 0) return IQGPU_OK;
     // (k_agc_scan adds the lengths of the 64 rows of a batch in 32 bits: the bound chain_create puts on agc_chunk_frames, here on

@@ -227,7 +227,7 @@ extern "C" int iqgpu_chain_load_state(iqgpu_chain *c, const void *blob, size_t b
     LOAD_TRY(hipMemcpyAsync(c->d_dc_state, &dc0, sizeof(cd2), hipMemcpyHostToDevice, c->stream));
     c->agc_locked_host = false; c->agc_seen_host = 0; c->agc_peak_clean = false; c->agc_rms_pos = 0;
     if (c->agc) {
-        // the AGC state everywhere the chain keeps it (seek_impl's agc_variant branch): the device state, the host's mirrors; the
+        // the AGC state everywhere the chain keeps it (as seek_impl does with an agc_entry): the device state, the host's mirrors; the
         // verifier's words at their initial values, no pending verdict, the peak array marked dirty
         LOAD_TRY(hipMemcpyAsync(c->d_agc_state, &w.agc, sizeof(AgcState), hipMemcpyHostToDevice, c->stream));
         LOAD_TRY(hipMemcpyAsync(c->d_agc_flag, kAgcFlagInit, sizeof(kAgcFlagInit), hipMemcpyHostToDevice, c->stream));
