@@ -100,24 +100,29 @@ int cascade2_wave_lds(int K, int in_fmt)
     return 0;
 }
 
+// the compiled set of k_cascade2<KT, BPF, S8>: two to four stages, cu8 / cs8 (S8) / 16-bit frames
+constexpr bool casc2_compiled(int KT, int BPF, bool S8) { return KT >= 2 && KT <= 4 && (BPF == 2 || (BPF == 4 && !S8)); }
+
 // the chain shape: cu8 / cs8 / cs16 / sc16q11 frames with nothing between the unpack and stage 0, two to four stages of liquid's lengths
-bool cascade2_shape(const FrontArgs &a)
+Casc2Sel cascade2_select(const FrontArgs &a)
 {
-    if (casc2_bpf(a.in_fmt) == 0 || a.gain != 1.0f || a.dc_enable || a.iq_enable || a.nco_mode != 0) return false;
-    if (a.dbg & (kDbgNoRaw0 | kDbgNoKT | kDbgNoCasc2)) return false;
-    if (a.casc_K < 2 || a.casc_K > 4) return false;
-    for (int k = 0; k < a.casc_K; ++k) if (a.m[k] != (k == a.casc_K - 1 ? 5 : 3)) return false;
-    return true;
+    Casc2Sel k{};
+    k.KT = a.casc_K; k.BPF = casc2_bpf(a.in_fmt); k.S8 = a.in_fmt == IQGPU_FMT_CS8;
+    if (a.gain != 1.0f || a.dc_enable || a.iq_enable || a.nco_mode != 0 || (a.dbg & (kDbgNoRaw0 | kDbgNoKT | kDbgNoCasc2)) || !casc2_compiled(k.KT, k.BPF, k.S8)) return k;
+    for (int q = 0; q < a.casc_K; ++q) if (a.m[q] != (q == a.casc_K - 1 ? 5 : 3)) return k;
+    k.ok = true;
+    return k;
 }
 
 // ... and the call: streaming runs of two tiles and more, the tile in front of the first run's warm-up loadable, the slice sized for both layouts
-bool cascade2_applies(const FrontArgs &a, int min_run)
+Casc2Sel cascade2_select(const FrontArgs &a, int min_run)
 {
     // (min_run > 0: the chain's iqgpu_debug_set("casc2_min_run", n) -- where the two-tile trips start to pay, tools/gpu/r5_casc2_min.py)
     if (min_run <= 0) min_run = kCasc2MinRun;
-    if (!cascade2_shape(a) || a.w_n_stream <= 0 || a.w_run_q < min_run) return false;
-    if ((a.w_edge_ta - a.w_warm_tiles - 1) * (int64_t)kWTile - a.rem0 < 0) return false;
-    return a.casc_wave_lds >= cascade2_wave_lds(a.casc_K, a.in_fmt);
+    Casc2Sel k = cascade2_select(a);
+    k.ok = k.ok && a.w_n_stream > 0 && a.w_run_q >= min_run && (a.w_edge_ta - a.w_warm_tiles - 1) * (int64_t)kWTile - a.rem0 >= 0 &&
+           a.casc_wave_lds >= cascade2_wave_lds(a.casc_K, a.in_fmt);
+    return k;
 }
 
 template <int KT, int BPF, bool S8>
@@ -282,34 +287,19 @@ __global__ __launch_bounds__((Casc2<KT, BPF>::WAVES * 64)) void k_cascade2(const
 
 hipError_t launch_cascade2(const FrontArgs &a, int min_run, hipStream_t s)
 {
-    if (!cascade2_applies(a, min_run)) return hipErrorInvalidValue;
+    const Casc2Sel k = cascade2_select(a, min_run);
+    if (!k.ok) return hipErrorInvalidValue;
     const int waves = cascade_waves(a);
     const size_t lds = (size_t)waves * a.casc_wave_lds;
     const int64_t n_items = a.w_n_edge + a.w_n_stream;
     const unsigned grid = (unsigned)((n_items + waves - 1) / waves);
     if (grid == 0) return hipSuccess;
-#define IQGPU_LAUNCH_CASC2(KT, BPF, S8)                                                                                \
-    do {                                                                                                              \
-        static LdsAttrCache cache;                                                                                    \
-        if (waves > Casc2<KT, BPF>::WAVES) return hipErrorInvalidValue;                                               \
-        { const hipError_t e = cache.ensure((const void *)k_cascade2<KT, BPF, S8>, lds); if (e != hipSuccess) return e; } \
-        hipLaunchKernelGGL((k_cascade2<KT, BPF, S8>), dim3(grid), dim3(waves * 64), lds, s, a);                       \
-    } while (0)
-    if (a.in_fmt == IQGPU_FMT_CS8) {
-        if (a.casc_K == 2) IQGPU_LAUNCH_CASC2(2, 2, true);
-        else if (a.casc_K == 3) IQGPU_LAUNCH_CASC2(3, 2, true);
-        else IQGPU_LAUNCH_CASC2(4, 2, true);
-    } else if (casc2_bpf(a.in_fmt) == 2) {
-        if (a.casc_K == 2) IQGPU_LAUNCH_CASC2(2, 2, false);
-        else if (a.casc_K == 3) IQGPU_LAUNCH_CASC2(3, 2, false);
-        else IQGPU_LAUNCH_CASC2(4, 2, false);
-    } else {
-        if (a.casc_K == 2) IQGPU_LAUNCH_CASC2(2, 4, false);
-        else if (a.casc_K == 3) IQGPU_LAUNCH_CASC2(3, 4, false);
-        else IQGPU_LAUNCH_CASC2(4, 4, false);
-    }
-#undef IQGPU_LAUNCH_CASC2
-    return hipGetLastError();
+    return dispatch_int<2, 3, 4>(k.KT, [&](auto KT) { return dispatch_int<2, 4>(k.BPF, [&](auto BPF) { return dispatch_bool(k.S8, [&](auto S8) {
+        if constexpr (casc2_compiled(KT.value, BPF.value, S8.value)) {
+            if (waves > Casc2<KT.value, BPF.value>::WAVES) return hipErrorInvalidValue;
+            return launch_inst<k_cascade2<KT.value, BPF.value, S8.value>>(grid, waves * 64, lds, s, a);
+        } else return hipErrorInvalidValue;
+    }); }); });
 }
 
 } // namespace iqgpu

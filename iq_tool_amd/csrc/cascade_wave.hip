@@ -110,6 +110,26 @@ int cascade_waves(const FrontArgs &a)
     return w > cap ? cap : (w < 4 ? 4 : w);
 }
 
+// the compiled set of k_cascade<BPS, RAW0, KT>: per frame size the general stage loop (KT = 0) and liquid's 60 dB chains of one to
+// four stages; cu8 frames kept raw in LDS (RAW0) likewise; formats without a vector path (BPS = 0) the general loop only
+constexpr bool casc_compiled(int BPS, bool RAW0, int KT)
+{
+    return KT >= 0 && KT <= 4 && (BPS == 0 ? (!RAW0 && KT == 0) : RAW0 ? BPS == 2 : (BPS == 2 || BPS == 4 || BPS == 8));
+}
+
+CascSel cascade_select(const FrontArgs &a)
+{
+    CascSel k{};
+    k.BPS = frame_bytes_class(a.in_fmt);
+    // cu8 frames with nothing between the unpack and stage 0: the streaming waves keep them raw in LDS (casc_stage_raw8)
+    k.RAW0 = a.in_fmt == IQGPU_FMT_CU8 && a.gain == 1.0f && !a.dc_enable && !a.iq_enable && a.nco_mode == 0 && !(a.dbg & kDbgNoRaw0);
+    // liquid's 60 dB semi-lengths (3 .. 3 5): stage count and lengths resolved at compile time (casc_tiles, KT)
+    k.KT = (k.BPS == 0 || (a.dbg & kDbgNoKT) || a.casc_K < 1 || a.casc_K > 4) ? 0 : a.casc_K;
+    for (int q = 0; q < a.casc_K && q < kCascMaxK; ++q) if (a.m[q] != (q == a.casc_K - 1 ? 5 : 3)) k.KT = 0;
+    k.ok = casc_compiled(k.BPS, k.RAW0, k.KT);
+    return k;
+}
+
 hipError_t launch_cascade(const FrontArgs &a, int casc2_min_run, hipStream_t s)
 {
     if (cascade2_applies(a, casc2_min_run)) return launch_cascade2(a, casc2_min_run, s);
@@ -118,39 +138,11 @@ hipError_t launch_cascade(const FrontArgs &a, int casc2_min_run, hipStream_t s)
     const int64_t n_items = a.w_n_edge + a.w_n_stream;
     const unsigned grid = (unsigned)((n_items + waves - 1) / waves);
     if (grid == 0) return hipSuccess;
-    int cls;
-    switch (a.in_fmt) {
-    case IQGPU_FMT_CS8: case IQGPU_FMT_CU8: cls = 2; break;
-    case IQGPU_FMT_CS16: case IQGPU_FMT_CU16: case IQGPU_FMT_SC16Q11: cls = 4; break;
-    case IQGPU_FMT_CF32: cls = 8; break;
-    default: cls = 0; break;
-    }
-#define IQGPU_LAUNCH_CASC(...)                                                                                         \
-    do {                                                                                                              \
-        static LdsAttrCache cache;                /* per instantiation */                                          \
-        { const hipError_t e = cache.ensure((const void *)k_cascade<__VA_ARGS__>, lds); if (e != hipSuccess) return e; } \
-        hipLaunchKernelGGL((k_cascade<__VA_ARGS__>), dim3(grid), dim3(waves * 64), lds, s, a);                        \
-    } while (0)
-    // cu8 frames with nothing between the unpack and stage 0: the streaming waves keep them raw in LDS (casc_stage_raw8)
-    const bool raw0 = a.in_fmt == IQGPU_FMT_CU8 && a.gain == 1.0f && !a.dc_enable && !a.iq_enable && a.nco_mode == 0 && !(a.dbg & kDbgNoRaw0);
-    // liquid's 60 dB semi-lengths (3 .. 3 5): stage count and lengths resolved at compile time (casc_tiles, KT)
-    int kt = a.casc_K;
-    for (int k = 0; k < a.casc_K; ++k) if (a.m[k] != (k == a.casc_K - 1 ? 5 : 3)) kt = 0;
-    if (a.dbg & kDbgNoKT) kt = 0;
-#define IQGPU_LAUNCH_CASC_KT(BPS, RAW)                                                                                \
-    do {                                                                                                              \
-        if (kt == 1) IQGPU_LAUNCH_CASC(BPS, RAW, 1); else if (kt == 2) IQGPU_LAUNCH_CASC(BPS, RAW, 2);               \
-        else if (kt == 3) IQGPU_LAUNCH_CASC(BPS, RAW, 3); else if (kt == 4) IQGPU_LAUNCH_CASC(BPS, RAW, 4);          \
-        else IQGPU_LAUNCH_CASC(BPS, RAW, 0);                                                                          \
-    } while (0)
-    if (raw0) IQGPU_LAUNCH_CASC_KT(2, true);
-    else if (cls == 2) IQGPU_LAUNCH_CASC_KT(2, false);
-    else if (cls == 4) IQGPU_LAUNCH_CASC_KT(4, false);
-    else if (cls == 8) IQGPU_LAUNCH_CASC_KT(8, false);
-    else IQGPU_LAUNCH_CASC(0);
-#undef IQGPU_LAUNCH_CASC_KT
-#undef IQGPU_LAUNCH_CASC
-    return hipGetLastError();
+    const CascSel k = cascade_select(a);
+    return dispatch_int<0, 2, 4, 8>(k.BPS, [&](auto BPS) { return dispatch_bool(k.RAW0, [&](auto RAW0) { return dispatch_int<0, 1, 2, 3, 4>(k.KT, [&](auto KT) {
+        if constexpr (casc_compiled(BPS.value, RAW0.value, KT.value)) return launch_inst<k_cascade<BPS.value, RAW0.value, KT.value>>(grid, waves * 64, lds, s, a);
+        else return hipErrorInvalidValue;
+    }); }); });
 }
 
 } // namespace iqgpu

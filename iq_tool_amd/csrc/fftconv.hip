@@ -14,6 +14,7 @@
 // Twiddles come from an N-entry table in global memory (L2-resident; double-precision values
 // rounded to float -- v_sin/v_cos are not accurate enough for the 1e-5 budget).
 #include "fft16.hpp"
+#include "front_p0_common.hpp"
 
 namespace iqgpu {
 
@@ -195,20 +196,16 @@ bool fftconv_agc_fusable(int log2n, int ntaps, uint32_t dbg)
     return log2n >= 10 && (1 << log2n) <= kMaxFftN && (1 << log2n) > ntaps - 1 && !(dbg & (kDbgFftNoR16 | kDbgAgcNoFuse));
 }
 
-template <int LOG2N>
-static hipError_t launch_fftconv16(const FftConvArgs &a, unsigned nb, size_t lds, hipStream_t s)
+// the compiled set of k_fftconv16<LOG2N, LOOP>: N = 1024 .. 16384, one block per workgroup or (LOOP) a walk over the blocks
+constexpr bool fftconv16_compiled(int LOG2N, bool LOOP) { return LOG2N >= 10 && LOG2N <= 14; }
+
+// which launches take the radix-16 kernel (LOOP: the conditional fallback behind a fused launch); the others the radix-4 k_fftconv
+FftSel fftconv16_select(const FftConvArgs &a)
 {
-    static LdsAttrCache cache16, cache16l;
-    if (a.run_if) {
-        // the conditional fallback: about four rounds of resident workgroups, each walking its share of the blocks
-        const unsigned cap = 256u * 16u * 1024u / (unsigned)(1 << LOG2N) * 4u;
-        if (lds > 64 * 1024) { const hipError_t e = cache16l.ensure((const void *)k_fftconv16<LOG2N, true>, lds); if (e != hipSuccess) return e; }
-        hipLaunchKernelGGL((k_fftconv16<LOG2N, true>), dim3(nb < cap ? nb : cap), dim3((1 << LOG2N) / 16), lds, s, a);
-        return hipGetLastError();
-    }
-    if (lds > 64 * 1024) { const hipError_t e = cache16.ensure((const void *)k_fftconv16<LOG2N>, lds); if (e != hipSuccess) return e; }
-    hipLaunchKernelGGL(k_fftconv16<LOG2N>, dim3(nb), dim3((1 << LOG2N) / 16), lds, s, a);
-    return hipGetLastError();
+    FftSel k{};
+    k.LOG2N = a.log2n; k.LOOP = a.run_if != nullptr;
+    k.ok = !(a.dbg & kDbgFftNoR16) && fftconv16_compiled(k.LOG2N, k.LOOP);
+    return k;
 }
 
 bool p0fft_geometry(int log2n, int ntaps, int *win, int *vout)
@@ -231,6 +228,15 @@ bool p0fft_shape(const FrontArgs &front, int log2n, int ntaps)
     return front_p0_shape(fa) && p0fft_geometry(log2n, ntaps, &w, &v);
 }
 
+// the instantiation of k_p0fft16 for a fused launch: the transform, the input format (one translation unit each), the step class
+P0FftSel p0fft_select(const FftConvArgs &a)
+{
+    P0FftSel k{};
+    k.LOG2N = a.log2n; k.FMT = a.feed.in_fmt;
+    k.ok = p0_class(a.feed.step, &k.L3, &k.L4, &k.L2) && p0fft_compiled(k.LOG2N, k.FMT, k.L3, k.L4, k.L2);
+    return k;
+}
+
 // the fused launch: every operand shape the kernel and its grid assume is checked HERE, on the host
 static hipError_t launch_p0fft(const FftConvArgs &a, hipStream_t s)
 {
@@ -243,44 +249,38 @@ static hipError_t launch_p0fft(const FftConvArgs &a, hipStream_t s)
     if (a.n_emit == 0 && !f.write_state) return hipSuccess;
     const int N = 1 << a.log2n;
     const size_t lds = (size_t)(((N + (N >> 5) + 2) * 8 + 15) / 16 * 16) + p0fft_tap_lds() + (a.pnco_mode != 0 ? 1024 * sizeof(cf2) : 0);
-    if (f.in_fmt == IQGPU_FMT_CU8) return launch_p0fft_cu8(a, lds, s);
-    if (f.in_fmt == IQGPU_FMT_CS8) return launch_p0fft_cs8(a, lds, s);
-    if (f.in_fmt == IQGPU_FMT_CS16) return launch_p0fft_cs16(a, lds, s);
-    return hipErrorInvalidValue;
+    const P0FftSel k = p0fft_select(a);
+    if (!k.ok) return hipErrorInvalidValue;
+    return k.FMT == IQGPU_FMT_CU8 ? launch_p0fft_cu8(a, lds, s) : k.FMT == IQGPU_FMT_CS8 ? launch_p0fft_cs8(a, lds, s) : launch_p0fft_cs16(a, lds, s);
 }
 
 hipError_t launch_fftconv(const FftConvArgs &a, hipStream_t s)
 {
     if (a.feed.raw) return launch_p0fft(a, s);
-    if ((a.win > 0 || a.vout > 0) && !(a.log2n >= 10 && !(a.dbg & kDbgFftNoR16) && a.win >= a.ntaps && a.win <= (1 << a.log2n) && a.vout >= 1
-        && a.vout <= a.win - (a.ntaps - 1))) return hipErrorInvalidValue;
-    if ((a.agc_fused || a.run_if) && !(a.log2n >= 10 && !(a.dbg & kDbgFftNoR16))) return hipErrorInvalidValue;   // (the radix-16 kernel only)
-    if (a.n_emit > 0 && a.log2n >= 10 && !(a.dbg & kDbgFftNoR16)) {
+    const FftSel k = fftconv16_select(a);
+    const bool r16 = a.log2n >= 10 && !(a.dbg & kDbgFftNoR16);       // (k.ok, or a transform longer than the radix-16 kernel's: an error below)
+    if ((a.win > 0 || a.vout > 0) && !(r16 && a.win >= a.ntaps && a.win <= (1 << a.log2n) && a.vout >= 1 && a.vout <= a.win - (a.ntaps - 1))) return hipErrorInvalidValue;
+    if ((a.agc_fused || a.run_if) && !r16) return hipErrorInvalidValue;   // (the radix-16 kernel only)
+    if (a.n_emit > 0 && r16) {
         const int N = 1 << a.log2n, V = a.vout > 0 ? a.vout : N - (a.ntaps - 1);
-        if (V <= 0 || N > kMaxFftN) return hipErrorInvalidValue;
+        if (V <= 0 || N > kMaxFftN || !k.ok) return hipErrorInvalidValue;
         const unsigned nb = (unsigned)((a.n_emit + V - 1) / V);
         const size_t lds = (size_t)(N + (N >> 5) + 2) * sizeof(cf2) + (a.pnco_mode != 0 ? 1024 * sizeof(cf2) : 0);
-        switch (a.log2n) {
-        case 10: return launch_fftconv16<10>(a, nb, lds, s);
-        case 11: return launch_fftconv16<11>(a, nb, lds, s);
-        case 12: return launch_fftconv16<12>(a, nb, lds, s);
-        case 13: return launch_fftconv16<13>(a, nb, lds, s);
-        case 14: return launch_fftconv16<14>(a, nb, lds, s);
-        default: return hipErrorInvalidValue;
-        }
+        // (LOOP, the conditional fallback: about four rounds of resident workgroups, each walking its share of the blocks)
+        const unsigned cap = 256u * 16u * 1024u / (unsigned)N * 4u, grid = k.LOOP && cap < nb ? cap : nb;
+        return dispatch_int<10, 11, 12, 13, 14>(k.LOG2N, [&](auto LOG2N) { return dispatch_bool(k.LOOP, [&](auto LOOP) {
+            return launch_inst<k_fftconv16<LOG2N.value, LOOP.value>>(grid, (unsigned)N / 16, lds, s, a, lds > 64 * 1024);
+        }); });
     }
     if (a.n_emit <= 0) return hipSuccess;
     const int N = 1 << a.log2n, V = N - (a.ntaps - 1);
     if (V <= 0 || N > kMaxFftN4) return hipErrorInvalidValue;
     const unsigned nb = (unsigned)((a.n_emit + V - 1) / V);
     const size_t lds = (size_t)2 * (N + (N >> 5) + 2) * sizeof(cf2) + (a.pnco_mode != 0 ? 1024 * sizeof(cf2) : 0);
-    static LdsAttrCache cache;
-    if (lds > 64 * 1024) { const hipError_t e = cache.ensure((const void *)k_fftconv, lds); if (e != hipSuccess) return e; }
     int nthr = a.threads > 0 ? a.threads : (N >= 8192 ? 1024 : (N >= 4096 ? 512 : 256));
     if (nthr > kFftMaxThreads) nthr = kFftMaxThreads;
     while (nthr * kFftMaxB < (N >> 2)) nthr *= 2;                   // at most kFftMaxB radix-4 butterflies per thread
-    hipLaunchKernelGGL(k_fftconv, dim3(nb), dim3(nthr), lds, s, a);
-    return hipGetLastError();
+    return launch_inst<k_fftconv>(nb, (unsigned)nthr, lds, s, a, lds > 64 * 1024);
 }
 
 } // namespace iqgpu

@@ -334,51 +334,35 @@ __global__ __launch_bounds__(kFatThreads) void k_front_fat(const FrontArgs a)
     }
 }
 
-// step class of the five-slot polyphase: 1.6 <= s < 2 (a lane's 8 samples hold 4 or 5 outputs), lo_3 = floor(3 s), lo_4 = floor(4 s)
-static int fat_step_class(uint32_t step)
-{
-    const uint64_t one = (uint64_t)1 << 24;
-    if ((uint64_t)step * 5 < 8 * one || (uint64_t)step >= 2 * one) return 0;      // s < 1.6 or s >= 2
-    const int l3 = (int)(((uint64_t)step * 3) >> 24), l4 = (int)(((uint64_t)step * 4) >> 24);
-    if (l3 == 4 && l4 == 6) return 1;
-    if (l3 == 5 && l4 == 6) return 2;
-    if (l3 == 5 && l4 == 7) return 3;
-    return 0;
-}
+// the compiled set: k_front_fat<NONCO, L3, L4> for both NONCO and the three step classes
+constexpr bool fat_compiled(int L3, int L4) { return step_class_hi(L3, L4); }
 
-// the shape k_front_fat exists for: the specialised (FAST) shape of k_front_s1 without the fused AGC, in a step class above
-bool front_fat_shape(const FrontArgs &a)
+// the shape k_front_fat exists for: the specialised (FAST) shape of k_front_s1 without the fused AGC, in a step class of the five-slot
+// polyphase: 1.6 <= s < 2 (a lane's 8 samples hold 4 or 5 outputs), lo_3 = floor(3 s), lo_4 = floor(4 s)
+FatSel front_fat_select(const FrontArgs &a)
 {
-    return a.S == 1 && a.in_fmt == IQGPU_FMT_CS16 && a.out_fmt == IQGPU_FMT_CS16 && a.gain == 1.0f && !a.iq_enable && !a.dc_enable &&
-           a.pnco_mode == 0 && !a.agc_fused && !(a.dbg & (kDbgNoFast | kDbgNoFat)) && fat_step_class(a.step) != 0;
+    FatSel k{};
+    k.NONCO = a.nco_mode == 0;
+    k.L3 = (int)(((uint64_t)a.step * 3) >> 24); k.L4 = (int)(((uint64_t)a.step * 4) >> 24);
+    k.ok = a.S == 1 && a.in_fmt == IQGPU_FMT_CS16 && a.out_fmt == IQGPU_FMT_CS16 && a.gain == 1.0f && !a.iq_enable && !a.dc_enable &&
+           a.pnco_mode == 0 && !a.agc_fused && !(a.dbg & (kDbgNoFast | kDbgNoFat)) && (uint64_t)a.step * 5 >= ((uint64_t)8 << 24) && (uint64_t)a.step < ((uint64_t)2 << 24) && fat_compiled(k.L3, k.L4);    // (1.6 <= s < 2)
+    return k;
 }
 
 hipError_t launch_front_fat(const FrontArgs &a_in, hipStream_t s)
 {
-    const bool nonco = a_in.nco_mode == 0;
+    const FatSel k = front_fat_select(a_in);
+    if (!k.ok) return hipErrorInvalidValue;
     FrontArgs a = a_in;
-    if (nonco) for (float &h : a.hb0) h *= 1.0f / 32768.0f;           // the cs16 normaliser rides on the half-band taps (exact: a power of two)
+    if (k.NONCO) for (float &h : a.hb0) h *= 1.0f / 32768.0f;         // the cs16 normaliser rides on the half-band taps (exact: a power of two)
     const size_t lds = front_fat_lds_bytes();
     const int64_t n_items = a.w_n_edge + a.w_n_stream;
     const unsigned grid = (unsigned)((n_items + kFatWaves - 1) / kFatWaves);
     if (grid == 0) return hipSuccess;
-#define IQGPU_LAUNCH_FAT(NONCO, L3, L4)                                                                              \
-    do {                                                                                                              \
-        static LdsAttrCache cache;                /* per instantiation */                                          \
-        { const hipError_t e = cache.ensure((const void *)k_front_fat<NONCO, L3, L4>, lds); if (e != hipSuccess) return e; } \
-        hipLaunchKernelGGL((k_front_fat<NONCO, L3, L4>), dim3(grid), dim3(kFatThreads), lds, s, a);                 \
-    } while (0)
-    switch (fat_step_class(a.step) * 2 + (nonco ? 1 : 0)) {
-    case 2: IQGPU_LAUNCH_FAT(false, 4, 6); break;
-    case 3: IQGPU_LAUNCH_FAT(true, 4, 6); break;
-    case 4: IQGPU_LAUNCH_FAT(false, 5, 6); break;
-    case 5: IQGPU_LAUNCH_FAT(true, 5, 6); break;
-    case 6: IQGPU_LAUNCH_FAT(false, 5, 7); break;
-    case 7: IQGPU_LAUNCH_FAT(true, 5, 7); break;
-    default: return hipErrorInvalidValue;
-    }
-#undef IQGPU_LAUNCH_FAT
-    return hipGetLastError();
+    return dispatch_bool(k.NONCO, [&](auto NONCO) { return dispatch_int<4, 5>(k.L3, [&](auto L3) { return dispatch_int<6, 7>(k.L4, [&](auto L4) {
+        if constexpr (fat_compiled(L3.value, L4.value)) return launch_inst<k_front_fat<NONCO.value, L3.value, L4.value>>(grid, kFatThreads, lds, s, a);
+        else return hipErrorInvalidValue;
+    }); }); });
 }
 
 } // namespace iqgpu

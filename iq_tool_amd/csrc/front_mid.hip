@@ -32,7 +32,6 @@ namespace iqgpu {
 #ifndef IQGPU_MID_WAVES
 #define IQGPU_MID_WAVES 12
 #endif
-constexpr int kMidN16 = 116;                  // INF of k_front_mid: 16-bit frames normalised at the unpack (a gain, sc16q11)
 constexpr int kMidWaves = IQGPU_MID_WAVES;    // (16 is an experiment: only the shape without a mixer fits LDS and 128 VGPRs then)
 constexpr int kMidThreads = kMidWaves * 64;
 // NL = half-band outputs per lane: 6 (768-frame tiles; rows need no padding: 6 cf32 = 48 bytes = 3 slots of 16, an odd number, so a
@@ -818,9 +817,24 @@ static bool mid_class(uint32_t step, int nl, int *l3, int *l4)
     return (*l3 == 4 && *l4 == 6) || (*l3 == 5 && *l4 == 6) || (*l3 == 5 && *l4 == 7);
 }
 
-// outputs per lane of the k_front_mid instantiation for these arguments: 6 (8 on request); 0 = not this kernel's shape
-int front_mid_nl(const FrontArgs &a)
+// the compiled set of k_front_mid<NL, NONCO, L3, L4, AGC, STEAL, CF32OUT, INF, OUT8>, for both NONCO.  Eight per lane: its three step
+// classes, cs16 in and out, nothing else.  Six per lane: its two step classes (L4 = 0), every input kind (cu8, cs8, cs16, kMidN16)
+// and every integer output (cs16, cu8, cs8) with and without the fused AGC; cf32 out for every input kind (no fused AGC); run
+// stealing for cs16 in and out only
+constexpr bool mid_compiled(int NL, bool NONCO, int L3, int L4, bool AGC, bool STEAL, bool CF, int INF, int O8)
 {
+    if (!(INF == IQGPU_FMT_CU8 || INF == IQGPU_FMT_CS8 || INF == IQGPU_FMT_CS16 || INF == kMidN16) || O8 < 0 || O8 > 2) return false;
+    if (NL == 8) return step_class_hi(L3, L4) && !AGC && !STEAL && !CF && INF == IQGPU_FMT_CS16 && O8 == 0;
+    if (NL != 6 || L4 != 0 || (L3 != 4 && L3 != 5)) return false;
+    if (CF) return !AGC && !STEAL && O8 == 0;
+    if (STEAL) return INF == IQGPU_FMT_CS16 && O8 == 0;
+    return true;
+}
+
+// the instantiation for these arguments: 6 outputs per lane (8 on request); !ok = not this kernel's shape
+MidSel front_mid_select(const FrontArgs &a)
+{
+    MidSel k{};
     // (cf32 out: a user filter behind the resampler takes the samples -- the -usb / -lsb presets; six outputs per lane, no fused AGC)
     const bool cf32_out = a.out_fmt == IQGPU_FMT_CF32 && !a.agc_fused;
     // (late round 5: 8-bit frames on either side -- cu8 / cs8 in, cu8 / cs8 out, any mix with cs16 and cf32 -- six outputs per lane)
@@ -830,106 +844,51 @@ int front_mid_nl(const FrontArgs &a)
     const bool any8 = (in8 || out8 || n16) && !(a.dbg & kDbgNoMid8bit);
     if (!(a.S == 1 && ((a.in_fmt == IQGPU_FMT_CS16 && !n16) || ((in8 || n16) && any8)) && (a.out_fmt == IQGPU_FMT_CS16 || cf32_out || (out8 && any8)) &&
           (a.gain == 1.0f || any8) && a.gain > 0.0f && a.gain < 1e30f &&
-          !a.iq_enable && !a.dc_enable && a.pnco_mode == 0 && !(a.dbg & (kDbgNoFast | kDbgNoFat)))) return 0;
-    int l3, l4;
+          !a.iq_enable && !a.dc_enable && a.pnco_mode == 0 && !(a.dbg & (kDbgNoFast | kDbgNoFat)))) return k;
+    k.NONCO = a.nco_mode == 0;
+    k.CF = cf32_out; k.AGC = a.agc_fused != 0;
+    k.INF = in8 ? a.in_fmt : n16 ? kMidN16 : (int)IQGPU_FMT_CS16;
+    k.O8 = a.out_fmt == IQGPU_FMT_CU8 ? 1 : a.out_fmt == IQGPU_FMT_CS8 ? 2 : 0;
     for (int nl : {8, 6}) {
         // 8 per lane is an experiment (iqgpu_debug_set("mid8", "1")): in 168 VGPRs it has no room to fetch a phase ahead, and without that it runs
         // 0.440 ms against 0.384 for 6 per lane on the NRSC-5 chain; with the fused AGC it does not fit at all
         if (nl == 8 && (!(a.dbg & kDbgMid8) || a.agc_fused || cf32_out || any8)) continue;
-        if (!mid_class(a.step, nl, &l3, &l4)) continue;
+        if (!mid_class(a.step, nl, &k.L3, &k.L4)) continue;
         if (a.agc_fused && !(a.agc_shift == 1 && a.agc_chunk_frames >= 128 * nl)) continue;
-        return nl;
+        k.NL = nl;
+        break;
     }
-    return 0;
+    // run stealing / fixed-length runs dealt out inside a workgroup: six per lane, cs16 in and out, and only when the host provides
+    // descriptors and asks for it
+    k.STEAL = k.NL == 6 && !k.CF && k.INF == IQGPU_FMT_CS16 && k.O8 == 0 && a.w_steal != nullptr && (a.w_steal_rounds > 0 || a.w_run_stride > 0);
+    k.ok = k.NL != 0;
+    return k;
 }
 int front_mid_tile(int nl) { return 128 * nl; }
 
 hipError_t launch_front_mid(const FrontArgs &a_in, hipStream_t s)
 {
-    const bool nonco = a_in.nco_mode == 0;
+    const MidSel k = front_mid_select(a_in);
+    if (!k.ok) return hipErrorInvalidValue;
     FrontArgs a = a_in;
-    const bool n16 = (a.in_fmt == IQGPU_FMT_CS16 && a.gain != 1.0f) || a.in_fmt == IQGPU_FMT_SC16Q11;
-    const bool in8 = a.in_fmt == IQGPU_FMT_CU8 || a.in_fmt == IQGPU_FMT_CS8 || n16, out8 = a.out_fmt == IQGPU_FMT_CU8 || a.out_fmt == IQGPU_FMT_CS8;
-    // (in8: every input that is normalised at the unpack -- the 8-bit formats and kMidN16)
-    if (nonco && !in8) for (float &h : a.hb0) h *= 1.0f / 32768.0f;  // the cs16 normaliser rides on the half-band taps (exact: a power of two)
-    const int nl = front_mid_nl(a);
-    int l3 = 0, l4 = 0;
-    if (nl == 0 || !mid_class(a.step, nl, &l3, &l4)) return hipErrorInvalidValue;
-    const size_t lds = mid_lds_bytes(nl, nonco);
-    // (fixed-length runs dealt out inside a workgroup need the multi-run instantiation, which exists for six outputs per lane only:
-    //  any other shape gets one static run per wave, however the caller filled w_run_stride)
-    if (nl != 6 || a.w_steal == nullptr || a.out_fmt == IQGPU_FMT_CF32 || in8 || out8) { a.w_run_stride = 0; if (a.out_fmt == IQGPU_FMT_CF32 || in8 || out8) a.w_steal = nullptr; }
+    // (INF other than cs16: every input that is normalised at the unpack -- the 8-bit formats and kMidN16)
+    if (k.NONCO && k.INF == IQGPU_FMT_CS16) for (float &h : a.hb0) h *= 1.0f / 32768.0f;  // the cs16 normaliser rides on the half-band taps (exact: a power of two)
+    const size_t lds = mid_lds_bytes(k.NL, k.NONCO);
+    // (fixed-length runs dealt out inside a workgroup need the multi-run instantiation, which exists for six outputs per lane, cs16 in
+    //  and out only: any other shape gets one static run per wave, however the caller filled w_run_stride)
+    const bool plain16 = !k.CF && k.INF == IQGPU_FMT_CS16 && k.O8 == 0;
+    if (k.NL != 6 || a.w_steal == nullptr || !plain16) { a.w_run_stride = 0; if (!plain16) a.w_steal = nullptr; }
     const int64_t n_items = a.w_n_edge + (a.w_run_stride > 0 && a.w_run_stride < a.w_n_stream ? a.w_run_stride : a.w_n_stream);
     const unsigned grid = (unsigned)((n_items + kMidWaves - 1) / kMidWaves);
     if (grid == 0) return hipSuccess;
-#define IQGPU_LAUNCH_MID1(NL, NONCO, L3, L4, AGC, STEAL, CF)                                                        \
-    do {                                                                                                              \
-        static LdsAttrCache cache;                /* per instantiation */                                          \
-        { const hipError_t e = cache.ensure((const void *)k_front_mid<NL, NONCO, L3, L4, AGC, STEAL, CF>, lds); if (e != hipSuccess) return e; } \
-        hipLaunchKernelGGL((k_front_mid<NL, NONCO, L3, L4, AGC, STEAL, CF>), dim3(grid), dim3(kMidThreads), lds, s, a); \
-    } while (0)
-    /* run stealing: six outputs per lane only, and only when the host provides descriptors and asks for it */
-    const bool steal = a.w_steal != nullptr && (a.w_steal_rounds > 0 || a.w_run_stride > 0);
-    /* cf32 out (a user filter behind the resampler): six per lane, static runs, no fused AGC */
-    const bool cf = a.out_fmt == IQGPU_FMT_CF32;
-    if (cf && (nl != 6 || a.agc_fused)) return hipErrorInvalidValue;
-    if (cf) { a.w_steal = nullptr; a.w_run_stride = 0; }
-#define IQGPU_LAUNCH_MID(NL, NONCO, L3, L4, AGC)                                                                    \
-    do {                                                                                                              \
-        if (NL == 6 && cf) IQGPU_LAUNCH_MID1(NL, NONCO, L3, L4, false, false, (NL == 6));                           \
-        else if (NL == 6 && steal) IQGPU_LAUNCH_MID1(NL, NONCO, L3, L4, AGC, (NL == 6), false);                     \
-        else IQGPU_LAUNCH_MID1(NL, NONCO, L3, L4, AGC, false, false);                                               \
-    } while (0)
-#define IQGPU_LAUNCH_MID2(NL, L3, L4)                                                                               \
-    do {                                                                                                              \
-        if (nonco && a.agc_fused) IQGPU_LAUNCH_MID(NL, true, L3, L4, (NL == 6));                                    \
-        else if (nonco) IQGPU_LAUNCH_MID(NL, true, L3, L4, false);                                                  \
-        else if (a.agc_fused) IQGPU_LAUNCH_MID(NL, false, L3, L4, (NL == 6));                                       \
-        else IQGPU_LAUNCH_MID(NL, false, L3, L4, false);                                                            \
-    } while (0)
-    if (in8 || out8) {
-        // 8-bit frames: six per lane, static runs; INF / OUT8 as the formats say, CF32OUT for a filter behind
-        if (nl != 6 || (cf && a.agc_fused)) return hipErrorInvalidValue;
-#define IQGPU_LAUNCH_MID8C(NONCO, L3, AGC, CF, INF, O8)                                                             \
-        do {                                                                                                          \
-            static LdsAttrCache cache;                                                                                \
-            { const hipError_t e = cache.ensure((const void *)k_front_mid<6, NONCO, L3, 0, AGC, false, CF, INF, O8>, lds); if (e != hipSuccess) return e; } \
-            hipLaunchKernelGGL((k_front_mid<6, NONCO, L3, 0, AGC, false, CF, INF, O8>), dim3(grid), dim3(kMidThreads), lds, s, a); \
-        } while (0)
-#define IQGPU_LAUNCH_MID8B(NONCO, L3, INF)                                                                          \
-        do {                                                                                                          \
-            if (cf) IQGPU_LAUNCH_MID8C(NONCO, L3, false, true, INF, 0);                                              \
-            else if (a.out_fmt == IQGPU_FMT_CU8 && a.agc_fused) IQGPU_LAUNCH_MID8C(NONCO, L3, true, false, INF, 1);  \
-            else if (a.out_fmt == IQGPU_FMT_CU8) IQGPU_LAUNCH_MID8C(NONCO, L3, false, false, INF, 1);                \
-            else if (a.out_fmt == IQGPU_FMT_CS8 && a.agc_fused) IQGPU_LAUNCH_MID8C(NONCO, L3, true, false, INF, 2);  \
-            else if (a.out_fmt == IQGPU_FMT_CS8) IQGPU_LAUNCH_MID8C(NONCO, L3, false, false, INF, 2);                \
-            else if (INF != IQGPU_FMT_CS16 && a.agc_fused) IQGPU_LAUNCH_MID8C(NONCO, L3, true, false, INF, 0);       \
-            else if (INF != IQGPU_FMT_CS16) IQGPU_LAUNCH_MID8C(NONCO, L3, false, false, INF, 0);                     \
-            else return hipErrorInvalidValue;                                                                         \
-        } while (0)
-#define IQGPU_LAUNCH_MID8A(NONCO, L3)                                                                               \
-        do {                                                                                                          \
-            if (a.in_fmt == IQGPU_FMT_CU8) IQGPU_LAUNCH_MID8B(NONCO, L3, IQGPU_FMT_CU8);                             \
-            else if (a.in_fmt == IQGPU_FMT_CS8) IQGPU_LAUNCH_MID8B(NONCO, L3, IQGPU_FMT_CS8);                        \
-            else if (n16) IQGPU_LAUNCH_MID8B(NONCO, L3, kMidN16);                                                    \
-            else IQGPU_LAUNCH_MID8B(NONCO, L3, IQGPU_FMT_CS16);                                                      \
-        } while (0)
-        if (l3 == 4) { if (nonco) IQGPU_LAUNCH_MID8A(true, 4); else IQGPU_LAUNCH_MID8A(false, 4); }
-        else         { if (nonco) IQGPU_LAUNCH_MID8A(true, 5); else IQGPU_LAUNCH_MID8A(false, 5); }
-#undef IQGPU_LAUNCH_MID8A
-#undef IQGPU_LAUNCH_MID8B
-#undef IQGPU_LAUNCH_MID8C
-        return hipGetLastError();
-    }
-    if (nl == 6 && l3 == 4) IQGPU_LAUNCH_MID2(6, 4, 0);
-    else if (nl == 6) IQGPU_LAUNCH_MID2(6, 5, 0);
-    else if (l3 == 4) IQGPU_LAUNCH_MID2(8, 4, 6);
-    else if (l4 == 6) IQGPU_LAUNCH_MID2(8, 5, 6);
-    else IQGPU_LAUNCH_MID2(8, 5, 7);
-#undef IQGPU_LAUNCH_MID2
-#undef IQGPU_LAUNCH_MID
-#undef IQGPU_LAUNCH_MID1
-    return hipGetLastError();
+    return dispatch_int<6, 8>(k.NL, [&](auto NL) { return dispatch_bool(k.NONCO, [&](auto NONCO) { return dispatch_int<4, 5>(k.L3, [&](auto L3) {
+        return dispatch_int<0, 6, 7>(k.L4, [&](auto L4) { return dispatch_bool(k.AGC, [&](auto AGC) { return dispatch_bool(k.STEAL, [&](auto STEAL) {
+        return dispatch_bool(k.CF, [&](auto CF) { return dispatch_int<IQGPU_FMT_CU8, IQGPU_FMT_CS8, IQGPU_FMT_CS16, kMidN16>(k.INF, [&](auto INF) {
+        return dispatch_int<0, 1, 2>(k.O8, [&](auto O8) {
+            if constexpr (mid_compiled(NL.value, NONCO.value, L3.value, L4.value, AGC.value, STEAL.value, CF.value, INF.value, O8.value))
+                return launch_inst<k_front_mid<NL.value, NONCO.value, L3.value, L4.value, AGC.value, STEAL.value, CF.value, INF.value, O8.value>>(grid, kMidThreads, lds, s, a);
+            else return hipErrorInvalidValue;
+        }); }); }); }); }); }); }); }); });
 }
 
 } // namespace iqgpu

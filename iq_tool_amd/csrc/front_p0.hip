@@ -331,16 +331,24 @@ __global__ __launch_bounds__(kP0Threads) void k_front_p0(const FrontArgs a)
     }
 }
 
-// which chains: no half-band stage, nothing pointwise but the unpack (unit gain, no dc blocker / iq correction / mixer on either
-// side), cu8 / cs8 / cs16 in, cu8 / cs8 / cs16 / cf32 out, a five-slot step class (1.016 <= s < 2); the fused AGC with chunks of 1024 frames and more
-bool front_p0_shape(const FrontArgs &a)
+// the compiled set of k_front_p0<FMT, L3, L4, OUTF, AGC, L2>: cu8 / cs8 / cs16 in, every step class, cu8 / cs8 / cs16 out with and
+// without the fused AGC, cf32 out without
+constexpr bool p0_compiled(int FMT, int L3, int L4, int OUTF, bool AGC, int L2)
 {
-    int l3, l4;
-    if (a.S != 0 || a.gain != 1.0f || a.iq_enable || a.dc_enable || a.nco_mode != 0 || a.pnco_mode != 0 || (a.dbg & (kDbgNoFast | kDbgNoFat))) return false;
-    if (!(a.in_fmt == IQGPU_FMT_CU8 || a.in_fmt == IQGPU_FMT_CS8 || a.in_fmt == IQGPU_FMT_CS16)) return false;
-    if (!(a.out_fmt == IQGPU_FMT_CU8 || a.out_fmt == IQGPU_FMT_CS8 || a.out_fmt == IQGPU_FMT_CS16 || a.out_fmt == IQGPU_FMT_CF32)) return false;
-    if (a.agc_fused && (a.out_fmt == IQGPU_FMT_CF32 || a.agc_chunk_frames < 1024 || a.agc_shift != 0)) return false;
-    return p0_class(a.step, &l3, &l4);
+    return (FMT == IQGPU_FMT_CU8 || FMT == IQGPU_FMT_CS8 || FMT == IQGPU_FMT_CS16) && p0_class_compiled(L2, L3, L4) &&
+           (OUTF == IQGPU_FMT_CU8 || OUTF == IQGPU_FMT_CS8 || OUTF == IQGPU_FMT_CS16 || (OUTF == IQGPU_FMT_CF32 && !AGC));
+}
+
+// which chains: no half-band stage, nothing pointwise but the unpack (unit gain, no dc blocker / iq correction / mixer on either
+// side), a compiled format pair and step class (1.016 <= s < 2); the fused AGC with chunks of 1024 frames and more
+P0Sel front_p0_select(const FrontArgs &a)
+{
+    P0Sel k{};
+    k.FMT = a.in_fmt; k.OUTF = a.out_fmt; k.AGC = a.agc_fused != 0;
+    k.ok = a.S == 0 && a.gain == 1.0f && !a.iq_enable && !a.dc_enable && a.nco_mode == 0 && a.pnco_mode == 0 && !(a.dbg & (kDbgNoFast | kDbgNoFat)) &&
+           !(a.agc_fused && (a.agc_chunk_frames < 1024 || a.agc_shift != 0)) && p0_class(a.step, &k.L3, &k.L4, &k.L2) &&
+           p0_compiled(k.FMT, k.L3, k.L4, k.OUTF, k.AGC, k.L2);
+    return k;
 }
 
 // the streaming part of a plan made by plan_front_s1 for 256-frame tiles: outputs whose position lies in tiles [ta, tb), as steps
@@ -351,11 +359,7 @@ void plan_front_p0(FrontArgs &a, int64_t wave_slots)
     const int64_t ta = a.w_edge_ta, tb = a.w_edge_tb;
     a.w_n_stream = 0; a.w_run_q = 0; a.w_run_r = 0;
     if (tb <= ta) return;
-    auto first_k = [&](int64_t pos) {
-        const uint64_t target = (uint64_t)pos << 24;
-        return (int64_t)(target > a.phi0 ? (target - a.phi0 + (uint64_t)a.step - 1) / (uint64_t)a.step : 0);
-    };
-    a.p0_k_a = first_k(ta * 256); a.p0_k_b = first_k(tb * 256);
+    a.p0_k_a = first_k(a.phi0, a.step, ta * 256); a.p0_k_b = first_k(a.phi0, a.step, tb * 256);
     a.p0_f_max = a.frames_in - 24;                                   // the last frame a 24-frame window load may start at
     const int64_t n_steps = (a.p0_k_b - a.p0_k_a + kP0Step - 1) / kP0Step;
     if (n_steps <= 0) return;
@@ -367,44 +371,19 @@ void plan_front_p0(FrontArgs &a, int64_t wave_slots)
 
 hipError_t launch_front_p0(const FrontArgs &a, hipStream_t s)
 {
-    int l2 = 0, l3 = 0, l4 = 0;
-    if (!front_p0_shape(a) || !p0_class(a.step, &l3, &l4, &l2) || a.w_n_edge > kP0EdgeMax || a.rem0 != 0) return hipErrorInvalidValue;
+    const P0Sel k = front_p0_select(a);
+    if (!k.ok || a.w_n_edge > kP0EdgeMax || a.rem0 != 0) return hipErrorInvalidValue;
     const size_t lds = p0_lds_bytes();
     const int64_t n_items = a.w_n_edge + a.w_n_stream;
     const unsigned grid = (unsigned)((n_items + kP0Waves - 1) / kP0Waves);
     if (grid == 0) return hipSuccess;
-#define IQGPU_LAUNCH_P0(FMT, L3, L4, OUTF, AGC, L2)                                                                 \
-    do {                                                                                                              \
-        static LdsAttrCache cache;                /* per instantiation */                                          \
-        { const hipError_t e = cache.ensure((const void *)k_front_p0<FMT, L3, L4, OUTF, AGC, L2>, lds); if (e != hipSuccess) return e; } \
-        hipLaunchKernelGGL((k_front_p0<FMT, L3, L4, OUTF, AGC, L2>), dim3(grid), dim3(kP0Threads), lds, s, a);      \
-    } while (0)
-#define IQGPU_LAUNCH_P0_AGC(FMT, L3, L4, OUTF, L2)                                                                  \
-    do { if (a.agc_fused) IQGPU_LAUNCH_P0(FMT, L3, L4, OUTF, true, L2); else IQGPU_LAUNCH_P0(FMT, L3, L4, OUTF, false, L2); } while (0)
-#define IQGPU_LAUNCH_P0_OUT(FMT, L3, L4, L2)                                                                        \
-    do {                                                                                                              \
-        if (a.out_fmt == IQGPU_FMT_CF32) IQGPU_LAUNCH_P0(FMT, L3, L4, IQGPU_FMT_CF32, false, L2);                   \
-        else if (a.out_fmt == IQGPU_FMT_CS16) IQGPU_LAUNCH_P0_AGC(FMT, L3, L4, IQGPU_FMT_CS16, L2);                 \
-        else if (a.out_fmt == IQGPU_FMT_CU8) IQGPU_LAUNCH_P0_AGC(FMT, L3, L4, IQGPU_FMT_CU8, L2);                   \
-        else IQGPU_LAUNCH_P0_AGC(FMT, L3, L4, IQGPU_FMT_CS8, L2);                                                   \
-    } while (0)
-#define IQGPU_LAUNCH_P0_CLS(FMT)                                                                                    \
-    do {                                                                                                              \
-        if (l2 == 2 && l3 == 3 && l4 == 4) IQGPU_LAUNCH_P0_OUT(FMT, 3, 4, 2);                                       \
-        else if (l2 == 2 && l3 == 3) IQGPU_LAUNCH_P0_OUT(FMT, 3, 5, 2);                                             \
-        else if (l2 == 2) IQGPU_LAUNCH_P0_OUT(FMT, 4, 5, 2);                                                        \
-        else if (l3 == 4) IQGPU_LAUNCH_P0_OUT(FMT, 4, 6, 3);                                                        \
-        else if (l4 == 6) IQGPU_LAUNCH_P0_OUT(FMT, 5, 6, 3);                                                        \
-        else IQGPU_LAUNCH_P0_OUT(FMT, 5, 7, 3);                                                                     \
-    } while (0)
-    if (a.in_fmt == IQGPU_FMT_CU8) IQGPU_LAUNCH_P0_CLS(IQGPU_FMT_CU8);
-    else if (a.in_fmt == IQGPU_FMT_CS8) IQGPU_LAUNCH_P0_CLS(IQGPU_FMT_CS8);
-    else IQGPU_LAUNCH_P0_CLS(IQGPU_FMT_CS16);
-#undef IQGPU_LAUNCH_P0_CLS
-#undef IQGPU_LAUNCH_P0_OUT
-#undef IQGPU_LAUNCH_P0_AGC
-#undef IQGPU_LAUNCH_P0
-    return hipGetLastError();
+    return dispatch_int<IQGPU_FMT_CU8, IQGPU_FMT_CS8, IQGPU_FMT_CS16>(k.FMT, [&](auto FMT) { return dispatch_int<3, 4, 5>(k.L3, [&](auto L3) {
+        return dispatch_int<4, 5, 6, 7>(k.L4, [&](auto L4) { return dispatch_int<IQGPU_FMT_CU8, IQGPU_FMT_CS8, IQGPU_FMT_CS16, IQGPU_FMT_CF32>(k.OUTF, [&](auto OUTF) {
+        return dispatch_bool(k.AGC, [&](auto AGC) { return dispatch_int<2, 3>(k.L2, [&](auto L2) {
+            if constexpr (p0_compiled(FMT.value, L3.value, L4.value, OUTF.value, AGC.value, L2.value))
+                return launch_inst<k_front_p0<FMT.value, L3.value, L4.value, OUTF.value, AGC.value, L2.value>>(grid, kP0Threads, lds, s, a);
+            else return hipErrorInvalidValue;
+        }); }); }); }); }); });
 }
 
 } // namespace iqgpu

@@ -30,16 +30,27 @@ __device__ __forceinline__ v2f p0_unpack(const uint32_t *r, const int i)
 // outputs span less than 4 s + 1 < 9 samples behind its first (own[9]); the slots' shifted tap rows cover position offsets 0 and 1
 // past lo_j.  (Until late round 5: 1.6 <= s only -- the bound of the eight-samples-per-lane kernel this one grew out of, which the
 // output-major form does not have: a 2.048 MS/s capture to the cu8-nrsc5 preset's 1.488375 MS/s has s = 1.376.)
-inline bool p0_class(uint32_t step, int *l3, int *l4, int *l2 = nullptr)
+// (the compiled classes: the three of 1.5 <= s < 2 that the eight-per-lane kernels know, and three of 1 <= s < 1.5)
+constexpr bool p0_class_compiled(int L2, int L3, int L4)
+{
+    return L2 == 3 ? step_class_hi(L3, L4) : L2 == 2 && ((L3 == 3 && L4 == 4) || (L3 == 3 && L4 == 5) || (L3 == 4 && L4 == 5));
+}
+inline bool p0_class(uint32_t step, int *l3, int *l4, int *l2)
 {
     const uint64_t one = (uint64_t)1 << 24;
     if ((uint64_t)step >= 2 * one || (uint64_t)step < one + one / 64) return false;     // (s >= 1.016: clear of the no-resampling edge)
-    const int k2 = (int)(((uint64_t)step * 2) >> 24);
-    *l3 = (int)(((uint64_t)step * 3) >> 24); *l4 = (int)(((uint64_t)step * 4) >> 24);
-    if (l2) *l2 = k2;
-    if (k2 == 3) return (*l3 == 4 && *l4 == 6) || (*l3 == 5 && *l4 == 6) || (*l3 == 5 && *l4 == 7);
-    return k2 == 2 && ((*l3 == 3 && *l4 == 4) || (*l3 == 3 && *l4 == 5) || (*l3 == 4 && *l4 == 5));
+    *l2 = (int)(((uint64_t)step * 2) >> 24); *l3 = (int)(((uint64_t)step * 3) >> 24); *l4 = (int)(((uint64_t)step * 4) >> 24);
+    return p0_class_compiled(*l2, *l3, *l4);
 }
 
+// the compiled set of k_p0fft16<LOG2N, FMT, L3, L4, L2>: N = 4096, the format of the translation unit, every step class
+constexpr bool p0fft_compiled(int LOG2N, int FMT, int L3, int L4, int L2)
+{
+#ifdef IQGPU_P0FFT_QUICK
+    // (development builds: the one instantiation of the cu8-nrsc5-usb / -lsb presets -- the full set takes minutes to compile)
+    if (!(FMT == IQGPU_FMT_CU8 && L2 == 3 && L3 == 4 && L4 == 6)) return false;
+#endif
+    return LOG2N == 12 && (FMT == IQGPU_FMT_CU8 || FMT == IQGPU_FMT_CS8 || FMT == IQGPU_FMT_CS16) && p0_class_compiled(L2, L3, L4);
+}
 
 } // namespace iqgpu

@@ -239,20 +239,35 @@ __global__ __launch_bounds__(kS2Threads) void k_front_s2(const S2Args p)
 int front_s2_waves() { return kS2Waves; }
 int64_t front_s2_mid_samples(const FrontArgs &a2) { return (a2.w_n_edge + 1) * s2_edge_slots(a2.w_edge_tpw); }
 
-// which chains: two stages with liquid's 60 dB lengths, a vector-loadable input format, no fused AGC (that path keeps the two
-// kernels), the call aligned on a decimation group (the streaming waves read whole 16-byte words)
-bool front_s2_shape(const FrontArgs &a1)
+// the compiled set of k_front_s2<BPS, M0, SPEC>: the run-time-switched kernel per frame size, the switch sets of s2_spec for cu8 and
+// cs16 frames; both of liquid's 60 dB lengths of stage 0
+constexpr bool s2_compiled(int BPS, int M0, int SPEC)
 {
-    if (a1.casc_K != 1 || (a1.m[0] != 3 && a1.m[0] != 5)) return false;
-    switch (a1.in_fmt) {
-    case IQGPU_FMT_CS8: case IQGPU_FMT_CU8: case IQGPU_FMT_CS16: case IQGPU_FMT_CU16: case IQGPU_FMT_SC16Q11: case IQGPU_FMT_CF32: return true;
-    default: return false;
+    return (M0 == 3 || M0 == 5) && (SPEC == 0 ? (BPS == 2 || BPS == 4 || BPS == 8) : (SPEC >= 1 && SPEC <= 7 && (BPS == 2 || BPS == 4)));
+}
+
+// which chains: two stages with liquid's 60 dB lengths, a vector-loadable input format (no fused AGC: that path keeps the two kernels);
+// with the last stage's arguments a2, the switch set with an instantiation of its own (cu8 / cs16, unit gain, no mixer behind the
+// resampler: s2_spec), else the run-time-switched kernel
+S2Sel front_s2_select(const FrontArgs &a1, const FrontArgs *a2)
+{
+    S2Sel k{};
+    k.BPS = frame_bytes_class(a1.in_fmt); k.M0 = a1.m[0];
+    if (a2 && (a1.in_fmt == IQGPU_FMT_CS16 || a1.in_fmt == IQGPU_FMT_CU8) && a1.gain == 1.0f && a2->pnco_mode == 0 && !(a1.dbg & kDbgNoFast)) {
+        for (int q = 1; q <= 7 && k.SPEC == 0; ++q) {
+            const S2Spec sp = s2_spec(q);
+            if ((a1.dc_enable != 0) == (sp.dcq != 0) && (a1.iq_enable != 0) == (sp.dcq != 0) && (a1.nco_mode != 0) == (sp.nco != 0) && a2->out_fmt == sp.out) k.SPEC = q;
+        }
     }
+    k.ok = a1.casc_K == 1 && !(a2 && a2->agc_fused) && s2_compiled(k.BPS, k.M0, k.SPEC);
+    return k;
 }
 
 hipError_t launch_front_s2(const FrontArgs &a1, const FrontArgs &a2, hipStream_t s)
 {
-    if (!front_s2_shape(a1) || a1.rem0 != 0 || a2.rem0 != 0 || a2.agc_fused) return hipErrorInvalidValue;
+    // (the call aligned on a decimation group: the streaming waves read whole 16-byte words)
+    const S2Sel k = front_s2_select(a1, &a2);
+    if (!k.ok || a1.rem0 != 0 || a2.rem0 != 0) return hipErrorInvalidValue;
     // S2Feed::produce fetches the 512 input frames behind a streaming run's last sub-tile ahead, and the tail of the call must stay
     // with the edge waves that leave stage 0's history: both hold for the plans plan_geometry makes (a2's streaming region ends
     // hist2_cap intermediate samples and a whole tile in front of the call's end) -- checked here, not assumed
@@ -264,45 +279,10 @@ hipError_t launch_front_s2(const FrontArgs &a1, const FrontArgs &a2, hipStream_t
     S2Args p;
     p.a1 = a1; p.a2 = a2;
     const size_t lds = (size_t)kS2NcoLds + kS2ArbLds + (size_t)kS2Waves * s2_wave_lds(a1.m[0]);
-    int cls;
-    switch (a1.in_fmt) {
-    case IQGPU_FMT_CS8: case IQGPU_FMT_CU8: cls = 2; break;
-    case IQGPU_FMT_CF32: cls = 8; break;
-    default: cls = 4; break;
-    }
-#define IQGPU_LAUNCH_S2X(BPS, M0, SPEC)                                                                              \
-    do {                                                                                                              \
-        static LdsAttrCache cache;                /* per instantiation */                                          \
-        { const hipError_t e = cache.ensure((const void *)k_front_s2<BPS, M0, SPEC>, lds); if (e != hipSuccess) return e; } \
-        hipLaunchKernelGGL((k_front_s2<BPS, M0, SPEC>), dim3(grid), dim3(kS2Threads), lds, s, p);                   \
-    } while (0)
-#define IQGPU_LAUNCH_S2(BPS, M0) IQGPU_LAUNCH_S2X(BPS, M0, 0)
-    // the switch sets with an instantiation of their own (cs16, unit gain, no mixer behind the resampler): s2_spec
-    int spec = 0;
-    if ((a1.in_fmt == IQGPU_FMT_CS16 || a1.in_fmt == IQGPU_FMT_CU8) && a1.gain == 1.0f && a2.pnco_mode == 0 && !(a1.dbg & kDbgNoFast)) {
-        for (int k = 1; k <= 7 && spec == 0; ++k) {
-            const S2Spec sp = s2_spec(k);
-            if ((a1.dc_enable != 0) == (sp.dcq != 0) && (a1.iq_enable != 0) == (sp.dcq != 0) && (a1.nco_mode != 0) == (sp.nco != 0) && a2.out_fmt == sp.out) spec = k;
-        }
-    }
-    if (spec != 0) {
-#define IQGPU_LAUNCH_S2S(BPS, M0)                                                                                    \
-        do {                                                                                                          \
-            if (spec == 1) IQGPU_LAUNCH_S2X(BPS, M0, 1); else if (spec == 2) IQGPU_LAUNCH_S2X(BPS, M0, 2);           \
-            else if (spec == 3) IQGPU_LAUNCH_S2X(BPS, M0, 3); else if (spec == 4) IQGPU_LAUNCH_S2X(BPS, M0, 4);      \
-            else if (spec == 5) IQGPU_LAUNCH_S2X(BPS, M0, 5); else if (spec == 6) IQGPU_LAUNCH_S2X(BPS, M0, 6);      \
-            else IQGPU_LAUNCH_S2X(BPS, M0, 7);                                                                        \
-        } while (0)
-        if (cls == 2) { if (a1.m[0] == 5) IQGPU_LAUNCH_S2S(2, 5); else IQGPU_LAUNCH_S2S(2, 3); }
-        else          { if (a1.m[0] == 5) IQGPU_LAUNCH_S2S(4, 5); else IQGPU_LAUNCH_S2S(4, 3); }
-#undef IQGPU_LAUNCH_S2S
-        return hipGetLastError();
-    }
-    if (a1.m[0] == 5) { if (cls == 2) IQGPU_LAUNCH_S2(2, 5); else if (cls == 4) IQGPU_LAUNCH_S2(4, 5); else IQGPU_LAUNCH_S2(8, 5); }
-    else              { if (cls == 2) IQGPU_LAUNCH_S2(2, 3); else if (cls == 4) IQGPU_LAUNCH_S2(4, 3); else IQGPU_LAUNCH_S2(8, 3); }
-#undef IQGPU_LAUNCH_S2
-#undef IQGPU_LAUNCH_S2X
-    return hipGetLastError();
+    return dispatch_int<2, 4, 8>(k.BPS, [&](auto BPS) { return dispatch_int<3, 5>(k.M0, [&](auto M0) { return dispatch_int<0, 1, 2, 3, 4, 5, 6, 7>(k.SPEC, [&](auto SPEC) {
+        if constexpr (s2_compiled(BPS.value, M0.value, SPEC.value)) return launch_inst<k_front_s2<BPS.value, M0.value, SPEC.value>>(grid, kS2Threads, lds, s, p);
+        else return hipErrorInvalidValue;
+    }); }); });
 }
 
 } // namespace iqgpu

@@ -147,7 +147,6 @@ static bool front_s1_fast_shape(const FrontArgs &a)
     return a.S == 1 && a.in_fmt == IQGPU_FMT_CS16 && a.out_fmt == IQGPU_FMT_CS16 && a.gain == 1.0f && !a.iq_enable &&
            !a.dc_enable && a.pnco_mode == 0 && !(a.dbg & kDbgNoFast);
 }
-static bool front_s1_fast_nonco(const FrontArgs &a) { return front_s1_fast_shape(a) && a.nco_mode == 0; }
 // the fused AGC exists for the 8- and 16-bit-input instantiations, with or without the half-band stage (the shipped
 // NRSC-5 presets: cs16 / cu8 in, cs16 or cu8 out, shift or none); chunks at least a tile long (one boundary per tile)
 bool front_s1_agc_fusable(const FrontArgs &a)
@@ -187,87 +186,59 @@ static int front_s1_s0_mixer_var(const FrontArgs &a)
     if (a.dc_enable) return a.nco_mode != 0 ? 8 : 9;      // ... with `--dc-block`
     return a.nco_mode != 0 ? 7 : 0;
 }
-// wavefronts per workgroup of the instantiation that launch_front_s1() will pick for these arguments
-static bool front_s1_sixteen(const FrontArgs &a)
+// the compiled set of k_front_s1<BPS, FAST, S0, AGC, VAR>: the run-time-switched kernel per frame size with and without the half-band
+// stage (the fused AGC where front_s1_agc_fusable() allows it), the FAST shape, and one BPS / S0 per specialised VAR -- each with
+// and without the fused AGC
+constexpr bool s1_compiled(int BPS, bool FAST, bool S0, bool AGC, int VAR)
 {
-    if (front_s1_plain_var(a) != 0 || front_s1_mid_var(a) || front_s1_s0_mixer_var(a) != 0) return true;
-    // 4 waves per SIMD where the instantiation fits 128 VGPRs (nearly) without scratch: the specialised one,
-    // and the 8-bit-input ones (2 - 4 spilled dwords; measured -8 % on the cu8-nrsc5 shape, -4 % on cu8 -> cs16).
-    // The cs16 / cf32-input run-time-switched ones spill 7 - 21 dwords there and are faster with 12 waves.
-    return front_s1_fast_shape(a) || ((a.in_fmt == IQGPU_FMT_CU8 || a.in_fmt == IQGPU_FMT_CS8) && !a.agc_fused);
+    switch (VAR) {
+    case 0: return FAST ? (BPS == 4 && !S0) : (BPS == 2 || BPS == 4 || (BPS == 8 && (!AGC || !S0)) || (BPS == 0 && !AGC));
+    case 1: return BPS == 4 && FAST && !S0;
+    case 2: case 7: case 8: case 9: return BPS == 2 && !FAST && S0;
+    case 3: return BPS == 4 && !FAST && S0;
+    case 4: return BPS == 8 && !FAST && !S0;
+    case 5: case 6: return BPS == 4 && !FAST && !S0;
+    default: return false;
+    }
 }
-int front_s1_waves(const FrontArgs &a) { return front_s1_sixteen(a) ? kS1Waves : kWaves; }
+
+// the instantiation for these arguments: the most specialised VAR whose shape they have, else the run-time-switched kernel of the
+// frame size (its wavefronts per workgroup: s1_sixteen)
+S1Sel front_s1_select(const FrontArgs &a)
+{
+    S1Sel k{};
+    k.BPS = frame_bytes_class(a.in_fmt); k.S0 = a.S == 0; k.AGC = a.agc_fused != 0;
+    if (front_s1_plain_var(a) != 0) k.VAR = front_s1_plain_var(a);
+    else if (front_s1_s0_mixer_var(a) != 0) k.VAR = front_s1_s0_mixer_var(a);
+    else if (k.S0) k.VAR = 0;
+    else if (front_s1_fast_shape(a)) { k.FAST = true; k.VAR = a.nco_mode == 0 ? 1 : 0; }
+    else if (front_s1_dc_var(a) != 0) k.VAR = front_s1_dc_var(a);
+    else if (front_s1_mid_var(a)) k.VAR = 4;
+    k.ok = !(k.AGC && !(k.BPS == 2 || k.BPS == 4 || (k.BPS == 8 && a.S == 1)));       // (front_s1_agc_fusable)
+    return k;
+}
 
 hipError_t launch_front_s1(const FrontArgs &a_in, hipStream_t s)
 {
-    const bool fast = front_s1_fast_shape(a_in), nonco = front_s1_fast_nonco(a_in);
+    const S1Sel k = front_s1_select(a_in);
     FrontArgs a_scaled;
-    if (nonco) {                      // the cs16 normaliser rides on the half-band taps (exact: a power of two)
+    if (k.VAR == 1) {                 // the cs16 normaliser rides on the half-band taps (exact: a power of two)
         a_scaled = a_in;
         for (float &h : a_scaled.hb0) h *= 1.0f / 32768.0f;
     }
-    const FrontArgs &a = nonco ? a_scaled : a_in;
-    const int waves = front_s1_sixteen(a) ? kS1Waves : kWaves;
+    const FrontArgs &a = k.VAR == 1 ? a_scaled : a_in;
+    const int waves = s1_sixteen(k.BPS, k.FAST, k.AGC, k.VAR) ? kS1Waves : kWaves;
     const size_t lds = (size_t)kTabLds + (size_t)waves * kWaveLds;
     const int64_t n_items = a.w_n_edge + a.w_n_stream;
     const unsigned grid = (unsigned)((n_items + waves - 1) / waves);
     if (grid == 0) return hipSuccess;
-    int cls;
-    switch (a.in_fmt) {
-    case IQGPU_FMT_CS8: case IQGPU_FMT_CU8: cls = 2; break;
-    case IQGPU_FMT_CS16: case IQGPU_FMT_CU16: case IQGPU_FMT_SC16Q11: cls = 4; break;
-    case IQGPU_FMT_CF32: cls = 8; break;
-    default: cls = 0; break;
-    }
-#define IQGPU_LAUNCH_S1Y(BPS, FAST, S0, AGC, VAR)                                                                     \
-    do {                                                                                                              \
-        static LdsAttrCache cache;                /* per instantiation */                                          \
-        { const hipError_t e = cache.ensure((const void *)k_front_s1<BPS, FAST, S0, AGC, VAR>, lds); if (e != hipSuccess) return e; } \
-        hipLaunchKernelGGL((k_front_s1<BPS, FAST, S0, AGC, VAR>), dim3(grid), dim3(waves * 64), lds, s, a);         \
-    } while (0)
-#define IQGPU_LAUNCH_S1X(BPS, FAST, S0, AGC) IQGPU_LAUNCH_S1Y(BPS, FAST, S0, AGC, 0)
-#define IQGPU_LAUNCH_S1(BPS, FAST, S0) IQGPU_LAUNCH_S1X(BPS, FAST, S0, false)
-    if (a.agc_fused && !(cls == 2 || cls == 4 || (cls == 8 && a.S == 1))) return hipErrorInvalidValue;     // (front_s1_agc_fusable)
-    const int pvar = front_s1_plain_var(a);
-    if (pvar == 2 && a.agc_fused) IQGPU_LAUNCH_S1Y(2, false, true, true, 2);
-    else if (pvar == 2) IQGPU_LAUNCH_S1Y(2, false, true, false, 2);
-    else if (pvar == 3 && a.agc_fused) IQGPU_LAUNCH_S1Y(4, false, true, true, 3);
-    else if (pvar == 3) IQGPU_LAUNCH_S1Y(4, false, true, false, 3);
-    else if (front_s1_s0_mixer_var(a) == 7 && a.agc_fused) IQGPU_LAUNCH_S1Y(2, false, true, true, 7);
-    else if (front_s1_s0_mixer_var(a) == 7) IQGPU_LAUNCH_S1Y(2, false, true, false, 7);
-    else if (front_s1_s0_mixer_var(a) == 8 && a.agc_fused) IQGPU_LAUNCH_S1Y(2, false, true, true, 8);
-    else if (front_s1_s0_mixer_var(a) == 8) IQGPU_LAUNCH_S1Y(2, false, true, false, 8);
-    else if (front_s1_s0_mixer_var(a) == 9 && a.agc_fused) IQGPU_LAUNCH_S1Y(2, false, true, true, 9);
-    else if (front_s1_s0_mixer_var(a) == 9) IQGPU_LAUNCH_S1Y(2, false, true, false, 9);
-    else if (a.S == 0) {
-        if (cls == 2 && a.agc_fused) IQGPU_LAUNCH_S1X(2, false, true, true);
-        else if (cls == 2) IQGPU_LAUNCH_S1(2, false, true);
-        else if (cls == 4 && a.agc_fused) IQGPU_LAUNCH_S1X(4, false, true, true);
-        else if (cls == 4) IQGPU_LAUNCH_S1(4, false, true);
-        else if (cls == 8) IQGPU_LAUNCH_S1(8, false, true);
-        else IQGPU_LAUNCH_S1(0, false, true);
-    }
-    else if (cls == 2 && a.agc_fused) IQGPU_LAUNCH_S1X(2, false, false, true);
-    else if (cls == 2) IQGPU_LAUNCH_S1(2, false, false);
-    else if (cls == 4 && nonco && a.agc_fused) IQGPU_LAUNCH_S1Y(4, true, false, true, 1);
-    else if (cls == 4 && nonco) IQGPU_LAUNCH_S1Y(4, true, false, false, 1);
-    else if (cls == 4 && fast && a.agc_fused) IQGPU_LAUNCH_S1X(4, true, false, true);
-    else if (cls == 4 && front_s1_dc_var(a) == 5 && a.agc_fused) IQGPU_LAUNCH_S1Y(4, false, false, true, 5);
-    else if (cls == 4 && front_s1_dc_var(a) == 5) IQGPU_LAUNCH_S1Y(4, false, false, false, 5);
-    else if (cls == 4 && front_s1_dc_var(a) == 6 && a.agc_fused) IQGPU_LAUNCH_S1Y(4, false, false, true, 6);
-    else if (cls == 4 && front_s1_dc_var(a) == 6) IQGPU_LAUNCH_S1Y(4, false, false, false, 6);
-    else if (cls == 4 && a.agc_fused) IQGPU_LAUNCH_S1X(4, false, false, true);
-    else if (cls == 4 && fast) IQGPU_LAUNCH_S1(4, true, false);
-    else if (cls == 4) IQGPU_LAUNCH_S1(4, false, false);
-    else if (cls == 8 && front_s1_mid_var(a) && a.agc_fused) IQGPU_LAUNCH_S1Y(8, false, false, true, 4);
-    else if (cls == 8 && front_s1_mid_var(a)) IQGPU_LAUNCH_S1Y(8, false, false, false, 4);
-    else if (cls == 8 && a.agc_fused) IQGPU_LAUNCH_S1X(8, false, false, true);
-    else if (cls == 8) IQGPU_LAUNCH_S1(8, false, false);
-    else IQGPU_LAUNCH_S1(0, false, false);
-#undef IQGPU_LAUNCH_S1
-#undef IQGPU_LAUNCH_S1X
-#undef IQGPU_LAUNCH_S1Y
-    return hipGetLastError();
+    if (!k.ok) return hipErrorInvalidValue;
+    return dispatch_int<0, 2, 4, 8>(k.BPS, [&](auto BPS) { return dispatch_bool(k.FAST, [&](auto FAST) { return dispatch_bool(k.S0, [&](auto S0) {
+        return dispatch_bool(k.AGC, [&](auto AGC) { return dispatch_int<0, 1, 2, 3, 4, 5, 6, 7, 8, 9>(k.VAR, [&](auto VAR) {
+            if constexpr (s1_compiled(BPS.value, FAST.value, S0.value, AGC.value, VAR.value))
+                return launch_inst<k_front_s1<BPS.value, FAST.value, S0.value, AGC.value, VAR.value>>(grid, waves * 64, lds, s, a);
+            else return hipErrorInvalidValue;
+        }); }); }); }); });
 }
 
 // Splits the call's tiles into streaming runs (all tiles vector-loadable) and edge runs.  With fixed_tpw == 0
@@ -281,13 +252,7 @@ void plan_front_s1(FrontArgs &a, int64_t wave_slots, int fixed_tpw, int warm_til
 {
     const int kWTile = tile_frames;                 // 512 with a half-band stage in the kernel, 256 without
     const int64_t total = a.w_total_tiles;
-    int vb;
-    switch (a.in_fmt) {
-    case IQGPU_FMT_CS8: case IQGPU_FMT_CU8: vb = 2; break;
-    case IQGPU_FMT_CS16: case IQGPU_FMT_CU16: case IQGPU_FMT_SC16Q11: vb = 4; break;
-    case IQGPU_FMT_CF32: vb = 8; break;
-    default: vb = 0; break;
-    }
+    const int vb = frame_bytes_class(a.in_fmt);
     a.w_warm_tiles = warm_tiles;
     a.w_edge_tpw = edge_tpw;
     a.w_wsum = 0; a.w_wpw = 0;                       // equal runs unless the caller weights them afterwards (weight_runs)

@@ -4,7 +4,12 @@
 #include <mutex>
 
 #include <cstdint>
+#include <type_traits>
 #include <hip/hip_runtime_api.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
+#include "../../include/iqgpu.h"
 
 #if defined(__HIPCC__)
 #define IQGPU_HD __host__ __device__
@@ -51,6 +56,54 @@ struct LdsAttrCache {
         return e;
     }
 };
+
+// ---------------------------------------------------------------------------------------------
+// From launch arguments to ONE kernel instantiation.  Every templated kernel family states three things next to its kernel:
+//   * a selection struct with exactly the kernel's template arguments (+ ok: false = not this family's arguments) and ONE function
+//     that fills it from the launch arguments (front_mid_select(), ...): the shape predicates and the launcher read it, nothing else;
+//   * a constexpr predicate of the template tuples that are compiled (mid_compiled(), ...): the family's compiled set, in one place;
+//   * a launcher that turns the selection into template arguments with the two dispatch helpers below and launches it through
+//     launch_inst<> under `if constexpr (compiled(...))`, so that exactly the stated tuples are instantiated.
+// ---------------------------------------------------------------------------------------------
+// f(std::integral_constant) for the run-time value v: a bool, or one of the listed integers (none of them: hipErrorInvalidValue)
+template <class F> inline hipError_t dispatch_bool(bool v, F &&f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+template <int... Vs, class F> inline hipError_t dispatch_int(int v, F &&f)
+{
+    hipError_t e = hipErrorInvalidValue;
+    (void)((v == Vs ? (e = f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+    return e;
+}
+#if defined(__HIPCC__)
+// the launch of one kernel instantiation; set_lds: raise its dynamic-LDS limit first (one cache per instantiation)
+template <auto Kernel, class Args>
+inline hipError_t launch_inst(unsigned grid, unsigned block, size_t lds, hipStream_t s, const Args &a, bool set_lds = true)
+{
+    static LdsAttrCache cache;
+    if (set_lds) { const hipError_t e = cache.ensure((const void *)Kernel, lds); if (e != hipSuccess) return e; }
+    hipLaunchKernelGGL(Kernel, dim3(grid), dim3(block), lds, s, a);
+    return hipGetLastError();
+}
+#endif
+// bytes per frame of the input formats the wave kernels load by vectors (2, 4, 8); 0 = a format they read frame by frame
+inline int frame_bytes_class(int in_fmt)
+{
+    switch (in_fmt) {
+    case IQGPU_FMT_CS8: case IQGPU_FMT_CU8: return 2;
+    case IQGPU_FMT_CS16: case IQGPU_FMT_CU16: case IQGPU_FMT_SC16Q11: return 4;
+    case IQGPU_FMT_CF32: return 8;
+    default: return 0;
+    }
+}
+// the first resampler output at or behind position pos (polyphase-input samples of the call) for a call that starts at phase phi0:
+// the smallest k with phi0 + k step >= pos 2^24 (plan_call's law for the outputs in front of a position)
+inline int64_t first_k(uint64_t phi0, uint32_t step, int64_t pos)
+{
+    if (pos <= 0) return 0;
+    const uint64_t target = (uint64_t)pos << 24;
+    return (int64_t)(target > phi0 ? (target - phi0 + (uint64_t)step - 1) / (uint64_t)step : 0);
+}
+// the five-slot step classes (floor(3 s), floor(4 s)) of 1.6 <= s < 2 that k_front_fat, k_front_mid<8> and k_front_p0 are compiled for
+constexpr bool step_class_hi(int l3, int l4) { return (l3 == 4 && l4 == 6) || (l3 == 5 && l4 == 6) || (l3 == 5 && l4 == 7); }
 
 struct cf2 { float x, y; };
 struct AgcState;
@@ -223,30 +276,49 @@ hipError_t launch_front(const FrontArgs &a, int n_blocks, hipStream_t s);
 constexpr int kCascMaxK = 4;
 bool cascade_supported(const int *m_run_order, int S);
 size_t cascade_wave_lds(const FrontArgs &a, bool two_tile_trips = true);   // (false: k_cascade's own layout only)
+struct CascSel { bool ok; int BPS; bool RAW0; int KT; };         // k_cascade<BPS, RAW0, KT>
+CascSel cascade_select(const FrontArgs &a);
 hipError_t launch_cascade(const FrontArgs &a, int casc2_min_run, hipStream_t s);   // (k_cascade2 where it applies)
 int cascade_waves(const FrontArgs &a);    // needs casc_wave_lds
 // ... with two tiles per trip of a streaming wave for raw cu8 frames (cascade2.hip): the chain shape (needs in_fmt, gain, the
 // pointwise switches, casc_K, m[]); the call (needs the run geometry and casc_wave_lds too); bytes of a wave's slice
-bool cascade2_shape(const FrontArgs &a);
-bool cascade2_applies(const FrontArgs &a, int min_run);   // min_run: shortest streaming run in tiles (0 = the built-in bound)
+struct Casc2Sel { bool ok; int KT, BPF; bool S8; };               // k_cascade2<KT, BPF, S8>
+Casc2Sel cascade2_select(const FrontArgs &a);                 // the chain shape alone
+Casc2Sel cascade2_select(const FrontArgs &a, int min_run);    // ... and the call; min_run: shortest streaming run in tiles (0 = the built-in bound)
+inline bool cascade2_shape(const FrontArgs &a) { return cascade2_select(a).ok; }
+inline bool cascade2_applies(const FrontArgs &a, int min_run) { return cascade2_select(a, min_run).ok; }
 int cascade2_wave_lds(int K, int in_fmt);
 hipError_t launch_cascade2(const FrontArgs &a, int min_run, hipStream_t s);
 // one half-band stage (m = 10), no dc blocker: wave-autonomous kernel (front_wave.hip)
 size_t front_s1_lds_bytes();
+struct S1Sel { bool ok; int BPS; bool FAST, S0, AGC; int VAR; };  // k_front_s1<BPS, FAST, S0, AGC, VAR>
+S1Sel front_s1_select(const FrontArgs &a);  // needs S, formats, gain, iq / dc / nco switches, agc_fused, dbg
+// the instantiations that run 16 waves per workgroup instead of 12 (k_front_s1's launch bounds): 4 waves per SIMD where the
+// instantiation fits 128 VGPRs (nearly) without scratch -- the specialised ones, and the 8-bit-input ones (2 - 4 spilled dwords;
+// measured -8 % on the cu8-nrsc5 shape, -4 % on cu8 -> cs16).  The cs16 / cf32-input run-time-switched ones spill 7 - 21 dwords
+// there and are faster with 12 waves.
+constexpr bool s1_sixteen(int BPS, bool FAST, bool AGC, int VAR) { return FAST || (BPS == 2 && !AGC) || (VAR >= 2 && VAR <= 4) || VAR >= 7; }
 hipError_t launch_front_s1(const FrontArgs &a, hipStream_t s);
-int front_s1_waves(const FrontArgs &a);   // needs S, formats, gain, iq / dc / nco switches
+inline bool front_s1_sixteen(const FrontArgs &a) { const S1Sel k = front_s1_select(a); return s1_sixteen(k.BPS, k.FAST, k.AGC, k.VAR); }
+inline int front_s1_waves(const FrontArgs &a) { return front_s1_sixteen(a) ? kS1Waves : kWaves; }
 // the same shape as fewer, fatter waves (front_fat.hip): 8 waves per CU, 1024-frame tiles, software-pipelined LDS reads
 constexpr int kFatTile = 1024;
 constexpr int kFatMinTilesPerWave = 8;      // calls shorter than this many tiles per fat wave keep k_front_s1
 int front_fat_waves();
-bool front_fat_shape(const FrontArgs &a);  // needs S, formats, gain, iq / dc / nco switches, step, agc_fused, dbg
+struct FatSel { bool ok; bool NONCO; int L3, L4; };                // k_front_fat<NONCO, L3, L4>
+FatSel front_fat_select(const FrontArgs &a);  // needs S, formats, gain, iq / dc / nco switches, step, agc_fused, dbg
+inline bool front_fat_shape(const FrontArgs &a) { return front_fat_select(a).ok; }
 size_t front_fat_lds_bytes();
 hipError_t launch_front_fat(const FrontArgs &a, hipStream_t s);
 // ... and with 6 half-band outputs per lane, 12 waves per CU, 768-frame tiles (front_mid.hip)
 constexpr int kMidLead = 20;                 // a streaming run of k_front_mid reads this many frames in front of its first tile
 int front_mid_waves();
 int front_mid_max_edge_waves();          // launches with more edge runs than this stay on k_front_s1
-int front_mid_nl(const FrontArgs &a);    // half-band outputs per lane of the instantiation for these arguments (8, 6; 0 = not its shape)
+constexpr int kMidN16 = 116;             // INF of k_front_mid: 16-bit frames normalised at the unpack (a gain, sc16q11)
+struct MidSel { bool ok; int NL; bool NONCO; int L3, L4; bool AGC, STEAL, CF; int INF, O8; };   // k_front_mid<NL, NONCO, L3, L4, AGC, STEAL, CF32OUT, INF, OUT8>
+MidSel front_mid_select(const FrontArgs &a);
+// half-band outputs per lane of the instantiation for these arguments (8, 6; 0 = not its shape)
+inline int front_mid_nl(const FrontArgs &a) { const MidSel k = front_mid_select(a); return k.ok ? k.NL : 0; }
 int front_mid_tile(int nl);              // its tile: 128 nl frames
 // placement of the arms in the tap planes for a chain's step and nl outputs per lane: 1 = folded, 0 = linear (whichever a model of
 // the half-wave's bank pairs prices lower, the fold's two extra instructions per slot counted)
@@ -259,14 +331,18 @@ hipError_t launch_front_mid(const FrontArgs &a, hipStream_t s);
 int front_p0_waves();
 int front_p0_max_edge_waves();
 int front_p0_edge_tpw();
-bool front_p0_shape(const FrontArgs &a);        // needs S, formats, gain, iq / dc / nco switches, step, agc_fused, agc_chunk_frames, agc_shift, dbg
+struct P0Sel { bool ok; int FMT, L3, L4, OUTF; bool AGC; int L2; };  // k_front_p0<FMT, L3, L4, OUTF, AGC, L2>
+P0Sel front_p0_select(const FrontArgs &a);      // needs S, formats, gain, iq / dc / nco switches, step, agc_fused, agc_chunk_frames, agc_shift, dbg
+inline bool front_p0_shape(const FrontArgs &a) { return front_p0_select(a).ok; }
 void plan_front_p0(FrontArgs &a, int64_t wave_slots);   // after plan_front_s1 (256-frame tiles): needs phi0, step, frames_in, in_fmt
 hipError_t launch_front_p0(const FrontArgs &a, hipStream_t s);
 // two-stage chains (S = 2) with both half-bands and the polyphase in one kernel (front_s2.hip): a1 = the chain as k_cascade sees
 // it (K = 1), a2 = the last stage as k_front_s1 sees it, planned in ITS tiles (512 intermediate samples = 1024 input frames)
 int front_s2_waves();
 int64_t front_s2_mid_samples(const FrontArgs &a2);  // cf32 samples of the intermediate buffer it needs (edge waves only): needs the plan
-bool front_s2_shape(const FrontArgs &a1);          // needs casc_K, m[0], in_fmt
+struct S2Sel { bool ok; int BPS, M0, SPEC; };                      // k_front_s2<BPS, M0, SPEC>
+S2Sel front_s2_select(const FrontArgs &a1, const FrontArgs *a2);   // a2 == NULL: the chain shape alone (needs casc_K, m[0], in_fmt), SPEC = 0
+inline bool front_s2_shape(const FrontArgs &a1) { return front_s2_select(a1, nullptr).ok; }
 hipError_t launch_front_s2(const FrontArgs &a1, const FrontArgs &a2, hipStream_t s);
 // fills the w_* geometry from frames_in / rem0 / hist_cap / alignment (w_total_tiles must be set): at most
 // wave_slots runs in all (edge runs included) when fixed_tpw == 0, else streaming runs of fixed_tpw tiles
@@ -477,6 +553,10 @@ struct FftConvArgs {
     int32_t    win, vout;
     P0Feed     feed;
 };
+struct FftSel { bool ok; int LOG2N; bool LOOP; };                  // k_fftconv16<LOG2N, LOOP>; !ok: the radix-4 k_fftconv (below N = 1024, fft_no_r16)
+FftSel fftconv16_select(const FftConvArgs &a);
+struct P0FftSel { bool ok; int LOG2N, FMT, L3, L4, L2; };         // k_p0fft16<LOG2N, FMT, L3, L4, L2>
+P0FftSel p0fft_select(const FftConvArgs &a);
 hipError_t launch_fftconv(const FftConvArgs &a, hipStream_t s);
 // the geometry k_p0fft16 runs a filter of ntaps at N = 2^log2n with: false when no whole number of steps fits
 bool p0fft_geometry(int log2n, int ntaps, int *win, int *vout);

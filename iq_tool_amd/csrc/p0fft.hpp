@@ -217,48 +217,21 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) __attribute__((amdgpu_waves_per_
     }
 }
 
-template <int LOG2N, int FMT>
-static hipError_t launch_p0fft_n(const FftConvArgs &a, size_t lds, hipStream_t s)
-{
-    int l2 = 0, l3 = 0, l4 = 0;
-    if (!p0_class(a.feed.step, &l3, &l4, &l2)) return hipErrorInvalidValue;
-    const int64_t n_blocks = (a.n_emit + a.vout - 1) / a.vout;
-    unsigned grid = (unsigned)(n_blocks < (int64_t)a.feed.grid ? n_blocks : (int64_t)a.feed.grid);
-    if (grid == 0) grid = 1;                                          // (nothing to emit: the state of the next call is still due)
-    constexpr int T = (1 << LOG2N) / 16;
-#define IQGPU_LAUNCH_PF(FMT, L3, L4, L2)                                                                            \
-    do {                                                                                                              \
-        static LdsAttrCache cache;                /* per instantiation */                                          \
-        { const hipError_t e = cache.ensure((const void *)k_p0fft16<LOG2N, FMT, L3, L4, L2>, lds); if (e != hipSuccess) return e; } \
-        hipLaunchKernelGGL((k_p0fft16<LOG2N, FMT, L3, L4, L2>), dim3(grid), dim3(T), lds, s, a);                    \
-    } while (0)
-#define IQGPU_LAUNCH_PF_CLS(FMT)                                                                                    \
-    do {                                                                                                              \
-        if (l2 == 2 && l3 == 3 && l4 == 4) IQGPU_LAUNCH_PF(FMT, 3, 4, 2);                                           \
-        else if (l2 == 2 && l3 == 3) IQGPU_LAUNCH_PF(FMT, 3, 5, 2);                                                 \
-        else if (l2 == 2) IQGPU_LAUNCH_PF(FMT, 4, 5, 2);                                                            \
-        else if (l3 == 4) IQGPU_LAUNCH_PF(FMT, 4, 6, 3);                                                            \
-        else if (l4 == 6) IQGPU_LAUNCH_PF(FMT, 5, 6, 3);                                                            \
-        else IQGPU_LAUNCH_PF(FMT, 5, 7, 3);                                                                         \
-    } while (0)
-#ifdef IQGPU_P0FFT_QUICK
-    // (development builds: the one instantiation of the cu8-nrsc5-usb / -lsb presets -- the full set takes minutes to compile)
-    if (FMT == IQGPU_FMT_CU8 && l2 == 3 && l3 == 4 && l4 == 6) IQGPU_LAUNCH_PF(FMT, 4, 6, 3);
-    else return hipErrorInvalidValue;
-#else
-    IQGPU_LAUNCH_PF_CLS(FMT);
-#endif
-#undef IQGPU_LAUNCH_PF_CLS
-#undef IQGPU_LAUNCH_PF
-    return hipGetLastError();
-}
-
-
-// the launch for one input format (operands checked by launch_p0fft, fftconv.hip)
+// the launch for one input format (operands checked by launch_p0fft, fftconv.hip, which made the selection)
 template <int FMT>
 static hipError_t launch_p0fft_fmt(const FftConvArgs &a, size_t lds, hipStream_t s)
 {
-    return launch_p0fft_n<12, FMT>(a, lds, s);
+    const P0FftSel k = p0fft_select(a);
+    if (!k.ok || k.FMT != FMT) return hipErrorInvalidValue;
+    const int64_t n_blocks = (a.n_emit + a.vout - 1) / a.vout;
+    unsigned grid = (unsigned)(n_blocks < (int64_t)a.feed.grid ? n_blocks : (int64_t)a.feed.grid);
+    if (grid == 0) grid = 1;                                          // (nothing to emit: the state of the next call is still due)
+    return dispatch_int<12>(k.LOG2N, [&](auto LOG2N) { return dispatch_int<3, 4, 5>(k.L3, [&](auto L3) { return dispatch_int<4, 5, 6, 7>(k.L4, [&](auto L4) {
+        return dispatch_int<2, 3>(k.L2, [&](auto L2) {
+            if constexpr (p0fft_compiled(LOG2N.value, FMT, L3.value, L4.value, L2.value))
+                return launch_inst<k_p0fft16<LOG2N.value, FMT, L3.value, L4.value, L2.value>>(grid, (1u << LOG2N.value) / 16, lds, s, a);
+            else return hipErrorInvalidValue;
+        }); }); }); });
 }
 
 } // namespace iqgpu

@@ -216,17 +216,16 @@ int Call::stage_front()
             a.w_steal_stride = c->sw.steal_stride; a.w_steal_lanes = c->sw.steal_lanes; a.w_steal_rounds = 0;
             a.w_run_stride = wave_slots(front_mid_waves()) - a.w_n_edge;
         }
-        const int mid_nl = mid ? front_mid_nl(a) : 0;
-        a.tap_fold = (uint32_t)(fat ? c->tap_fold8 : mid ? (mid_nl == 8 ? c->tap_fold8 : c->tap_fold6) : 0);
-        a.nco_hold = (uint32_t)(mid ? (mid_nl == 8 ? c->nco_hold8 : c->nco_hold6) : 0);
+        const MidSel msel = mid ? front_mid_select(a) : MidSel{};
+        a.tap_fold = (uint32_t)(fat ? c->tap_fold8 : mid ? (msel.NL == 8 ? c->tap_fold8 : c->tap_fold6) : 0);
+        a.nco_hold = (uint32_t)(mid ? (msel.NL == 8 ? c->nco_hold8 : c->nco_hold6) : 0);
         // (k_front_p0: consecutive lanes are five outputs apart -- for the NRSC-5 step 16 arms -- so the lanes that re-read a slot in
         //  the same step would meet in two bank pairs of a linear plane: always the folded placement)
         if (p0) a.tap_fold = 1u;
         if (mid) {
-            const bool b8 = a.in_fmt == IQGPU_FMT_CU8 || a.in_fmt == IQGPU_FMT_CS8 || a.out_fmt == IQGPU_FMT_CU8 || a.out_fmt == IQGPU_FMT_CS8;
-            const bool n16 = (a.in_fmt == IQGPU_FMT_CS16 && a.gain != 1.0f) || a.in_fmt == IQGPU_FMT_SC16Q11;
-            snprintf(mid_name, sizeof(mid_name), "k_front_mid<%d,%s%s%s%s>", mid_nl, c->nco_mode ? "nco" : "nonco", a.out_fmt == IQGPU_FMT_CF32 ? ",cf32" : "",
-                     b8 ? ",8bit" : "", n16 ? ",gain" : "");
+            const bool b8 = msel.INF == IQGPU_FMT_CU8 || msel.INF == IQGPU_FMT_CS8 || msel.O8 != 0;
+            snprintf(mid_name, sizeof(mid_name), "k_front_mid<%d,%s%s%s%s>", msel.NL, msel.NONCO ? "nonco" : "nco", msel.CF ? ",cf32" : "",
+                     b8 ? ",8bit" : "", msel.INF == kMidN16 ? ",gain" : "");
         }
         { KernelTimer kt(c, IQGPU_K_FRONT); HIP_TRY(fat ? launch_front_fat(a, c->stream) : mid ? launch_front_mid(a, c->stream)
             : p0 ? launch_front_p0(a, c->stream) : launch_front_s1(a, c->stream)); }
@@ -274,12 +273,7 @@ int Call::stage_filter()
             f.arb_table = c->d_arb; f.step = c->rp.step; f.tap_fold = 1u; f.phi0 = c->phi;
             f.n_res = p.n_res; f.pre = (int64_t)(L1 + (size_t)c->fpending);
             // outputs whose 24-frame window load lies inside this call's input: q_k = (phi0 + k step) >> 24 in [13, frames_in - 11]
-            auto first_k = [&](int64_t pos) {
-                if (pos <= 0) return (int64_t)0;
-                const uint64_t target = (uint64_t)pos << 24;
-                return (int64_t)(target > c->phi ? (target - c->phi + (uint64_t)c->rp.step - 1) / (uint64_t)c->rp.step : 0);
-            };
-            f.k_a = first_k(13); f.k_b = first_k((int64_t)frames_in - 10);
+            f.k_a = first_k(c->phi, c->rp.step, 13); f.k_b = first_k(c->phi, c->rp.step, (int64_t)frames_in - 10);
             if (f.k_b > f.n_res) f.k_b = f.n_res;
             if (f.k_a > f.k_b) f.k_a = f.k_b;
             f.write_state = 1;
