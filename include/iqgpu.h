@@ -480,11 +480,69 @@ int    iqgpu_chain_dcagc_measure_device(iqgpu_chain *c, const void *d_raw_in, si
  * calls behind a seek may have any lengths.  Cost: the preroll, plus at most warm + C dependent loop steps on one lane.
  * Errors.  IQGPU_EINVAL: a chain without the output AGC, a NULL argument, a position beyond 2^39 frames, a preroll shorter than
  * min(first_frame, P_rms) or longer than first_frame.  IQGPU_EUNSUPPORTED: the digital profile (it has iqgpu_chain_seek_agc); a chain
- * with the DC blocker (its exact route needs a call grid and a walked state, iqgpu_chain_seek_dc; composing the two is not done
- * yet).  A refused seek leaves the chain reset. */
+ * with the DC blocker (its exact route needs a call grid and a walked state, iqgpu_chain_seek_dc; iqgpu_chain_dcrms_* below compose
+ * the two).  A refused seek leaves the chain reset. */
 int    iqgpu_design_preroll_frames_rms(const iqgpu_chain_desc *d, uint64_t *frames);
 int    iqgpu_chain_seek_rms(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames);
 int    iqgpu_chain_seek_rms_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames);
+/* ---- EXACT seamless range sharding of chains with the DC blocker AND the DX / LOCAL output AGC (additive, still ABI v9) ----
+ * The last chain shape without a seek: iqgpu_chain_seek_rms* refuses the blocker, iqgpu_chain_dc_measure* / _dc_advance / _seek_dc*
+ * refuse a chain with the AGC, iqgpu_chain_dcagc_* refuse dx / local -- and all of them keep doing so.  The calls below compose
+ * iqgpu_chain_seek_dc and iqgpu_chain_seek_rms.  Why they fit: a dx / local chain never cuts a call (only the digital profile has its
+ * gain fused into the chain's last kernel), so every call is ONE piece on the unfused route -- cf32 into the AGC's buffer, then the RMS
+ * kernels -- and the blocker's map of a call is one row, planned as that call.  iqgpu_chain_seek_rms needs the pre-AGC cf32 samples in
+ * front of the cut to be the single stream's bit for bit; behind the blocker they are only if the blocker's state is, which the 1e-6
+ * warm-up of iqgpu_chain_seek does not give: the state is walked and the preroll is made of the single stream's own calls, as for
+ * iqgpu_chain_seek_dc.  The cf32 outputs of those preroll calls are gathered contiguously on the device and k_agc_rms_seek runs over
+ * them as in iqgpu_chain_seek_rms.
+ * Contract: the union of the two.  The single stream is processed in calls on a grid of C frames (the last call may be shorter); C and
+ * every cut are multiples of 4096.  P = iqgpu_design_preroll_frames_dcrms = iqgpu_design_preroll_frames_rms of the description with
+ * dc_block_enable = 0.  The preroll of a range is the ceil(P / C) whole grid calls in front of its cut (all of [0, cut) when that is
+ * less), passed with call_frames = C, and dc_at_preroll_start is the walked state in front of the first of those calls.  With the
+ * _device variants give every call the alignment (mod 16 bytes) the single stream's call has.  Behind such a seek the SEAM CERTIFICATE
+ * of iqgpu_chain_seek_rms and its checkpoint fallback apply unchanged (a cut in or behind a stretch whose AGC output energy stays
+ * <= 1e-6 for more than a chunk does not certify; behind the blocker a constant input, digital silence included, comes out as the
+ * blocker's decaying state, which may or may not stay under that threshold).  The calls behind the seek are the grid's calls: the blocker's
+ * state is rounded once per call.  Placement: iqgpu_design_out_frames_range of the description with agc_enable = 0.
+ * Recipe:
+ *   1. DC measure (all ranges but the last, in parallel): iqgpu_chain_dcrms_dc_measure for every grid call, one row each, in order.
+ *   2. Walk (any one chain): st = {0, 0}; ONE iqgpu_chain_dcrms_dc_advance over all rows with before[]: before[k] is the state in
+ *      front of grid call k.
+ *   3. Process (all ranges in parallel): iqgpu_chain_dcrms_seek(c, cut, preroll, n C, C, &before[cut / C - n]), read S[s] =
+ *      iqgpu_chain_get_agc_state, then the ordinary process / process_device / submit loop over the range on the grid; read E[s] and
+ *      keep the iqgpu_chain_save_state blob.
+ *   4. The certificate per seam, in order (see iqgpu_chain_seek_rms): a range behind a seam that does not certify is redone from
+ *      iqgpu_chain_load_state of the range in front.
+ * Where the seams certify, the stitched bytes, the DC state and the AGC state are the single stream's bit for bit; elsewhere the
+ * fallback makes them so.
+ * FFT user filters.  iqgpu_chain_seek_rms certifies such a chain only where the single stream made the very call its preroll is.  Here
+ * the preroll calls ARE the single stream's calls (same position, same length, same pending samples, so the same overlap-save
+ * windows).  Observed (tests/test_gpu_seek_dcrms.py, shape local_fft_cf32: NRSC-5 rate, passband FFT filter, cf32 out, C = 65 536, cuts
+ * at 4 C and 10 C): both seams certified and the stitched bytes were the single stream's without the fallback.  This is an
+ * observation, not a promise: the certificate decides, and the fallback covers a seam that does not certify.
+ * iqgpu_design_preroll_frames_dcrms (no device): validation and error codes of iqgpu_design_probe, then IQGPU_EINVAL for a description
+ * without the blocker or without the AGC and IQGPU_EUNSUPPORTED for the digital profile.
+ * iqgpu_chain_dcrms_dc_measure[_device]: iqgpu_chain_dc_measure for these chains -- ONE row, the call planned as the ordinary call at
+ * first_frame, only k_dc_prefix and the scan launched, the handle left exactly as it was.
+ * iqgpu_chain_dcrms_dc_advance: iqgpu_chain_dc_advance's walk (same kernel, one definition, same row checks) for these chains.
+ * iqgpu_chain_dcrms_seek[_device]: reset; *dc_at_preroll_start (NULL: zero) becomes the blocker's state in front of the preroll; the
+ * preroll runs in calls of call_frames frames (0: one call), each staged like a call of iqgpu_chain_process, with the AGC out of the
+ * way and the I/Q probe left alone; then one launch of k_agc_rms_seek over the gathered cf32 samples leaves gain, peak_memory and
+ * samples_seen at first_frame, the last warm samples become the warm-up window of the calls to come, and iqgpu_chain_tell reports
+ * first_frame.  Preroll rule: min(first_frame, P) <= preroll_frames <= first_frame, a whole number of calls when call_frames != 0.
+ * first_frame == 0 leaves a fresh chain.  Returns with the stream idle.
+ * Errors.  IQGPU_EINVAL: a chain without the blocker or without the AGC; a NULL argument; a position beyond 2^39 frames; a preroll
+ * shorter than min(first_frame, P), longer than first_frame or not whole calls; a DC state that is not finite; a row
+ * iqgpu_chain_dc_advance refuses.  IQGPU_EUNSUPPORTED: the digital profile (iqgpu_chain_dcagc_*).  A refused seek leaves the chain
+ * reset; a refused measure leaves the handle as it was. */
+int    iqgpu_design_preroll_frames_dcrms(const iqgpu_chain_desc *d, uint64_t *frames);
+int    iqgpu_chain_dcrms_dc_measure(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, iqgpu_dc_row *row);
+int    iqgpu_chain_dcrms_dc_measure_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, iqgpu_dc_row *row);
+int    iqgpu_chain_dcrms_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before);
+int    iqgpu_chain_dcrms_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
+                              const iqgpu_dc_state *dc_at_preroll_start);
+int    iqgpu_chain_dcrms_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames, size_t call_frames,
+                                     const iqgpu_dc_state *dc_at_preroll_start);
 /* ---- checkpoint / resume: everything a chain carries from call to call, in a caller-owned blob (additive, still ABI v9) ----
  * The seek calls above rebuild the state at a stream position from a closed form and a preroll, and refuse what has no such form.
  * These two calls need none: iqgpu_chain_save_state copies the state out between two calls, iqgpu_chain_load_state puts it into a
@@ -582,9 +640,10 @@ int   iqgpu_iq_optimizer_touch(iqgpu_iq_optimizer *o, double now_sec); /* restar
  *      those at its submit).  While a block is staged and unread no later call replaces it; once read it is returned by every
  *      read until a later call has left the next one.  The block is the head of the whole call, however the library cuts it.
  *   2. Calls that are no chunk of the running stream neither leave a block nor occupy the slot: the preroll inside
- *      iqgpu_chain_seek*, _seek_agc*, _seek_dc*, _dcagc_seek*, _seek_rms*, and iqgpu_chain_measure, _measure_device, _measure_submit,
- *      _dc_measure*, _dcagc_dc_measure*, _dcagc_measure* (shadow calls leave no block).
- *   3. iqgpu_chain_reset, every iqgpu_chain_seek* (iqgpu_chain_dcagc_seek* and iqgpu_chain_seek_rms* too) and iqgpu_chain_load_state drop a staged or held block (it belongs to the
+ *      iqgpu_chain_seek*, _seek_agc*, _seek_dc*, _dcagc_seek*, _seek_rms*, _dcrms_seek*, and iqgpu_chain_measure, _measure_device,
+ *      _measure_submit, _dc_measure*, _dcagc_dc_measure*, _dcagc_measure* (shadow calls leave no block), _dcrms_dc_measure*.
+ *   3. iqgpu_chain_reset, every iqgpu_chain_seek* (iqgpu_chain_dcagc_seek*, iqgpu_chain_seek_rms* and iqgpu_chain_dcrms_seek* too) and
+ *      iqgpu_chain_load_state drop a staged or held block (it belongs to the
  *      stream position the chain leaves): *valid = 0 until the next call of rule 1.
  *   4. A call shorter than 1024 frames leaves the slot as it is. */
 int   iqgpu_chain_enable_iq_probe(iqgpu_chain *c, int enable);

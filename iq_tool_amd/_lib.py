@@ -155,6 +155,12 @@ SYMBOLS = [
     ("iqgpu_design_preroll_frames_rms", C.c_int, [C.POINTER(ChainDesc), C.POINTER(C.c_uint64)]),
     ("iqgpu_chain_seek_rms", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
     ("iqgpu_chain_seek_rms_device", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
+    ("iqgpu_design_preroll_frames_dcrms", C.c_int, [C.POINTER(ChainDesc), C.POINTER(C.c_uint64)]),
+    ("iqgpu_chain_dcrms_dc_measure", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
+    ("iqgpu_chain_dcrms_dc_measure_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
+    ("iqgpu_chain_dcrms_dc_advance", C.c_int, [_vp, C.POINTER(DcState), _vp, _sz, _vp]),
+    ("iqgpu_chain_dcrms_seek", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
+    ("iqgpu_chain_dcrms_seek_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
     ("iqgpu_design_state_size", C.c_int, [C.POINTER(ChainDesc), C.POINTER(_sz)]),
     ("iqgpu_state_inspect", C.c_int, [_vp, _sz, C.POINTER(StateInfo)]),
     ("iqgpu_chain_tell", C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -98,6 +98,15 @@ def design_preroll_frames_rms(desc=None, **kw):
     return int(n.value)
 
 
+def design_preroll_frames_dcrms(desc=None, **kw):
+    """P of Chain.dcrms_seek, for a chain with the DC blocker and the dx / local output AGC: design_preroll_frames_rms of the same
+    description without the blocker (iqgpu_design_preroll_frames_dcrms; no device needed).  desc: a ChainDesc, or make_desc keywords"""
+    d = desc if desc is not None else make_desc(**kw)
+    n = C.c_uint64(0)
+    check(_lib.load().iqgpu_design_preroll_frames_dcrms(C.byref(d), C.byref(n)))
+    return int(n.value)
+
+
 def design_out_frames_range(first_frame, frames_in, **kw):
     """(out_first, frames_out): what ONE stream of this description emits while it consumes input frames
     [first_frame, first_frame + frames_in) -- where a seamless shard's output goes and how long it is (no device needed)"""
@@ -491,6 +500,58 @@ class Chain:
         check(self._lib.iqgpu_chain_dcagc_measure_device(self._h, C.c_void_p(d_in), int(frames_in), rows.ctypes.data_as(C.c_void_p),
                                                          rows.size, C.byref(got)))
         return rows[:got.value]
+
+    # ---- exact seamless sharding of chains with the DC blocker AND the dx / local AGC (include/iqgpu.h, iqgpu_chain_dcrms_*) ----
+    def dcrms_dc_measure(self, first_frame, raw):
+        """dc_measure() for these chains: the map of the call process(raw) would be at stream frame first_frame, ONE DC_ROW record
+        (a dx / local chain never cuts a call); the chain itself stays exactly as it was"""
+        raw = np.ascontiguousarray(raw)
+        n = raw.nbytes // self.in_bytes
+        row = np.zeros((), DC_ROW)
+        check(self._lib.iqgpu_chain_dcrms_dc_measure(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n,
+                                                     row.ctypes.data_as(C.POINTER(_lib.DcRow))))
+        return row
+
+    def dcrms_dc_measure_device(self, first_frame, d_in, frames_in):
+        """dcrms_dc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
+        row = np.zeros((), DC_ROW)
+        check(self._lib.iqgpu_chain_dcrms_dc_measure_device(self._h, int(first_frame), C.c_void_p(d_in), int(frames_in),
+                                                            row.ctypes.data_as(C.POINTER(_lib.DcRow))))
+        return row
+
+    def dcrms_dc_advance(self, state, rows):
+        """dc_advance() for these chains: (state behind the last row, before) with before[k] the state in front of row k"""
+        rows = np.ascontiguousarray(rows, DC_ROW).reshape(-1)
+        st = np.zeros((), DC_STATE)
+        if state is not None:
+            st[...] = state
+        before = np.zeros(rows.size, DC_STATE)
+        check(self._lib.iqgpu_chain_dcrms_dc_advance(self._h, st.ctypes.data_as(C.POINTER(DcState)),
+                                                     rows.ctypes.data_as(C.c_void_p) if rows.size else None, rows.size,
+                                                     before.ctypes.data_as(C.c_void_p) if rows.size else None))
+        return st, before
+
+    def dcrms_seek(self, first_frame, preroll_raw=None, call_frames=0, dc_state=None):
+        """puts the chain at first_frame: `dc_state` (a DC_STATE record from dcrms_dc_advance; None: zero) is the blocker's state in
+        front of the preroll, which runs in calls of call_frames (0: one call) with the AGC out of the way; the AGC loop's state at
+        first_frame is then rebuilt from the preroll's own output, as by seek_rms -- and certified at the seam in the same way"""
+        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
+        n = raw.nbytes // self.in_bytes
+        st = None
+        if dc_state is not None:
+            st = np.zeros((), DC_STATE)
+            st[...] = dc_state
+        check(self._lib.iqgpu_chain_dcrms_seek(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n, int(call_frames),
+                                               st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
+
+    def dcrms_seek_device(self, first_frame, d_preroll, preroll_frames, call_frames=0, dc_state=None):
+        """dcrms_seek() with the preroll already in device memory of this chain's GPU (a device address as an int)"""
+        st = None
+        if dc_state is not None:
+            st = np.zeros((), DC_STATE)
+            st[...] = dc_state
+        check(self._lib.iqgpu_chain_dcrms_seek_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames), int(call_frames),
+                                                      st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
 
     # ---- checkpoint / resume (include/iqgpu.h): the whole carried state in a blob, into a chain of the same description ----
     def tell(self):

@@ -4,7 +4,7 @@
 //   plan.cpp       stream-position arithmetic (plan_call), per-call run geometry of the wave kernels (Call::plan_geometry)
 //   process.cpp    one process() call: buffers, the stages in stream order, iqgpu_chain_process[_device]
 //   seek.cpp       seamless range sharding: iqgpu_chain_seek[_agc | _dc], iqgpu_chain_measure, iqgpu_chain_agc_initial_state / _advance,
-//                  iqgpu_chain_dc_measure / _dc_advance, iqgpu_chain_dcagc_*
+//                  iqgpu_chain_dc_measure / _dc_advance, iqgpu_chain_dcagc_*, iqgpu_chain_dcrms_*
 //   agc_host.cpp   host side of the output AGC: chunk map, fused / unfused split, verifier + fallback launches
 //   pipeline.cpp   iqgpu_chain_submit / _measure_submit / _collect (pinned host buffers, three stages moved along by the host)
 //   state.cpp      checkpoint / resume: iqgpu_chain_tell, iqgpu_chain_save_state / _load_state, iqgpu_design_state_size (the blob's
@@ -202,6 +202,7 @@ struct iqgpu_chain {
     float *d_ihb = nullptr;
     DevBuf stage_in, stage_out;
     DevBuf seek_sink;             // where iqgpu_chain_seek's warm-up run writes what it emits (dropped)
+    DevBuf seek_win;              // iqgpu_chain_dcrms_seek: the cf32 output of all its preroll calls, contiguous, for k_agc_rms_seek
     // pipelined host entry point (iqgpu_chain_submit / _measure_submit / _collect): kPipeSlots batches in flight.  H2D copies,
     // kernels (the chain's stream) and D2H copies each have their own stream; a batch moves to the next stage inside a later
     // submit / collect, once the host has seen the previous stage finish (no device-side event waits: see pipe_advance)
@@ -279,7 +280,7 @@ uint64_t seek_preroll_frames(const iqgpu_chain *c, bool with_dc = true);
 // what iqgpu_chain_seek_rms asks for (dx / local): that FIR memory, plus input frames that make the chain emit at least
 // warm + chunk outputs wherever in the stream they lie (the closed form in iqgpu.h)
 uint64_t seek_rms_preroll_frames(const iqgpu_chain *c);
-int rms_seek_check(const iqgpu_chain *c, const char *who);      // an output AGC of profile dx / local, no DC blocker
+int rms_seek_check(const iqgpu_chain *c, const char *who);      // an output AGC of profile dx / local, no DC blocker (with it: iqgpu_chain_dcrms_seek)
 
 // ---- profiling (process.cpp): HIP events around every launch while profiling is on ----
 hipEvent_t get_event(iqgpu_chain *c);

@@ -58,6 +58,12 @@
  * (iqgpu_chain_dcagc_measure, synchronous).  Step 4: the AGC walk.  Step 5: every shard seeks with both states and runs the usual
  * chunk loop.  The stitched file is the file --shards 1 writes, byte for byte.
  *
+ * --shards N --seamless-dc-rms is the exact --seamless for chains with the DC blocker AND the dx / local output AGC (--dc-block
+ * --agc-profile dx|local): --seamless-dc's measure pass and walk (iqgpu_chain_dcrms_dc_measure, one row per call; one
+ * iqgpu_chain_dcrms_dc_advance), then --seamless-rms's pass: every shard seeks with iqgpu_chain_dcrms_seek -- a preroll of
+ * iqgpu_design_preroll_frames_dcrms frames rounded up to whole calls, entered with the walked state -- processes its range on the call
+ * grid, and the seams are certified in order, a range behind a seam that does not certify redone from the checkpoint in front.
+ *
  * --synthetic FRAMES [--synthetic-hash SEED]: no input file.  Without a seed one constant pinned buffer is sent again and again
  * (the PCIe-inclusive rate of the path, nothing else); with one, shard s is the stream frame n -> splitmix64((SEED + s) * K + n)
  * of its own (iq_tool_amd/synth.py hash_stream restates it): configs[4] at its real size -- 8 x 2.5 G frames -- without 80 GB of
@@ -83,13 +89,13 @@
 
 #define NBUF 2
 
-/* what the shards of a job are to each other: streams of their own, or ranges of ONE stream under one of the five recipes above */
-typedef enum { M_INDEPENDENT, M_SEAMLESS, M_AGC, M_DC, M_DC_AGC, M_RMS, M_COUNT } Mode;
+/* what the shards of a job are to each other: streams of their own, or ranges of ONE stream under one of the six recipes above */
+typedef enum { M_INDEPENDENT, M_SEAMLESS, M_AGC, M_DC, M_DC_AGC, M_RMS, M_DC_RMS, M_COUNT } Mode;
 
 /* What a mode asks of the command line and of the chain, each named after what it refuses: no --shards; a chain with / without the
- * output AGC; without the DC blocker; an AGC profile other than digital; an input that cannot be read twice; --chunk-frames 0 / not a
- * multiple of the AGC chunk.  validate() goes through a row's list in the row's order */
-enum { C_END, C_SHARDS, C_HAS_AGC, C_NO_AGC, C_NO_DC, C_PROFILE, C_TWICE, C_CHUNK0, C_CHUNK_AGC };
+ * output AGC; without the DC blocker; an AGC profile other than digital; the digital profile; an input that cannot be read twice;
+ * --chunk-frames 0 / not a multiple of the AGC chunk.  validate() goes through a row's list in the row's order */
+enum { C_END, C_SHARDS, C_HAS_AGC, C_NO_AGC, C_NO_DC, C_PROFILE, C_DIGITAL, C_TWICE, C_CHUNK0, C_CHUNK_AGC };
 /* the two stages the exact recipes carry a state for.  As bits: dc_block_enable / agc_enable cleared for a design query; rows predicted */
 enum { F_DC = 1, F_AGC = 2 };
 
@@ -104,6 +110,7 @@ typedef struct {
     const char *grid_words;           /* an empty shard is refused, with the grid in these words; NULL: it is planned */
     int barriers;                     /* rendezvous of the shard threads: two per walk */
     int dry_rows;                     /* F_*: the row counts --dry-placement predicts */
+    int certify;                      /* the seam certificate of the dx / local AGC: states and checkpoints kept, the seams checked after the join */
 } ModeRow;
 
 static const ModeRow MODES[M_COUNT] = {
@@ -120,7 +127,11 @@ static const ModeRow MODES[M_COUNT] = {
                   .preroll_fn = iqgpu_design_preroll_frames, .whole_calls = 1, .grid_words = " (lcm of 4096 and --chunk-frames)", .barriers = 4,
                   .dry_rows = F_DC | F_AGC},
     [M_RMS] = {.flag = "--seamless-rms", .json_key = "seamless_rms", .checks = {C_SHARDS, C_TWICE, C_CHUNK0}, .place_off = F_AGC,
-               .preroll_fn = iqgpu_design_preroll_frames_rms, .grid_words = ""},
+               .preroll_fn = iqgpu_design_preroll_frames_rms, .grid_words = "", .certify = 1},
+    [M_DC_RMS] = {.flag = "--seamless-dc-rms", .json_key = "seamless_dc_rms", .checks = {C_SHARDS, C_NO_DC, C_NO_AGC, C_DIGITAL, C_TWICE, C_CHUNK0},
+                  .sans_agc = "--seamless-dc", .sans_dc = "--seamless-rms", .grid_chunk = 1, .place_off = F_AGC,
+                  .preroll_fn = iqgpu_design_preroll_frames_dcrms, .whole_calls = 1, .grid_words = " (lcm of 4096 and --chunk-frames)", .barriers = 2,
+                  .dry_rows = F_DC, .certify = 1},
 };
 
 typedef struct {
@@ -156,7 +167,7 @@ typedef struct {
     iqgpu_dc_state dc_entry;                     /* the blocker's state in front of this shard's preroll, from the walk */
     unsigned char *dc_call_rows; long long n_dc_calls;   /* how many rows every call of the range gave (--seamless-dc-agc: 1 or 2) */
     double measure_seconds;
-    /* --seamless-rms: the AGC state right after the seek and behind the range, the checkpoint behind the range; redo_blob: this
+    /* --seamless-rms, --seamless-dc-rms: the AGC state right after the seek and behind the range, the checkpoint behind the range; redo_blob: this
      * range again from the checkpoint of the range in front (its seam did not certify) */
     iqgpu_agc_state rms_seek_state, rms_end_state;
     void *blob; size_t blob_bytes;
@@ -334,12 +345,13 @@ static int measure_agc_call(Ctx *x, long long at, size_t n)
     return 0;
 }
 
-/* the DC map of one call: one row (iqgpu_chain_dc_measure: no front kernel, no output), with the digital AGC one row per piece */
+/* the DC map of one call: one row (iqgpu_chain_dc_measure, _dcrms_dc_measure: no front kernel, no output), with the digital AGC one row per piece */
 static int measure_dc_call(Ctx *x, long long at, size_t n)
 {
     Shard *sh = x->sh;
     size_t got = 1;
     if (x->o->mode == M_DC) CK(iqgpu_chain_dc_measure(x->chain, (uint64_t)(sh->first_frame + at), x->h_in[0], n, &sh->dc_rows[sh->n_dc_rows]));
+    else if (x->o->mode == M_DC_RMS) CK(iqgpu_chain_dcrms_dc_measure(x->chain, (uint64_t)(sh->first_frame + at), x->h_in[0], n, &sh->dc_rows[sh->n_dc_rows]));
     else CK(iqgpu_chain_dcagc_dc_measure(x->chain, (uint64_t)(sh->first_frame + at), x->h_in[0], n, &sh->dc_rows[sh->n_dc_rows], 2, &got));
     sh->dc_call_rows[sh->n_dc_calls++] = (unsigned char)got;
     sh->n_dc_rows += (long long)got;
@@ -350,7 +362,7 @@ static int measure_dc_call(Ctx *x, long long at, size_t n)
 static int measure_dc(Ctx *x)
 {
     Shard *sh = x->sh;
-    const size_t calls = range_calls(x), most = (x->o->mode == M_DC ? 1 : 2) * calls;
+    const size_t calls = range_calls(x), most = (x->o->mode == M_DC_AGC ? 2 : 1) * calls;
     sh->dc_rows = (iqgpu_dc_row *)malloc((most + 1) * sizeof(iqgpu_dc_row));
     sh->dc_call_rows = (unsigned char *)malloc(calls + 1);
     if (!sh->dc_rows || !sh->dc_call_rows) FAIL("out of memory for a table of %zu rows", most);
@@ -379,8 +391,11 @@ static int walk_agc(Ctx *x)
 static int walk_dc(Ctx *x)
 {
     Shard *sh = x->sh;
-    const int shards = x->o->shards, plain = x->o->mode == M_DC;
-    const char *who = plain ? "iqgpu_chain_dc_advance" : "iqgpu_chain_dcagc_dc_advance";
+    const int shards = x->o->shards;
+    const Mode mode = x->o->mode;
+    const char *who = mode == M_DC ? "iqgpu_chain_dc_advance" : mode == M_DC_RMS ? "iqgpu_chain_dcrms_dc_advance" : "iqgpu_chain_dcagc_dc_advance";
+    int (*const advance)(iqgpu_chain *, iqgpu_dc_state *, const iqgpu_dc_row *, size_t, iqgpu_dc_state *) =
+        mode == M_DC ? iqgpu_chain_dc_advance : mode == M_DC_RMS ? iqgpu_chain_dcrms_dc_advance : iqgpu_chain_dcagc_dc_advance;
     int ok = 1;
     long long total = 0, total_calls = 0, k = 0, call = 0;
     for (int q = 0; q < shards; q++) { total += g_shards[q].n_dc_rows; total_calls += g_shards[q].n_dc_calls; }
@@ -396,7 +411,7 @@ static int walk_dc(Ctx *x)
         k += g_shards[q].n_dc_rows;
     }
     if (ok) first_row[call] = k;
-    if (ok && (plain ? iqgpu_chain_dc_advance : iqgpu_chain_dcagc_dc_advance)(x->chain, &st, all, (size_t)total, before) != IQGPU_OK) {
+    if (ok && advance(x->chain, &st, all, (size_t)total, before) != IQGPU_OK) {
         snprintf(sh->err, sizeof(sh->err), "%s: %s", who, iqgpu_last_error()); sh->rc = -1; ok = 0;
     }
     for (int q = 1; q < shards && ok; q++) {
@@ -562,6 +577,23 @@ static int enter_stream(Ctx *x)
         if (rendezvous(x, walk_agc, "the AGC measure pass or the walk of another shard failed")) return -1;
         CK(iqgpu_chain_dcagc_seek(x->chain, first, x->pre, x->np, x->chunk, &sh->dc_entry, &sh->entry));
         break;
+    case M_DC_RMS:
+        if (sh->redo_blob) {
+            /* the seam in front of this range did not certify: the range again, from where the range in front really ended (the
+             * measure pass, the walk and their rendezvous lie behind this shard: its first run has been through them) */
+            CK(iqgpu_chain_load_state(x->chain, sh->redo_blob, sh->redo_bytes));
+            break;
+        }
+        if (measures && measure_dc(x)) return -1;
+        sh->measure_seconds = now_s() - t_m;
+        if (rendezvous(x, walk_dc, "the measure pass or the walk of another shard failed")) return -1;
+        /* the chain at the start of the range, behind a preroll of whole calls entered with the walked state; its AGC state for the seam */
+        if (sh->first_frame > 0) {
+            if (load_preroll(x)) return -1;
+            CK(iqgpu_chain_dcrms_seek(x->chain, first, x->pre, x->np, x->chunk, &sh->dc_entry));
+            CK(iqgpu_chain_get_agc_state(x->chain, &sh->rms_seek_state));
+        }
+        break;
     }
     free(x->pre); x->pre = NULL;
     return 0;
@@ -611,7 +643,7 @@ static int stream_range(Ctx *x)
     return 0;
 }
 
-/* --seamless-rms: what the seam behind this range is checked against, and what the range behind it restarts from if the check fails */
+/* --seamless-rms, --seamless-dc-rms: what the seam behind this range is checked against, and what the range behind it restarts from if the check fails */
 static int save_checkpoint(Ctx *x)
 {
     Shard *sh = x->sh;
@@ -644,7 +676,7 @@ static void *run_shard(void *arg)
 
     if (o->dry) dry_shard(&x);
     else {
-        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && o->mode == M_RMS) save_checkpoint(&x);
+        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && MODES[o->mode].certify) save_checkpoint(&x);
         /* (a shard that fails early still keeps the rendezvous of the passes: the others wait there) */
         while (sh->barriers < MODES[o->mode].barriers) rendezvous(&x, NULL, NULL);
     }
@@ -665,6 +697,7 @@ static void usage(void)
             "          [--seamless-agc (--seamless for chains with the digital output AGC: a measure pass, one walk, then the ordinary pass)]\n"
             "          [--seamless-dc (the exact --seamless for --dc-block chains without an AGC: a measure pass over the input, one walk, then the ordinary pass)]\n"
             "          [--seamless-rms (--seamless for chains with the dx / local output AGC: seek from a bounded window, seams certified, a range behind a seam that is not is redone)]\n"
+            "          [--seamless-dc-rms (the exact --seamless for --dc-block chains with the dx / local AGC: DC measure, walk, then --seamless-rms's seek, certificate and redo)]\n"
             "          [--seamless-dc-agc (the exact --seamless for --dc-block chains with the digital AGC: DC measure, walk, shadow AGC measure, walk, then the ordinary pass)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
             "          [--dry-placement (plan the shards, bind every shard thread, size its buffers, report as JSON: no GPU call)]\n");
@@ -760,6 +793,8 @@ static int validate(const Options *o)
         "than its process route)%s\n", m->flag, o->desc.agc_profile == IQGPU_AGC_DIGITAL ? "; --seamless-agc shards it to the DC bound" : ""); break;
     case C_NO_AGC: if (!o->desc.agc_enable) REFUSE(1, "%s: the chain has no output AGC (use %s)\n", m->flag, m->sans_agc); break;
     case C_NO_DC: if (!o->desc.dc_block_enable) REFUSE(1, "%s: the chain has no DC blocker: give --dc-block, or use %s\n", m->flag, m->sans_dc); break;
+    case C_DIGITAL: if (o->desc.agc_profile == IQGPU_AGC_DIGITAL) REFUSE(1, "%s: the digital AGC profile works chunk by chunk; this mode is for the profiles "
+        "dx / local (use --seamless-dc-agc)\n", m->flag); break;
     case C_PROFILE: if (o->desc.agc_profile != IQGPU_AGC_DIGITAL) REFUSE(1, "%s: the AGC profiles dx / local carry a per-sample loop state that no table of "
         "per-chunk figures reproduces exactly; only the digital profile is sharded seamlessly\n", m->flag); break;
     /* (the passes have to read the SAME stream: the constant filling of a bare --synthetic is no stream, its buffers differ) */
@@ -829,7 +864,7 @@ static int plan_shards(const Options *o, Shard *sh, long long total_frames, size
     return 0;
 }
 
-/* --seamless-rms: the seam certificate (iqgpu.h), in order.  Shard s started from the state shard s-1 ended in, bit for bit: its
+/* --seamless-rms, --seamless-dc-rms: the seam certificate (iqgpu.h), in order.  Shard s started from the state shard s-1 ended in, bit for bit: its
  * bytes are the single stream's, given that shard s-1's are.  Otherwise its range again from shard s-1's checkpoint, in a thread
  * of its own like the first time, and the seam behind it is checked against the new end state.  seams: certified, ranges redone */
 static int certify_seams(const Options *o, Shard *sh, pthread_t *th, long long *frames_out, int seams[2])
@@ -858,7 +893,7 @@ static void mode_keys(char *kv, size_t cap, const Options *o, const Shard *sh, c
     if (o->mode == M_INDEPENDENT) return;
     if (!sh) {
         const int n = snprintf(kv, cap, "\"%s\": true, ", m->json_key);
-        if (o->mode == M_RMS && !o->dry) snprintf(kv + n, cap - (size_t)n, "\"seams\": %d, \"seams_certified\": %d, \"ranges_redone\": %d, ", o->shards - 1, seams[0], seams[1]);
+        if (m->certify && !o->dry) snprintf(kv + n, cap - (size_t)n, "\"seams\": %d, \"seams_certified\": %d, \"ranges_redone\": %d, ", o->shards - 1, seams[0], seams[1]);
         return;
     }
     int n = snprintf(kv, cap, ", \"preroll_frames\": %lld", sh->preroll_frames);
@@ -871,6 +906,12 @@ static void mode_keys(char *kv, size_t cap, const Options *o, const Shard *sh, c
     switch (o->mode) {
     case M_RMS:
         snprintf(kv, cap, ", \"certified\": %s, \"redone\": %s, \"end\": {\"peak_memory\": %.9g, \"current_gain\": %.9g, \"samples_seen\": %llu}",
+                 sh->certified ? "true" : "false", sh->redone ? "true" : "false", (double)sh->rms_end_state.peak_memory, (double)sh->rms_end_state.current_gain,
+                 (unsigned long long)sh->rms_end_state.samples_seen);
+        break;
+    case M_DC_RMS:
+        snprintf(kv, cap, ", \"measure_seconds\": %.6f, \"dc_rows\": %lld, \"dc_entry\": {\"re\": %.17g, \"im\": %.17g}, \"certified\": %s, \"redone\": %s, "
+                 "\"end\": {\"peak_memory\": %.9g, \"current_gain\": %.9g, \"samples_seen\": %llu}", sh->measure_seconds, sh->n_dc_rows, sh->dc_entry.re, sh->dc_entry.im,
                  sh->certified ? "true" : "false", sh->redone ? "true" : "false", (double)sh->rms_end_state.peak_memory, (double)sh->rms_end_state.current_gain,
                  (unsigned long long)sh->rms_end_state.samples_seen);
         break;
@@ -959,7 +1000,7 @@ int main(int argc, char **argv)
         if (sh[s].stream_seconds > stream_s) stream_s = sh[s].stream_seconds;
     }
     int seams[2] = {0, 0};
-    if (o.mode == M_RMS && !o.dry && rc == 0) rc = certify_seams(&o, sh, th, &frames_out, seams);
+    if (MODES[o.mode].certify && !o.dry && rc == 0) rc = certify_seams(&o, sh, th, &frames_out, seams);
     if (o.dry || !o.quiet) report(&o, sh, total_frames, frames_out, now_s() - t0, stream_s, seams);
     for (int s = 0; s < o.shards; s++) if (sh[s].rows) iqgpu_host_free_pinned(sh[s].rows);
     for (int s = 0; s < o.shards; s++) { free(sh[s].dc_rows); free(sh[s].dc_call_rows); free(sh[s].blob); }

@@ -155,7 +155,7 @@ int rms_seek_check(const iqgpu_chain *c, const char *who)
     if (!(c->agc_rms_alpha > 0.0f)) return fail(IQGPU_EUNSUPPORTED, "%s: the digital AGC profile works chunk by chunk and is sharded by "
         "iqgpu_chain_seek_agc; this call is for the profiles dx / local", who);
     if (c->dc) return fail(IQGPU_EUNSUPPORTED, "%s: a chain with the DC blocker -- its exact route needs a call grid and a walked state "
-        "(iqgpu_chain_seek_dc); the two are not composed yet", who);
+        "(iqgpu_chain_seek_dc); iqgpu_chain_dcrms_seek composes the two", who);
     return IQGPU_OK;
 }
 
@@ -167,6 +167,25 @@ extern "C" int iqgpu_design_preroll_frames_rms(const iqgpu_chain_desc *d, uint64
     if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
     int rc = design_chain(c, d);
     if (rc == IQGPU_OK) rc = rms_seek_check(c, "iqgpu_design_preroll_frames_rms");
+    if (rc == IQGPU_OK) *frames = seek_rms_preroll_frames(c);
+    delete c;
+    return rc;
+}
+
+// P of iqgpu_chain_dcrms_seek: P_rms of the same description without the blocker (the blocker has no part in the FIR memory or in the
+// output count: seek_rms_preroll_frames does not read it).  The refusals are those of iqgpu_chain_dcrms_seek
+extern "C" int iqgpu_design_preroll_frames_dcrms(const iqgpu_chain_desc *d, uint64_t *frames)
+{
+    const char *who = "iqgpu_design_preroll_frames_dcrms";
+    if (!d || !frames) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
+    *frames = 0;
+    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
+    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
+    int rc = design_chain(c, d);
+    if (rc == IQGPU_OK && !c->dc) rc = fail(IQGPU_EINVAL, "%s: the description has no DC blocker (without it: iqgpu_design_preroll_frames_rms)", who);
+    if (rc == IQGPU_OK && !c->agc) rc = fail(IQGPU_EINVAL, "%s: the description has no output AGC", who);
+    if (rc == IQGPU_OK && !(c->agc_rms_alpha > 0.0f)) rc = fail(IQGPU_EUNSUPPORTED, "%s: the digital AGC profile works chunk by chunk and is "
+        "sharded by iqgpu_chain_dcagc_*; this call is for the profiles dx / local", who);
     if (rc == IQGPU_OK) *frames = seek_rms_preroll_frames(c);
     delete c;
     return rc;

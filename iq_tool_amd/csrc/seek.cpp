@@ -14,7 +14,8 @@ static int two_pass_check(const iqgpu_chain *c, const char *who, unsigned needs)
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
     if ((needs & kNeedDc) && !c->dc) return fail(IQGPU_EINVAL, "%s: the chain has no DC blocker", who);
     if (needs == kNeedDc && c->agc) return fail(IQGPU_EUNSUPPORTED, "%s: a chain with the output AGC -- its measure route may cut a call into "
-        "other segments than the process route, so the two exact recipes do not combine yet", who);
+        "other segments than the process route, so the two exact recipes do not combine (such chains: iqgpu_chain_dcagc_* for the "
+        "digital profile, iqgpu_chain_dcrms_* for dx / local)", who);
     if (!(needs & kNeedAgc)) return IQGPU_OK;
     if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC", who);
     if (c->agc_rms_alpha > 0.0f) return fail(IQGPU_EUNSUPPORTED, "%s: the AGC profiles dx / local carry a per-sample loop state that no "
@@ -25,6 +26,19 @@ static int two_pass_check(const iqgpu_chain *c, const char *who, unsigned needs)
 }
 int agc_two_pass_check(const iqgpu_chain *c, const char *who) { return two_pass_check(c, who, kNeedAgc); }
 
+// what iqgpu_chain_dcrms_* ask of a chain: the DC blocker and the output AGC of profile dx / local.  Such a chain never cuts a call
+// (agc_fusable and agc_fusable_filter want the digital profile): every call runs whole on the unfused route, so the reason the DC
+// blocker's calls have to refuse an AGC chain does not hold for it
+static int dcrms_check(const iqgpu_chain *c, const char *who)
+{
+    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
+    if (!c->dc) return fail(IQGPU_EINVAL, "%s: the chain has no DC blocker (without it: iqgpu_chain_seek_rms)", who);
+    if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC (without it: iqgpu_chain_seek_dc)", who);
+    if (!(c->agc_rms_alpha > 0.0f)) return fail(IQGPU_EUNSUPPORTED, "%s: the digital AGC profile works chunk by chunk and is sharded by "
+        "iqgpu_chain_dcagc_*; this call is for the profiles dx / local", who);
+    return IQGPU_OK;
+}
+
 // Which seek is running, and what it was given beyond the position and the preroll.
 //   Plain  iqgpu_chain_seek: the preroll as ordinary calls, their output into seek_sink
 //   Agc    iqgpu_chain_seek_agc: the preroll with the AGC out of the way, then *agc_entry (or the fresh state) installed
@@ -33,13 +47,15 @@ int agc_two_pass_check(const iqgpu_chain *c, const char *who) { return two_pass_
 //   DcAgc  iqgpu_chain_dcagc_seek: both at once: the preroll as SHADOW calls (chain.hpp, AgcMode) from the host mirrors' closed form
 //   Rms    iqgpu_chain_seek_rms: dx / local: the preroll with the AGC out of the way and its cf32 output kept on the device, then the
 //          loop's state at first_frame from k_agc_rms_seek over those samples
-enum class SeekKind { Plain, Agc, Dc, DcAgc, Rms };
+//   DcRms  iqgpu_chain_dcrms_seek: Dc and Rms at once: *dc_at in front of a preroll in calls of call_frames, the cf32 output of every
+//          one of them gathered in seek_win, k_agc_rms_seek over that
+enum class SeekKind { Plain, Agc, Dc, DcAgc, Rms, DcRms };
 struct SeekRequest {
     SeekKind kind = SeekKind::Plain;
     bool on_device = false;                        // the preroll is in device memory
     const iqgpu_agc_state *agc_entry = nullptr;    // Agc, DcAgc
-    const iqgpu_dc_state *dc_at = nullptr;         // Dc, DcAgc
-    size_t call_frames = 0;                        // Dc, DcAgc
+    const iqgpu_dc_state *dc_at = nullptr;         // Dc, DcAgc, DcRms
+    size_t call_frames = 0;                        // Dc, DcAgc, DcRms
 };
 
 static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, const SeekRequest &rq)
@@ -55,8 +71,12 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
     case SeekKind::Dc:    who = "iqgpu_chain_seek_dc";    needs = kNeedDc;                                           break;
     case SeekKind::DcAgc: who = "iqgpu_chain_dcagc_seek"; needs = kNeedAgc | kNeedDc; preroll_agc = AgcMode::Shadow; break;
     case SeekKind::Rms:   who = "iqgpu_chain_seek_rms";                               preroll_agc = AgcMode::Drop;   break;
+    case SeekKind::DcRms: who = "iqgpu_chain_dcrms_seek";                             preroll_agc = AgcMode::Drop;   break;
     }
-    const bool with_agc = needs & kNeedAgc, with_dc = needs & kNeedDc, rms = rq.kind == SeekKind::Rms, shadow = preroll_agc == AgcMode::Shadow;
+    // (DcRms asks for the blocker and the AGC through dcrms_check, not through `needs`: those bits carry the digital profile's rules)
+    const bool dcrms = rq.kind == SeekKind::DcRms;
+    const bool with_agc = needs & kNeedAgc, with_dc = (needs & kNeedDc) || dcrms, rms = rq.kind == SeekKind::Rms || dcrms;
+    const bool shadow = preroll_agc == AgcMode::Shadow;
     const bool to_sink = preroll_agc == AgcMode::Ordinary;
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
     // what iqgpu_chain_reset does comes first: batches in flight and a pending verdict resolved, histories and dc state zeroed,
@@ -68,10 +88,10 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         const iqgpu_agc_state *e = rq.agc_entry;
         if (e && (e->locked != 0 && e->locked != 1)) return fail(IQGPU_EINVAL, "%s: entry state with locked = %d", who, e->locked);
     }
-    if (rms) { rc = rms_seek_check(c, who); if (rc) return rc; }
+    if (rms) { rc = dcrms ? dcrms_check(c, who) : rms_seek_check(c, who); if (rc) return rc; }
     cd2 dc_at{0.0, 0.0};
     if (with_dc) {
-        if (!with_agc) { rc = two_pass_check(c, who, needs); if (rc) return rc; }
+        if (!with_agc && !dcrms) { rc = two_pass_check(c, who, needs); if (rc) return rc; }
         if (rq.dc_at) { dc_at.x = rq.dc_at->re; dc_at.y = rq.dc_at->im; }
         if (!std::isfinite(dc_at.x) || !std::isfinite(dc_at.y)) return fail(IQGPU_EINVAL, "%s: the state in front of the preroll is not finite", who);
         if (rq.call_frames && preroll_frames % rq.call_frames != 0) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames is not a whole number "
@@ -100,7 +120,11 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     if (first_frame > 0) {
-        const StreamAt from = stream_at(c, first_frame - (uint64_t)preroll_frames);
+        const StreamAt from = stream_at(c, first_frame - (uint64_t)preroll_frames), to = stream_at(c, first_frame);
+        // DcRms: room for the cf32 output of ALL preroll calls, sized before the first launch (a failure here leaves the chain reset)
+        const size_t win_total = (size_t)(to.n_out - from.n_out);
+        size_t win_at = 0;
+        if (dcrms) { rc = c->seek_win.ensure((win_total + 1) * sizeof(cf2)); if (rc) return rc; }
         if (c->fp.enabled) {
             // [L-1 history][pending]: zeros stand for the samples in front of the warm-up
             const size_t front = c->fp.taps.size() - 1 + (size_t)from.pos.fpending;
@@ -112,7 +136,8 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         // (the preroll lies in front of the range the caller asked for: the I/Q probe takes no block from it and keeps its slot free
         //  for the head of the first call behind the seek)
         // Drop: nothing of the preroll is kept and the AGC must not see it: the unfused route into abuf, no AGC kernel behind it
-        // (rms: the call's cf32 samples stay in abuf, behind its lead of agc_rms_warm samples, for k_agc_rms_seek below).
+        // (rms: the call's cf32 samples stay in abuf, behind its lead of agc_rms_warm samples, for k_agc_rms_seek below; DcRms: every
+        //  call writes there, where the single stream's call writes, and its samples are copied behind those of the calls in front).
         // Shadow: cut as the single stream's calls are, from the mirrors the single stream has in front of the preroll
         CallOpts preroll_call; preroll_call.no_probe = true; preroll_call.agc = preroll_agc;
         if (shadow) agc_mirrors_at(c, first_frame - (uint64_t)preroll_frames, &c->agc_locked_host, &c->agc_seen_host);
@@ -128,12 +153,18 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             if (to_sink) { rc = c->seek_sink.ensure((size_t)plan_call(c, per).n_emit * obps + 16); if (rc) return rc; }
             rc = process_device_impl(c, d_in, per, to_sink ? c->seek_sink.p : nullptr, to_sink ? c->seek_sink.cap : 0, &dropped, preroll_call);
             if (rc) return rc;
+            if (dcrms) {
+                const hipError_t e = win_at + dropped <= win_total
+                    ? launch_copy_cf((cf2 *)c->seek_win.p + win_at, (const cf2 *)c->abuf.p + c->agc_rms_warm, (int64_t)dropped, c->stream)
+                    : hipErrorInvalidValue;
+                if (e != hipSuccess) { c->poisoned = true; return fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e)); }
+                win_at += dropped;
+            }
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
         // the warm-up has walked the position forward call-wise: it has to stand on the closed form at first_frame
-        const StreamAt to = stream_at(c, first_frame);
         if (c->rem != to.pos.rem || c->phi != to.pos.phi || c->fpending != to.pos.fpending || c->nco_theta != to.nco_theta ||
-            c->pnco_theta != to.pnco_theta) {
+            c->pnco_theta != to.pnco_theta || (dcrms && win_at != win_total)) {
             c->poisoned = true;
             return fail(IQGPU_EINVAL, "internal: the position behind the preroll is not the closed form at frame %llu", (unsigned long long)first_frame);
         }
@@ -152,13 +183,15 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             const int64_t a0 = (cut - 1) / ra.chunk * ra.chunk - ra.warm, start = a0 > 0 ? a0 : 0;
             const int64_t clean = (uint64_t)preroll_frames == first_frame ? 0
                 : (int64_t)stream_at(c, first_frame - (uint64_t)preroll_frames + seek_preroll_frames(c, false)).n_out;
-            if (clean > start || pos0 > start || (int64_t)c->abuf.cap < (W + cut - pos0) * (int64_t)sizeof(cf2)) {
+            const bool room = dcrms ? (int64_t)c->seek_win.cap >= (cut - pos0) * (int64_t)sizeof(cf2)
+                                    : (int64_t)c->abuf.cap >= (W + cut - pos0) * (int64_t)sizeof(cf2);
+            if (clean > start || pos0 > start || !room) {
                 c->poisoned = true;
                 return fail(IQGPU_EINVAL, "internal: the preroll's outputs [%lld, %lld) (exact from %lld) do not reach back to %lld, where the AGC "
                     "trajectory in front of frame %llu starts", (long long)pos0, (long long)cut, (long long)clean, (long long)start,
                     (unsigned long long)first_frame);
             }
-            ra.x = (const cf2 *)c->abuf.p + W; ra.n = cut - pos0; ra.pos0 = pos0; ra.hist_valid = 0;
+            ra.x = dcrms ? (const cf2 *)c->seek_win.p : (const cf2 *)c->abuf.p + W; ra.n = cut - pos0; ra.pos0 = pos0; ra.hist_valid = 0;
             ra.alpha = c->agc_rms_alpha; ra.state = c->d_agc_state;
             hipError_t e = launch_agc_rms_seek(ra, c->stream);
             // the warm-up window of the calls to come: the last W samples in front of the cut (a stream shorter than that: its own
@@ -234,6 +267,19 @@ extern "C" int iqgpu_chain_seek_dc_device(iqgpu_chain *c, uint64_t first_frame, 
     return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
 }
 
+extern "C" int iqgpu_chain_dcrms_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
+                                      const iqgpu_dc_state *dc_at_preroll_start)
+{
+    SeekRequest rq; rq.kind = SeekKind::DcRms; rq.dc_at = dc_at_preroll_start; rq.call_frames = call_frames;
+    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
+}
+extern "C" int iqgpu_chain_dcrms_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
+                                             size_t call_frames, const iqgpu_dc_state *dc_at_preroll_start)
+{
+    SeekRequest rq; rq.kind = SeekKind::DcRms; rq.on_device = true; rq.dc_at = dc_at_preroll_start; rq.call_frames = call_frames;
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
+}
+
 extern "C" int iqgpu_chain_dcagc_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
                                       const iqgpu_dc_state *dc_at_preroll_start, const iqgpu_agc_state *agc_entry)
 {
@@ -250,10 +296,13 @@ extern "C" int iqgpu_chain_dcagc_seek_device(iqgpu_chain *c, uint64_t first_fram
 // ------------------------------------------------------------------------------------------------
 // exact seamless sharding of DC-blocker chains: the map of a call (k_dc_prefix + k_dc_scan's map output), the walk over the maps
 // ------------------------------------------------------------------------------------------------
-static int dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const void *in, size_t frames_in, iqgpu_dc_row *row, bool on_device)
+// (dcrms: iqgpu_chain_dcrms_dc_measure -- the call of a dx / local chain is one piece on the unfused route, which is what
+//  dc_measure_call plans for a chain with the AGC: one row)
+static int dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const void *in, size_t frames_in, iqgpu_dc_row *row, bool on_device,
+                           bool dcrms = false)
 {
-    const char *who = "iqgpu_chain_dc_measure";
-    int rc = two_pass_check(c, who, kNeedDc); if (rc) return rc;
+    const char *who = dcrms ? "iqgpu_chain_dcrms_dc_measure" : "iqgpu_chain_dc_measure";
+    int rc = dcrms ? dcrms_check(c, who) : two_pass_check(c, who, kNeedDc); if (rc) return rc;
     if (!row) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     if (first_frame > kMaxStreamFrames || (uint64_t)frames_in > kMaxStreamFrames - first_frame) return fail(IQGPU_EINVAL, "%s: stream position "
         "%llu + %zu frames is beyond 2^39 frames", who, (unsigned long long)first_frame, frames_in);
@@ -282,14 +331,24 @@ extern "C" int iqgpu_chain_dc_measure_device(iqgpu_chain *c, uint64_t first_fram
 {
     return dc_measure_impl(c, first_frame, d_raw_in, frames_in, row, true);
 }
+extern "C" int iqgpu_chain_dcrms_dc_measure(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, iqgpu_dc_row *row)
+{
+    return dc_measure_impl(c, first_frame, raw_in, frames_in, row, false, true);
+}
+extern "C" int iqgpu_chain_dcrms_dc_measure_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, iqgpu_dc_row *row)
+{
+    return dc_measure_impl(c, first_frame, d_raw_in, frames_in, row, true, true);
+}
 
 // One definition of the walk: k_dc_walk applies the helper behind k_dc_scan's state update, in the translation unit of k_dc_scan, a
 // batch of 2^16 rows per launch from a scratch copy of *st
-static int dc_advance_impl(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before, bool dcagc)
+enum class DcWalk { Dc, DcAgc, DcRms };      // whose walk: iqgpu_chain_dc_advance, _dcagc_dc_advance, _dcrms_dc_advance
+static int dc_advance_impl(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before, DcWalk family)
 {
     static_assert(sizeof(iqgpu_dc_row) == sizeof(DcMapRow) && sizeof(DcMapRow) == 32 && sizeof(iqgpu_dc_state) == sizeof(cd2), "DC row layout");
-    const char *who = dcagc ? "iqgpu_chain_dcagc_dc_advance" : "iqgpu_chain_dc_advance";
-    int rc = two_pass_check(c, who, dcagc ? kNeedDc | kNeedAgc : kNeedDc); if (rc) return rc;
+    const bool dcagc = family == DcWalk::DcAgc, dcrms = family == DcWalk::DcRms;
+    const char *who = dcrms ? "iqgpu_chain_dcrms_dc_advance" : dcagc ? "iqgpu_chain_dcagc_dc_advance" : "iqgpu_chain_dc_advance";
+    int rc = dcrms ? dcrms_check(c, who) : two_pass_check(c, who, dcagc ? kNeedDc | kNeedAgc : kNeedDc); if (rc) return rc;
     if (!st || (n && !rows)) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     if (!std::isfinite(st->re) || !std::isfinite(st->im)) return fail(IQGPU_EINVAL, "%s: the state is not finite", who);
     for (size_t i = 0; i < n; ++i)
@@ -321,11 +380,15 @@ static int dc_advance_impl(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_ro
 
 extern "C" int iqgpu_chain_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
 {
-    return dc_advance_impl(c, st, rows, n, before, false);
+    return dc_advance_impl(c, st, rows, n, before, DcWalk::Dc);
 }
 extern "C" int iqgpu_chain_dcagc_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
 {
-    return dc_advance_impl(c, st, rows, n, before, true);
+    return dc_advance_impl(c, st, rows, n, before, DcWalk::DcAgc);
+}
+extern "C" int iqgpu_chain_dcrms_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
+{
+    return dc_advance_impl(c, st, rows, n, before, DcWalk::DcRms);
 }
 
 // iqgpu_chain_dcagc_dc_measure: the maps of the ordinary call at first_frame, ONE ROW PER PIECE -- the call is cut as
