@@ -107,6 +107,14 @@ class IqgpuError(RuntimeError):
 
 # every symbol include/iqgpu.h declares: (name, restype, argtypes)
 _vp, _sz = C.c_void_p, C.c_size_t
+
+
+
+def _with_device(name, res, args):
+    """an entry point that takes host memory and its _device form: the same signature"""
+    return (name, res, args), (name + "_device", res, args)
+
+
 SYMBOLS = [
     ("iqgpu_abi_version", C.c_int, []),
     ("iqgpu_last_error", C.c_char_p, []),
@@ -123,44 +131,32 @@ SYMBOLS = [
     ("iqgpu_design_out_frames", C.c_int, [C.POINTER(ChainDesc), _sz, C.POINTER(_sz)]),
     ("iqgpu_design_preroll_frames", C.c_int, [C.POINTER(ChainDesc), C.POINTER(C.c_uint64)]),
     ("iqgpu_design_out_frames_range", C.c_int, [C.POINTER(ChainDesc), C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
-    ("iqgpu_chain_process", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
-    ("iqgpu_chain_process_device", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    *_with_device("iqgpu_chain_process", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     ("iqgpu_chain_submit", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64)]),
     ("iqgpu_chain_collect", C.c_int, [_vp, C.c_uint64]),
     ("iqgpu_chain_pipeline_depth", C.c_int, []),
     ("iqgpu_chain_reset", C.c_int, [_vp]),
-    ("iqgpu_chain_seek", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
-    ("iqgpu_chain_seek_device", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
-    ("iqgpu_chain_measure", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
-    ("iqgpu_chain_measure_device", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    *_with_device("iqgpu_chain_seek", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
+    *_with_device("iqgpu_chain_measure", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     ("iqgpu_chain_measure_submit", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz), C.POINTER(C.c_uint64)]),
     ("iqgpu_chain_agc_advance", C.c_int, [_vp, C.POINTER(AgcState), _vp, _sz, _vp]),
     ("iqgpu_chain_agc_initial_state", C.c_int, [_vp, C.POINTER(AgcState)]),
-    ("iqgpu_chain_seek_agc", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(AgcState)]),
-    ("iqgpu_chain_seek_agc_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(AgcState)]),
+    *_with_device("iqgpu_chain_seek_agc", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(AgcState)]),
     ("iqgpu_chain_get_agc_state", C.c_int, [_vp, C.POINTER(AgcState)]),
     ("iqgpu_chain_get_dc_state", C.c_int, [_vp, C.POINTER(DcState)]),
-    ("iqgpu_chain_dc_measure", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
-    ("iqgpu_chain_dc_measure_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
+    *_with_device("iqgpu_chain_dc_measure", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
     ("iqgpu_chain_dc_advance", C.c_int, [_vp, C.POINTER(DcState), _vp, _sz, _vp]),
-    ("iqgpu_chain_seek_dc", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
-    ("iqgpu_chain_seek_dc_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
-    ("iqgpu_chain_dcagc_dc_measure", C.c_int, [_vp, C.c_uint64, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
-    ("iqgpu_chain_dcagc_dc_measure_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    *_with_device("iqgpu_chain_seek_dc", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
+    *_with_device("iqgpu_chain_dcagc_dc_measure", C.c_int, [_vp, C.c_uint64, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     ("iqgpu_chain_dcagc_dc_advance", C.c_int, [_vp, C.POINTER(DcState), _vp, _sz, _vp]),
-    ("iqgpu_chain_dcagc_seek", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState), C.POINTER(AgcState)]),
-    ("iqgpu_chain_dcagc_seek_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState), C.POINTER(AgcState)]),
-    ("iqgpu_chain_dcagc_measure", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
-    ("iqgpu_chain_dcagc_measure_device", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
+    *_with_device("iqgpu_chain_dcagc_seek", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState), C.POINTER(AgcState)]),
+    *_with_device("iqgpu_chain_dcagc_measure", C.c_int, [_vp, _vp, _sz, _vp, _sz, C.POINTER(_sz)]),
     ("iqgpu_design_preroll_frames_rms", C.c_int, [C.POINTER(ChainDesc), C.POINTER(C.c_uint64)]),
-    ("iqgpu_chain_seek_rms", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
-    ("iqgpu_chain_seek_rms_device", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
+    *_with_device("iqgpu_chain_seek_rms", C.c_int, [_vp, C.c_uint64, _vp, _sz]),
     ("iqgpu_design_preroll_frames_dcrms", C.c_int, [C.POINTER(ChainDesc), C.POINTER(C.c_uint64)]),
-    ("iqgpu_chain_dcrms_dc_measure", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
-    ("iqgpu_chain_dcrms_dc_measure_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
+    *_with_device("iqgpu_chain_dcrms_dc_measure", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
     ("iqgpu_chain_dcrms_dc_advance", C.c_int, [_vp, C.POINTER(DcState), _vp, _sz, _vp]),
-    ("iqgpu_chain_dcrms_seek", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
-    ("iqgpu_chain_dcrms_seek_device", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
+    *_with_device("iqgpu_chain_dcrms_seek", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
     ("iqgpu_design_state_size", C.c_int, [C.POINTER(ChainDesc), C.POINTER(_sz)]),
     ("iqgpu_state_inspect", C.c_int, [_vp, _sz, C.POINTER(StateInfo)]),
     ("iqgpu_chain_tell", C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

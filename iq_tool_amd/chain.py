@@ -252,13 +252,65 @@ class Chain:
     def reset(self):
         check(self._lib.iqgpu_chain_reset(self._h))
 
+    # ---- marshalling the seamless-sharding calls below share ----
+    def _host_input(self, preroll_raw):
+        """(pointer or None, frames) of raw frames on the host: a call's input, or a seek's preroll (None: no frames).  The pointer
+        keeps the array alive (ndarray.ctypes.data_as)"""
+        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
+        n = raw.nbytes // self.in_bytes
+        return (raw.ctypes.data_as(C.c_void_p) if n else None), n
+
+    @staticmethod
+    def _dc_ptr(state):
+        """a DC_STATE record as the POINTER(DcState) the library takes, or None (zero)"""
+        if state is None:
+            return None
+        st = np.zeros((), DC_STATE)
+        st[...] = state
+        return st.ctypes.data_as(C.POINTER(DcState))
+
+    @staticmethod
+    def _agc_ptr(entry):
+        return C.byref(entry) if entry is not None else None
+
+    def _agc_rows(self, frames):
+        """an empty AGC_ROW table for a call of `frames` input frames: one row per chunk"""
+        chunk = int(self.desc.agc_chunk_frames) or 16384
+        return np.zeros(-(-int(frames) // chunk), AGC_ROW)
+
+    def _measure(self, fn, ptr, n):
+        """measure, dcagc_measure and their _device forms: the rows the call has filled"""
+        rows = self._agc_rows(n)
+        got = C.c_size_t(0)
+        check(fn(self._h, ptr, n, rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
+        return rows[:got.value]
+
+    def _dc_measure(self, fn, first_frame, ptr, n):
+        row = np.zeros((), DC_ROW)
+        check(fn(self._h, int(first_frame), ptr, n, row.ctypes.data_as(C.POINTER(_lib.DcRow))))
+        return row
+
+    def _dcagc_dc_measure(self, fn, first_frame, ptr, n):
+        rows = np.zeros(2, DC_ROW)
+        got = C.c_size_t(0)
+        check(fn(self._h, int(first_frame), ptr, n, rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
+        return rows[:got.value]
+
+    def _dc_advance(self, fn, state, rows):
+        rows = np.ascontiguousarray(rows, DC_ROW).reshape(-1)
+        st = np.zeros((), DC_STATE)
+        if state is not None:
+            st[...] = state
+        before = np.zeros(rows.size, DC_STATE)
+        check(fn(self._h, st.ctypes.data_as(C.POINTER(DcState)), rows.ctypes.data_as(C.c_void_p) if rows.size else None, rows.size,
+                 before.ctypes.data_as(C.c_void_p) if rows.size else None))
+        return st, before
+
     def seek(self, first_frame, preroll_raw=None):
         """puts the chain at frame first_frame of the stream: preroll_raw is a numpy array with the input frames that END at
         first_frame (at least min(first_frame, design_preroll_frames) of them); what the chain emits afterwards is what one chain
         emits behind frames [0, first_frame) (iqgpu_chain_seek)"""
-        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
-        n = raw.nbytes // self.in_bytes
-        check(self._lib.iqgpu_chain_seek(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n))
+        check(self._lib.iqgpu_chain_seek(self._h, int(first_frame), *self._host_input(preroll_raw)))
 
     def seek_device(self, first_frame, d_preroll, preroll_frames):
         """seek() with the preroll already in device memory of this chain's GPU (a device address as an int)"""
@@ -268,23 +320,11 @@ class Chain:
     def measure(self, raw):
         """consumes raw exactly as process() would, emits nothing, leaves the AGC state alone; returns one AGC_ROW record per
         agc_chunk_frames-sized chunk of this call: the peak (squared, double) in front of the gain and the chunk's frames"""
-        raw = np.ascontiguousarray(raw)
-        n = raw.nbytes // self.in_bytes
-        chunk = int(self.desc.agc_chunk_frames) or 16384
-        rows = np.zeros(-(-n // chunk), AGC_ROW)
-        got = C.c_size_t(0)
-        check(self._lib.iqgpu_chain_measure(self._h, raw.ctypes.data_as(C.c_void_p) if n else None, n,
-                                            rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
-        return rows[:got.value]
+        return self._measure(self._lib.iqgpu_chain_measure, *self._host_input(raw))
 
     def measure_device(self, d_in, frames_in):
         """measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
-        chunk = int(self.desc.agc_chunk_frames) or 16384
-        rows = np.zeros(-(-int(frames_in) // chunk), AGC_ROW)
-        got = C.c_size_t(0)
-        check(self._lib.iqgpu_chain_measure_device(self._h, C.c_void_p(d_in), int(frames_in), rows.ctypes.data_as(C.c_void_p), rows.size,
-                                                   C.byref(got)))
-        return rows[:got.value]
+        return self._measure(self._lib.iqgpu_chain_measure_device, C.c_void_p(d_in), int(frames_in))
 
     def measure_submit(self, in_ptr, frames_in, rows_ptr, cap):
         """measure() through the pipeline of submit(): queues one batch (host addresses, preferably pinned; rows_ptr holds cap
@@ -301,8 +341,7 @@ class Chain:
         raw = np.ascontiguousarray(raw).view(np.uint8).reshape(-1)
         n = raw.nbytes // self.in_bytes
         depth = self._lib.iqgpu_chain_pipeline_depth()
-        chunk = int(self.desc.agc_chunk_frames) or 16384
-        cap = -(-int(batch_frames) // chunk)
+        cap = self._agc_rows(batch_frames).size
         slots = [(PinnedBuffer(batch_frames * self.in_bytes), PinnedBuffer(cap * AGC_ROW.itemsize)) for _ in range(depth)]
         outs, flight = [], []
 
@@ -345,14 +384,10 @@ class Chain:
     def seek_agc(self, first_frame, preroll_raw=None, entry=None):
         """seek() for a chain with the digital AGC: the preroll runs with the AGC out of the way, then the chain carries `entry`
         (an AgcState from agc_advance) as its AGC state; entry None leaves the fresh state, which is all a measuring chain needs"""
-        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
-        n = raw.nbytes // self.in_bytes
-        check(self._lib.iqgpu_chain_seek_agc(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n,
-                                             C.byref(entry) if entry is not None else None))
+        check(self._lib.iqgpu_chain_seek_agc(self._h, int(first_frame), *self._host_input(preroll_raw), self._agc_ptr(entry)))
 
     def seek_agc_device(self, first_frame, d_preroll, preroll_frames, entry=None):
-        check(self._lib.iqgpu_chain_seek_agc_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames),
-                                                    C.byref(entry) if entry is not None else None))
+        check(self._lib.iqgpu_chain_seek_agc_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames), self._agc_ptr(entry)))
 
     # ---- seamless sharding of dx / local AGC chains: a bounded window, certified at the seam (include/iqgpu.h) ----
     def seek_rms(self, first_frame, preroll_raw=None):
@@ -360,9 +395,7 @@ class Chain:
         min(first_frame, design_preroll_frames_rms) of them; the AGC loop's state at first_frame is rebuilt from the preroll's own
         output.  The seam is certified when agc_state_raw() right after this call equals, in gain, peak_memory and samples_seen, the
         state of the chain that processed the range in front; otherwise load_state() that chain's blob and process the range again"""
-        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
-        n = raw.nbytes // self.in_bytes
-        check(self._lib.iqgpu_chain_seek_rms(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n))
+        check(self._lib.iqgpu_chain_seek_rms(self._h, int(first_frame), *self._host_input(preroll_raw)))
 
     def seek_rms_device(self, first_frame, d_preroll, preroll_frames):
         """seek_rms() with the preroll already in device memory of this chain's GPU (a device address as an int)"""
@@ -378,180 +411,85 @@ class Chain:
     def dc_measure(self, first_frame, raw):
         """the map v_after = f v_before + g of the call process(raw) would be at stream frame first_frame, as a DC_ROW record;
         the chain itself stays exactly as it was"""
-        raw = np.ascontiguousarray(raw)
-        n = raw.nbytes // self.in_bytes
-        row = np.zeros((), DC_ROW)
-        check(self._lib.iqgpu_chain_dc_measure(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n,
-                                               row.ctypes.data_as(C.POINTER(_lib.DcRow))))
-        return row
+        return self._dc_measure(self._lib.iqgpu_chain_dc_measure, first_frame, *self._host_input(raw))
 
     def dc_measure_device(self, first_frame, d_in, frames_in):
         """dc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
-        row = np.zeros((), DC_ROW)
-        check(self._lib.iqgpu_chain_dc_measure_device(self._h, int(first_frame), C.c_void_p(d_in), int(frames_in),
-                                                      row.ctypes.data_as(C.POINTER(_lib.DcRow))))
-        return row
+        return self._dc_measure(self._lib.iqgpu_chain_dc_measure_device, first_frame, C.c_void_p(d_in), int(frames_in))
 
     def dc_advance(self, state, rows):
         """walks a DC state (a DC_STATE record, or None for zero) over dc_measure() rows on the device: returns (state behind the
         last row, before) where before[k] is the state in front of row k"""
-        rows = np.ascontiguousarray(rows, DC_ROW).reshape(-1)
-        st = np.zeros((), DC_STATE)
-        if state is not None:
-            st[...] = state
-        before = np.zeros(rows.size, DC_STATE)
-        check(self._lib.iqgpu_chain_dc_advance(self._h, st.ctypes.data_as(C.POINTER(DcState)),
-                                               rows.ctypes.data_as(C.c_void_p) if rows.size else None, rows.size,
-                                               before.ctypes.data_as(C.c_void_p) if rows.size else None))
-        return st, before
+        return self._dc_advance(self._lib.iqgpu_chain_dc_advance, state, rows)
 
     def seek_dc(self, first_frame, preroll_raw=None, call_frames=0, state=None):
         """seek() for a chain with the DC blocker, exact: the preroll is only the filters' memory, it runs in calls of call_frames
         (0: one call) and `state` (a DC_STATE record from dc_advance; None: zero) is the blocker's state in front of it"""
-        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
-        n = raw.nbytes // self.in_bytes
-        st = None
-        if state is not None:
-            st = np.zeros((), DC_STATE)
-            st[...] = state
-        check(self._lib.iqgpu_chain_seek_dc(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n, int(call_frames),
-                                            st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
+        check(self._lib.iqgpu_chain_seek_dc(self._h, int(first_frame), *self._host_input(preroll_raw), int(call_frames), self._dc_ptr(state)))
 
     def seek_dc_device(self, first_frame, d_preroll, preroll_frames, call_frames=0, state=None):
-        st = None
-        if state is not None:
-            st = np.zeros((), DC_STATE)
-            st[...] = state
         check(self._lib.iqgpu_chain_seek_dc_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames), int(call_frames),
-                                                   st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
+                                                   self._dc_ptr(state)))
 
     # ---- exact seamless sharding of chains with the DC blocker AND the digital AGC (include/iqgpu.h, iqgpu_chain_dcagc_*) ----
     def dcagc_dc_measure(self, first_frame, raw):
         """the DC maps of the call process(raw) would be at stream frame first_frame: DC_ROW records, ONE PER PIECE (two for the
         call the stream cuts at the AGC's lock), in order; the chain itself stays exactly as it was"""
-        raw = np.ascontiguousarray(raw)
-        n = raw.nbytes // self.in_bytes
-        rows = np.zeros(2, DC_ROW)
-        got = C.c_size_t(0)
-        check(self._lib.iqgpu_chain_dcagc_dc_measure(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n,
-                                                     rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
-        return rows[:got.value]
+        return self._dcagc_dc_measure(self._lib.iqgpu_chain_dcagc_dc_measure, first_frame, *self._host_input(raw))
 
     def dcagc_dc_measure_device(self, first_frame, d_in, frames_in):
         """dcagc_dc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
-        rows = np.zeros(2, DC_ROW)
-        got = C.c_size_t(0)
-        check(self._lib.iqgpu_chain_dcagc_dc_measure_device(self._h, int(first_frame), C.c_void_p(d_in), int(frames_in),
-                                                            rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
-        return rows[:got.value]
+        return self._dcagc_dc_measure(self._lib.iqgpu_chain_dcagc_dc_measure_device, first_frame, C.c_void_p(d_in), int(frames_in))
 
     def dcagc_dc_advance(self, state, rows):
         """dc_advance() for these chains: (state behind the last row, before) with before[k] the state in front of row k"""
-        rows = np.ascontiguousarray(rows, DC_ROW).reshape(-1)
-        st = np.zeros((), DC_STATE)
-        if state is not None:
-            st[...] = state
-        before = np.zeros(rows.size, DC_STATE)
-        check(self._lib.iqgpu_chain_dcagc_dc_advance(self._h, st.ctypes.data_as(C.POINTER(DcState)),
-                                                     rows.ctypes.data_as(C.c_void_p) if rows.size else None, rows.size,
-                                                     before.ctypes.data_as(C.c_void_p) if rows.size else None))
-        return st, before
+        return self._dc_advance(self._lib.iqgpu_chain_dcagc_dc_advance, state, rows)
 
     def dcagc_seek(self, first_frame, preroll_raw=None, call_frames=0, dc_state=None, entry=None):
         """puts the chain at first_frame, exact in both states: `dc_state` (a DC_STATE record from dcagc_dc_advance; None: zero) is
         the blocker's state in front of the preroll, which runs as shadow calls of call_frames (0: one call); then the chain carries
         `entry` (an AgcState from agc_advance; None: the fresh state, for a measuring chain)"""
-        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
-        n = raw.nbytes // self.in_bytes
-        st = None
-        if dc_state is not None:
-            st = np.zeros((), DC_STATE)
-            st[...] = dc_state
-        check(self._lib.iqgpu_chain_dcagc_seek(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n, int(call_frames),
-                                               st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None,
-                                               C.byref(entry) if entry is not None else None))
+        check(self._lib.iqgpu_chain_dcagc_seek(self._h, int(first_frame), *self._host_input(preroll_raw), int(call_frames),
+                                               self._dc_ptr(dc_state), self._agc_ptr(entry)))
 
     def dcagc_seek_device(self, first_frame, d_preroll, preroll_frames, call_frames=0, dc_state=None, entry=None):
-        st = None
-        if dc_state is not None:
-            st = np.zeros((), DC_STATE)
-            st[...] = dc_state
         check(self._lib.iqgpu_chain_dcagc_seek_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames), int(call_frames),
-                                                      st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None,
-                                                      C.byref(entry) if entry is not None else None))
+                                                      self._dc_ptr(dc_state), self._agc_ptr(entry)))
 
     def dcagc_measure(self, raw):
         """the AGC_ROW records of the call process(raw) would be at the chain's position, as a shadow call: consumes raw like
         process() (position, histories, DC state), emits nothing, leaves the AGC state alone"""
-        raw = np.ascontiguousarray(raw)
-        n = raw.nbytes // self.in_bytes
-        chunk = int(self.desc.agc_chunk_frames) or 16384
-        rows = np.zeros(-(-n // chunk), AGC_ROW)
-        got = C.c_size_t(0)
-        check(self._lib.iqgpu_chain_dcagc_measure(self._h, raw.ctypes.data_as(C.c_void_p) if n else None, n,
-                                                  rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
-        return rows[:got.value]
+        return self._measure(self._lib.iqgpu_chain_dcagc_measure, *self._host_input(raw))
 
     def dcagc_measure_device(self, d_in, frames_in):
         """dcagc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
-        chunk = int(self.desc.agc_chunk_frames) or 16384
-        rows = np.zeros(-(-int(frames_in) // chunk), AGC_ROW)
-        got = C.c_size_t(0)
-        check(self._lib.iqgpu_chain_dcagc_measure_device(self._h, C.c_void_p(d_in), int(frames_in), rows.ctypes.data_as(C.c_void_p),
-                                                         rows.size, C.byref(got)))
-        return rows[:got.value]
+        return self._measure(self._lib.iqgpu_chain_dcagc_measure_device, C.c_void_p(d_in), int(frames_in))
 
     # ---- exact seamless sharding of chains with the DC blocker AND the dx / local AGC (include/iqgpu.h, iqgpu_chain_dcrms_*) ----
     def dcrms_dc_measure(self, first_frame, raw):
         """dc_measure() for these chains: the map of the call process(raw) would be at stream frame first_frame, ONE DC_ROW record
         (a dx / local chain never cuts a call); the chain itself stays exactly as it was"""
-        raw = np.ascontiguousarray(raw)
-        n = raw.nbytes // self.in_bytes
-        row = np.zeros((), DC_ROW)
-        check(self._lib.iqgpu_chain_dcrms_dc_measure(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n,
-                                                     row.ctypes.data_as(C.POINTER(_lib.DcRow))))
-        return row
+        return self._dc_measure(self._lib.iqgpu_chain_dcrms_dc_measure, first_frame, *self._host_input(raw))
 
     def dcrms_dc_measure_device(self, first_frame, d_in, frames_in):
         """dcrms_dc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
-        row = np.zeros((), DC_ROW)
-        check(self._lib.iqgpu_chain_dcrms_dc_measure_device(self._h, int(first_frame), C.c_void_p(d_in), int(frames_in),
-                                                            row.ctypes.data_as(C.POINTER(_lib.DcRow))))
-        return row
+        return self._dc_measure(self._lib.iqgpu_chain_dcrms_dc_measure_device, first_frame, C.c_void_p(d_in), int(frames_in))
 
     def dcrms_dc_advance(self, state, rows):
         """dc_advance() for these chains: (state behind the last row, before) with before[k] the state in front of row k"""
-        rows = np.ascontiguousarray(rows, DC_ROW).reshape(-1)
-        st = np.zeros((), DC_STATE)
-        if state is not None:
-            st[...] = state
-        before = np.zeros(rows.size, DC_STATE)
-        check(self._lib.iqgpu_chain_dcrms_dc_advance(self._h, st.ctypes.data_as(C.POINTER(DcState)),
-                                                     rows.ctypes.data_as(C.c_void_p) if rows.size else None, rows.size,
-                                                     before.ctypes.data_as(C.c_void_p) if rows.size else None))
-        return st, before
+        return self._dc_advance(self._lib.iqgpu_chain_dcrms_dc_advance, state, rows)
 
     def dcrms_seek(self, first_frame, preroll_raw=None, call_frames=0, dc_state=None):
         """puts the chain at first_frame: `dc_state` (a DC_STATE record from dcrms_dc_advance; None: zero) is the blocker's state in
         front of the preroll, which runs in calls of call_frames (0: one call) with the AGC out of the way; the AGC loop's state at
         first_frame is then rebuilt from the preroll's own output, as by seek_rms -- and certified at the seam in the same way"""
-        raw = np.ascontiguousarray(preroll_raw if preroll_raw is not None else np.empty(0, np.uint8))
-        n = raw.nbytes // self.in_bytes
-        st = None
-        if dc_state is not None:
-            st = np.zeros((), DC_STATE)
-            st[...] = dc_state
-        check(self._lib.iqgpu_chain_dcrms_seek(self._h, int(first_frame), raw.ctypes.data_as(C.c_void_p) if n else None, n, int(call_frames),
-                                               st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
+        check(self._lib.iqgpu_chain_dcrms_seek(self._h, int(first_frame), *self._host_input(preroll_raw), int(call_frames),
+                                               self._dc_ptr(dc_state)))
 
     def dcrms_seek_device(self, first_frame, d_preroll, preroll_frames, call_frames=0, dc_state=None):
         """dcrms_seek() with the preroll already in device memory of this chain's GPU (a device address as an int)"""
-        st = None
-        if dc_state is not None:
-            st = np.zeros((), DC_STATE)
-            st[...] = dc_state
         check(self._lib.iqgpu_chain_dcrms_seek_device(self._h, int(first_frame), C.c_void_p(d_preroll), int(preroll_frames), int(call_frames),
-                                                      st.ctypes.data_as(C.POINTER(DcState)) if st is not None else None))
+                                                      self._dc_ptr(dc_state)))
 
     # ---- checkpoint / resume (include/iqgpu.h): the whole carried state in a blob, into a chain of the same description ----
     def tell(self):

@@ -280,7 +280,6 @@ uint64_t seek_preroll_frames(const iqgpu_chain *c, bool with_dc = true);
 // what iqgpu_chain_seek_rms asks for (dx / local): that FIR memory, plus input frames that make the chain emit at least
 // warm + chunk outputs wherever in the stream they lie (the closed form in iqgpu.h)
 uint64_t seek_rms_preroll_frames(const iqgpu_chain *c);
-int rms_seek_check(const iqgpu_chain *c, const char *who);      // an output AGC of profile dx / local, no DC blocker (with it: iqgpu_chain_dcrms_seek)
 
 // ---- profiling (process.cpp): HIP events around every launch while profiling is on ----
 hipEvent_t get_event(iqgpu_chain *c);
@@ -432,6 +431,25 @@ int agc_resolve_pending(iqgpu_chain *c, bool *ran = nullptr);                   
 // seek.cpp: what the two-pass calls ask of a chain (the digital output AGC on the sample clock), and the route of its measure pass
 int agc_two_pass_check(const iqgpu_chain *c, const char *who);
 AgcMode measure_route(const iqgpu_chain *c);
+// seek.cpp: the six ways a chain is started mid-stream -- iqgpu_chain_seek, _seek_agc, _seek_dc, _dcagc_seek, _seek_rms, _dcrms_seek --
+// and, one row per family in shard_family's table, everything its entry points do differently.  The checks themselves are in seek.cpp
+enum class SeekKind { Plain, Agc, Dc, DcAgc, Rms, DcRms };
+enum class ShardCheck { None, TwoPass, Rms, DcRms };          // none, two_pass_check(needs), rms_seek_check, dcrms_check
+struct ShardFamily {
+    ShardCheck check; unsigned needs;     // what every entry point of the family asks of a chain (needs: kNeedAgc | kNeedDc of TwoPass)
+    AgcMode preroll_agc;                  // the AGC stage of the preroll's calls (Ordinary: their output goes to seek_sink, else nowhere)
+    bool dc_at;                           // takes the blocker's state in front of the preroll, and the grid of calls the preroll runs in
+    bool agc_entry;                       // takes the AGC state at first_frame and installs it
+    bool rebuild_agc;                     // the AGC loop's state at first_frame is rebuilt from the preroll's cf32 output ...
+    bool gather;                          // ... of every call, gathered in seek_win (else: of the one call, where it lies in abuf)
+    uint64_t (*memory)(const iqgpu_chain *);      // the preroll the chain needs far enough into the stream
+    const char *seek, *dc_measure, *dc_advance, *measure, *design_preroll;      // its entry points (nullptr: it has none)
+};
+// (hidden: between seek.cpp and plan.cpp only -- the library's dynamic symbol table stays as it was)
+__attribute__((visibility("hidden"))) const ShardFamily &shard_family(SeekKind k);
+// the family's check under the name of the entry point that asks (description: in the words of a design_* call, where they differ)
+__attribute__((visibility("hidden"))) int shard_check(const ShardFamily &f, const iqgpu_chain *c, const char *who, bool description = false);
+int rms_seek_check(const iqgpu_chain *c, const char *who);      // an output AGC of profile dx / local, no DC blocker (with it: iqgpu_chain_dcrms_seek)
 // abi.cpp: empties the I/Q probe's slot -- a block staged or held belongs to the stream the chain is leaving (reset, seek, load_state).
 // Called behind the batches in flight; waits for a staged copy, so that it cannot land in the pinned buffer later
 int probe_drop(iqgpu_chain *c);

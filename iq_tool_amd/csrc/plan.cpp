@@ -59,6 +59,18 @@ extern "C" size_t iqgpu_chain_next_out_frames(const iqgpu_chain *c, size_t frame
     return (size_t)plan_call(c, frames_in).n_emit;
 }
 
+// What the design_* calls below share: a throw-away chain designed from the description (create's validation), `ask` put to it --
+// its refusals, then its answer -- and the chain gone again.  No device
+template <class Ask> static int ask_design(const iqgpu_chain_desc *d, Ask ask)
+{
+    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
+    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
+    int rc = design_chain(c, d);
+    if (rc == IQGPU_OK) rc = ask(c);
+    delete c;
+    return rc;
+}
+
 // frames a FRESH chain of this description emits for frames_in input frames in one stream: the same closed form
 // the calls use (resampler law either way round, FFT-block quantisation in front of or behind the resampler),
 // without a device -- what a sharding writer needs to place shard outputs (BASELINE configs[4])
@@ -66,12 +78,7 @@ extern "C" int iqgpu_design_out_frames(const iqgpu_chain_desc *d, size_t frames_
 {
     if (!d || !frames_out) return fail(IQGPU_EINVAL, "iqgpu_design_out_frames: NULL argument");
     *frames_out = 0;
-    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
-    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
-    const int rc = design_chain(c, d);
-    if (rc == IQGPU_OK) *frames_out = (size_t)plan_call(c, frames_in).n_emit;
-    delete c;
-    return rc;
+    return ask_design(d, [&](const iqgpu_chain *c) { *frames_out = (size_t)plan_call(c, frames_in).n_emit; return (int)IQGPU_OK; });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -147,89 +154,51 @@ uint64_t seek_rms_preroll_frames(const iqgpu_chain *c)
     return seek_preroll_frames(c, false) + frames_for_outputs(c, (uint64_t)(warm + chunk));
 }
 
-// what iqgpu_chain_seek_rms asks of a chain (seek.cpp) and iqgpu_design_preroll_frames_rms of a description
-int rms_seek_check(const iqgpu_chain *c, const char *who)
+// what seamless sharding without a recipe for the output AGC cannot do (the words of iqgpu_design_preroll_frames and _out_frames_range)
+static int no_agc_check(const iqgpu_chain *c)
 {
-    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
-    if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC", who);
-    if (!(c->agc_rms_alpha > 0.0f)) return fail(IQGPU_EUNSUPPORTED, "%s: the digital AGC profile works chunk by chunk and is sharded by "
-        "iqgpu_chain_seek_agc; this call is for the profiles dx / local", who);
-    if (c->dc) return fail(IQGPU_EUNSUPPORTED, "%s: a chain with the DC blocker -- its exact route needs a call grid and a walked state "
-        "(iqgpu_chain_seek_dc); iqgpu_chain_dcrms_seek composes the two", who);
-    return IQGPU_OK;
-}
-
-extern "C" int iqgpu_design_preroll_frames_rms(const iqgpu_chain_desc *d, uint64_t *frames)
-{
-    if (!d || !frames) return fail(IQGPU_EINVAL, "iqgpu_design_preroll_frames_rms: NULL argument");
-    *frames = 0;
-    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
-    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
-    int rc = design_chain(c, d);
-    if (rc == IQGPU_OK) rc = rms_seek_check(c, "iqgpu_design_preroll_frames_rms");
-    if (rc == IQGPU_OK) *frames = seek_rms_preroll_frames(c);
-    delete c;
-    return rc;
-}
-
-// P of iqgpu_chain_dcrms_seek: P_rms of the same description without the blocker (the blocker has no part in the FIR memory or in the
-// output count: seek_rms_preroll_frames does not read it).  The refusals are those of iqgpu_chain_dcrms_seek
-extern "C" int iqgpu_design_preroll_frames_dcrms(const iqgpu_chain_desc *d, uint64_t *frames)
-{
-    const char *who = "iqgpu_design_preroll_frames_dcrms";
-    if (!d || !frames) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
-    *frames = 0;
-    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
-    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
-    int rc = design_chain(c, d);
-    if (rc == IQGPU_OK && !c->dc) rc = fail(IQGPU_EINVAL, "%s: the description has no DC blocker (without it: iqgpu_design_preroll_frames_rms)", who);
-    if (rc == IQGPU_OK && !c->agc) rc = fail(IQGPU_EINVAL, "%s: the description has no output AGC", who);
-    if (rc == IQGPU_OK && !(c->agc_rms_alpha > 0.0f)) rc = fail(IQGPU_EUNSUPPORTED, "%s: the digital AGC profile works chunk by chunk and is "
-        "sharded by iqgpu_chain_dcagc_*; this call is for the profiles dx / local", who);
-    if (rc == IQGPU_OK) *frames = seek_rms_preroll_frames(c);
-    delete c;
-    return rc;
-}
-
-// design of a throw-away chain for the two calls below: create's validation first, then what seamless sharding cannot do
-static int design_for_seek(iqgpu_chain *c, const iqgpu_chain_desc *d)
-{
-    const int rc = design_chain(c, d);
-    if (rc != IQGPU_OK) return rc;
     if (c->agc) return fail(IQGPU_EUNSUPPORTED, "seamless sharding does not cover the output AGC: its state depends on the whole stream "
                                                 "in front of a position, not on a bounded warm-up");
     return IQGPU_OK;
 }
 
-extern "C" int iqgpu_design_preroll_frames(const iqgpu_chain_desc *d, uint64_t *frames)
+// P of a family's seek for a description: the family's own check (seek.cpp), put in the words of a description, then its preroll memory.
+//   Plain  no check of its own: no output AGC
+//   Rms    P_rms (seek_rms_preroll_frames)
+//   DcRms  P_rms of the same description without the blocker (the blocker has no part in the FIR memory or in the output count:
+//          seek_rms_preroll_frames does not read it).  The refusals are those of iqgpu_chain_dcrms_seek
+static int design_preroll(const iqgpu_chain_desc *d, uint64_t *frames, SeekKind kind)
 {
-    if (!d || !frames) return fail(IQGPU_EINVAL, "iqgpu_design_preroll_frames: NULL argument");
+    const ShardFamily &fam = shard_family(kind);
+    const char *who = fam.design_preroll;
+    if (!d || !frames) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     *frames = 0;
-    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
-    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
-    const int rc = design_for_seek(c, d);
-    if (rc == IQGPU_OK) *frames = seek_preroll_frames(c);
-    delete c;
-    return rc;
+    return ask_design(d, [&](const iqgpu_chain *c) {
+        const int rc = fam.check == ShardCheck::None ? no_agc_check(c) : shard_check(fam, c, who, true);
+        if (rc == IQGPU_OK) *frames = fam.memory(c);
+        return rc;
+    });
 }
+
+extern "C" int iqgpu_design_preroll_frames(const iqgpu_chain_desc *d, uint64_t *frames) { return design_preroll(d, frames, SeekKind::Plain); }
+extern "C" int iqgpu_design_preroll_frames_rms(const iqgpu_chain_desc *d, uint64_t *frames) { return design_preroll(d, frames, SeekKind::Rms); }
+extern "C" int iqgpu_design_preroll_frames_dcrms(const iqgpu_chain_desc *d, uint64_t *frames) { return design_preroll(d, frames, SeekKind::DcRms); }
 
 extern "C" int iqgpu_design_out_frames_range(const iqgpu_chain_desc *d, uint64_t first_frame, uint64_t frames_in,
                                              uint64_t *out_first, uint64_t *frames_out)
 {
     if (!d || !out_first || !frames_out) return fail(IQGPU_EINVAL, "iqgpu_design_out_frames_range: NULL argument");
     *out_first = 0; *frames_out = 0;
-    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
-    if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
-    int rc = design_for_seek(c, d);
-    if (rc == IQGPU_OK && (first_frame > kMaxStreamFrames || frames_in > kMaxStreamFrames - first_frame))
-        rc = fail(IQGPU_EINVAL, "stream position %llu + %llu frames is beyond 2^39 frames", (unsigned long long)first_frame,
-                  (unsigned long long)frames_in);
-    if (rc == IQGPU_OK) {
+    return ask_design(d, [&](const iqgpu_chain *c) {
+        const int rc = no_agc_check(c);
+        if (rc != IQGPU_OK) return rc;
+        if (first_frame > kMaxStreamFrames || frames_in > kMaxStreamFrames - first_frame)
+            return fail(IQGPU_EINVAL, "stream position %llu + %llu frames is beyond 2^39 frames", (unsigned long long)first_frame,
+                        (unsigned long long)frames_in);
         *out_first = stream_at(c, first_frame).n_out;
         *frames_out = stream_at(c, first_frame + frames_in).n_out - *out_first;
-    }
-    delete c;
-    return rc;
+        return (int)IQGPU_OK;
+    });
 }
 
 extern "C" size_t iqgpu_chain_max_out_frames(const iqgpu_chain *c, size_t frames_in)

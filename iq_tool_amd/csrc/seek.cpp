@@ -1,5 +1,6 @@
 // seek.cpp -- seamless range sharding: a chain started mid-stream, the AGC measure pass (both: modes of process.cpp's call; its pipelined
-// form is in pipeline.cpp), the AGC walk; the DC blocker's measure pass, walk and seek
+// form is in pipeline.cpp), the AGC walk; the DC blocker's measure pass, walk and seek.  What the six seek families ask of a chain
+// (two_pass_check, rms_seek_check, dcrms_check) and everything else they do differently: shard_family's table, below
 #include "chain.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -26,78 +27,112 @@ static int two_pass_check(const iqgpu_chain *c, const char *who, unsigned needs)
 }
 int agc_two_pass_check(const iqgpu_chain *c, const char *who) { return two_pass_check(c, who, kNeedAgc); }
 
-// what iqgpu_chain_dcrms_* ask of a chain: the DC blocker and the output AGC of profile dx / local.  Such a chain never cuts a call
-// (agc_fusable and agc_fusable_filter want the digital profile): every call runs whole on the unfused route, so the reason the DC
-// blocker's calls have to refuse an AGC chain does not hold for it
-static int dcrms_check(const iqgpu_chain *c, const char *who)
+// what iqgpu_chain_seek_rms asks of a chain, and iqgpu_design_preroll_frames_rms of a description (in the same words): an output AGC of
+// profile dx / local, no DC blocker
+int rms_seek_check(const iqgpu_chain *c, const char *who)
 {
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
-    if (!c->dc) return fail(IQGPU_EINVAL, "%s: the chain has no DC blocker (without it: iqgpu_chain_seek_rms)", who);
-    if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC (without it: iqgpu_chain_seek_dc)", who);
+    if (!c->agc) return fail(IQGPU_EINVAL, "%s: the chain has no output AGC", who);
+    if (!(c->agc_rms_alpha > 0.0f)) return fail(IQGPU_EUNSUPPORTED, "%s: the digital AGC profile works chunk by chunk and is sharded by "
+        "iqgpu_chain_seek_agc; this call is for the profiles dx / local", who);
+    if (c->dc) return fail(IQGPU_EUNSUPPORTED, "%s: a chain with the DC blocker -- its exact route needs a call grid and a walked state "
+        "(iqgpu_chain_seek_dc); iqgpu_chain_dcrms_seek composes the two", who);
+    return IQGPU_OK;
+}
+
+// what iqgpu_chain_dcrms_* ask of a chain: the DC blocker and the output AGC of profile dx / local.  Such a chain never cuts a call
+// (agc_fusable and agc_fusable_filter want the digital profile): every call runs whole on the unfused route, so the reason the DC
+// blocker's calls have to refuse an AGC chain does not hold for it.  (description: asked by iqgpu_design_preroll_frames_dcrms, which
+// names its own siblings)
+static int dcrms_check(const iqgpu_chain *c, const char *who, bool description)
+{
+    const char *what = description ? "description" : "chain";
+    if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
+    if (!c->dc) return fail(IQGPU_EINVAL, "%s: the %s has no DC blocker (without it: %s)", who, what,
+        description ? "iqgpu_design_preroll_frames_rms" : "iqgpu_chain_seek_rms");
+    if (!c->agc) return fail(IQGPU_EINVAL, "%s: the %s has no output AGC%s", who, what, description ? "" : " (without it: iqgpu_chain_seek_dc)");
     if (!(c->agc_rms_alpha > 0.0f)) return fail(IQGPU_EUNSUPPORTED, "%s: the digital AGC profile works chunk by chunk and is sharded by "
         "iqgpu_chain_dcagc_*; this call is for the profiles dx / local", who);
     return IQGPU_OK;
 }
 
-// Which seek is running, and what it was given beyond the position and the preroll.
-//   Plain  iqgpu_chain_seek: the preroll as ordinary calls, their output into seek_sink
-//   Agc    iqgpu_chain_seek_agc: the preroll with the AGC out of the way, then *agc_entry (or the fresh state) installed
-//   Dc     iqgpu_chain_seek_dc: no warm-up of the DC blocker asked for: *dc_at (or zero) is its state in front of the preroll, which
-//          runs in calls of call_frames (0: one call)
-//   DcAgc  iqgpu_chain_dcagc_seek: both at once: the preroll as SHADOW calls (chain.hpp, AgcMode) from the host mirrors' closed form
-//   Rms    iqgpu_chain_seek_rms: dx / local: the preroll with the AGC out of the way and its cf32 output kept on the device, then the
-//          loop's state at first_frame from k_agc_rms_seek over those samples
-//   DcRms  iqgpu_chain_dcrms_seek: Dc and Rms at once: *dc_at in front of a preroll in calls of call_frames, the cf32 output of every
-//          one of them gathered in seek_win, k_agc_rms_seek over that
-enum class SeekKind { Plain, Agc, Dc, DcAgc, Rms, DcRms };
+// The six families, one row each, in SeekKind's order (chain.hpp: SeekKind, ShardFamily).  How their seeks run:
+//   Plain  the preroll as ordinary calls, their output into seek_sink
+//   Agc    the preroll with the AGC out of the way, then *agc_entry (or the fresh state) installed
+//   Dc     no warm-up of the DC blocker asked for: *dc_at (or zero) is its state in front of the preroll, which runs in calls of
+//          call_frames (0: one call)
+//   DcAgc  both at once: the preroll as SHADOW calls (chain.hpp, AgcMode) from the host mirrors' closed form
+//   Rms    dx / local: the preroll with the AGC out of the way and its cf32 output kept on the device, then the loop's state at
+//          first_frame from k_agc_rms_seek over those samples
+//   DcRms  Dc and Rms at once: *dc_at in front of a preroll in calls of call_frames, the cf32 output of every one of them gathered in
+//          seek_win, k_agc_rms_seek over that
+static uint64_t fir_and_dc_memory(const iqgpu_chain *c) { return seek_preroll_frames(c, true); }
+static uint64_t fir_memory(const iqgpu_chain *c) { return seek_preroll_frames(c, false); }
+const ShardFamily &shard_family(SeekKind k)
+{
+    using SC = ShardCheck;
+    using AM = AgcMode;
+    static const ShardFamily rows[6] = {
+        //        check      needs               preroll_agc   dc_at  entry  rebuild gather memory
+        /*Plain*/ {SC::None,    0,                  AM::Ordinary, false, false, false, false, fir_and_dc_memory,
+                   "iqgpu_chain_seek", nullptr, nullptr, nullptr, "iqgpu_design_preroll_frames"},
+        /*Agc*/   {SC::TwoPass, kNeedAgc,           AM::Drop,     false, true,  false, false, fir_and_dc_memory,
+                   "iqgpu_chain_seek_agc", nullptr, nullptr, "iqgpu_chain_measure", nullptr},
+        /*Dc*/    {SC::TwoPass, kNeedDc,            AM::Ordinary, true,  false, false, false, fir_memory,
+                   "iqgpu_chain_seek_dc", "iqgpu_chain_dc_measure", "iqgpu_chain_dc_advance", nullptr, nullptr},
+        /*DcAgc*/ {SC::TwoPass, kNeedDc | kNeedAgc, AM::Shadow,   true,  true,  false, false, fir_memory,
+                   "iqgpu_chain_dcagc_seek", "iqgpu_chain_dcagc_dc_measure", "iqgpu_chain_dcagc_dc_advance", "iqgpu_chain_dcagc_measure", nullptr},
+        /*Rms*/   {SC::Rms,     0,                  AM::Drop,     false, false, true,  false, seek_rms_preroll_frames,
+                   "iqgpu_chain_seek_rms", nullptr, nullptr, nullptr, "iqgpu_design_preroll_frames_rms"},
+        /*DcRms*/ {SC::DcRms,   0,                  AM::Drop,     true,  false, true,  true,  seek_rms_preroll_frames,
+                   "iqgpu_chain_dcrms_seek", "iqgpu_chain_dcrms_dc_measure", "iqgpu_chain_dcrms_dc_advance", nullptr,
+                   "iqgpu_design_preroll_frames_dcrms"},
+    };
+    return rows[(int)k];
+}
+
+int shard_check(const ShardFamily &f, const iqgpu_chain *c, const char *who, bool description)
+{
+    switch (f.check) {
+    case ShardCheck::None:    return IQGPU_OK;
+    case ShardCheck::TwoPass: return two_pass_check(c, who, f.needs);
+    case ShardCheck::Rms:     return rms_seek_check(c, who);
+    case ShardCheck::DcRms:   return dcrms_check(c, who, description);
+    }
+    return IQGPU_OK;
+}
+
+// what a seek was given beyond the position and the preroll
 struct SeekRequest {
     SeekKind kind = SeekKind::Plain;
     bool on_device = false;                        // the preroll is in device memory
-    const iqgpu_agc_state *agc_entry = nullptr;    // Agc, DcAgc
-    const iqgpu_dc_state *dc_at = nullptr;         // Dc, DcAgc, DcRms
-    size_t call_frames = 0;                        // Dc, DcAgc, DcRms
+    const iqgpu_agc_state *agc_entry = nullptr;    // families with agc_entry
+    const iqgpu_dc_state *dc_at = nullptr;         // families with dc_at
+    size_t call_frames = 0;                        // families with dc_at
 };
 
 static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, const SeekRequest &rq)
 {
-    // everything that depends on the kind: the entry point's name, what it asks of the chain, and how its preroll runs -- the AGC
-    // stage of the preroll's calls, and whether their output goes to seek_sink (ordinary calls) or nowhere
-    const char *who = "iqgpu_chain_seek";
-    unsigned needs = 0;
-    AgcMode preroll_agc = AgcMode::Ordinary;
-    switch (rq.kind) {
-    case SeekKind::Plain: break;
-    case SeekKind::Agc:   who = "iqgpu_chain_seek_agc";   needs = kNeedAgc;           preroll_agc = AgcMode::Drop;   break;
-    case SeekKind::Dc:    who = "iqgpu_chain_seek_dc";    needs = kNeedDc;                                           break;
-    case SeekKind::DcAgc: who = "iqgpu_chain_dcagc_seek"; needs = kNeedAgc | kNeedDc; preroll_agc = AgcMode::Shadow; break;
-    case SeekKind::Rms:   who = "iqgpu_chain_seek_rms";                               preroll_agc = AgcMode::Drop;   break;
-    case SeekKind::DcRms: who = "iqgpu_chain_dcrms_seek";                             preroll_agc = AgcMode::Drop;   break;
-    }
-    // (DcRms asks for the blocker and the AGC through dcrms_check, not through `needs`: those bits carry the digital profile's rules)
-    const bool dcrms = rq.kind == SeekKind::DcRms;
-    const bool with_agc = needs & kNeedAgc, with_dc = (needs & kNeedDc) || dcrms, rms = rq.kind == SeekKind::Rms || dcrms;
-    const bool shadow = preroll_agc == AgcMode::Shadow;
-    const bool to_sink = preroll_agc == AgcMode::Ordinary;
+    const ShardFamily &fam = shard_family(rq.kind);
+    const char *who = fam.seek;
     if (!c) return fail(IQGPU_EINVAL, "%s: NULL chain", who);
     // what iqgpu_chain_reset does comes first: batches in flight and a pending verdict resolved, histories and dc state zeroed,
     // the poison cleared -- a refused argument below leaves the chain reset
     int rc = iqgpu_chain_reset(c); if (rc) return rc;
     c->fpending = 0;                                          // (reset keeps the FFT remainder queued: a seek starts a stream)
-    if (with_agc) {
-        rc = two_pass_check(c, who, needs); if (rc) return rc;
+    rc = shard_check(fam, c, who); if (rc) return rc;
+    if (fam.agc_entry) {
         const iqgpu_agc_state *e = rq.agc_entry;
         if (e && (e->locked != 0 && e->locked != 1)) return fail(IQGPU_EINVAL, "%s: entry state with locked = %d", who, e->locked);
     }
-    if (rms) { rc = dcrms ? dcrms_check(c, who) : rms_seek_check(c, who); if (rc) return rc; }
     cd2 dc_at{0.0, 0.0};
-    if (with_dc) {
-        if (!with_agc && !dcrms) { rc = two_pass_check(c, who, needs); if (rc) return rc; }
+    if (fam.dc_at) {
         if (rq.dc_at) { dc_at.x = rq.dc_at->re; dc_at.y = rq.dc_at->im; }
         if (!std::isfinite(dc_at.x) || !std::isfinite(dc_at.y)) return fail(IQGPU_EINVAL, "%s: the state in front of the preroll is not finite", who);
         if (rq.call_frames && preroll_frames % rq.call_frames != 0) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames is not a whole number "
             "of calls of %zu frames", who, preroll_frames, rq.call_frames);
         // (the cut of a call is a closed form of the position only on the chunk grid)
-        if (with_agc && (first_frame % (uint64_t)c->agc_chunk || rq.call_frames % (size_t)c->agc_chunk || preroll_frames % (size_t)c->agc_chunk))
+        if (fam.preroll_agc == AgcMode::Shadow && (first_frame % (uint64_t)c->agc_chunk || rq.call_frames % (size_t)c->agc_chunk || preroll_frames % (size_t)c->agc_chunk))
             return fail(IQGPU_EINVAL, "%s: first_frame %llu, call_frames %zu and the preroll of %zu frames have to be multiples of "
                 "agc_chunk_frames = %lld", who, (unsigned long long)first_frame, rq.call_frames, preroll_frames, (long long)c->agc_chunk);
     }
@@ -105,15 +140,15 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
     if ((uint64_t)preroll_frames > first_frame) return fail(IQGPU_EINVAL, "%s: a preroll of %zu frames would start in front of "
         "frame 0 (first_frame %llu)", who, preroll_frames, (unsigned long long)first_frame);
     if (first_frame > 0) {
-        // (Dc never gets here with an AGC: its check above has refused the chain)
-        if (c->agc && !with_agc && !rms) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
+        // (a family without a check of its own has no way with the output AGC)
+        if (c->agc && fam.check == ShardCheck::None) return fail(IQGPU_EUNSUPPORTED, "iqgpu_chain_seek: the output AGC depends on the whole stream in front of a position, "
             "not on a bounded warm-up");
-        const uint64_t memory = rms ? seek_rms_preroll_frames(c) : seek_preroll_frames(c, !with_dc), need = first_frame < memory ? first_frame : memory;
+        const uint64_t memory = fam.memory(c), need = first_frame < memory ? first_frame : memory;
         if ((uint64_t)preroll_frames < need) return fail(IQGPU_EINVAL, "%s: preroll of %zu frames is shorter than the %llu "
             "this chain needs at frame %llu", who, preroll_frames, (unsigned long long)need, (unsigned long long)first_frame);
         if (preroll_frames && !preroll) return fail(IQGPU_EINVAL, "%s: NULL preroll", who);
     }
-    if (with_dc) {
+    if (fam.dc_at) {
         // the blocker's state in front of the preroll (at frame 0: of the stream), where the reset has left zero -- behind every
         // refusal, so that a refused call leaves the chain reset
         HIP_TRY(hipMemcpyAsync(c->d_dc_state, &dc_at, sizeof(cd2), hipMemcpyHostToDevice, c->stream));
@@ -121,10 +156,10 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
     }
     if (first_frame > 0) {
         const StreamAt from = stream_at(c, first_frame - (uint64_t)preroll_frames), to = stream_at(c, first_frame);
-        // DcRms: room for the cf32 output of ALL preroll calls, sized before the first launch (a failure here leaves the chain reset)
+        // gather: room for the cf32 output of ALL preroll calls, sized before the first launch (a failure here leaves the chain reset)
         const size_t win_total = (size_t)(to.n_out - from.n_out);
         size_t win_at = 0;
-        if (dcrms) { rc = c->seek_win.ensure((win_total + 1) * sizeof(cf2)); if (rc) return rc; }
+        if (fam.gather) { rc = c->seek_win.ensure((win_total + 1) * sizeof(cf2)); if (rc) return rc; }
         if (c->fp.enabled) {
             // [L-1 history][pending]: zeros stand for the samples in front of the warm-up
             const size_t front = c->fp.taps.size() - 1 + (size_t)from.pos.fpending;
@@ -136,16 +171,17 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         // (the preroll lies in front of the range the caller asked for: the I/Q probe takes no block from it and keeps its slot free
         //  for the head of the first call behind the seek)
         // Drop: nothing of the preroll is kept and the AGC must not see it: the unfused route into abuf, no AGC kernel behind it
-        // (rms: the call's cf32 samples stay in abuf, behind its lead of agc_rms_warm samples, for k_agc_rms_seek below; DcRms: every
-        //  call writes there, where the single stream's call writes, and its samples are copied behind those of the calls in front).
+        // (rebuild_agc: the call's cf32 samples stay in abuf, behind its lead of agc_rms_warm samples, for k_agc_rms_seek below; gather:
+        //  every call writes there, where the single stream's call writes, and its samples are copied behind those of the calls in front).
         // Shadow: cut as the single stream's calls are, from the mirrors the single stream has in front of the preroll
-        CallOpts preroll_call; preroll_call.no_probe = true; preroll_call.agc = preroll_agc;
+        const bool shadow = fam.preroll_agc == AgcMode::Shadow, to_sink = fam.preroll_agc == AgcMode::Ordinary;
+        CallOpts preroll_call; preroll_call.no_probe = true; preroll_call.agc = fam.preroll_agc;
         if (shadow) agc_mirrors_at(c, first_frame - (uint64_t)preroll_frames, &c->agc_locked_host, &c->agc_seen_host);
 
         // with call_frames the preroll runs in the single stream's own calls -- every one staged like a call of iqgpu_chain_process --
         // from the single stream's own state; otherwise in one call.  No frames: no call
         const size_t obps = bytes_per_frame(c->desc.out_format), ibps = bytes_per_frame(c->desc.in_format);
-        const size_t per = with_dc && rq.call_frames ? rq.call_frames : preroll_frames;
+        const size_t per = fam.dc_at && rq.call_frames ? rq.call_frames : preroll_frames;
         for (size_t at = 0; at < preroll_frames; at += per) {
             const void *src = (const char *)preroll + at * ibps, *d_in = src;
             if (!rq.on_device) { rc = stage_host_input(c, src, per, &d_in); if (rc) return rc; }
@@ -153,7 +189,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             if (to_sink) { rc = c->seek_sink.ensure((size_t)plan_call(c, per).n_emit * obps + 16); if (rc) return rc; }
             rc = process_device_impl(c, d_in, per, to_sink ? c->seek_sink.p : nullptr, to_sink ? c->seek_sink.cap : 0, &dropped, preroll_call);
             if (rc) return rc;
-            if (dcrms) {
+            if (fam.gather) {
                 const hipError_t e = win_at + dropped <= win_total
                     ? launch_copy_cf((cf2 *)c->seek_win.p + win_at, (const cf2 *)c->abuf.p + c->agc_rms_warm, (int64_t)dropped, c->stream)
                     : hipErrorInvalidValue;
@@ -164,7 +200,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         HIP_TRY(hipStreamSynchronize(c->stream));
         // the warm-up has walked the position forward call-wise: it has to stand on the closed form at first_frame
         if (c->rem != to.pos.rem || c->phi != to.pos.phi || c->fpending != to.pos.fpending || c->nco_theta != to.nco_theta ||
-            c->pnco_theta != to.pnco_theta || (dcrms && win_at != win_total)) {
+            c->pnco_theta != to.pnco_theta || (fam.gather && win_at != win_total)) {
             c->poisoned = true;
             return fail(IQGPU_EINVAL, "internal: the position behind the preroll is not the closed form at frame %llu", (unsigned long long)first_frame);
         }
@@ -172,7 +208,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
         // (the mirrors the shadow calls have walked forward: the closed form at first_frame -- stated, so that a chain which never cuts
         //  a call, and so never moves them, carries them too)
         if (shadow) agc_mirrors_at(c, first_frame, &c->agc_locked_host, &c->agc_seen_host);
-        if (rms && to.n_out > 0) {
+        if (fam.rebuild_agc && to.n_out > 0) {
             // The loop's state at the cut from the samples the preroll has left at abuf + W: stream positions [pos0, cut).  The
             // trajectory of the chunk that holds sample cut - 1 starts at `start`; the preroll's outputs are the single stream's from
             // `clean` on (position 0 when it began at frame 0, else the first output behind the frames that refill the FIR memory).
@@ -183,7 +219,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             const int64_t a0 = (cut - 1) / ra.chunk * ra.chunk - ra.warm, start = a0 > 0 ? a0 : 0;
             const int64_t clean = (uint64_t)preroll_frames == first_frame ? 0
                 : (int64_t)stream_at(c, first_frame - (uint64_t)preroll_frames + seek_preroll_frames(c, false)).n_out;
-            const bool room = dcrms ? (int64_t)c->seek_win.cap >= (cut - pos0) * (int64_t)sizeof(cf2)
+            const bool room = fam.gather ? (int64_t)c->seek_win.cap >= (cut - pos0) * (int64_t)sizeof(cf2)
                                     : (int64_t)c->abuf.cap >= (W + cut - pos0) * (int64_t)sizeof(cf2);
             if (clean > start || pos0 > start || !room) {
                 c->poisoned = true;
@@ -191,7 +227,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
                     "trajectory in front of frame %llu starts", (long long)pos0, (long long)cut, (long long)clean, (long long)start,
                     (unsigned long long)first_frame);
             }
-            ra.x = dcrms ? (const cf2 *)c->seek_win.p : (const cf2 *)c->abuf.p + W; ra.n = cut - pos0; ra.pos0 = pos0; ra.hist_valid = 0;
+            ra.x = fam.gather ? (const cf2 *)c->seek_win.p : (const cf2 *)c->abuf.p + W; ra.n = cut - pos0; ra.pos0 = pos0; ra.hist_valid = 0;
             ra.alpha = c->agc_rms_alpha; ra.state = c->d_agc_state;
             hipError_t e = launch_agc_rms_seek(ra, c->stream);
             // the warm-up window of the calls to come: the last W samples in front of the cut (a stream shorter than that: its own
@@ -203,7 +239,7 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
             c->agc_rms_pos = to.n_out;
         }
     }
-    if (with_agc && rq.agc_entry) {
+    if (fam.agc_entry && rq.agc_entry) {
         // The AGC state of the stream at first_frame, everywhere the chain keeps it: the device state the kernels read, and the host's
         // mirrors of "has the stream locked" and of samples_seen, from which the fused / unfused split of every later call follows
         // (agc_unfused_head).  The reset above has left the rest as on a chain that arrived here by processing: no pending verdict,
@@ -221,88 +257,73 @@ static int seek_impl(iqgpu_chain *c, uint64_t first_frame, const void *preroll, 
     return IQGPU_OK;
 }
 
+// (a request in SeekRequest's order: kind, on_device, agc_entry, dc_at, call_frames)
 extern "C" int iqgpu_chain_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames)
 {
-    SeekRequest rq; rq.kind = SeekKind::Plain;
-    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, preroll, preroll_frames, {SeekKind::Plain, false});
 }
 extern "C" int iqgpu_chain_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames)
 {
-    SeekRequest rq; rq.kind = SeekKind::Plain; rq.on_device = true;
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, {SeekKind::Plain, true});
 }
 extern "C" int iqgpu_chain_seek_agc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, const iqgpu_agc_state *entry)
 {
-    SeekRequest rq; rq.kind = SeekKind::Agc; rq.agc_entry = entry;
-    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, preroll, preroll_frames, {SeekKind::Agc, false, entry});
 }
 extern "C" int iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
                                            const iqgpu_agc_state *entry)
 {
-    SeekRequest rq; rq.kind = SeekKind::Agc; rq.on_device = true; rq.agc_entry = entry;
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, {SeekKind::Agc, true, entry});
 }
-
 extern "C" int iqgpu_chain_seek_rms(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames)
 {
-    SeekRequest rq; rq.kind = SeekKind::Rms;
-    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, preroll, preroll_frames, {SeekKind::Rms, false});
 }
 extern "C" int iqgpu_chain_seek_rms_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames)
 {
-    SeekRequest rq; rq.kind = SeekKind::Rms; rq.on_device = true;
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, {SeekKind::Rms, true});
 }
-
 extern "C" int iqgpu_chain_seek_dc(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
                                    const iqgpu_dc_state *at_preroll_start)
 {
-    SeekRequest rq; rq.kind = SeekKind::Dc; rq.dc_at = at_preroll_start; rq.call_frames = call_frames;
-    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, preroll, preroll_frames, {SeekKind::Dc, false, nullptr, at_preroll_start, call_frames});
 }
 extern "C" int iqgpu_chain_seek_dc_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
                                           size_t call_frames, const iqgpu_dc_state *at_preroll_start)
 {
-    SeekRequest rq; rq.kind = SeekKind::Dc; rq.on_device = true; rq.dc_at = at_preroll_start; rq.call_frames = call_frames;
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, {SeekKind::Dc, true, nullptr, at_preroll_start, call_frames});
 }
-
 extern "C" int iqgpu_chain_dcrms_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
                                       const iqgpu_dc_state *dc_at_preroll_start)
 {
-    SeekRequest rq; rq.kind = SeekKind::DcRms; rq.dc_at = dc_at_preroll_start; rq.call_frames = call_frames;
-    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, preroll, preroll_frames, {SeekKind::DcRms, false, nullptr, dc_at_preroll_start, call_frames});
 }
 extern "C" int iqgpu_chain_dcrms_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
                                              size_t call_frames, const iqgpu_dc_state *dc_at_preroll_start)
 {
-    SeekRequest rq; rq.kind = SeekKind::DcRms; rq.on_device = true; rq.dc_at = dc_at_preroll_start; rq.call_frames = call_frames;
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, {SeekKind::DcRms, true, nullptr, dc_at_preroll_start, call_frames});
 }
-
 extern "C" int iqgpu_chain_dcagc_seek(iqgpu_chain *c, uint64_t first_frame, const void *preroll, size_t preroll_frames, size_t call_frames,
                                       const iqgpu_dc_state *dc_at_preroll_start, const iqgpu_agc_state *agc_entry)
 {
-    SeekRequest rq; rq.kind = SeekKind::DcAgc; rq.agc_entry = agc_entry; rq.dc_at = dc_at_preroll_start; rq.call_frames = call_frames;
-    return seek_impl(c, first_frame, preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, preroll, preroll_frames, {SeekKind::DcAgc, false, agc_entry, dc_at_preroll_start, call_frames});
 }
 extern "C" int iqgpu_chain_dcagc_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames,
                                              size_t call_frames, const iqgpu_dc_state *dc_at_preroll_start, const iqgpu_agc_state *agc_entry)
 {
-    SeekRequest rq; rq.kind = SeekKind::DcAgc; rq.on_device = true; rq.agc_entry = agc_entry; rq.dc_at = dc_at_preroll_start; rq.call_frames = call_frames;
-    return seek_impl(c, first_frame, d_preroll, preroll_frames, rq);
+    return seek_impl(c, first_frame, d_preroll, preroll_frames, {SeekKind::DcAgc, true, agc_entry, dc_at_preroll_start, call_frames});
 }
 
 // ------------------------------------------------------------------------------------------------
 // exact seamless sharding of DC-blocker chains: the map of a call (k_dc_prefix + k_dc_scan's map output), the walk over the maps
 // ------------------------------------------------------------------------------------------------
-// (dcrms: iqgpu_chain_dcrms_dc_measure -- the call of a dx / local chain is one piece on the unfused route, which is what
-//  dc_measure_call plans for a chain with the AGC: one row)
-static int dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const void *in, size_t frames_in, iqgpu_dc_row *row, bool on_device,
-                           bool dcrms = false)
+// (Dc and DcRms; the call of a dx / local chain is one piece on the unfused route, which is what dc_measure_call plans for a chain with
+//  the AGC: one row)
+static int dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const void *in, size_t frames_in, iqgpu_dc_row *row, bool on_device, SeekKind kind)
 {
-    const char *who = dcrms ? "iqgpu_chain_dcrms_dc_measure" : "iqgpu_chain_dc_measure";
-    int rc = dcrms ? dcrms_check(c, who) : two_pass_check(c, who, kNeedDc); if (rc) return rc;
+    const ShardFamily &fam = shard_family(kind);
+    const char *who = fam.dc_measure;
+    int rc = shard_check(fam, c, who); if (rc) return rc;
     if (!row) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     if (first_frame > kMaxStreamFrames || (uint64_t)frames_in > kMaxStreamFrames - first_frame) return fail(IQGPU_EINVAL, "%s: stream position "
         "%llu + %zu frames is beyond 2^39 frames", who, (unsigned long long)first_frame, frames_in);
@@ -325,30 +346,29 @@ static int dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const void *in,
 
 extern "C" int iqgpu_chain_dc_measure(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, iqgpu_dc_row *row)
 {
-    return dc_measure_impl(c, first_frame, raw_in, frames_in, row, false);
+    return dc_measure_impl(c, first_frame, raw_in, frames_in, row, false, SeekKind::Dc);
 }
 extern "C" int iqgpu_chain_dc_measure_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, iqgpu_dc_row *row)
 {
-    return dc_measure_impl(c, first_frame, d_raw_in, frames_in, row, true);
+    return dc_measure_impl(c, first_frame, d_raw_in, frames_in, row, true, SeekKind::Dc);
 }
 extern "C" int iqgpu_chain_dcrms_dc_measure(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, iqgpu_dc_row *row)
 {
-    return dc_measure_impl(c, first_frame, raw_in, frames_in, row, false, true);
+    return dc_measure_impl(c, first_frame, raw_in, frames_in, row, false, SeekKind::DcRms);
 }
 extern "C" int iqgpu_chain_dcrms_dc_measure_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, iqgpu_dc_row *row)
 {
-    return dc_measure_impl(c, first_frame, d_raw_in, frames_in, row, true, true);
+    return dc_measure_impl(c, first_frame, d_raw_in, frames_in, row, true, SeekKind::DcRms);
 }
 
 // One definition of the walk: k_dc_walk applies the helper behind k_dc_scan's state update, in the translation unit of k_dc_scan, a
 // batch of 2^16 rows per launch from a scratch copy of *st
-enum class DcWalk { Dc, DcAgc, DcRms };      // whose walk: iqgpu_chain_dc_advance, _dcagc_dc_advance, _dcrms_dc_advance
-static int dc_advance_impl(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before, DcWalk family)
+static int dc_advance_impl(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before, SeekKind kind)
 {
     static_assert(sizeof(iqgpu_dc_row) == sizeof(DcMapRow) && sizeof(DcMapRow) == 32 && sizeof(iqgpu_dc_state) == sizeof(cd2), "DC row layout");
-    const bool dcagc = family == DcWalk::DcAgc, dcrms = family == DcWalk::DcRms;
-    const char *who = dcrms ? "iqgpu_chain_dcrms_dc_advance" : dcagc ? "iqgpu_chain_dcagc_dc_advance" : "iqgpu_chain_dc_advance";
-    int rc = dcrms ? dcrms_check(c, who) : two_pass_check(c, who, dcagc ? kNeedDc | kNeedAgc : kNeedDc); if (rc) return rc;
+    const ShardFamily &fam = shard_family(kind);
+    const char *who = fam.dc_advance;
+    int rc = shard_check(fam, c, who); if (rc) return rc;
     if (!st || (n && !rows)) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     if (!std::isfinite(st->re) || !std::isfinite(st->im)) return fail(IQGPU_EINVAL, "%s: the state is not finite", who);
     for (size_t i = 0; i < n; ++i)
@@ -380,15 +400,15 @@ static int dc_advance_impl(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_ro
 
 extern "C" int iqgpu_chain_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
 {
-    return dc_advance_impl(c, st, rows, n, before, DcWalk::Dc);
+    return dc_advance_impl(c, st, rows, n, before, SeekKind::Dc);
 }
 extern "C" int iqgpu_chain_dcagc_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
 {
-    return dc_advance_impl(c, st, rows, n, before, DcWalk::DcAgc);
+    return dc_advance_impl(c, st, rows, n, before, SeekKind::DcAgc);
 }
 extern "C" int iqgpu_chain_dcrms_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, const iqgpu_dc_row *rows, size_t n, iqgpu_dc_state *before)
 {
-    return dc_advance_impl(c, st, rows, n, before, DcWalk::DcRms);
+    return dc_advance_impl(c, st, rows, n, before, SeekKind::DcRms);
 }
 
 // iqgpu_chain_dcagc_dc_measure: the maps of the ordinary call at first_frame, ONE ROW PER PIECE -- the call is cut as
@@ -397,8 +417,9 @@ extern "C" int iqgpu_chain_dcrms_dc_advance(iqgpu_chain *c, iqgpu_dc_state *st, 
 static int dcagc_dc_measure_impl(iqgpu_chain *c, uint64_t first_frame, const void *in, size_t frames_in, iqgpu_dc_row *rows, size_t cap,
                                  size_t *n_rows, bool on_device)
 {
-    const char *who = "iqgpu_chain_dcagc_dc_measure";
-    int rc = two_pass_check(c, who, kNeedDc | kNeedAgc); if (rc) return rc;
+    const ShardFamily &fam = shard_family(SeekKind::DcAgc);
+    const char *who = fam.dc_measure;
+    int rc = shard_check(fam, c, who); if (rc) return rc;
     if (!rows || !n_rows) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     *n_rows = 0;
     if (cap < 2) return fail(IQGPU_EINVAL, "%s: the table holds %zu rows, a call can be two pieces", who, cap);
@@ -464,13 +485,15 @@ AgcMode measure_route(const iqgpu_chain *c)
     return s1 ? AgcMode::MeasureS1 : AgcMode::Measure;
 }
 
-// (shadow: iqgpu_chain_dcagc_measure -- the call cut and planned as the ordinary call at the chain's position, chain.hpp AgcMode::Shadow)
+// (Agc and DcAgc; the family whose preroll runs as shadow calls measures as one: the call cut and planned as the ordinary call at the
+//  chain's position, chain.hpp AgcMode::Shadow)
 static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows, bool on_device,
-                        bool shadow = false)
+                        SeekKind kind)
 {
     static_assert(sizeof(iqgpu_agc_chunk) == sizeof(AgcRow) && sizeof(AgcRow) == 16, "AGC row layout");
-    const char *who = shadow ? "iqgpu_chain_dcagc_measure" : "iqgpu_chain_measure";
-    int rc = two_pass_check(c, who, shadow ? kNeedDc | kNeedAgc : kNeedAgc); if (rc) return rc;
+    const ShardFamily &fam = shard_family(kind);
+    const char *who = fam.measure;
+    int rc = shard_check(fam, c, who); if (rc) return rc;
     if (!n_rows) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
     *n_rows = 0;
     if (frames_in == 0) return IQGPU_OK;
@@ -483,7 +506,7 @@ static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_
     const void *d_in = in;
     if (!on_device) { rc = stage_host_input(c, in, frames_in, &d_in); if (rc) return rc; }
     size_t dropped = 0;
-    CallOpts mo; mo.agc = shadow ? AgcMode::Shadow : measure_route(c); mo.no_probe = true;      // (a pass whose output nobody keeps: nothing for the I/Q optimiser)
+    CallOpts mo; mo.agc = fam.preroll_agc == AgcMode::Shadow ? AgcMode::Shadow : measure_route(c); mo.no_probe = true;      // (a pass whose output nobody keeps: nothing for the I/Q optimiser)
     rc = process_device_impl(c, d_in, frames_in, nullptr, 0, &dropped, mo);
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(rows, c->agc_rows.p, n * sizeof(AgcRow), hipMemcpyDeviceToHost, c->stream));
@@ -494,22 +517,22 @@ static int measure_impl(iqgpu_chain *c, const void *in, size_t frames_in, iqgpu_
 
 extern "C" int iqgpu_chain_measure(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows)
 {
-    return measure_impl(c, raw_in, frames_in, rows, cap, n_rows, false);
+    return measure_impl(c, raw_in, frames_in, rows, cap, n_rows, false, SeekKind::Agc);
 }
 extern "C" int iqgpu_chain_measure_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap,
                                           size_t *n_rows)
 {
-    return measure_impl(c, d_raw_in, frames_in, rows, cap, n_rows, true);
+    return measure_impl(c, d_raw_in, frames_in, rows, cap, n_rows, true, SeekKind::Agc);
 }
 
 extern "C" int iqgpu_chain_dcagc_measure(iqgpu_chain *c, const void *raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap, size_t *n_rows)
 {
-    return measure_impl(c, raw_in, frames_in, rows, cap, n_rows, false, true);
+    return measure_impl(c, raw_in, frames_in, rows, cap, n_rows, false, SeekKind::DcAgc);
 }
 extern "C" int iqgpu_chain_dcagc_measure_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, iqgpu_agc_chunk *rows, size_t cap,
                                                 size_t *n_rows)
 {
-    return measure_impl(c, d_raw_in, frames_in, rows, cap, n_rows, true, true);
+    return measure_impl(c, d_raw_in, frames_in, rows, cap, n_rows, true, SeekKind::DcAgc);
 }
 
 extern "C" int iqgpu_chain_agc_initial_state(const iqgpu_chain *c, iqgpu_agc_state *st)

@@ -7,19 +7,15 @@ clock with agc_chunk_frames = 4096 (the harness case: its default of 16384, it h
 
 Every comparison prints its figure before it asserts (pytest -s shows them)."""
 import ctypes as C
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from iq_tool_amd import synth
 
+from shard_support import ECAPACITY, EINVAL, EUNSUPPORTED, fr, run
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "iq_tool_amd", "lib", "iqgpu_run")
-EINVAL, ECAPACITY, EUNSUPPORTED = -1, -8, -10
 CHUNK = 4096
 B = 3 * CHUNK
 TAIL = 8192                                      # the process call behind the batches
@@ -53,10 +49,6 @@ def no_switches(monkeypatch):
 
 def stream(fmt, n, seed=83):
     return synth.raw_stream(n, 2.4e6, seed, fmt)
-
-
-def fr(x, a, b):
-    return x[2 * a:2 * b]
 
 
 def no_agc(kw):
@@ -294,12 +286,6 @@ def test_measure_pipelined_is_measure_per_batch(gpu):
 HARNESS_ARGS = ["--raw-file-input-rate", "96e3", "--raw-file-input-sample-format", "cs16", "--output-rate", "29767.5",
                 "--output-sample-format", "cs16", "--freq-shift", "8000", "--agc-profile", "digital"]
 HARNESS_KW = dict(in_format="cs16", out_format="cs16", input_rate_hz=96e3, target_rate_hz=29767.5, shift_hz=8000.0, agc=True)
-
-
-def run(*args):
-    r = subprocess.run([EXE, *args], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr + r.stdout
-    return json.loads(r.stdout.strip().splitlines()[-1])
 
 
 def test_harness_seamless_agc_writes_the_single_streams_file(gpu, tmp_path):

@@ -42,7 +42,8 @@ import numpy as np
 import pytest
 
 from iq_tool_amd import synth
-from test_gpu_seek import CASES as SEEK_CASES, set_switches
+from shard_support import set_switches
+from test_gpu_seek import CASES as SEEK_CASES, SWITCHES
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
@@ -259,7 +260,7 @@ def test_overdriven_chain_clamps_as_the_oracle(gpu, oracle, monkeypatch, name, o
     tap, fast = taps_of(oracle, dict(kw, out_format=fam["outs"][0]), raw, ("over", name))
     what = "%s overdriven x%.1f -> %s" % (name, kw["gain"], out_format)
     assert_stimulus_is_hard(tap, out_format, what)
-    set_switches(monkeypatch, fam["sw"])
+    set_switches(monkeypatch, SWITCHES, fam["sw"])
     for i, got in enumerate(run_device(gpu, kw, raw, n, fam["gain_kernel"], what, filter_check(fam))[:2 if fam["filtered"] else 1]):
         compare(oracle, got, tap, fast, out_format, fam["filtered"], what + (", three-way split" if i else ""))
 
@@ -289,7 +290,7 @@ def test_rail_codes_in_clamp_as_the_oracle(gpu, oracle, monkeypatch, name, in_fo
     tap, fast = taps_of(oracle, dict(kw, out_format=fam["outs"][0]), raw, ("rails", name, in_format))
     what = "%s rails %s (held %d) -> %s" % (name, in_format, fam["hold"], out_format)
     assert_stimulus_is_hard(tap, out_format, what)
-    set_switches(monkeypatch, fam["sw"])
+    set_switches(monkeypatch, SWITCHES, fam["sw"])
     for i, got in enumerate(run_device(gpu, kw, raw, n, fam["kernel"], what, filter_check(fam))[:2 if fam["filtered"] else 1]):
         compare(oracle, got, tap, fast, out_format, fam["filtered"], what + (", three-way split" if i else ""))
 
@@ -311,7 +312,7 @@ def test_constant_rails_give_the_rail_codes(gpu, monkeypatch, name, out_format):
     memory = gpu.design_preroll_frames(**kw)
     first, count = gpu.design_out_frames_range(memory, n - memory, **kw)
     assert 0 < memory < n // 8 and count > 1000
-    set_switches(monkeypatch, fam["sw"])
+    set_switches(monkeypatch, SWITCHES, fam["sw"])
     for const, (want_i, want_q) in (((2, 0), (hi, lo)), ((0, 2), (lo, hi))):
         raw = rails_stream(n, fmt_in, SEED, const=const)
         what = "%s constant %s (%s, %s) x1.25 -> %s" % (name, fmt_in, "max" if const[0] else "min", "max" if const[1] else "min", out_format)
@@ -347,7 +348,7 @@ def test_non_finite_frames_stay_inside_the_chains_memory(gpu, oracle, monkeypatc
     for a, b in spans:
         keep[a:b + 1] = False
     assert keep.mean() > 0.9
-    set_switches(monkeypatch, fam["sw"])
+    set_switches(monkeypatch, SWITCHES, fam["sw"])
     # calls that end a few frames behind each non-finite frame: it then sits in the history the next call starts from
     cuts = [0, p_nan + 5, p_inf + 16, n]
 

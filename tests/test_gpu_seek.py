@@ -10,8 +10,6 @@ bars (integer outputs +-1 LSB and >= 99.8 % identical codes, 99.5 % behind a fil
 seamless to 1e-6 of full scale by derivation (include/iqgpu.h); their bar here is the project's: int_close on cs16, 1e-5 on cf32.
 
 Every comparison prints its figure before it asserts (pytest -s shows them)."""
-import json
-import os
 import subprocess
 
 import numpy as np
@@ -19,11 +17,10 @@ import pytest
 
 from iq_tool_amd import synth
 
+from shard_support import EHIP, EINVAL, EUNSUPPORTED, EXE, frames, run, set_switches
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "iq_tool_amd", "lib", "iqgpu_run")
 TOL = 1e-5
-EINVAL, EHIP, EUNSUPPORTED = -1, -9, -10
 
 NRSC5 = dict(in_format="cs16", out_format="cs16", input_rate_hz=2.4e6, target_rate_hz=744187.5, shift_hz=200e3)
 CU8_NRSC5 = dict(in_format="cu8", out_format="cu8", input_rate_hz=2.4e6, target_rate_hz=1488375.0)
@@ -77,18 +74,6 @@ def run_oracle(oracle, raw, **kw):
     return oracle.Chain(**kw).process(raw)
 
 
-def frames(kw, raw, a, b):
-    bpf = 2 if kw["in_format"] in ("cu8", "cs8") else 4
-    return np.ascontiguousarray(raw).view(np.uint8)[a * bpf:b * bpf]
-
-
-def set_switches(monkeypatch, sw):
-    for k in SWITCHES:
-        monkeypatch.delenv("IQGPU_" + k, raising=False)
-    for k, v in sw.items():
-        monkeypatch.setenv("IQGPU_" + k, v)
-
-
 def seams(gpu, kw):
     """an aligned seam and a ragged one, both behind the chain's whole memory so that the warm-up is what is tested"""
     p = gpu.design_preroll_frames(**kw)
@@ -99,7 +84,7 @@ def seams(gpu, kw):
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_seek_continues_the_stream_byte_for_byte(gpu, oracle, monkeypatch, name):
     kw, sw, n, kernel, filtered = CASES[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     raw = synth.raw_stream(n, kw["input_rate_hz"], 51, kw["in_format"])
     obpf = 2                                                    # components per output frame
     want = run_oracle(oracle, raw, **kw)
@@ -258,7 +243,7 @@ def test_seek_clears_a_poisoned_handle(gpu, monkeypatch):
     HOST, before anything of the filter is launched: with the radix-16 transform switched off and a 16384-point transform asked
     for, launch_fftconv's own argument check turns the launch down (the radix-4 kernel stops at 8192 points).  Calls that emit no
     block never reach that check, which is how the handle shows that it works again."""
-    set_switches(monkeypatch, dict(FFT_NO_R16="1", FFT_LOG2N="14"))
+    set_switches(monkeypatch, SWITCHES, dict(FFT_NO_R16="1", FFT_LOG2N="14"))
     kw = dict(in_format="cs16", out_format="cs16", input_rate_hz=2.4e6, no_resample=True, filters=(("lowpass", 300e3, 0.0),), filter_taps=129,
               filter_impl="fft")
     raw = synth.raw_stream(8192, 2.4e6, 57, "cs16")
@@ -280,12 +265,6 @@ def test_seek_clears_a_poisoned_handle(gpu, monkeypatch):
 # --------------------------------------------------------------------------------------------
 ARGS = ["--raw-file-input-rate", "2.4e6", "--raw-file-input-sample-format", "cs16", "--output-rate", "744187.5",
         "--output-sample-format", "cs16", "--freq-shift", "200e3"]
-
-
-def run(*args):
-    r = subprocess.run([EXE, *args], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr + r.stdout
-    return json.loads(r.stdout.strip().splitlines()[-1])
 
 
 def check_seamless_report(gpu, info, shards, n):

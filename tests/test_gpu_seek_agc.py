@@ -12,20 +12,16 @@ what the new entry points say about themselves: states are compared with iqgpu_c
 with the ordinary chain's bytes, peaks with the oracle's stream in front of the AGC.
 
 Every comparison prints its figure before it asserts (pytest -s shows them)."""
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from iq_tool_amd import synth
 
+from shard_support import ECAPACITY, EINVAL, EUNSUPPORTED, fr, run, set_switches
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "iq_tool_amd", "lib", "iqgpu_run")
 TOL = 1e-5
-EINVAL, ECAPACITY, EUNSUPPORTED = -1, -8, -10
 RATE = 96e3                                     # 2.4 MS/s scaled by 0.04: every preset ratio below is the preset's
 K = RATE / 2.4e6
 CHUNK = 16384
@@ -55,13 +51,6 @@ ROUTINGS = {
 }
 
 
-def set_switches(monkeypatch, sw):
-    for k in SWITCHES:
-        monkeypatch.delenv("IQGPU_" + k, raising=False)
-    for k, v in sw.items():
-        monkeypatch.setenv("IQGPU_" + k, v)
-
-
 def stream(fmt, seed=61):
     """the synthetic stream under the envelope of the module docstring (frame times at 96 kHz)"""
     raw = synth.raw_stream(N, 2.4e6, seed, "cs16").astype(np.float64).reshape(-1, 2)
@@ -73,11 +62,6 @@ def stream(fmt, seed=61):
     if fmt == "cu8":
         return ((cs16.astype(np.int32) >> 8) + 128).astype(np.uint8)
     return cs16
-
-
-def fr(x, a, b):
-    """frames [a, b) of an interleaved stream"""
-    return x[2 * a:2 * b]
 
 
 def no_agc(kw, **over):
@@ -130,7 +114,7 @@ def int_close(a, b, min_same, what):
 @pytest.mark.parametrize("name", sorted(ROUTINGS))
 def test_walked_table_is_the_ordinary_chains_state(gpu, oracle, monkeypatch, name):
     kw, sw, _ = ROUTINGS[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream(kw["in_format"])
     _, _, states = single_stream(gpu, kw, x)
     m, per_call = measured_table(gpu, kw, x)
@@ -183,7 +167,7 @@ def test_walked_gains_are_the_gains_the_ordinary_path_applied(gpu, monkeypatch, 
     the stream in front of the AGC comes from the same chain without the AGC"""
     kw, sw, _ = ROUTINGS[name]
     kw = dict(kw, out_format="cf32")
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream(kw["in_format"])
     _, outs, _ = single_stream(gpu, kw, x)
     y = np.concatenate(outs).view(np.float32)
@@ -212,9 +196,9 @@ def test_both_routes_of_the_measure_pass_give_the_same_rows(gpu, monkeypatch, na
     first chunk that starts inside a tile)"""
     kw, sw, _ = ROUTINGS[name]
     x = stream(kw["in_format"])
-    set_switches(monkeypatch, dict(sw, MEASURE_ROUTE="unfused"))
+    set_switches(monkeypatch, SWITCHES, dict(sw, MEASURE_ROUTE="unfused"))
     a, per_a = measured_table(gpu, kw, x, 20 * B)
-    set_switches(monkeypatch, dict(sw, MEASURE_ROUTE="s1"))
+    set_switches(monkeypatch, SWITCHES, dict(sw, MEASURE_ROUTE="s1"))
     b, per_b = measured_table(gpu, kw, x, 20 * B)
     print("%s: measure on %s / %s" % (name, a.front_kernel(), b.front_kernel()))
     assert b.front_kernel().endswith("k_front_s1") and (name == "am_cascade" or a.front_kernel() != b.front_kernel())
@@ -225,7 +209,7 @@ def test_both_routes_of_the_measure_pass_give_the_same_rows(gpu, monkeypatch, na
         qa, qb = a.measure(fr(x, lo, hi)), b.measure(fr(x, lo, hi))
         assert qa.size == qb.size == -(-(hi - lo) // CHUNK) and np.array_equal(qa.view(np.uint8), qb.view(np.uint8)), (name, lo, hi)
     # ... and a chain that has measured that way processes on as any other: nothing of the ordinary path's AGC was touched
-    set_switches(monkeypatch, dict(sw, MEASURE_ROUTE="unfused"))
+    set_switches(monkeypatch, SWITCHES, dict(sw, MEASURE_ROUTE="unfused"))
     ref = gpu.Chain(**kw)
     ref.measure(fr(x, 0, 24 * B))
     assert np.array_equal(b.process(fr(x, 24 * B, 28 * B)), ref.process(fr(x, 24 * B, 28 * B)))
@@ -235,7 +219,7 @@ def test_default_route_of_the_measure_pass_per_shape(gpu, monkeypatch):
     """the faster route measured per shape: k_front_s1<.., AGC> without a half-band stage, the unfused kernels with one"""
     for name, want in (("cu8_nrsc5_p0", "k_front_s1"), ("nrsc5_cs16_mid", "k_front_mid<6,nco,cf32>")):
         kw, sw, _ = ROUTINGS[name]
-        set_switches(monkeypatch, sw)
+        set_switches(monkeypatch, SWITCHES, sw)
         ch = gpu.Chain(**kw)
         ch.measure(fr(stream(kw["in_format"]), 0, B))
         assert ch.front_kernel() == want, (name, ch.front_kernel())
@@ -247,7 +231,7 @@ def test_default_route_of_the_measure_pass_per_shape(gpu, monkeypatch):
 @pytest.mark.parametrize("name", sorted(ROUTINGS))
 def test_seek_agc_continues_the_stream_byte_for_byte(gpu, monkeypatch, name):
     kw, sw, family = ROUTINGS[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream(kw["in_format"])
     ref, outs, _ = single_stream(gpu, kw, x)
     final = ref.agc_state_raw()
@@ -273,7 +257,7 @@ def test_seek_agc_continues_the_stream_byte_for_byte(gpu, monkeypatch, name):
 
 def test_seek_agc_device_variant_longer_preroll_and_a_chain_that_has_run(gpu, monkeypatch):
     kw, sw, _ = ROUTINGS["nrsc5_cs16_mid"]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream("cs16")
     a, end = SEAMS["locked"], SEAMS["locked"] + 6 * B
     _, outs, _ = single_stream(gpu, kw, x, end)
@@ -340,7 +324,7 @@ def test_dc_blocker_chain_with_agc_is_seamless_to_the_project_bars(gpu, out_form
 def test_measure_leaves_the_agc_state_and_advances_the_stream(gpu, monkeypatch, name):
     kw, sw, _ = ROUTINGS[name]
     kw = dict(kw, out_format="cf32")
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream(kw["in_format"])
     a, b = 5 * B + 3 * CHUNK + 1234, 9 * B + 77                # ragged: an open group, a phase, samples pending in front of a block
     ch = gpu.Chain(**kw)
@@ -428,12 +412,6 @@ HARNESS = {
     "cu8_nrsc5": (["--raw-file-input-rate", "96e3", "--raw-file-input-sample-format", "cu8", "--output-rate", "59535",
                    "--output-sample-format", "cu8"], "cu8", np.uint8),
 }
-
-
-def run(*args):
-    r = subprocess.run([EXE, *args], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr + r.stdout
-    return json.loads(r.stdout.strip().splitlines()[-1])
 
 
 def check_report(info, shards, n, chunk):

@@ -10,7 +10,6 @@ order 1e4 and an error in its last bits would reach the output codes."""
 import ctypes as C
 import filecmp
 import functools
-import json
 import os
 import subprocess
 
@@ -19,10 +18,9 @@ import pytest
 
 from iq_tool_amd import synth
 
+from shard_support import EINVAL, EUNSUPPORTED, EXE, expect, frames, run, same as same_bytes, set_switches
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "iq_tool_amd", "lib", "iqgpu_run")
-EINVAL, EUNSUPPORTED = -1, -10
 CALL = 131072
 SWITCHES = ("FORCE_FAT", "FAT", "NO_P0", "NO_S2", "FORCE_GENERIC", "NO_FAST", "FFT_NO_R16", "FFT_LOG2N", "NO_FAT", "NO_CASC2", "CASC2_MIN_RUN")
 
@@ -45,13 +43,6 @@ ROUTINGS = {
 }
 
 
-def set_switches(monkeypatch, sw):
-    for k in SWITCHES:
-        monkeypatch.delenv("IQGPU_" + k, raising=False)
-    for k, v in sw.items():
-        monkeypatch.setenv("IQGPU_" + k, v)
-
-
 @functools.lru_cache(maxsize=None)
 def dc_stream(n, rate_hz, fmt):
     """synth.raw_stream plus a DC offset of about (0.2, -0.15) of full scale, as interleaved components of the raw format (read only)"""
@@ -65,21 +56,8 @@ def dc_stream(n, rate_hz, fmt):
     return out
 
 
-def bpf(kw):
-    return {"cu8": 2, "cs8": 2, "cf32": 8}.get(kw["in_format"], 4)
-
-
-def frames(kw, raw, a, b):
-    return np.ascontiguousarray(raw).view(np.uint8)[a * bpf(kw):b * bpf(kw)]
-
-
 def calls(n, c=CALL):
     return [(a, min(a + c, n)) for a in range(0, n, c)]
-
-
-def same_bytes(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.nbytes == b.nbytes and np.array_equal(a.reshape(-1).view(np.uint8), b.reshape(-1).view(np.uint8))
 
 
 def p_fir(gpu, kw):
@@ -120,7 +98,7 @@ def measure_all(gpu, ch, kw, raw, n, c=CALL, unaligned=()):
 @pytest.mark.parametrize("name", sorted(ROUTINGS))
 def test_walked_state_is_the_streams_bit_for_bit(gpu, monkeypatch, name):
     kw, sw, kernel = ROUTINGS[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     n = 6 * CALL + 50_001                                        # six whole calls and a ragged, odd one
     raw = dc_stream(n, kw["input_rate_hz"], kw["in_format"])
     outs, states, got_kernel = single_stream(gpu, kw, raw, n)
@@ -220,7 +198,7 @@ BYTE_CASES = [(name, fmt, False) for name in sorted(ROUTINGS) for fmt in ("cs16"
 def test_seek_dc_continues_the_stream_byte_for_byte(gpu, monkeypatch, name, out_format, filtered):
     kw, sw, _ = ROUTINGS[name]
     kw = dict(kw, out_format=out_format, **(CONFIG3_FILTER if filtered else {}))
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     n, k0 = 6 * CALL + 50_001, 3
     raw = dc_stream(n, kw["input_rate_hz"], kw["in_format"])
     assert p_fir(gpu, kw) <= CALL                                # the preroll is ONE grid call
@@ -309,14 +287,6 @@ def test_seek_refuses_the_short_preroll_that_seek_dc_accepts(gpu):
 # --------------------------------------------------------------------------------------------
 # 4. errors
 # --------------------------------------------------------------------------------------------
-def expect(gpu, code, fn, *args, word=None):
-    with pytest.raises(gpu.IqgpuError) as e:
-        fn(*args)
-    assert e.value.code == code, str(e.value)
-    if word:
-        assert word in str(e.value)
-
-
 def test_errors(gpu):
     from iq_tool_amd import _lib
     from iq_tool_amd.chain import DC_ROW
@@ -397,12 +367,6 @@ def test_seek_dc_at_frame_zero_is_a_fresh_chain(gpu):
 # --------------------------------------------------------------------------------------------
 ARGS = ["--raw-file-input-rate", "2.4e6", "--raw-file-input-sample-format", "cs16", "--output-rate", "744187.5",
         "--output-sample-format", "cs16", "--freq-shift", "200e3"]
-
-
-def run(*args):
-    r = subprocess.run([EXE, *args], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr + r.stdout
-    return json.loads(r.stdout.strip().splitlines()[-1])
 
 
 def test_harness_seamless_dc_shards_write_the_single_stream(gpu, tmp_path):

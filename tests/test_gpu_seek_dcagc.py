@@ -21,10 +21,9 @@ import pytest
 
 from iq_tool_amd import synth
 
+from shard_support import ECAPACITY, EINVAL, EUNSUPPORTED, EXE, expect, fr, same, set_switches
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "iq_tool_amd", "lib", "iqgpu_run")
-EINVAL, ECAPACITY, EUNSUPPORTED = -1, -8, -10
 RATE = 96e3
 K = RATE / 2.4e6
 CHUNK = 16384
@@ -56,13 +55,6 @@ ROUTINGS = {
 }
 
 
-def set_switches(monkeypatch, sw):
-    for k in SWITCHES:
-        monkeypatch.delenv("IQGPU_" + k, raising=False)
-    for k, v in sw.items():
-        monkeypatch.setenv("IQGPU_" + k, v)
-
-
 _streams = {}
 
 
@@ -78,15 +70,6 @@ def stream(fmt):
         _streams["cs16"] = cs16
         _streams["cu8"] = ((cs16.astype(np.int32) >> 8) + 128).astype(np.uint8)
     return _streams[fmt]
-
-
-def fr(x, a, b):
-    return x[2 * a:2 * b]
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.nbytes == b.nbytes and a.tobytes() == b.tobytes()
 
 
 def p_fir(gpu, kw):
@@ -147,7 +130,7 @@ def seek_to(gpu, kw, x, k, dc_before, first_row, st, entry):
 @pytest.mark.parametrize("name", sorted(ROUTINGS))
 def test_seams_are_invisible(gpu, monkeypatch, name):
     kw, sw, cuts = ROUTINGS[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream(kw["in_format"])
     one = single_stream(gpu, name)
     last = max(SEAMS.values()) // B
@@ -201,7 +184,7 @@ def test_seams_are_invisible(gpu, monkeypatch, name):
 @pytest.mark.parametrize("name", ["nrsc5_cs16_mid", "usb_filter_epilogue"])
 def test_four_range_stitch_from_one_pair_of_walks(gpu, monkeypatch, name):
     kw, sw, _ = ROUTINGS[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream(kw["in_format"])
     one = single_stream(gpu, name)
     cuts = [0, 3, 16, 30]                                        # in grid calls: in front of the locking call, in the hang interval, behind the ratchet
@@ -231,7 +214,7 @@ def test_four_range_stitch_from_one_pair_of_walks(gpu, monkeypatch, name):
 def test_shadow_calls_leave_the_rest_alone(gpu, monkeypatch):
     name = "nrsc5_cs16_mid"
     kw, sw, _ = ROUTINGS[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream(kw["in_format"])
     one = single_stream(gpu, name)
     # a dcagc_dc_measure between ordinary calls: the chain continues byte-identically
@@ -279,7 +262,7 @@ def test_device_variants_at_the_single_streams_alignment(gpu, monkeypatch, lead)
     header asks; at lead 0 that is the host variants' staging, whose rows and bytes the device variants then give"""
     name = "nrsc5_cs16_mid"
     kw, sw, _ = ROUTINGS[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream("cs16")
     n_calls, k0 = 8, 5
     buf = gpu.DeviceBuffer(n_calls * B * 4 + 64)
@@ -335,7 +318,7 @@ def test_device_variants_at_the_single_streams_alignment(gpu, monkeypatch, lead)
 # --------------------------------------------------------------------------------------------
 def test_dcagc_dc_advance_is_dc_advance(gpu, monkeypatch):
     kw, sw, _ = ROUTINGS["nrsc5_cs16_mid"]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream("cs16")
     per_call, _, before, st = dc_walk(gpu, kw, x, 6 * B)
     rows = np.concatenate(per_call)
@@ -347,20 +330,12 @@ def test_dcagc_dc_advance_is_dc_advance(gpu, monkeypatch):
 # --------------------------------------------------------------------------------------------
 # 6. errors
 # --------------------------------------------------------------------------------------------
-def expect(gpu, code, fn, *args, word=None):
-    with pytest.raises(gpu.IqgpuError) as e:
-        fn(*args)
-    assert e.value.code == code, str(e.value)
-    if word:
-        assert word in str(e.value)
-
-
 def test_errors(gpu, monkeypatch):
     from iq_tool_amd import _lib
     from iq_tool_amd.chain import AGC_ROW, DC_ROW, DC_STATE
     name = "usb_filter_epilogue"                                  # (a chain with filter memory: P_fir > 0)
     kw, sw, _ = ROUTINGS[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream("cs16")
     one = single_stream(gpu, name)
     assert 0 < p_fir(gpu, kw) <= B
@@ -480,7 +455,7 @@ def test_negative_control_seek_agc_meets_the_stream_only_to_the_dc_bound(gpu, mo
     single stream's, and the comparisons above would say so"""
     name = "nrsc5_cs16_mid"
     kw, sw, _ = ROUTINGS[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream("cs16")
     one = single_stream(gpu, name)
     k0 = SEAMS["locked"] // B

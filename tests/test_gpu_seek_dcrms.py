@@ -10,7 +10,7 @@ seam certifies); the checkpoint right after the seek is byte-equal to the single
 stitched bytes and the final DC and AGC states are equal.  The FFT-filter shape goes through the certificate procedure with its
 fallback instead, and the certificate has to tell the truth.
 
-Input: the noise generator and level steps of test_gpu_seek_rms.py, restated: seeded Gaussian noise under steps of -14, +14, +12
+Input: the noise generator and level steps of test_gpu_seek_rms.py (shard_support.noise): seeded Gaussian noise under steps of -14, +14, +12
 and -18 dB, never silent.  The seam in silence has its own stream.
 
 Geometry (agc_rms_geometry): local -> warm 2600, chunk 256; dx -> warm 260 000, chunk 16 250: a call of a dx chain costs ~50 ms
@@ -20,19 +20,16 @@ Every figure is printed before it is asserted (pytest -s)."""
 import ctypes as C
 import functools
 import json
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
+from shard_support import differing, EINVAL, EUNSUPPORTED, EXE, expect, fr, grid, noise, same, words
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "iq_tool_amd", "lib", "iqgpu_run")
-EINVAL, EUNSUPPORTED = -1, -10
 RATE = 2.4e6
 GEOM = {"local": (2600, 256), "dx": (260000, 16250)}          # profile -> (warm, chunk)
-LEVELS = (1.0, 0.2, 1.0, 4.0, 0.5)                            # steps of -14, +14, +12, -18 dB
 
 POINTWISE = dict(in_format="cs16", out_format="cs16", input_rate_hz=RATE, target_rate_hz=RATE, no_resample=True)
 NRSC5 = dict(in_format="cs16", out_format="cs16", input_rate_hz=RATE, target_rate_hz=744187.5, shift_hz=200e3)
@@ -50,38 +47,6 @@ SHAPES = {
     "local_fft_cf32": (USB_FFT, "local", 1_000_000, 65536, (4, 10), False),               # FFT filter on the grid: whatever the certificate says
     "dx_decim_cu8": (CU8, "dx", 1_700_000, 262144, (2, 5), True),                         # dx geometry: a preroll of two grid calls
 }
-
-
-def noise(n, fmt, seed, levels=LEVELS):
-    rng = np.random.default_rng(seed)
-    z = rng.standard_normal((n, 2))
-    env = np.repeat(np.asarray(levels, np.float64), -(-n // len(levels)))[:n, None]
-    if fmt == "cu8":
-        return np.clip(np.rint(127.5 + 6.0 * env * z), 0, 255).astype(np.uint8).reshape(-1)
-    return np.clip(np.rint(1500.0 * env * z), -32768, 32767).astype(np.int16).reshape(-1)
-
-
-def fr(x, a, b):
-    return x[2 * a:2 * b]
-
-
-def words(st):
-    """the three words of the seam certificate, as bits"""
-    return (np.float32(st.current_gain).view(np.uint32).item(), np.float32(st.peak_memory).view(np.uint32).item(), int(st.samples_seen))
-
-
-def same(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.nbytes == b.nbytes and a.tobytes() == b.tobytes()
-
-
-def differing(a, b):
-    return int((a.view(np.uint8) != b.view(np.uint8)).sum()) if a.nbytes == b.nbytes else -1
-
-
-def grid(a, b, c):
-    """the grid calls of [a, b): the last one of a stream may be shorter"""
-    return [(p, min(p + c, b)) for p in range(a, b, c)]
 
 
 def on_grid(ch, x, a, b, c):
@@ -287,15 +252,6 @@ def test_a_seam_in_silence_is_judged_truthfully_and_the_fallback_restores_the_st
 # --------------------------------------------------------------------------------------------
 # 4. refusals and argument checks
 # --------------------------------------------------------------------------------------------
-def expect(gpu, code, fn, *args, word=None):
-    with pytest.raises(gpu.IqgpuError) as e:
-        fn(*args)
-    print(e.value)
-    assert e.value.code == code, str(e.value)
-    if word:
-        assert word in str(e.value)
-
-
 def test_refusals_and_argument_checks(gpu):
     from iq_tool_amd import _lib
     from iq_tool_amd.chain import DC_ROW, DC_STATE

@@ -15,23 +15,17 @@ Input: seeded Gaussian noise under level steps of -14, +14, +12 and -18 dB, neve
 holds everywhere (the certificate at every seam is asserted, not assumed).  The seam that must NOT certify has its own stream.
 
 Every figure is printed before it is asserted (pytest -s)."""
-import ctypes as C
 import functools
-import json
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from shard_support import EINVAL, EUNSUPPORTED, fr, noise, run, words
+
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-EXE = os.path.join(ROOT, "iq_tool_amd", "lib", "iqgpu_run")
-EINVAL, EUNSUPPORTED = -1, -10
 RATE = 2.4e6
 GEOM = {"local": (2600, 256), "dx": (260000, 16250)}          # profile -> (warm, chunk)
 RAGGED = 4 * 16384 + 37                                       # the call length of the checkpoint tests: 4 chunks + 37 frames
-LEVELS = (1.0, 0.2, 1.0, 4.0, 0.5)                            # steps of -14, +14, +12, -18 dB
 
 POINTWISE = dict(in_format="cs16", out_format="cs16", input_rate_hz=RATE, target_rate_hz=RATE, no_resample=True)
 NRSC5 = dict(in_format="cs16", out_format="cs16", input_rate_hz=RATE, target_rate_hz=744187.5, shift_hz=200e3)
@@ -68,26 +62,8 @@ def calls_of(name, a, b, per, n, p_rms):
     return [(p, min(p + per, last)) for p in range(a, last, per)] + ([(last, b)] if last != b else [])
 
 
-def noise(n, fmt, seed, levels=LEVELS):
-    rng = np.random.default_rng(seed)
-    z = rng.standard_normal((n, 2))
-    env = np.repeat(np.asarray(levels, np.float64), -(-n // len(levels)))[:n, None]
-    if fmt == "cu8":
-        return np.clip(np.rint(127.5 + 6.0 * env * z), 0, 255).astype(np.uint8).reshape(-1)
-    return np.clip(np.rint(1500.0 * env * z), -32768, 32767).astype(np.int16).reshape(-1)
-
-
-def fr(x, a, b):
-    return x[2 * a:2 * b]
-
-
 def no_agc(kw):
     return dict(kw, agc=False)
-
-
-def words(st):
-    """the three words of the seam certificate, as bits"""
-    return (np.float32(st.current_gain).view(np.uint32).item(), np.float32(st.peak_memory).view(np.uint32).item(), int(st.samples_seen))
 
 
 def in_calls(ch, x, a, b, per):
@@ -290,12 +266,6 @@ def test_the_iq_probe_takes_no_block_from_the_preroll_and_holds_none_behind_the_
 # --------------------------------------------------------------------------------------------
 HARNESS_ARGS = ["--raw-file-input-rate", "2.4e6", "--raw-file-input-sample-format", "cs16", "--output-rate", "744187.5",
                 "--output-sample-format", "cs16", "--freq-shift", "200e3", "--agc-profile", "local", "--chunk-frames", "65536"]
-
-
-def run(*args):
-    r = subprocess.run([EXE, *args], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr + r.stdout
-    return json.loads(r.stdout.strip().splitlines()[-1])
 
 
 def harness_pair(tmp_path, x):

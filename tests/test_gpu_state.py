@@ -18,8 +18,9 @@ import pytest
 
 from iq_tool_amd import synth
 
+from shard_support import ECAPACITY, EHIP, EINVAL, EUNSUPPORTED, set_switches
+
 pytestmark = pytest.mark.gpu
-EINVAL, ECAPACITY, EHIP, EUNSUPPORTED = -1, -8, -9, -10
 RATE = 96e3
 K = RATE / 2.4e6                                # the 2.4 MS/s presets
 K10 = RATE / 10e6                               # BASELINE configs[2]: 10 MS/s -> 2.4 MS/s
@@ -72,13 +73,6 @@ SHAPES = {
     #  window, so the blob holds a partly filled one)
     "agc_dx": (dict(NRSC5, agc=True, agc_profile="dx"), dict(FORCE_FAT="1"), 6, dict(early=1, middle=3), "k_front_mid<6,nco"),
 }
-
-
-def set_switches(monkeypatch, sw):
-    for k in SWITCHES:
-        monkeypatch.delenv("IQGPU_" + k, raising=False)
-    for k, v in sw.items():
-        monkeypatch.setenv("IQGPU_" + k, v)
 
 
 @functools.lru_cache(maxsize=None)
@@ -175,7 +169,7 @@ def continuation(gpu, name, ref, cuts=None):
 @pytest.mark.parametrize("name", sorted(SHAPES))
 def test_a_loaded_chain_continues_the_stream_byte_for_byte(gpu, monkeypatch, name):
     kw, sw, n, cuts, _ = SHAPES[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     ref = reference(gpu, name, sw.items())
     assert sum(o.size for o in ref["outs"]) > 0 and ref["tells"][-1][0] == n * L
     x = continuation(gpu, name, ref)
@@ -203,7 +197,7 @@ def test_a_loaded_chain_continues_the_stream_byte_for_byte(gpu, monkeypatch, nam
 @pytest.mark.parametrize("name", ["nrsc5_agc", "config3_like", "agc_local", "interp", "am_cascade"])
 def test_a_chain_that_saves_after_every_call_writes_the_same_bytes(gpu, monkeypatch, name):
     kw, sw, n, _, _ = SHAPES[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     ref = reference(gpu, name, sw.items())
     x = stream(kw["in_format"])
     ch = gpu.Chain(**kw)
@@ -217,7 +211,7 @@ def test_a_chain_that_saves_after_every_call_writes_the_same_bytes(gpu, monkeypa
 @pytest.mark.parametrize("name", sorted(SHAPES))
 def test_the_blob_is_a_deterministic_function_of_the_state(gpu, monkeypatch, name):
     kw, sw, n, _, _ = SHAPES[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     x = stream(kw["in_format"])
     k = min(n, 4)
     one, two = gpu.Chain(**kw), gpu.Chain(**kw)
@@ -251,7 +245,7 @@ def test_save_behind_batches_in_flight(gpu, monkeypatch, name):
     """three batches submitted and not collected: save runs them to their end first, so the blob is the one of a twin that processed
     the same three calls one by one; the tickets are collected afterwards as usual"""
     kw, sw, n, _, _ = SHAPES[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     ref = reference(gpu, name, sw.items())
     x = stream(kw["in_format"])
     a, twin = gpu.Chain(**kw), gpu.Chain(**kw)
@@ -278,7 +272,7 @@ def test_save_behind_batches_in_flight(gpu, monkeypatch, name):
 @pytest.mark.parametrize("name", ["nrsc5_agc", "usb_filter_epilogue", "interp"])
 def test_a_loaded_chain_continues_through_submit_and_collect(gpu, monkeypatch, name):
     kw, sw, n, cuts, _ = SHAPES[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     ref = reference(gpu, name, sw.items())
     x = stream(kw["in_format"])
     k, n = 3, min(n, 16)
@@ -297,7 +291,7 @@ def test_a_loaded_chain_continues_through_submit_and_collect(gpu, monkeypatch, n
 @pytest.mark.parametrize("name", ["nrsc5_agc", "config3_like", "agc_local", "am_cascade", "interp"])
 def test_load_into_a_chain_that_has_run(gpu, monkeypatch, name):
     kw, sw, n, _, _ = SHAPES[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     ref = reference(gpu, name, sw.items())
     x = stream(kw["in_format"])
     k, n = 3, min(n, 12)
@@ -316,7 +310,7 @@ def test_load_clears_a_poisoned_handle_and_save_refuses_one(gpu, monkeypatch):
     """The failure is a refusal on the HOST (test_gpu_seek.py: with the radix-16 transform switched off and a 16384-point transform
     asked for, launch_fftconv's own argument check turns the launch down), which poisons the handle.  Calls that emit no block never
     reach that check: the state that is loaded, and compared, is 100 frames pending in front of the block."""
-    set_switches(monkeypatch, dict(FFT_NO_R16="1", FFT_LOG2N="14"))
+    set_switches(monkeypatch, SWITCHES, dict(FFT_NO_R16="1", FFT_LOG2N="14"))
     kw = dict(in_format="cs16", out_format="cs16", input_rate_hz=2.4e6, no_resample=True, filters=(("lowpass", 300e3, 0.0),), filter_taps=129,
               filter_impl="fft")
     raw = synth.raw_stream(8192, 2.4e6, 57, "cs16")
@@ -348,7 +342,7 @@ def test_load_clears_a_poisoned_handle_and_save_refuses_one(gpu, monkeypatch):
 def test_continuation_under_the_routing_switches(gpu, monkeypatch, name, switch):
     kw, _, n, cuts, _ = SHAPES[name]
     sw = {switch: "1"}
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     ref = reference(gpu, name, sw.items())
     x = stream(kw["in_format"])
     print("%s under %s: first call on %s" % (name, switch, ref["first"]))
@@ -364,18 +358,18 @@ def test_continuation_under_the_routing_switches(gpu, monkeypatch, name, switch)
 def test_a_blob_is_refused_under_another_switch_snapshot(gpu, monkeypatch):
     kw = SHAPES["nrsc5_agc"][0]
     x = stream("cs16")
-    set_switches(monkeypatch, {})
+    set_switches(monkeypatch, SWITCHES, {})
     saver = gpu.Chain(**kw)
     saver.process(call(x, 0))
     blob = saver.save_state()
     for sw in (dict(FORCE_GENERIC="1"), dict(NO_FAST="1"), dict(AGC_NOFUSE="1"), dict(FORCE_FAT="1")):
-        set_switches(monkeypatch, sw)
+        set_switches(monkeypatch, SWITCHES, sw)
         other, twin = gpu.Chain(**kw), gpu.Chain(**kw)
         with pytest.raises(gpu.IqgpuError) as e:
             other.load_state(blob)
         assert e.value.code == EINVAL and "fingerprint" in str(e.value) and "switches" in str(e.value), sw
         assert same(other.process(call(x, 0)), twin.process(call(x, 0)))
-    set_switches(monkeypatch, {})
+    set_switches(monkeypatch, SWITCHES, {})
     gpu.Chain(**kw).load_state(blob)                           # the snapshot it was saved under takes it
 
 
@@ -384,7 +378,7 @@ def test_a_blob_is_refused_under_another_switch_snapshot(gpu, monkeypatch):
 # --------------------------------------------------------------------------------------------
 def test_iq_factors_set_mid_stream_are_restored(gpu, monkeypatch):
     kw, sw, n, _, _ = SHAPES["config3_like"]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     ref = reference(gpu, "config3_like", sw.items())
     x = stream("cs16")
     mag, phase = 0.031, 0.047
@@ -420,7 +414,7 @@ def test_iq_factors_set_mid_stream_are_restored(gpu, monkeypatch):
 # --------------------------------------------------------------------------------------------
 def test_tell_and_seek_then_restore(gpu, monkeypatch):
     kw, sw, n, _, _ = SHAPES["nrsc5_mid"]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     ref = reference(gpu, "nrsc5_mid", sw.items())
     x = stream("cs16")
     fi = fo = 0
@@ -456,7 +450,7 @@ def test_tell_and_seek_then_restore(gpu, monkeypatch):
 def test_refusals_leave_the_chain_as_it_was(gpu, monkeypatch):
     name = "usb_filter_epilogue"
     kw, sw, n, _, _ = SHAPES[name]
-    set_switches(monkeypatch, sw)
+    set_switches(monkeypatch, SWITCHES, sw)
     ref = reference(gpu, name, sw.items())
     x = stream("cs16")
     ch = gpu.Chain(**kw)
