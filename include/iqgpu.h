@@ -335,7 +335,8 @@ int    iqgpu_chain_seek_agc_device(iqgpu_chain *c, uint64_t first_frame, const v
  * the single stream's call has.)  A preroll off the grid keeps the DC state exact and leaves the histories, and so the first
  * outputs, only within the bound of iqgpu_chain_seek.
  * Recipe:
- *   1. Measure (all ranges but the last, in parallel): iqgpu_chain_dc_measure for every grid call of the range, one row each, in order.
+ *   1. Measure (all ranges but the last, in parallel): ONE iqgpu_chain_dc_measure_range over the range (below: every grid call of it in
+ *      one submission), or iqgpu_chain_dc_measure for every grid call of the range; one row per call, in order, the same rows either way.
  *   2. Walk (any one chain): st = {0, 0}; ONE iqgpu_chain_dc_advance over all rows with before[]: before[k] is the state in front of
  *      grid call k.
  *   3. Process (all ranges in parallel): iqgpu_chain_seek_dc(c, cut, preroll, n C, C, &before[cut / C - n]), then the ordinary
@@ -390,7 +391,8 @@ int    iqgpu_chain_seek_dc_device(iqgpu_chain *c, uint64_t first_frame, const vo
  * agc_chunk_frames and of 4096; the preroll of a range is the ceil(P_fir / C) grid calls in front of its cut (all of [0, cut) when
  * that is less), with P_fir = iqgpu_design_preroll_frames of the description with dc_block_enable = 0 and agc_enable = 0.
  * Recipe:
- *   1. DC measure (all ranges but the last, in parallel): iqgpu_chain_dcagc_dc_measure for every grid call, in order.  A call yields
+ *   1. DC measure (all ranges but the last, in parallel): ONE iqgpu_chain_dcagc_dc_measure_range over the range (it returns first_row[]),
+ *      or iqgpu_chain_dcagc_dc_measure for every grid call, in order -- the same rows either way.  A call yields
  *      ONE ROW PER PIECE (1 or 2: two for the call the single stream cuts); keep all rows and note the first row index of every call.
  *      The two maps of a cut call must not be merged: the single stream rounds its state behind each piece.
  *   2. DC walk (any one chain): st = {0, 0}; one iqgpu_chain_dcagc_dc_advance over all rows with before[]: the state in front of
@@ -505,7 +507,8 @@ int    iqgpu_chain_seek_rms_device(iqgpu_chain *c, uint64_t first_frame, const v
  * blocker's decaying state, which may or may not stay under that threshold).  The calls behind the seek are the grid's calls: the blocker's
  * state is rounded once per call.  Placement: iqgpu_design_out_frames_range of the description with agc_enable = 0.
  * Recipe:
- *   1. DC measure (all ranges but the last, in parallel): iqgpu_chain_dcrms_dc_measure for every grid call, one row each, in order.
+ *   1. DC measure (all ranges but the last, in parallel): ONE iqgpu_chain_dcrms_dc_measure_range over the range, or
+ *      iqgpu_chain_dcrms_dc_measure for every grid call; one row each, in order, the same rows either way.
  *   2. Walk (any one chain): st = {0, 0}; ONE iqgpu_chain_dcrms_dc_advance over all rows with before[]: before[k] is the state in
  *      front of grid call k.
  *   3. Process (all ranges in parallel): iqgpu_chain_dcrms_seek(c, cut, preroll, n C, C, &before[cut / C - n]), read S[s] =
@@ -543,6 +546,43 @@ int    iqgpu_chain_dcrms_seek(iqgpu_chain *c, uint64_t first_frame, const void *
                               const iqgpu_dc_state *dc_at_preroll_start);
 int    iqgpu_chain_dcrms_seek_device(iqgpu_chain *c, uint64_t first_frame, const void *d_preroll, size_t preroll_frames, size_t call_frames,
                                      const iqgpu_dc_state *dc_at_preroll_start);
+/* ---- pass 1 of the three exact recipes over a whole RANGE in one call (additive, still ABI v9) ----
+ * iqgpu_chain_dc_measure, _dcagc_dc_measure and _dcrms_dc_measure plan a call, launch two small kernels, copy 32 bytes back and
+ * synchronise -- once per grid call, so that the pass spends most of its time between its kernels.  The calls below measure every grid
+ * call of a range in ONE submission and synchronise once.  The frames [first_frame, first_frame + frames_in) are cut into the grid
+ * calls [first_frame + k call_frames, ...), the last one may be shorter; first_frame is a multiple of call_frames.  rows receives
+ * exactly the rows a loop of the family's per-call form over those calls writes, in order and BIT FOR BIT: one row per call (Dc,
+ * DcRms); one row per piece, 1 or 2 per call, cut as iqgpu_chain_dcagc_dc_measure cuts it and never merged (DcAgc).  first_row, when
+ * not NULL, receives the index of every call's first row (ceil(frames_in / call_frames) entries); *n_rows the total.  Every piece is
+ * planned by the planning of the per-call form and computed by the device functions behind k_dc_prefix and k_dc_scan (k_dc_prefix_batch,
+ * k_dc_scan_batch: a table of pieces in device memory, iqgpu_dc_measure_range_launch_entries() of them per launch, longer ranges in
+ * several launches).  The handle is left exactly as it was -- position, histories, DC state, pipeline -- and the call returns with the
+ * stream idle.  Rows with f == 0 (calls past the underflow length) are returned as the per-call form returns them.
+ * _device: call k reads d_raw_in + k call_frames bytes_per_frame, and the alignment (mod 16 bytes) of THAT address enters its plan, as
+ * for the per-call _device form: a misaligned base gives the rows of the per-call _device loop on the same addresses.
+ * Host variants: the input is staged through device memory in slices of whole calls (2^24 frames, at least one call), two buffers,
+ * the copy of slice s + 1 queued while the kernels of slice s run.  call_frames is a multiple of 4096, so every staged call starts
+ * 16-byte aligned, as iqgpu_chain_process stages it: the rows are the per-call host form's rows.
+ * Rules: call_frames is a non-zero multiple of 4096 -- for DcAgc, call_frames and first_frame are multiples of agc_chunk_frames too --
+ * and positions stay within 2^39 frames, else IQGPU_EINVAL; so are a NULL chain, rows or n_rows, and a NULL buffer with frames_in != 0.
+ * The chain is checked as by the family's other calls (IQGPU_EINVAL without the blocker, IQGPU_EUNSUPPORTED for the AGC shapes the
+ * family refuses), under the new call's name.  cap below the row count: IQGPU_ECAPACITY with *n_rows set to the count needed (no
+ * device call is made; cap = 2 ceil(frames_in / call_frames) always suffices).  frames_in == 0 writes no rows and succeeds.  A refused
+ * call leaves the handle as it was. */
+int    iqgpu_chain_dc_measure_range(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, size_t call_frames,
+                                    iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row);
+int    iqgpu_chain_dc_measure_range_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, size_t call_frames,
+                                           iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row);
+int    iqgpu_chain_dcagc_dc_measure_range(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, size_t call_frames,
+                                          iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row);
+int    iqgpu_chain_dcagc_dc_measure_range_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in,
+                                                 size_t call_frames, iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row);
+int    iqgpu_chain_dcrms_dc_measure_range(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, size_t call_frames,
+                                          iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row);
+int    iqgpu_chain_dcrms_dc_measure_range_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in,
+                                                 size_t call_frames, iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row);
+/* entries (pieces of calls) one launch of the range form's kernels holds; no device call */
+size_t iqgpu_dc_measure_range_launch_entries(void);
 /* ---- checkpoint / resume: everything a chain carries from call to call, in a caller-owned blob (additive, still ABI v9) ----
  * The seek calls above rebuild the state at a stream position from a closed form and a preroll, and refuse what has no such form.
  * These two calls need none: iqgpu_chain_save_state copies the state out between two calls, iqgpu_chain_load_state puts it into a
@@ -641,7 +681,8 @@ int   iqgpu_iq_optimizer_touch(iqgpu_iq_optimizer *o, double now_sec); /* restar
  *      read until a later call has left the next one.  The block is the head of the whole call, however the library cuts it.
  *   2. Calls that are no chunk of the running stream neither leave a block nor occupy the slot: the preroll inside
  *      iqgpu_chain_seek*, _seek_agc*, _seek_dc*, _dcagc_seek*, _seek_rms*, _dcrms_seek*, and iqgpu_chain_measure, _measure_device,
- *      _measure_submit, _dc_measure*, _dcagc_dc_measure*, _dcagc_measure* (shadow calls leave no block), _dcrms_dc_measure*.
+ *      _measure_submit, _dc_measure* (the _range forms too), _dcagc_dc_measure*, _dcagc_measure* (shadow calls leave no block),
+ *      _dcrms_dc_measure*.
  *   3. iqgpu_chain_reset, every iqgpu_chain_seek* (iqgpu_chain_dcagc_seek*, iqgpu_chain_seek_rms* and iqgpu_chain_dcrms_seek* too) and
  *      iqgpu_chain_load_state drop a staged or held block (it belongs to the
  *      stream position the chain leaves): *valid = 0 until the next call of rule 1.

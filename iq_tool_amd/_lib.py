@@ -157,6 +157,10 @@ SYMBOLS = [
     *_with_device("iqgpu_chain_dcrms_dc_measure", C.c_int, [_vp, C.c_uint64, _vp, _sz, C.POINTER(DcRow)]),
     ("iqgpu_chain_dcrms_dc_advance", C.c_int, [_vp, C.POINTER(DcState), _vp, _sz, _vp]),
     *_with_device("iqgpu_chain_dcrms_seek", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, C.POINTER(DcState)]),
+    *_with_device("iqgpu_chain_dc_measure_range", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    *_with_device("iqgpu_chain_dcagc_dc_measure_range", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    *_with_device("iqgpu_chain_dcrms_dc_measure_range", C.c_int, [_vp, C.c_uint64, _vp, _sz, _sz, _vp, _sz, C.POINTER(_sz), _vp]),
+    ("iqgpu_dc_measure_range_launch_entries", _sz, []),
     ("iqgpu_design_state_size", C.c_int, [C.POINTER(ChainDesc), C.POINTER(_sz)]),
     ("iqgpu_state_inspect", C.c_int, [_vp, _sz, C.POINTER(StateInfo)]),
     ("iqgpu_chain_tell", C.c_int, [_vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -240,7 +244,7 @@ def load():
 DEBUG_NAMES = ("force_generic", "no_fast", "agc_nofuse", "no_raw0", "no_kt", "fft_no_r16", "no_fat", "force_fat", "fat", "mid8",
                "no_s2", "no_fused_move", "no_p0", "no_casc2", "no_mid_8bit", "fuse_filter", "tap_fold", "steal", "steal_min",
                "steal_rounds", "steal_stride", "steal_lanes", "run_weights", "cus", "fft_log2n", "fft_threads", "fft_geometry", "casc2_min_run",
-               "sysfs_root", "nco_hold", "measure_route")
+               "sysfs_root", "nco_hold", "measure_route", "dc_range_slice_frames")
 _forwarded = set()      # names whose switch apply_debug_env set from the environment and has not cleared since
 
 

@@ -296,6 +296,18 @@ class Chain:
         check(fn(self._h, int(first_frame), ptr, n, rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got)))
         return rows[:got.value]
 
+    def _dc_measure_range(self, fn, first_frame, ptr, n, call_frames):
+        """the three families' range forms and their _device forms: (rows, first_row) -- the DC_ROW records of every grid call of
+        the range in order, and the index of every call's first row"""
+        n, call_frames = int(n), int(call_frames)
+        calls = -(-n // call_frames) if call_frames > 0 else 0
+        rows = np.zeros(2 * calls + 1, DC_ROW)              # (a call is at most two pieces)
+        first_row = np.zeros(calls + 1, np.uint32)
+        got = C.c_size_t(0)
+        check(fn(self._h, int(first_frame), ptr, n, call_frames, rows.ctypes.data_as(C.c_void_p), rows.size, C.byref(got),
+                 first_row.ctypes.data_as(C.c_void_p)))
+        return rows[:got.value], first_row[:calls]
+
     def _dc_advance(self, fn, state, rows):
         rows = np.ascontiguousarray(rows, DC_ROW).reshape(-1)
         st = np.zeros((), DC_STATE)
@@ -417,6 +429,16 @@ class Chain:
         """dc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
         return self._dc_measure(self._lib.iqgpu_chain_dc_measure_device, first_frame, C.c_void_p(d_in), int(frames_in))
 
+    def dc_measure_range(self, first_frame, raw, call_frames):
+        """dc_measure() of every grid call of a range in one submission: raw holds the frames from stream frame first_frame (a
+        multiple of call_frames) on, cut into calls of call_frames (the last may be shorter).  Returns (rows, first_row): the rows a
+        dc_measure() loop over those calls gives, bit for bit, and the index of every call's first row"""
+        return self._dc_measure_range(self._lib.iqgpu_chain_dc_measure_range, first_frame, *self._host_input(raw), call_frames)
+
+    def dc_measure_range_device(self, first_frame, d_in, frames_in, call_frames):
+        """dc_measure_range() with the range already in device memory of this chain's GPU (a device address as an int)"""
+        return self._dc_measure_range(self._lib.iqgpu_chain_dc_measure_range_device, first_frame, C.c_void_p(d_in), frames_in, call_frames)
+
     def dc_advance(self, state, rows):
         """walks a DC state (a DC_STATE record, or None for zero) over dc_measure() rows on the device: returns (state behind the
         last row, before) where before[k] is the state in front of row k"""
@@ -440,6 +462,16 @@ class Chain:
     def dcagc_dc_measure_device(self, first_frame, d_in, frames_in):
         """dcagc_dc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
         return self._dcagc_dc_measure(self._lib.iqgpu_chain_dcagc_dc_measure_device, first_frame, C.c_void_p(d_in), int(frames_in))
+
+    def dcagc_dc_measure_range(self, first_frame, raw, call_frames):
+        """dcagc_dc_measure() of every grid call of a range in one submission: (rows, first_row) with ONE ROW PER PIECE, the rows of
+        call k from first_row[k] on -- the rows of a dcagc_dc_measure() loop, bit for bit"""
+        return self._dc_measure_range(self._lib.iqgpu_chain_dcagc_dc_measure_range, first_frame, *self._host_input(raw), call_frames)
+
+    def dcagc_dc_measure_range_device(self, first_frame, d_in, frames_in, call_frames):
+        """dcagc_dc_measure_range() with the range already in device memory of this chain's GPU (a device address as an int)"""
+        return self._dc_measure_range(self._lib.iqgpu_chain_dcagc_dc_measure_range_device, first_frame, C.c_void_p(d_in), frames_in,
+                                      call_frames)
 
     def dcagc_dc_advance(self, state, rows):
         """dc_advance() for these chains: (state behind the last row, before) with before[k] the state in front of row k"""
@@ -474,6 +506,15 @@ class Chain:
     def dcrms_dc_measure_device(self, first_frame, d_in, frames_in):
         """dcrms_dc_measure() with the input already in device memory of this chain's GPU (a device address as an int)"""
         return self._dc_measure(self._lib.iqgpu_chain_dcrms_dc_measure_device, first_frame, C.c_void_p(d_in), int(frames_in))
+
+    def dcrms_dc_measure_range(self, first_frame, raw, call_frames):
+        """dcrms_dc_measure() of every grid call of a range in one submission: (rows, first_row), one row per call"""
+        return self._dc_measure_range(self._lib.iqgpu_chain_dcrms_dc_measure_range, first_frame, *self._host_input(raw), call_frames)
+
+    def dcrms_dc_measure_range_device(self, first_frame, d_in, frames_in, call_frames):
+        """dcrms_dc_measure_range() with the range already in device memory of this chain's GPU (a device address as an int)"""
+        return self._dc_measure_range(self._lib.iqgpu_chain_dcrms_dc_measure_range_device, first_frame, C.c_void_p(d_in), frames_in,
+                                      call_frames)
 
     def dcrms_dc_advance(self, state, rows):
         """dc_advance() for these chains: (state behind the last row, before) with before[k] the state in front of row k"""

@@ -51,6 +51,7 @@ static const struct { const char *name; void (*parse)(DebugSwitches &, const cha
     {"casc2_min_run", [](DebugSwitches &s, const char *v) { const int x = atoi(v); s.casc2_min_run = x > 0 ? x : 0; }},
     {"measure_route", [](DebugSwitches &s, const char *v) { s.measure_route = !strcmp(v, "s1") ? 1 : !strcmp(v, "unfused") ? 0 : -1; }},
     {"nco_hold", [](DebugSwitches &s, const char *v) { s.nco_hold = v[0] != '0'; }},
+    {"dc_range_slice_frames", [](DebugSwitches &s, const char *v) { const long long x = atoll(v); s.dc_range_slice_frames = x > 0 ? x : 0; }},
     {"sysfs_root", nullptr},                                                              // topology.cpp
 };
 static std::mutex g_dbg_mu;
@@ -163,6 +164,12 @@ static void free_device_state(iqgpu_chain *c)
     if (c->d_sink) (void)hipFree(c->d_sink);
     c->steal_buf.release();
     c->dc_agg.release(); c->dc_carry.release(); c->dc_walk.release();
+    c->dc_range_tab.release(); c->dc_range_map.release(); c->dc_range_in[0].release(); c->dc_range_in[1].release();
+    for (int i = 0; i < 2; ++i) {
+        if (c->dc_range_in_done[i]) (void)hipEventDestroy(c->dc_range_in_done[i]);
+        if (c->dc_range_k_done[i]) (void)hipEventDestroy(c->dc_range_k_done[i]);
+    }
+    if (c->dc_range_h2d) (void)hipStreamDestroy(c->dc_range_h2d);
     c->fbuf[0].release(); c->fbuf[1].release();
     c->ibuf[0].release(); c->ibuf[1].release();
     c->stage_in.release(); c->stage_out.release(); c->seek_sink.release(); c->seek_win.release();

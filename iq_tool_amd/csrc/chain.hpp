@@ -4,7 +4,7 @@
 //   plan.cpp       stream-position arithmetic (plan_call), per-call run geometry of the wave kernels (Call::plan_geometry)
 //   process.cpp    one process() call: buffers, the stages in stream order, iqgpu_chain_process[_device]
 //   seek.cpp       seamless range sharding: iqgpu_chain_seek[_agc | _dc], iqgpu_chain_measure, iqgpu_chain_agc_initial_state / _advance,
-//                  iqgpu_chain_dc_measure / _dc_advance, iqgpu_chain_dcagc_*, iqgpu_chain_dcrms_*
+//                  iqgpu_chain_dc_measure / _dc_measure_range / _dc_advance, iqgpu_chain_dcagc_*, iqgpu_chain_dcrms_*
 //   agc_host.cpp   host side of the output AGC: chunk map, fused / unfused split, verifier + fallback launches
 //   pipeline.cpp   iqgpu_chain_submit / _measure_submit / _collect (pinned host buffers, three stages moved along by the host)
 //   state.cpp      checkpoint / resume: iqgpu_chain_tell, iqgpu_chain_save_state / _load_state, iqgpu_design_state_size (the blob's
@@ -74,6 +74,9 @@ struct DebugSwitches {
     bool fft_keep_geometry = false;   // "fft_geometry" = "keep": the two filter kernels on k_p0fft16's transform size and windows
     int measure_route = -1;       // "measure_route" = "unfused" | "s1": the route of iqgpu_chain_measure (-1: the faster one measured for the shape, measure_route() in seek.cpp)
     int casc2_min_run = 0;        // "casc2_min_run": shortest streaming run (tiles) that takes k_cascade2 (0 = the built-in bound)
+    // "dc_range_slice_frames": frames per staging slice of the host variants of iqgpu_chain_*_dc_measure_range (0 = kDcRangeSliceFrames;
+    // a slice is whole calls, at least one).  No part of a saved state's fingerprint: it decides no routing
+    long long dc_range_slice_frames = 0;
 };
 DebugSwitches debug_switches();                        // abi.cpp: the table as it stands, under one lock
 std::string debug_value(const char *name);             // ... one raw value ("" when unset): process-level switches only (sysfs_root)
@@ -162,6 +165,10 @@ struct iqgpu_chain {
     DevBuf dc_agg, dc_carry;
     // exact seamless sharding of DC-blocker chains (seek.cpp): the map of a measured call, the state and the tables of iqgpu_chain_dc_advance
     DevBuf dc_walk;
+    // ... and the measure pass over a whole range (iqgpu_chain_*_dc_measure_range): the entry table and the maps of all its pieces;
+    // the host variants' two staging slices, their copy stream and, per slice, "copy landed" / "kernels done" (created on first use)
+    DevBuf dc_range_tab, dc_range_map, dc_range_in[2];
+    hipStream_t dc_range_h2d = nullptr; hipEvent_t dc_range_in_done[2] = {}, dc_range_k_done[2] = {};
     DevBuf fbuf[2]; int fcur = 0;
     // output AGC (digital profile)
     bool agc = false; float agc_target = 0.9f; int64_t agc_chunk = 16384;
@@ -419,6 +426,9 @@ int stage_host_input(iqgpu_chain *c, const void *in, size_t frames, const void *
 // process.cpp: the DC blocker's map of the call process_device_impl would make of these frames at stream position `at`, into d_map[0 .. 2)
 // (past_lock: the piece of an AGC chain's call behind the lock, planned with the gain in its last kernel -- iqgpu_chain_dcagc_dc_measure)
 int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, cd2 *d_map, bool past_lock = false);
+// ... its planning alone (host arithmetic; the chain's position is put back): the segments of that call and the alignment of its address
+struct DcMeasurePlan { DcGeom geom; int raw_aligned; };
+DcMeasurePlan dc_measure_plan(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, bool past_lock = false);
 // agc_host.cpp: ONE definition of how a call of a chain with the digital AGC is cut -- the frames of its unfused head (0: none,
 // frames_in: the whole call); the rest runs with the gain fused into its last kernel.  A function of the lock / seen mirrors, the
 // stream position and the call's length alone; *locks: the locking chunk lies in this call
@@ -443,7 +453,7 @@ struct ShardFamily {
     bool rebuild_agc;                     // the AGC loop's state at first_frame is rebuilt from the preroll's cf32 output ...
     bool gather;                          // ... of every call, gathered in seek_win (else: of the one call, where it lies in abuf)
     uint64_t (*memory)(const iqgpu_chain *);      // the preroll the chain needs far enough into the stream
-    const char *seek, *dc_measure, *dc_advance, *measure, *design_preroll;      // its entry points (nullptr: it has none)
+    const char *seek, *dc_measure, *dc_advance, *measure, *design_preroll, *dc_measure_range;      // its entry points (nullptr: it has none)
 };
 // (hidden: between seek.cpp and plan.cpp only -- the library's dynamic symbol table stays as it was)
 __attribute__((visibility("hidden"))) const ShardFamily &shard_family(SeekKind k);

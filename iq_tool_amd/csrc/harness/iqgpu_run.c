@@ -35,8 +35,8 @@
  *
  * --shards N --seamless-dc is the EXACT --seamless for chains with the DC blocker (--dc-block, no AGC option), in the three passes of
  * iqgpu.h's DC block.  Shard starts are s * (frames / N) rounded down to a multiple of lcm(4096, --chunk-frames): every call of every
- * shard is a call of the single stream.  Pass 1: shards 0 .. N-2 measure the map of every call of their range
- * (iqgpu_chain_dc_measure: one read of the input, no front kernel, no output).  One walk over all rows (iqgpu_chain_dc_advance) then
+ * shard is a call of the single stream.  Pass 1: shards 0 .. N-2 measure the map of every call of their range, a batch of whole calls
+ * per library call (iqgpu_chain_dc_measure_range: one read of the input, no front kernel, no output).  One walk over all rows (iqgpu_chain_dc_advance) then
  * gives the blocker's state in front of every call.  Pass 2: every shard puts its chain at its start with iqgpu_chain_seek_dc -- the
  * preroll is the filters' memory rounded up to whole chunks, with NO warm-up of the blocker, entered with the walked state -- and runs
  * the usual chunk loop.  The stitched file is the file --shards 1 writes, byte for byte.
@@ -52,14 +52,14 @@
  * --shards N --seamless-dc-agc is the exact --seamless for chains with the DC blocker AND the digital output AGC (--dc-block
  * --agc-profile digital), in the five steps of iqgpu.h's block on such chains.  Shard starts lie on lcm(4096, --chunk-frames), and
  * --chunk-frames is a multiple of the AGC chunk.  Step 1: shards 0 .. N-2 measure the DC maps of every call of their range
- * (iqgpu_chain_dcagc_dc_measure: one row per piece, two for the call the stream cuts at the AGC's lock).  Step 2: one walk over all
+ * (iqgpu_chain_dcagc_dc_measure_range: one row per piece, two for the call the stream cuts at the AGC's lock).  Step 2: one walk over all
  * rows; the state in front of a call is the one in front of its first row.  Step 3: the same shards put their chain at their start
  * with the walked DC state and no AGC entry (iqgpu_chain_dcagc_seek) and measure the AGC rows of their range in shadow calls
  * (iqgpu_chain_dcagc_measure, synchronous).  Step 4: the AGC walk.  Step 5: every shard seeks with both states and runs the usual
  * chunk loop.  The stitched file is the file --shards 1 writes, byte for byte.
  *
  * --shards N --seamless-dc-rms is the exact --seamless for chains with the DC blocker AND the dx / local output AGC (--dc-block
- * --agc-profile dx|local): --seamless-dc's measure pass and walk (iqgpu_chain_dcrms_dc_measure, one row per call; one
+ * --agc-profile dx|local): --seamless-dc's measure pass and walk (iqgpu_chain_dcrms_dc_measure_range, one row per call; one
  * iqgpu_chain_dcrms_dc_advance), then --seamless-rms's pass: every shard seeks with iqgpu_chain_dcrms_seek -- a preroll of
  * iqgpu_design_preroll_frames_dcrms frames rounded up to whole calls, entered with the walked state -- processes its range on the call
  * grid, and the seams are certified in order, a range behind a seam that does not certify redone from the checkpoint in front.
@@ -345,28 +345,58 @@ static int measure_agc_call(Ctx *x, long long at, size_t n)
     return 0;
 }
 
-/* the DC map of one call: one row (iqgpu_chain_dc_measure, _dcrms_dc_measure: no front kernel, no output), with the digital AGC one row per piece */
-static int measure_dc_call(Ctx *x, long long at, size_t n)
-{
-    Shard *sh = x->sh;
-    size_t got = 1;
-    if (x->o->mode == M_DC) CK(iqgpu_chain_dc_measure(x->chain, (uint64_t)(sh->first_frame + at), x->h_in[0], n, &sh->dc_rows[sh->n_dc_rows]));
-    else if (x->o->mode == M_DC_RMS) CK(iqgpu_chain_dcrms_dc_measure(x->chain, (uint64_t)(sh->first_frame + at), x->h_in[0], n, &sh->dc_rows[sh->n_dc_rows]));
-    else CK(iqgpu_chain_dcagc_dc_measure(x->chain, (uint64_t)(sh->first_frame + at), x->h_in[0], n, &sh->dc_rows[sh->n_dc_rows], 2, &got));
-    sh->dc_call_rows[sh->n_dc_calls++] = (unsigned char)got;
-    sh->n_dc_rows += (long long)got;
-    return 0;
-}
+/* pass 1 of the three DC modes reads its range in batches of whole calls -- one pinned buffer of up to this many bytes, at least one
+ * call -- and hands every batch to the range form of its family's DC measure in ONE call.  (The range form wants calls of a multiple
+ * of 4096 frames; a grid of other calls -- only the cuts have to be such multiples -- is measured call by call, as before it existed) */
+#define DC_BATCH_BYTES ((size_t)256 << 20)
 
-/* the DC maps of every call the ordinary pass will make of this range */
+/* the DC maps of every call the ordinary pass will make of this range: one row per call (iqgpu_chain_dc_measure_range,
+ * _dcrms_dc_measure_range: no front kernel, no output), with the digital AGC one row per piece (_dcagc_dc_measure_range) */
 static int measure_dc(Ctx *x)
 {
     Shard *sh = x->sh;
-    const size_t calls = range_calls(x), most = (x->o->mode == M_DC_AGC ? 2 : 1) * calls;
+    const Mode mode = x->o->mode;
+    int (*const range)(iqgpu_chain *, uint64_t, const void *, size_t, size_t, iqgpu_dc_row *, size_t, size_t *, uint32_t *) =
+        mode == M_DC ? iqgpu_chain_dc_measure_range : mode == M_DC_RMS ? iqgpu_chain_dcrms_dc_measure_range : iqgpu_chain_dcagc_dc_measure_range;
+    const char *who = mode == M_DC ? "iqgpu_chain_dc_measure_range" : mode == M_DC_RMS ? "iqgpu_chain_dcrms_dc_measure_range" : "iqgpu_chain_dcagc_dc_measure_range";
+    const size_t calls = range_calls(x), most = 2 * calls;
+    const int by_range = x->chunk % 4096 == 0;
+    size_t per = by_range ? DC_BATCH_BYTES / (x->chunk * x->ibps) : 1;
+    if (per < 1) per = 1;
+    if (per > calls) per = calls;
     sh->dc_rows = (iqgpu_dc_row *)malloc((most + 1) * sizeof(iqgpu_dc_row));
     sh->dc_call_rows = (unsigned char *)malloc(calls + 1);
-    if (!sh->dc_rows || !sh->dc_call_rows) FAIL("out of memory for a table of %zu rows", most);
-    return for_each_call(x, measure_dc_call);
+    uint32_t *first = (uint32_t *)malloc((per + 1) * sizeof(uint32_t));
+    void *batch = NULL;
+    int rc = -1;
+    if (!sh->dc_rows || !sh->dc_call_rows || !first) { snprintf(sh->err, sizeof(sh->err), "out of memory for a table of %zu rows", most); sh->rc = -1; goto out; }
+    if (per > 1 && iqgpu_host_malloc_pinned(per * x->chunk * x->ibps, &batch) != IQGPU_OK) {
+        snprintf(sh->err, sizeof(sh->err), "out of pinned memory for a batch of %zu calls: %s", per, iqgpu_last_error()); sh->rc = -1; goto out;
+    }
+    for (long long at = 0; at < sh->frames; at += (long long)(per * x->chunk)) {
+        size_t n = per * x->chunk, got = 0;
+        if ((long long)n > sh->frames - at) n = (size_t)(sh->frames - at);
+        const size_t nc = (n + x->chunk - 1) / x->chunk;
+        void *buf = batch ? batch : x->h_in[0];                /* (a batch of one call: the pinned buffer of the ordinary pass) */
+        if (read_range(x, at, n, buf)) goto out;
+        iqgpu_dc_row *rows = sh->dc_rows + sh->n_dc_rows;
+        const uint64_t pos = (uint64_t)(sh->first_frame + at);
+        int r;
+        if (by_range) r = range(x->chain, pos, buf, n, x->chunk, rows, most - (size_t)sh->n_dc_rows, &got, first);
+        else {
+            first[0] = 0; got = 1;
+            r = mode == M_DC ? iqgpu_chain_dc_measure(x->chain, pos, buf, n, rows) : mode == M_DC_RMS ? iqgpu_chain_dcrms_dc_measure(x->chain, pos, buf, n, rows)
+                : iqgpu_chain_dcagc_dc_measure(x->chain, pos, buf, n, rows, 2, &got);
+        }
+        if (r != IQGPU_OK) { snprintf(sh->err, sizeof(sh->err), "%s: %s", by_range ? who : "the DC measure of one call", iqgpu_last_error()); sh->rc = r; goto out; }
+        for (size_t k = 0; k < nc; k++) sh->dc_call_rows[sh->n_dc_calls++] = (unsigned char)((k + 1 < nc ? first[k + 1] : (uint32_t)got) - first[k]);
+        sh->n_dc_rows += (long long)got;
+    }
+    rc = 0;
+out:
+    if (batch) iqgpu_host_free_pinned(batch);
+    free(first);
+    return rc;
 }
 
 /* the AGC walk: the tables in shard order, the state in front of every shard kept.  (The walks run in shard 0's thread, on its chain,

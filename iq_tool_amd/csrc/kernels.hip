@@ -369,12 +369,12 @@ hipError_t launch_front(const FrontArgs &a, int n_blocks, hipStream_t s)
 // ============================================================================================
 // DC-blocker carries
 // ============================================================================================
-// One workgroup per segment: A = sum_k c^(end-1-k) x[k] over the segment's new samples.
-__global__ __launch_bounds__(kThreads) void k_dc_prefix(const DcPrefixArgs a)
+// One workgroup per segment: A = sum_k c^(end-1-k) x[k] over the segment's new samples.  ONE definition of a segment's aggregate:
+// k_dc_prefix (a call) and k_dc_prefix_batch (the calls of a range, iqgpu_chain_*_dc_measure_range) both run it
+__device__ __forceinline__ void dc_prefix_segment(const DcPrefixArgs &a, const int sgm)
 {
     __shared__ float red[2 * 4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int sgm = blockIdx.x;
     const int64_t beg = dc_seg_start(a.geom, sgm);
     const int64_t end = (sgm == a.geom.n_seg - 1) ? a.geom.frames_in : dc_seg_start(a.geom, sgm + 1);
     const int64_t len = end - beg;
@@ -506,6 +506,27 @@ __global__ __launch_bounds__(kThreads) void k_dc_prefix(const DcPrefixArgs a)
     }
 }
 
+__global__ __launch_bounds__(kThreads) void k_dc_prefix(const DcPrefixArgs a) { dc_prefix_segment(a, (int)blockIdx.x); }
+
+// grid (segment, entry): entry blockIdx.y of the table is one piece of one call -- its geometry, where its frames start in raw, the
+// alignment of that address, where its aggregates go -- and this workgroup does for segment blockIdx.x of it what k_dc_prefix does
+__global__ __launch_bounds__(kThreads) void k_dc_prefix_batch(const DcPrefixBatchArgs b)
+{
+    const DcBatchEntry e = b.entries[blockIdx.y];
+    if ((int)blockIdx.x >= e.geom.n_seg) return;
+    DcPrefixArgs a;
+    a.raw = (const char *)b.raw + e.raw_off; a.in_fmt = b.in_fmt; a.gain = b.gain; a.raw_aligned = e.raw_aligned;
+    a.c = b.c; a.logc = b.logc; a.geom = e.geom; a.agg = b.agg + e.agg_off;
+    dc_prefix_segment(a, (int)blockIdx.x);
+}
+
+hipError_t launch_dc_prefix_batch(const DcPrefixBatchArgs &b, int n_entries, int max_seg, hipStream_t s)
+{
+    if (n_entries < 1 || n_entries > kDcBatchEntries || max_seg < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dc_prefix_batch, dim3((unsigned)max_seg, (unsigned)n_entries), dim3(kThreads), 0, s, b);
+    return hipGetLastError();
+}
+
 hipError_t launch_dc_prefix(const DcPrefixArgs &a, hipStream_t s)
 {
     hipLaunchKernelGGL(k_dc_prefix, dim3((unsigned)a.geom.n_seg), dim3(kThreads), 0, s, a);
@@ -522,26 +543,29 @@ constexpr int kDcScanThreads = 1024;      // one workgroup, 3 segments a thread 
 // v -> f_s v + g_s (f_s = c^len_s, g_s = the segment's aggregate) compose associatively: each of the
 // threads folds a contiguous slice of segments, the slices are scanned through LDS, then every thread
 // replays its slice from its prefix.  All in double.
-__global__ __launch_bounds__(kDcScanThreads) void k_dc_scan(const DcScanArgs a)
+// ONE definition of the fold and the scan: k_dc_scan (a call) and k_dc_scan_batch (the calls of a range) both run it.  Behind it
+// sf / sr / si[tid] hold the inclusive scan of the slices' maps; [kDcScanThreads - 1]: the map of the whole call
+struct DcScanSlice { int s0, s1; };
+__device__ __forceinline__ int64_t dc_seg_len(const DcGeom &g, int sgm)
 {
-    __shared__ double sf[kDcScanThreads], sr[kDcScanThreads], si[kDcScanThreads];
+    const int64_t beg = dc_seg_start(g, sgm);
+    const int64_t end = (sgm == g.n_seg - 1) ? g.frames_in : dc_seg_start(g, sgm + 1);
+    return end > beg ? end - beg : (int64_t)0;
+}
+__device__ __forceinline__ DcScanSlice dc_scan_fold(const DcGeom &geom, const cf2 *agg, const double logc, double *sf, double *sr, double *si)
+{
     const int tid = threadIdx.x;
-    const int n = a.geom.n_seg;
+    const int n = geom.n_seg;
     const int per = (n + kDcScanThreads - 1) / kDcScanThreads;
     const int s0 = tid * per, s1 = (s0 + per < n) ? s0 + per : n;
-    auto seg_len = [&](int sgm) {
-        const int64_t beg = dc_seg_start(a.geom, sgm);
-        const int64_t end = (sgm == n - 1) ? a.geom.frames_in : dc_seg_start(a.geom, sgm + 1);
-        return end > beg ? end - beg : (int64_t)0;
-    };
     // fold the slice: v_out = F v_in + (Gr, Gi)
     double F = 1.0, Gr = 0.0, Gi = 0.0;
     {
         int64_t prev_len = -1; double f = 1.0;
         for (int sgm = s0; sgm < s1; ++sgm) {
-            const int64_t len = seg_len(sgm);
-            if (len != prev_len) { f = exp((double)len * a.logc); prev_len = len; }
-            const cf2 g = a.agg[sgm];
+            const int64_t len = dc_seg_len(geom, sgm);
+            if (len != prev_len) { f = exp((double)len * logc); prev_len = len; }
+            const cf2 g = agg[sgm];
             F *= f; Gr = Gr * f + (double)g.x; Gi = Gi * f + (double)g.y;
         }
     }
@@ -556,11 +580,23 @@ __global__ __launch_bounds__(kDcScanThreads) void k_dc_scan(const DcScanArgs a)
         if (has) { sr[tid] = sr[tid] + sf[tid] * pr; si[tid] = si[tid] + sf[tid] * pi; sf[tid] = sf[tid] * pf; }
         __syncthreads();
     }
-    // the measure pass (iqgpu_chain_dc_measure): the call's whole map and nothing else -- state and carries stay as they are
-    if (a.map) {
-        if (tid == kDcScanThreads - 1) { a.map[0] = cd2{sf[tid], 0.0}; a.map[1] = cd2{sr[tid], si[tid]}; }
-        return;
-    }
+    return DcScanSlice{s0, s1};
+}
+// the measure pass: the call's whole map and nothing else, map[0] = {F, 0}, map[1] = G
+__device__ __forceinline__ void dc_scan_store_map(cd2 *map, const double *sf, const double *sr, const double *si)
+{
+    const int tid = threadIdx.x;
+    if (tid == kDcScanThreads - 1) { map[0] = cd2{sf[tid], 0.0}; map[1] = cd2{sr[tid], si[tid]}; }
+}
+
+__global__ __launch_bounds__(kDcScanThreads) void k_dc_scan(const DcScanArgs a)
+{
+    __shared__ double sf[kDcScanThreads], sr[kDcScanThreads], si[kDcScanThreads];
+    const int tid = threadIdx.x;
+    const DcScanSlice sl = dc_scan_fold(a.geom, a.agg, a.logc, sf, sr, si);
+    const int s0 = sl.s0, s1 = sl.s1;
+    // the measure pass (iqgpu_chain_dc_measure): state and carries stay as they are
+    if (a.map) { dc_scan_store_map(a.map, sf, sr, si); return; }
     const double v0r = a.state->x, v0i = a.state->y;
     // state before this thread's slice = (inclusive scan of the previous thread) applied to v0
     double vr = v0r, vi = v0i;
@@ -569,7 +605,7 @@ __global__ __launch_bounds__(kDcScanThreads) void k_dc_scan(const DcScanArgs a)
         int64_t prev_len = -1; double f = 1.0;
         for (int sgm = s0; sgm < s1; ++sgm) {
             a.carry[sgm] = cd2{vr, vi};
-            const int64_t len = seg_len(sgm);
+            const int64_t len = dc_seg_len(a.geom, sgm);
             if (len != prev_len) { f = exp((double)len * a.logc); prev_len = len; }
             const cf2 g = a.agg[sgm];
             vr = vr * f + (double)g.x; vi = vi * f + (double)g.y;
@@ -577,6 +613,22 @@ __global__ __launch_bounds__(kDcScanThreads) void k_dc_scan(const DcScanArgs a)
     }
     __syncthreads();
     if (tid == kDcScanThreads - 1) *a.state = dc_map_apply(sf[tid], sr[tid], si[tid], cd2{v0r, v0i});
+}
+
+// one workgroup per entry of the table: the map-only branch of k_dc_scan for that piece, into map[2 entry], map[2 entry + 1]
+__global__ __launch_bounds__(kDcScanThreads) void k_dc_scan_batch(const DcScanBatchArgs b)
+{
+    __shared__ double sf[kDcScanThreads], sr[kDcScanThreads], si[kDcScanThreads];
+    const DcBatchEntry e = b.entries[blockIdx.x];
+    dc_scan_fold(e.geom, b.agg + e.agg_off, b.logc, sf, sr, si);
+    dc_scan_store_map(b.map + 2 * (size_t)blockIdx.x, sf, sr, si);
+}
+
+hipError_t launch_dc_scan_batch(const DcScanBatchArgs &b, int n_entries, hipStream_t s)
+{
+    if (n_entries < 1 || n_entries > kDcBatchEntries) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_dc_scan_batch, dim3((unsigned)n_entries), dim3(kDcScanThreads), 0, s, b);
+    return hipGetLastError();
 }
 
 hipError_t launch_dc_scan(const DcScanArgs &a, hipStream_t s)

@@ -406,6 +406,36 @@ struct DcScanArgs {
 };
 hipError_t launch_dc_scan(const DcScanArgs &a, hipStream_t s);
 
+// The measure pass over a whole RANGE of calls in one submission (iqgpu_chain_*_dc_measure_range): a table of entries in device
+// memory, one per piece of a call -- what DcPrefixArgs / DcScanArgs hold per call -- k_dc_prefix_batch on a grid of (segment, entry),
+// k_dc_scan_batch with one workgroup per entry.  Both run the device functions behind k_dc_prefix and k_dc_scan's map-only branch:
+// the map of an entry is the per-call kernels' map of that piece bit for bit.
+constexpr int kDcBatchEntries = 1024;     // entries per launch (grid.y of k_dc_prefix_batch); longer ranges: several launches
+struct DcBatchEntry {
+    DcGeom  geom;
+    int64_t raw_off;          // bytes from DcPrefixBatchArgs::raw to the piece's first frame
+    int32_t raw_aligned;      // of that address (Call::raw_aligned)
+    int32_t agg_off;          // its aggregates: agg[agg_off .. agg_off + geom.n_seg)
+};
+struct DcPrefixBatchArgs {
+    const void *raw;
+    int32_t     in_fmt;
+    float       gain;
+    float       c;
+    double      logc;
+    const DcBatchEntry *entries;
+    cf2        *agg;
+};
+// grid.x = max_seg: the largest n_seg of the launch's entries (workgroups past an entry's n_seg return at once)
+hipError_t launch_dc_prefix_batch(const DcPrefixBatchArgs &b, int n_entries, int max_seg, hipStream_t s);
+struct DcScanBatchArgs {
+    const DcBatchEntry *entries;
+    const cf2 *agg;
+    double     logc;
+    cd2       *map;           // [2 n_entries]: map[2 e] = {F, 0}, map[2 e + 1] = G of entry e
+};
+hipError_t launch_dc_scan_batch(const DcScanBatchArgs &b, int n_entries, hipStream_t s);
+
 // one CALL's map of the blocker's state, v_after = f v_before + g (iqgpu_dc_row's layout), and the walk over a table of them
 struct DcMapRow { double f, g_re, g_im; uint64_t frames; };
 struct DcWalkArgs {

@@ -346,7 +346,8 @@ static Call begin_call(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, v
 // launched; the scan writes the map to d_map and leaves the chain's DC state and carries alone.  The chain's position is put back.
 // (a chain with the AGC: the piece in front of the lock leaves cf32 for the AGC kernels, the piece behind it -- past_lock -- has the
 //  gain in its last kernel; both enter the plan as in process_one)
-int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, cd2 *d_map, bool past_lock)
+// (the planning alone, host arithmetic: shared with the range form, seek.cpp, which plans every piece of a range up front)
+DcMeasurePlan dc_measure_plan(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, bool past_lock)
 {
     const StreamPos was{c->rem, c->phi, c->fpending};
     c->rem = at.rem; c->phi = at.phi; c->fpending = at.fpending;
@@ -354,12 +355,19 @@ int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, s
     k.agc_fused = past_lock;
     if (c->agc && !past_lock) k.fin_fmt = IQGPU_FMT_CF32;
     k.plan_geometry();
-    const DcGeom dg = k.dc_geom();
+    const DcMeasurePlan mp{k.dc_geom(), k.raw_aligned()};
     c->rem = was.rem; c->phi = was.phi; c->fpending = was.fpending;
+    return mp;
+}
+
+int dc_measure_call(iqgpu_chain *c, const StreamPos &at, const void *d_raw_in, size_t frames_in, cd2 *d_map, bool past_lock)
+{
+    const DcMeasurePlan mp = dc_measure_plan(c, at, d_raw_in, frames_in, past_lock);
+    const DcGeom &dg = mp.geom;
     int rc = c->dc_agg.ensure((size_t)dg.n_seg * sizeof(cf2)); if (rc) return rc;
     DcPrefixArgs pa{};
     pa.raw = d_raw_in; pa.in_fmt = c->desc.in_format; pa.gain = c->desc.gain;
-    pa.raw_aligned = k.raw_aligned();
+    pa.raw_aligned = mp.raw_aligned;
     pa.c = c->dc_c; pa.logc = c->dc_logc; pa.geom = dg; pa.agg = (cf2 *)c->dc_agg.p;
     HIP_TRY(launch_dc_prefix(pa, c->stream));
     DcScanArgs sa{};

@@ -75,18 +75,19 @@ const ShardFamily &shard_family(SeekKind k)
     static const ShardFamily rows[6] = {
         //        check      needs               preroll_agc   dc_at  entry  rebuild gather memory
         /*Plain*/ {SC::None,    0,                  AM::Ordinary, false, false, false, false, fir_and_dc_memory,
-                   "iqgpu_chain_seek", nullptr, nullptr, nullptr, "iqgpu_design_preroll_frames"},
+                   "iqgpu_chain_seek", nullptr, nullptr, nullptr, "iqgpu_design_preroll_frames", nullptr},
         /*Agc*/   {SC::TwoPass, kNeedAgc,           AM::Drop,     false, true,  false, false, fir_and_dc_memory,
-                   "iqgpu_chain_seek_agc", nullptr, nullptr, "iqgpu_chain_measure", nullptr},
+                   "iqgpu_chain_seek_agc", nullptr, nullptr, "iqgpu_chain_measure", nullptr, nullptr},
         /*Dc*/    {SC::TwoPass, kNeedDc,            AM::Ordinary, true,  false, false, false, fir_memory,
-                   "iqgpu_chain_seek_dc", "iqgpu_chain_dc_measure", "iqgpu_chain_dc_advance", nullptr, nullptr},
+                   "iqgpu_chain_seek_dc", "iqgpu_chain_dc_measure", "iqgpu_chain_dc_advance", nullptr, nullptr, "iqgpu_chain_dc_measure_range"},
         /*DcAgc*/ {SC::TwoPass, kNeedDc | kNeedAgc, AM::Shadow,   true,  true,  false, false, fir_memory,
-                   "iqgpu_chain_dcagc_seek", "iqgpu_chain_dcagc_dc_measure", "iqgpu_chain_dcagc_dc_advance", "iqgpu_chain_dcagc_measure", nullptr},
+                   "iqgpu_chain_dcagc_seek", "iqgpu_chain_dcagc_dc_measure", "iqgpu_chain_dcagc_dc_advance", "iqgpu_chain_dcagc_measure", nullptr,
+                   "iqgpu_chain_dcagc_dc_measure_range"},
         /*Rms*/   {SC::Rms,     0,                  AM::Drop,     false, false, true,  false, seek_rms_preroll_frames,
-                   "iqgpu_chain_seek_rms", nullptr, nullptr, nullptr, "iqgpu_design_preroll_frames_rms"},
+                   "iqgpu_chain_seek_rms", nullptr, nullptr, nullptr, "iqgpu_design_preroll_frames_rms", nullptr},
         /*DcRms*/ {SC::DcRms,   0,                  AM::Drop,     true,  false, true,  true,  seek_rms_preroll_frames,
                    "iqgpu_chain_dcrms_seek", "iqgpu_chain_dcrms_dc_measure", "iqgpu_chain_dcrms_dc_advance", nullptr,
-                   "iqgpu_design_preroll_frames_dcrms"},
+                   "iqgpu_design_preroll_frames_dcrms", "iqgpu_chain_dcrms_dc_measure_range"},
     };
     return rows[(int)k];
 }
@@ -470,6 +471,200 @@ extern "C" int iqgpu_chain_dcagc_dc_measure_device(iqgpu_chain *c, uint64_t firs
                                                    iqgpu_dc_row *rows, size_t cap, size_t *n_rows)
 {
     return dcagc_dc_measure_impl(c, first_frame, d_raw_in, frames_in, rows, cap, n_rows, true);
+}
+
+// ------------------------------------------------------------------------------------------------
+// iqgpu_chain_*_dc_measure_range: pass 1 of the three exact recipes over a whole range in ONE submission.  Every piece of every grid
+// call is planned up front by the planning of the per-call form (dc_measure_plan: host arithmetic), the plans go to the device as one
+// table, k_dc_prefix_batch / k_dc_scan_batch run the per-call kernels' device functions over kDcBatchEntries entries per launch, the
+// maps of all pieces come back in one copy behind one synchronisation.  The handle is read, never moved.
+// ------------------------------------------------------------------------------------------------
+constexpr size_t kDcRangeSliceFrames = (size_t)1 << 24;     // the host variants' staging slice (whole calls, at least one): 64 MiB of cs16
+constexpr int64_t kDcBatchSegments = (int64_t)1 << 22;      // aggregates of one launch (dc_agg: 32 MiB); an entry beyond it starts the next launch
+
+extern "C" size_t iqgpu_dc_measure_range_launch_entries(void) { return (size_t)kDcBatchEntries; }
+
+namespace {
+struct RangePiece { size_t off, len; bool past_lock; };                     // frames from the range's first frame
+struct RangeLaunch { size_t e0, n; int max_seg; size_t slice; };            // entries [e0, e0 + n) of the table, all of one slice
+struct RangeSlice { size_t off, len; };                                     // host variants: the frames of one staging slice
+}
+
+static int dc_measure_range_run(iqgpu_chain *c, const char *who, uint64_t first_frame, const void *in, bool on_device,
+                                const std::vector<RangePiece> &pieces, const std::vector<RangeSlice> &slices, iqgpu_dc_row *rows)
+{
+    const size_t ibps = bytes_per_frame(c->desc.in_format), n_ent = pieces.size();
+    int rc;
+    if (!on_device) {
+        size_t most = 0;
+        for (const RangeSlice &sl : slices) most = sl.len > most ? sl.len : most;
+        for (size_t b = 0; b < 2 && b < slices.size(); ++b) { rc = c->dc_range_in[b].ensure(most * ibps); if (rc) return rc; }
+        if (!c->dc_range_h2d) HIP_TRY(hipStreamCreateWithFlags(&c->dc_range_h2d, hipStreamNonBlocking));
+        for (int b = 0; b < 2; ++b) {
+            if (!c->dc_range_in_done[b]) HIP_TRY(hipEventCreateWithFlags(&c->dc_range_in_done[b], hipEventDisableTiming));
+            if (!c->dc_range_k_done[b]) HIP_TRY(hipEventCreateWithFlags(&c->dc_range_k_done[b], hipEventDisableTiming));
+        }
+    }
+    // where slice s lies on the device, and the table: every piece planned from the address its frames will have
+    auto slice_base = [&](size_t s) { return on_device ? (const char *)in : (const char *)c->dc_range_in[s & 1].p; };
+    std::vector<DcBatchEntry> tab(n_ent);
+    std::vector<RangeLaunch> launches;
+    int64_t most_agg = 0, agg = 0;
+    size_t s = 0;
+    for (size_t e = 0; e < n_ent; ++e) {
+        const RangePiece &pc = pieces[e];
+        while (pc.off >= slices[s].off + slices[s].len) ++s;
+        const size_t raw_off = (pc.off - slices[s].off) * ibps;
+        const DcMeasurePlan mp = dc_measure_plan(c, stream_at(c, first_frame + (uint64_t)pc.off).pos, slice_base(s) + raw_off, pc.len, pc.past_lock);
+        if (launches.empty() || launches.back().slice != s || launches.back().n == (size_t)kDcBatchEntries || agg + mp.geom.n_seg > kDcBatchSegments) {
+            launches.push_back(RangeLaunch{e, 0, 1, s});
+            agg = 0;
+        }
+        tab[e].geom = mp.geom; tab[e].raw_off = (int64_t)raw_off; tab[e].raw_aligned = mp.raw_aligned; tab[e].agg_off = (int32_t)agg;
+        agg += mp.geom.n_seg;
+        if (agg > most_agg) most_agg = agg;
+        RangeLaunch &l = launches.back();
+        ++l.n;
+        if (mp.geom.n_seg > l.max_seg) l.max_seg = mp.geom.n_seg;
+    }
+    rc = c->dc_agg.ensure((size_t)most_agg * sizeof(cf2)); if (rc) return rc;
+    rc = c->dc_range_tab.ensure(n_ent * sizeof(DcBatchEntry)); if (rc) return rc;
+    rc = c->dc_range_map.ensure(n_ent * 2 * sizeof(cd2)); if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(c->dc_range_tab.p, tab.data(), n_ent * sizeof(DcBatchEntry), hipMemcpyHostToDevice, c->stream));
+
+    auto copy_slice = [&](size_t k) {
+        const hipError_t e = hipMemcpyAsync(c->dc_range_in[k & 1].p, (const char *)in + slices[k].off * ibps, slices[k].len * ibps,
+                                            hipMemcpyHostToDevice, c->dc_range_h2d);
+        return e != hipSuccess ? e : hipEventRecord(c->dc_range_in_done[k & 1], c->dc_range_h2d);
+    };
+    // the host variants: the copy of slice k + 1 is queued -- once the kernels of slice k - 1, which read its buffer, are done -- before
+    // the host waits for slice k's copy and queues its kernels (host-ordered, as the pipeline is: no stream waits on another)
+    if (!on_device) HIP_TRY(copy_slice(0));
+    size_t li = 0;
+    for (size_t k = 0; k < slices.size(); ++k) {
+        if (!on_device) {
+            if (k + 1 < slices.size()) {
+                if (k >= 1) HIP_TRY(hipEventSynchronize(c->dc_range_k_done[(k + 1) & 1]));
+                HIP_TRY(copy_slice(k + 1));
+            }
+            HIP_TRY(hipEventSynchronize(c->dc_range_in_done[k & 1]));
+        }
+        for (; li < launches.size() && launches[li].slice == k; ++li) {
+            const RangeLaunch &l = launches[li];
+            const DcBatchEntry *d_tab = (const DcBatchEntry *)c->dc_range_tab.p + l.e0;
+            DcPrefixBatchArgs pa{};
+            pa.raw = slice_base(k); pa.in_fmt = c->desc.in_format; pa.gain = c->desc.gain; pa.c = c->dc_c; pa.logc = c->dc_logc;
+            pa.entries = d_tab; pa.agg = (cf2 *)c->dc_agg.p;
+            HIP_TRY(launch_dc_prefix_batch(pa, (int)l.n, l.max_seg, c->stream));
+            DcScanBatchArgs sa{};
+            sa.entries = d_tab; sa.agg = (const cf2 *)c->dc_agg.p; sa.logc = c->dc_logc; sa.map = (cd2 *)c->dc_range_map.p + 2 * l.e0;
+            HIP_TRY(launch_dc_scan_batch(sa, (int)l.n, c->stream));
+        }
+        if (!on_device) HIP_TRY(hipEventRecord(c->dc_range_k_done[k & 1], c->stream));
+    }
+    if (li != launches.size()) return fail(IQGPU_EINVAL, "internal: %s planned %zu launches and queued %zu", who, launches.size(), li);
+    std::vector<cd2> m(2 * n_ent);
+    HIP_TRY(hipMemcpyAsync(m.data(), c->dc_range_map.p, m.size() * sizeof(cd2), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (size_t e = 0; e < n_ent; ++e) {
+        rows[e].f = m[2 * e].x; rows[e].g_re = m[2 * e + 1].x; rows[e].g_im = m[2 * e + 1].y; rows[e].frames = (uint64_t)pieces[e].len;
+    }
+    return IQGPU_OK;
+}
+
+// (all three families: Dc and DcRms give one row per call; DcAgc -- the family whose preroll runs as shadow calls -- cuts every call as
+//  iqgpu_chain_dcagc_dc_measure cuts it, one row per piece)
+static int dc_measure_range_impl(iqgpu_chain *c, uint64_t first_frame, const void *in, size_t frames_in, size_t call_frames, iqgpu_dc_row *rows,
+                                 size_t cap, size_t *n_rows, uint32_t *first_row, bool on_device, SeekKind kind)
+{
+    const ShardFamily &fam = shard_family(kind);
+    const char *who = fam.dc_measure_range;
+    int rc = shard_check(fam, c, who); if (rc) return rc;
+    if (!rows || !n_rows) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
+    *n_rows = 0;
+    const bool cuts = fam.preroll_agc == AgcMode::Shadow;
+    if (call_frames == 0 || call_frames % 4096) return fail(IQGPU_EINVAL, "%s: call_frames %zu is not a non-zero multiple of 4096", who, call_frames);
+    if (cuts && (call_frames % (size_t)c->agc_chunk || first_frame % (uint64_t)c->agc_chunk)) return fail(IQGPU_EINVAL, "%s: first_frame %llu and "
+        "call_frames %zu have to be multiples of agc_chunk_frames = %lld", who, (unsigned long long)first_frame, call_frames, (long long)c->agc_chunk);
+    if (first_frame % (uint64_t)call_frames) return fail(IQGPU_EINVAL, "%s: first_frame %llu is not on the grid of calls of %zu frames", who,
+        (unsigned long long)first_frame, call_frames);
+    if (first_frame > kMaxStreamFrames || (uint64_t)frames_in > kMaxStreamFrames - first_frame) return fail(IQGPU_EINVAL, "%s: stream position "
+        "%llu + %zu frames is beyond 2^39 frames", who, (unsigned long long)first_frame, frames_in);
+    if (frames_in == 0) return IQGPU_OK;
+    // the pieces of every grid call, in stream order
+    const size_t n_calls = (frames_in + call_frames - 1) / call_frames;
+    const bool may_cut = cuts && (c->agc_fusable || c->agc_fusable_filter);
+    std::vector<RangePiece> pieces;
+    std::vector<uint32_t> first(n_calls);
+    pieces.reserve(n_calls + 1);
+    for (size_t k = 0; k < n_calls; ++k) {
+        const size_t off = k * call_frames, len = frames_in - off < call_frames ? frames_in - off : call_frames;
+        size_t head = len;
+        if (may_cut) {
+            bool locked = false, locks = false; uint64_t seen = 0;
+            agc_mirrors_at(c, first_frame + (uint64_t)off, &locked, &seen);
+            head = agc_call_cut(c, locked, seen, stream_at(c, first_frame + (uint64_t)off).pos, len, &locks);
+        }
+        first[k] = (uint32_t)pieces.size();
+        if (head > 0) pieces.push_back(RangePiece{off, head, false});
+        if (head < len) pieces.push_back(RangePiece{off + head, len - head, true});
+    }
+    *n_rows = pieces.size();
+    if (cap < pieces.size()) return fail(IQGPU_ECAPACITY, "%s: %zu calls are %zu rows, the table holds %zu", who, n_calls, pieces.size(), cap);
+    *n_rows = 0;
+    if (!in) return fail(IQGPU_EINVAL, "%s: NULL buffer", who);
+    if (c->poisoned) return fail(IQGPU_EHIP, "an earlier call failed half way through: the stream state is undefined until iqgpu_chain_reset()");
+    HIP_TRY(hipSetDevice(c->device));
+    rc = pipe_advance(c, c->pipe_seq); if (rc) return rc;         // batches submitted earlier come first (same stream)
+    // the host variants' slices: whole calls; the _device variants read the range where it lies (one "slice")
+    std::vector<RangeSlice> slices;
+    if (on_device) slices.push_back(RangeSlice{0, frames_in});
+    else {
+        const size_t want = c->sw.dc_range_slice_frames > 0 ? (size_t)c->sw.dc_range_slice_frames : kDcRangeSliceFrames;
+        const size_t per = (want / call_frames ? want / call_frames : 1) * call_frames;
+        for (size_t off = 0; off < frames_in; off += per) slices.push_back(RangeSlice{off, frames_in - off < per ? frames_in - off : per});
+    }
+    rc = dc_measure_range_run(c, who, first_frame, in, on_device, pieces, slices, rows);
+    if (rc) {
+        // (whatever was queued reads host vectors of this call and the caller's buffer: nothing of it outlives the call)
+        (void)hipStreamSynchronize(c->stream);
+        if (c->dc_range_h2d) (void)hipStreamSynchronize(c->dc_range_h2d);
+        return rc;
+    }
+    if (first_row) memcpy(first_row, first.data(), n_calls * sizeof(uint32_t));
+    *n_rows = pieces.size();
+    return IQGPU_OK;
+}
+
+extern "C" int iqgpu_chain_dc_measure_range(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, size_t call_frames,
+                                            iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row)
+{
+    return dc_measure_range_impl(c, first_frame, raw_in, frames_in, call_frames, rows, cap, n_rows, first_row, false, SeekKind::Dc);
+}
+extern "C" int iqgpu_chain_dc_measure_range_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, size_t call_frames,
+                                                   iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row)
+{
+    return dc_measure_range_impl(c, first_frame, d_raw_in, frames_in, call_frames, rows, cap, n_rows, first_row, true, SeekKind::Dc);
+}
+extern "C" int iqgpu_chain_dcagc_dc_measure_range(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, size_t call_frames,
+                                                  iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row)
+{
+    return dc_measure_range_impl(c, first_frame, raw_in, frames_in, call_frames, rows, cap, n_rows, first_row, false, SeekKind::DcAgc);
+}
+extern "C" int iqgpu_chain_dcagc_dc_measure_range_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, size_t call_frames,
+                                                         iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row)
+{
+    return dc_measure_range_impl(c, first_frame, d_raw_in, frames_in, call_frames, rows, cap, n_rows, first_row, true, SeekKind::DcAgc);
+}
+extern "C" int iqgpu_chain_dcrms_dc_measure_range(iqgpu_chain *c, uint64_t first_frame, const void *raw_in, size_t frames_in, size_t call_frames,
+                                                  iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row)
+{
+    return dc_measure_range_impl(c, first_frame, raw_in, frames_in, call_frames, rows, cap, n_rows, first_row, false, SeekKind::DcRms);
+}
+extern "C" int iqgpu_chain_dcrms_dc_measure_range_device(iqgpu_chain *c, uint64_t first_frame, const void *d_raw_in, size_t frames_in, size_t call_frames,
+                                                         iqgpu_dc_row *rows, size_t cap, size_t *n_rows, uint32_t *first_row)
+{
+    return dc_measure_range_impl(c, first_frame, d_raw_in, frames_in, call_frames, rows, cap, n_rows, first_row, true, SeekKind::DcRms);
 }
 
 // ------------------------------------------------------------------------------------------------

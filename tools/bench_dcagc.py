@@ -2,14 +2,17 @@
 ordinary pass, on NRSC-5 cs16 + dc_block + digital AGC, device-resident, behind the lock:
 
     pass 1  iqgpu_chain_dcagc_dc_measure_device   (k_dc_prefix + the scan's map, one row copy per call)
+    pass 1  iqgpu_chain_dcagc_dc_measure_range_device   (the same rows, every call of the range in ONE submission: k_dc_prefix_batch +
+            k_dc_scan_batch, one copy of all rows, one synchronisation) -- beside the per-call loop, interleaved with it
     pass 3  iqgpu_chain_dcagc_measure_device      (shadow calls: the ordinary kernels, no output kept, one row copy per call)
     pass 5  iqgpu_chain_process_device            (the ordinary pass: what a shard runs behind its seek -- and the yardstick)
 
-    python tools/bench_dcagc.py [--log2 28] [--call-log2 22] [--rounds 7] [--ordinary-only] [--out FILE.json]
+    python tools/bench_dcagc.py [--log2 28] [--call-log2 22] [--rounds 7] [--ordinary-only] [--host-fed] [--out FILE.json]
 
 One range of 2^log2 frames in device memory, walked in calls of 2^call-log2 frames.  One warm ordinary pass (it holds the lock), then
 `rounds` interleaved rounds of one pass of each kind, host wall clock around the pass + synchronise (ms); median, minimum and maximum
-per kind.  --ordinary-only times pass 5 alone (a library without the new entry points: the parent's figure on the same box)."""
+per kind.  --ordinary-only times pass 5 alone (a library without the new entry points: the parent's figure on the same box).
+--host-fed adds pass 1 through the range form's HOST variant from pinned memory (staging slices, copy and kernels overlapping)."""
 import argparse
 import json
 import os
@@ -32,6 +35,7 @@ def main():
     ap.add_argument("--call-log2", type=int, default=22)
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--ordinary-only", action="store_true")
+    ap.add_argument("--host-fed", action="store_true")
     ap.add_argument("--out")
     args = ap.parse_args()
     n, call = 1 << args.log2, 1 << args.call_log2
@@ -55,13 +59,31 @@ def main():
         for a in range(0, n, call):
             ch.dcagc_dc_measure_device(first + a, buf.ptr + a * 4, call)
 
+    def dc_measure_range():
+        rows, _ = ch.dcagc_dc_measure_range_device(ch.tell()[0], buf.ptr, n, call)
+        assert rows.size >= n // call
+
+    pinned = None
+    if args.host_fed:
+        pinned = gpu.PinnedBuffer(n * 4)
+        for at in range(0, n * 4, seg.nbytes):
+            m = min(seg.nbytes, n * 4 - at)
+            pinned.array[at:at + m] = seg[:m]
+
+    def dc_measure_range_host():
+        rows, _ = ch.dcagc_dc_measure_range(ch.tell()[0], pinned.array[:n * 4], call)
+        assert rows.size >= n // call
+
     def shadow():
         for a in range(0, n, call):
             ch.dcagc_measure_device(buf.ptr + a * 4, call)
 
     kinds = {"pass5_process": ordinary}
     if not args.ordinary_only:
-        kinds = {"pass1_dc_measure": dc_measure, "pass3_shadow_measure": shadow, "pass5_process": ordinary}
+        kinds = {"pass1_dc_measure": dc_measure, "pass1_dc_measure_range": dc_measure_range, "pass3_shadow_measure": shadow,
+                 "pass5_process": ordinary}
+        if args.host_fed:
+            kinds["pass1_dc_measure_range_host_pinned"] = dc_measure_range_host
     ordinary()                                               # warm: allocations, and the stream locks
     ordinary()
     assert ch.agc_state()["locked"]

@@ -2,6 +2,7 @@
 ordinary single-stream pass, on NRSC-5 cs16 + dc_block + AGC local (or dx), device-resident:
 
     pass 1  iqgpu_chain_dcrms_dc_measure_device   (k_dc_prefix + the scan's map, one row copy per call)
+    pass 1  iqgpu_chain_dcrms_dc_measure_range_device   (the same rows, every call of the range in ONE submission) -- beside the loop
     pass 2  iqgpu_chain_dcrms_dc_advance          (one walk over all rows)
     pass 3  iqgpu_chain_dcrms_seek_device         (the preroll in grid calls with the AGC out of the way, then k_agc_rms_seek) ...
             ... + iqgpu_chain_process_device      (the ordinary pass over the range: what a shard runs behind its seek -- and the
@@ -58,6 +59,10 @@ def main():
     def dc_measure():
         rows[:] = [ch.dcrms_dc_measure_device(a, buf.ptr + a * 4, call) for a in range(0, n, call)]
 
+    def dc_measure_range():
+        got, _ = ch.dcrms_dc_measure_range_device(0, buf.ptr, n, call)
+        assert got.size == n // call
+
     def dc_walk():
         ch.dcrms_dc_advance(None, np.concatenate([r.reshape(1) for r in rows]))
 
@@ -65,7 +70,7 @@ def main():
         # (a cut at frame n of a stream that repeats the buffer: its preroll is the buffer's last grid calls)
         ch.dcrms_seek_device(n, buf.ptr + (n - pre) * 4, pre, call, None)
 
-    kinds = {"pass1_dc_measure": dc_measure, "pass2_dc_walk": dc_walk, "pass3_seek": seek, "pass3_process_single_stream": ordinary}
+    kinds = {"pass1_dc_measure": dc_measure, "pass1_dc_measure_range": dc_measure_range, "pass2_dc_walk": dc_walk, "pass3_seek": seek, "pass3_process_single_stream": ordinary}
     ordinary()                                               # warm: allocations
     ordinary()
     ms = {k: [] for k in kinds}
