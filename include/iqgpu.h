@@ -692,6 +692,89 @@ int   iqgpu_chain_read_iq_probe(iqgpu_chain *c, float *block_re_im_1024, int *va
 /* the optimiser thread's loop body: read the probe, run, publish with iqgpu_chain_set_iq_factors */
 int   iqgpu_iq_optimizer_service(iqgpu_iq_optimizer *o, iqgpu_chain *c, double now_sec, int *updated);
 
+/* ---- I/Q calibration: the optimiser's utility over many blocks and a grid of candidates, searched deterministically (additive, still ABI v9) ----
+ * No counterpart in the reference.  Its optimiser above is a randomised +-1e-4 climb on ONE 1024-sample block per run behind a
+ * 500 ms wall clock: its factors are a function of wall time, which no sharded or checkpointed job can reproduce.  The calls below
+ * evaluate the reference's OWN utility -- same Hamming window, same dB spectrum, same bins i in [25, 486) with the pair 1023 - i, same
+ * -80 dB gate, the same 20 dB peak-to-average gate per block -- over many blocks of a capture and a grid of candidate factors, and
+ * search that surface by a fixed rule.  The result is one (mag, phase) pair, a pure function of the capture bytes and the options:
+ * computed once in front of a job and handed to every shard with iqgpu_chain_set_iq_factors or in the description.  The streaming
+ * optimiser, the probe and every other entry point are as they were.
+ * The search (one function, iq_optimizer.cpp; the evaluator -- host metric or k_iq_metric -- is its only parameter).  A level's
+ * candidates are the grid x grid pairs (centre_mag + (im - h) step, centre_phase + (ip - h) step), h = (grid - 1) / 2, candidate
+ * index c = im * grid + ip, in float; level 0 is centred on (center_mag, center_phase) with step = 2 span / (grid - 1).
+ * total[c] = the sum, in double and in block order, of metric[b][c] over the blocks whose power_range_db >= power_threshold_db.  The
+ * pick is the candidate with the largest total; ties go to the one nearest the centre ((im - h)^2 + (ip - h)^2), then to the lowest
+ * index.  The next level is centred on the pick with step <- step * 2 / (grid - 1); the search stops behind the first level whose step
+ * is <= min_step, or behind 16 levels (grid = 3 keeps its step: it walks, up to 16 levels, and does not refine).  The factors are
+ * the last level's pick.  power_threshold_db may be zero or negative: every block then counts.
+ * Errors: IQGPU_EINVAL for a NULL argument, grid even or outside [3, 15], span, min_step or max_blocks not positive, any option
+ * not finite, n_blocks == 0, a stride or an input below 1024 frames; the report is then all zero. */
+typedef struct { float mag, phase; } iqgpu_iq_cand;
+typedef struct {
+    uint32_t max_blocks;          /* chain calls: blocks taken from the input, evenly spread (64) */
+    uint32_t grid;                /* candidates per axis and level: odd, 3 .. 15 (9) */
+    float    span;                /* level 0 reaches centre +- span on both axes (0.1) */
+    float    min_step;            /* the level whose step is <= this is the last (1e-4: IQ_BASE_INCREMENT) */
+    float    power_threshold_db;  /* blocks below this peak-to-average power do not count (20: IQ_CORRECTION_POWER_THRESHOLD_DB) */
+    float    center_mag, center_phase;   /* centre of level 0 (0, 0) */
+} iqgpu_iq_calib_opts;
+void iqgpu_iq_calib_opts_init(iqgpu_iq_calib_opts *o);             /* the defaults in parentheses above */
+typedef struct { float center_mag, center_phase, step; uint32_t pick; uint32_t reserved; double total_at_pick; } iqgpu_iq_calib_level;
+typedef struct {
+    int      found;               /* 0: no block passed the power gate -- mag, phase are the centre, n_levels = 0 */
+    float    mag, phase;          /* the result: what iqgpu_chain_set_iq_factors / iq_mag, iq_phase of a description take */
+    double   total_at_center0;    /* total of the centre of level 0: the utility before calibration */
+    double   total_at_best;       /* total of the last level's pick */
+    uint32_t blocks_taken;        /* blocks evaluated */
+    uint32_t blocks_used;         /* ... of which passed the power gate */
+    uint32_t n_levels;            /* entries of level[] */
+    uint32_t evaluations;         /* candidates evaluated, over all levels (each on every block taken) */
+    iqgpu_iq_calib_level level[16];
+} iqgpu_iq_calib_report;
+/* The utility (_calculate_imbalance_metric) of every (block, candidate) on the device: block b is the 1024 cf32 samples at
+ * blocks_re_im + 2 * b * stride_frames floats (stride_frames >= 1024), metric[b * n_cand + c] its utility under cands[c], and
+ * power_range_db[b] (NULL: not wanted) its peak-to-average power (_estimate_power).  One forward transform per block and tile of
+ * candidates -- the correction is linear and the window real, so a candidate needs none of its own -- and a fixed summation order:
+ * two calls on the same input give the same bits, and so do the host and the _device form.  Any n_cand >= 1: lists longer than
+ * the per-launch bound (iqgpu_iq_metric_geometry) go in several launches.  The host form stages the blocks, not the gaps between
+ * them; the _device form reads device memory of `device` on hip_stream (NULL: the null stream), writes host memory, and returns with
+ * that stream idle.  Within 2e-4 max(1, |m|) of iqgpu_iq_optimizer_metric where no compared bin stands at the -80 dB gate.
+ * d_blocks_re_im and every block start in it are aligned to 8 bytes (one cf32 sample; any stride_frames keeps that).  A
+ * diagnostic and test entry point, not one for a loop: every call allocates and frees its device buffers and uploads its tables
+ * (12 KB) again; iqgpu_chain_calibrate_iq keeps them with the chain. */
+int   iqgpu_iq_metric_batch(int device, const float *blocks_re_im, size_t n_blocks, size_t stride_frames,
+                            const iqgpu_iq_cand *cands, size_t n_cand, float *metric, float *power_range_db);
+int   iqgpu_iq_metric_batch_device(int device, const float *d_blocks_re_im, size_t n_blocks, size_t stride_frames,
+                                   const iqgpu_iq_cand *cands, size_t n_cand, float *metric, float *power_range_db, void *hip_stream);
+/* diagnostics: candidates per launch of k_iq_metric and per wave of it (either pointer may be NULL); what a test needs to reach
+ * the boundaries of iqgpu_iq_metric_batch, nothing a caller has to know */
+void  iqgpu_iq_metric_geometry(size_t *cands_per_launch, size_t *cand_tile);
+/* The search with the HOST metric (iqgpu_iq_optimizer_metric's, one definition) over blocks laid out as for iqgpu_iq_metric_batch.
+ * No device.  Neither reads nor moves the optimiser's own factors, clock or statistics. */
+int   iqgpu_iq_optimizer_calibrate(iqgpu_iq_optimizer *o, const float *blocks_re_im, size_t n_blocks, size_t stride_frames,
+                                   const iqgpu_iq_calib_opts *opts, iqgpu_iq_calib_report *rep);
+/* The search with k_iq_metric over blocks k_iq_blocks gathers from raw input in the chain's in_format: n = min(max_blocks,
+ * frames_in / 1024) blocks, block b the 1024 frames from frame b * max(1024, frames_in / n).  A block is taken where iq_correct_apply
+ * acts: behind unpack, gain and -- on a chain with the DC blocker -- the blocker run from a ZERO state with the chain's alpha (what
+ * iq_correct_run_initial_calibration sees: a fresh pre-processor), with NO I/Q correction and NO NCO.  This differs from the
+ * streaming probe (iqgpu_chain_read_iq_probe) on a chain with a pre-resample shift, on purpose: in front of the mixer the image of
+ * the imbalance is mirror-symmetric about bin 0, which is what the utility measures; behind it, it is not.
+ * Leaves the handle exactly as it was -- position, histories, DC state, AGC state, I/Q factors, probe slot and pipeline untouched --
+ * and returns with the stream idle, like iqgpu_chain_dc_measure.  Neither needs nor sets iq_correct_enable: the caller publishes
+ * rep->mag, rep->phase.  The host form stages the blocks it needs, not the whole input. */
+int   iqgpu_chain_calibrate_iq(iqgpu_chain *c, const void *raw_in, size_t frames_in,
+                               const iqgpu_iq_calib_opts *opts, iqgpu_iq_calib_report *rep);
+int   iqgpu_chain_calibrate_iq_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in,
+                                      const iqgpu_iq_calib_opts *opts, iqgpu_iq_calib_report *rep);
+/* diagnostics and tests, no part of the calibration recipe: the blocks iqgpu_chain_calibrate_iq[_device] would evaluate, as cf32,
+ * e.g. to evaluate them with the host metric.  blocks_re_im holds cap_blocks x 1024
+ * samples, *n_blocks the number written.  Same selection, same kernel, same guarantees for the handle. */
+int   iqgpu_chain_calibrate_iq_blocks(iqgpu_chain *c, const void *raw_in, size_t frames_in, uint32_t max_blocks,
+                                      float *blocks_re_im, size_t cap_blocks, size_t *n_blocks);
+int   iqgpu_chain_calibrate_iq_blocks_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, uint32_t max_blocks,
+                                             float *blocks_re_im, size_t cap_blocks, size_t *n_blocks);
+
 /* ---- WAV capture metadata -> frequency shift (host only): the step in front of the path for real captures ----
  * SdrMetadata and its parsers (src/input_wav.c:54-100, 146-438), the shift rule of wav_initialize (592-629). */
 enum { IQGPU_SDR_UNKNOWN = 0, IQGPU_SDR_CONSOLE = 1, IQGPU_SDR_SHARP = 2, IQGPU_SDR_UNO = 3, IQGPU_SDR_CONNECT = 4 };

@@ -86,6 +86,30 @@ class IqOptimizerStats(C.Structure):
 RAND_DIR_FN = C.CFUNCTYPE(C.c_float, C.c_void_p)
 
 
+class IqCand(C.Structure):
+    """iqgpu_iq_cand: one candidate pair of correction factors"""
+    _fields_ = [("mag", C.c_float), ("phase", C.c_float)]
+
+
+class IqCalibOpts(C.Structure):
+    """iqgpu_iq_calib_opts: the options of the calibration search (iqgpu_iq_calib_opts_init sets the defaults)"""
+    _fields_ = [("max_blocks", C.c_uint32), ("grid", C.c_uint32), ("span", C.c_float), ("min_step", C.c_float),
+                ("power_threshold_db", C.c_float), ("center_mag", C.c_float), ("center_phase", C.c_float)]
+
+
+class IqCalibLevel(C.Structure):
+    _fields_ = [("center_mag", C.c_float), ("center_phase", C.c_float), ("step", C.c_float), ("pick", C.c_uint32),
+                ("reserved", C.c_uint32), ("total_at_pick", C.c_double)]
+
+
+class IqCalibReport(C.Structure):
+    """iqgpu_iq_calib_report: the result of a calibration with its level trace"""
+    _fields_ = [("found", C.c_int), ("mag", C.c_float), ("phase", C.c_float),
+                ("total_at_center0", C.c_double), ("total_at_best", C.c_double),
+                ("blocks_taken", C.c_uint32), ("blocks_used", C.c_uint32), ("n_levels", C.c_uint32), ("evaluations", C.c_uint32),
+                ("level", IqCalibLevel * 16)]
+
+
 class WavInfo(C.Structure):
     _fields_ = [("source_software", C.c_int),
                 ("software_name", C.c_char * 64), ("software_version", C.c_char * 64), ("radio_model", C.c_char * 128),
@@ -182,6 +206,13 @@ SYMBOLS = [
     ("iqgpu_chain_enable_iq_probe", C.c_int, [_vp, C.c_int]),
     ("iqgpu_chain_read_iq_probe", C.c_int, [_vp, _vp, C.POINTER(C.c_int)]),
     ("iqgpu_iq_optimizer_service", C.c_int, [_vp, _vp, C.c_double, C.POINTER(C.c_int)]),
+    ("iqgpu_iq_calib_opts_init", None, [C.POINTER(IqCalibOpts)]),
+    ("iqgpu_iq_metric_batch", C.c_int, [C.c_int, _vp, _sz, _sz, _vp, _sz, _vp, _vp]),
+    ("iqgpu_iq_metric_batch_device", C.c_int, [C.c_int, _vp, _sz, _sz, _vp, _sz, _vp, _vp, _vp]),
+    ("iqgpu_iq_metric_geometry", None, [C.POINTER(_sz), C.POINTER(_sz)]),
+    ("iqgpu_iq_optimizer_calibrate", C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(IqCalibOpts), C.POINTER(IqCalibReport)]),
+    *_with_device("iqgpu_chain_calibrate_iq", C.c_int, [_vp, _vp, _sz, C.POINTER(IqCalibOpts), C.POINTER(IqCalibReport)]),
+    *_with_device("iqgpu_chain_calibrate_iq_blocks", C.c_int, [_vp, _vp, _sz, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
     ("iqgpu_wav_info_init", None, [C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_auxi", C.c_int, [_vp, _sz, C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_filename", C.c_int, [C.c_char_p, C.POINTER(WavInfo)]),

@@ -588,6 +588,38 @@ class Chain:
         check(self._lib.iqgpu_chain_read_iq_probe(self._h, blk.ctypes.data_as(C.c_void_p), C.byref(valid)))
         return blk if valid.value else None
 
+    # ---- I/Q calibration (include/iqgpu.h): the optimiser's utility over many blocks of the input and a grid of candidates ----
+    def _calibrate_iq(self, fn, ptr, n, opts):
+        from .iq_optimizer import IqCalibration, calib_opts
+        o = calib_opts(**opts)
+        rep = _lib.IqCalibReport()
+        check(fn(self._h, ptr, n, C.byref(o), C.byref(rep)))
+        return IqCalibration(rep, o)
+
+    def _calibrate_iq_blocks(self, fn, ptr, n, max_blocks):
+        cap = max(1, min(int(max_blocks), n // 1024))
+        blocks = np.empty((cap, 1024), np.complex64)
+        got = C.c_size_t(0)
+        check(fn(self._h, ptr, n, int(max_blocks), blocks.ctypes.data_as(C.c_void_p), cap, C.byref(got)))
+        return blocks[:got.value]
+
+    def calibrate_iq(self, raw, **opts):
+        """one (mag, phase) pair for this input, a pure function of its bytes and the options: the deterministic grid search of the
+        optimiser's utility over up to max_blocks blocks of raw (frames in in_format), evaluated on the GPU.  Returns an
+        IqCalibration; the chain itself stays exactly as it was -- publish the result with set_iq_factors or in the description"""
+        return self._calibrate_iq(self._lib.iqgpu_chain_calibrate_iq, *self._host_input(raw), opts)
+
+    def calibrate_iq_device(self, d_in, frames_in, **opts):
+        """calibrate_iq() with the input already in device memory of this chain's GPU (a device address as an int)"""
+        return self._calibrate_iq(self._lib.iqgpu_chain_calibrate_iq_device, C.c_void_p(d_in), int(frames_in), opts)
+
+    def calibrate_iq_blocks(self, raw, max_blocks=64):
+        """the cf32 blocks calibrate_iq() evaluates, [n, 1024]: behind unpack, gain and the DC blocker from a zero state"""
+        return self._calibrate_iq_blocks(self._lib.iqgpu_chain_calibrate_iq_blocks, *self._host_input(raw), max_blocks)
+
+    def calibrate_iq_blocks_device(self, d_in, frames_in, max_blocks=64):
+        return self._calibrate_iq_blocks(self._lib.iqgpu_chain_calibrate_iq_blocks_device, C.c_void_p(d_in), int(frames_in), max_blocks)
+
     # ---- plumbing ----
     def set_stream(self, hip_stream):
         check(self._lib.iqgpu_chain_set_stream(self._h, C.c_void_p(hip_stream)))

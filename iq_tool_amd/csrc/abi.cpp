@@ -173,6 +173,7 @@ static void free_device_state(iqgpu_chain *c)
     c->fbuf[0].release(); c->fbuf[1].release();
     c->ibuf[0].release(); c->ibuf[1].release();
     c->stage_in.release(); c->stage_out.release(); c->seek_sink.release(); c->seek_win.release();
+    c->iq_cal_tab.release(); c->iq_cal_in.release(); c->iq_cal_blocks.release(); c->iq_cal_work.release();
     if (c->d_probe) (void)hipFree(c->d_probe);
     if (c->h_probe) (void)hipHostFree(c->h_probe);
     if (c->probe_done) (void)hipEventDestroy(c->probe_done);

@@ -7,6 +7,7 @@
 //                  iqgpu_chain_dc_measure / _dc_measure_range / _dc_advance, iqgpu_chain_dcagc_*, iqgpu_chain_dcrms_*
 //   agc_host.cpp   host side of the output AGC: chunk map, fused / unfused split, verifier + fallback launches
 //   pipeline.cpp   iqgpu_chain_submit / _measure_submit / _collect (pinned host buffers, three stages moved along by the host)
+//   iq_calib.cpp   I/Q calibration: iqgpu_iq_metric_batch, iqgpu_chain_calibrate_iq (the search itself: iq_optimizer.cpp, no HIP)
 //   state.cpp      checkpoint / resume: iqgpu_chain_tell, iqgpu_chain_save_state / _load_state, iqgpu_design_state_size (the blob's
 //                  header, checksum and iqgpu_state_inspect: state_blob.cpp, which includes nothing of HIP)
 #pragma once
@@ -239,6 +240,9 @@ struct iqgpu_chain {
     uint64_t probe_gen = 0;       // counts probe_drop calls: a reader that waited for a copy meanwhile dropped does not publish it
     cf2 *d_probe = nullptr; cf2 *h_probe = nullptr; hipEvent_t probe_done = nullptr;
     cf2 probe_last[1024];
+    // I/Q calibration (iq_calib.cpp; buffers of its own, so that a call touches nothing the stream carries): window + twiddle table
+    // (uploaded when allocated), the host form's raw blocks, the gathered cf32 blocks, candidates + metrics + power statistics
+    DevBuf iq_cal_tab, iq_cal_in, iq_cal_blocks, iq_cal_work;
     char front_kernel[48] = "";   // which front kernel the last call launched (iqgpu_chain_front_kernel)
     bool poisoned = false;        // a call failed after device state had been touched: reset() clears it
     // placement of the arms in the tap planes of k_front_mid / k_front_fat for this chain's step (front_tap_fold, or sw.tap_fold)

@@ -146,6 +146,7 @@ typedef struct {
     int have_shards;                  /* --shards was given */
     int dry;                          /* --dry-placement: plan, bind, size the buffers, report -- no GPU call */
     int quiet;
+    int iq_calibrate, have_iq_factors;   /* --iq-calibrate: the I/Q factors come from the head of the input (calibrate_head); --iq-factors was given */
 } Options;
 
 typedef struct {
@@ -720,7 +721,7 @@ static void usage(void)
     fprintf(stderr,
             "iqgpu_run -i IN --raw-file-input-rate HZ --raw-file-input-sample-format FMT -o OUT --output-rate HZ\n"
             "          [--output-sample-format FMT] [--freq-shift HZ] [--shift-after-resample] [--gain G] [--dc-block]\n"
-            "          [--iq-factors MAG:PHASE] [--no-resample] [--lowpass HZ] [--highpass HZ] [--pass-range A:B] [--stopband A:B]\n"
+            "          [--iq-factors MAG:PHASE | --iq-calibrate (the factors from the head of the input, printed as --iq-factors takes them)] [--no-resample] [--lowpass HZ] [--highpass HZ] [--pass-range A:B] [--stopband A:B]\n"
             "          [--transition-width HZ] [--attenuation DB] [--filter-taps N] [--filter-type fir|fft] [--filter-fft-size N]\n"
             "          [--chunk-frames N (default 4194304)] [--shards N] [--devices N] [--device D] [--synthetic FRAMES [--synthetic-hash SEED]]\n"
             "          [--seamless (with --shards: the shards continue ONE stream -- the stitched output is what --shards 1 writes)]\n"
@@ -753,7 +754,8 @@ static int parse_args(int argc, char **argv, Options *o)
         else if (!strcmp(a, "--shift-after-resample")) o->desc.shift_after_resample = 1;
         else if (!strcmp(a, "--gain")) o->desc.gain = (float)atof(NEXT);
         else if (!strcmp(a, "--dc-block")) o->desc.dc_block_enable = 1;
-        else if (!strcmp(a, "--iq-factors")) { o->desc.iq_correct_enable = 1; sscanf(NEXT, "%f:%f", &o->desc.iq_mag, &o->desc.iq_phase); }
+        else if (!strcmp(a, "--iq-factors")) { o->desc.iq_correct_enable = 1; o->have_iq_factors = 1; sscanf(NEXT, "%f:%f", &o->desc.iq_mag, &o->desc.iq_phase); }
+        else if (!strcmp(a, "--iq-calibrate")) o->iq_calibrate = 1;
         else if (!strcmp(a, "--no-resample")) o->desc.no_resample = 1;
         else if (!strcmp(a, "--lowpass") || !strcmp(a, "--highpass")) {
             if (o->desc.n_filters >= 5) REFUSE(2, "at most 5 filters\n");
@@ -817,6 +819,7 @@ static int validate(const Options *o)
     const ModeRow *m = &MODES[o->mode];
     const size_t agc_chunk = agc_chunk_of(&o->desc);
     if (o->clash != M_INDEPENDENT) REFUSE(2, "%s excludes %s\n", m->flag, MODES[o->clash].flag);
+    if (o->iq_calibrate && o->have_iq_factors) REFUSE(2, "--iq-calibrate excludes --iq-factors\n");
     for (const unsigned char *c = m->checks; *c != C_END; c++) switch (*c) {
     case C_SHARDS: if (!o->have_shards) REFUSE(2, "%s needs --shards N\n", m->flag); break;
     case C_HAS_AGC: if (o->desc.agc_enable) REFUSE(1, "%s: a chain with the output AGC is not covered (its measure route may cut a call into other segments "
@@ -834,6 +837,45 @@ static int validate(const Options *o)
     case C_CHUNK_AGC: if (o->chunk_frames == 0 || o->chunk_frames % agc_chunk) REFUSE(2, "%s: --chunk-frames has to be a multiple of the AGC chunk (%zu frames)\n",
         m->flag, agc_chunk); break;
     }
+    return 0;
+}
+
+/* --iq-calibrate: before any shard starts, ONE chain calibrates on the head of the input -- the blocks iqgpu_chain_calibrate_iq picks from
+ * its first 2^24 frames (blocks are independent of what lies between them, so only they are read) -- and the result goes into the
+ * description every shard is created from, as --iq-factors would have put it there.  0, or the exit status */
+static int calibrate_head(Options *o, long long total_frames, size_t ibps)
+{
+    iqgpu_iq_calib_opts co;
+    iqgpu_iq_calib_opts_init(&co);
+    const long long head = total_frames < (1ll << 24) ? total_frames : (1ll << 24);
+    if (head < 1024) REFUSE(1, "--iq-calibrate: the input has fewer than 1024 frames\n");
+    const long long n = head / 1024 < (long long)co.max_blocks ? head / 1024 : (long long)co.max_blocks;
+    const long long stride = head / n > 1024 ? head / n : 1024;
+    char err[256] = "";
+    int in_fd = -1, rc = 0;
+    if (o->in_path && o->synthetic_frames <= 0 && (in_fd = open(o->in_path, O_RDONLY)) < 0) REFUSE(1, "open %s: %s\n", o->in_path, strerror(errno));
+    void *buf = malloc((size_t)n * 1024 * ibps);
+    iqgpu_chain *c = NULL;
+    iqgpu_iq_calib_report r;
+    if (!buf) { fprintf(stderr, "--iq-calibrate: out of memory\n"); rc = 1; }
+    for (long long b = 0; !rc && b < n; b++)
+        if (read_frames(o, in_fd, o->desc.in_format, ibps, b * stride, 1024, (char *)buf + (size_t)b * 1024 * ibps, err, sizeof(err))) { fprintf(stderr, "--iq-calibrate: %s\n", err); rc = 1; }
+    if (!rc) {
+        iqgpu_chain_desc d = o->desc;
+        d.device_ordinal = o->device0;
+        co.max_blocks = (uint32_t)n;
+        if (iqgpu_chain_create(&d, &c) != IQGPU_OK || iqgpu_chain_calibrate_iq(c, buf, (size_t)n * 1024, &co, &r) != IQGPU_OK) { fprintf(stderr, "--iq-calibrate: %s\n", iqgpu_last_error()); rc = 1; }
+    }
+    if (c) iqgpu_chain_destroy(c);
+    free(buf);
+    if (in_fd >= 0) close(in_fd);
+    if (rc) return rc;
+    o->desc.iq_correct_enable = 1; o->desc.iq_mag = r.mag; o->desc.iq_phase = r.phase;
+    printf("iq_calibrate: --iq-factors %.9g:%.9g found=%d blocks=%u/%u levels=%u total=%.9g->%.9g\n", r.mag, r.phase, r.found, r.blocks_used, r.blocks_taken,
+           r.n_levels, r.total_at_center0, r.total_at_best);
+    fflush(stdout);
+    if (!r.found) fprintf(stderr, "--iq-calibrate: no block of the head has %g dB of peak-to-average power: the factors stay %g:%g (no correction measured)\n",
+                          (double)co.power_threshold_db, (double)r.mag, (double)r.phase);
     return 0;
 }
 
@@ -1012,6 +1054,7 @@ int main(int argc, char **argv)
     Shard *sh = (Shard *)calloc((size_t)o.shards, sizeof(Shard));
     iqgpu_chain_info info;
     if (iqgpu_design_probe(&o.desc, &info, NULL, 0, NULL, 0, NULL, 0) != IQGPU_OK) REFUSE(1, "%s\n", iqgpu_last_error());
+    if (o.iq_calibrate && !o.dry && (rc = calibrate_head(&o, total_frames, ibps)) != 0) { free(sh); return rc; }
     rc = plan_shards(&o, sh, total_frames, obps);
     if (rc) return rc;
     g_shards = sh;

@@ -14,6 +14,8 @@
 //   power gate  max - mean of the same bins, at least 20 dB                         362-389, 170-176
 //   climb       25 candidates current +- 1e-4 (gain, then phase direction), keep a candidate that raises the metric   191-201
 //   publish     factor <- 0.95 factor + 0.05 best                                   206-216
+// Beside it, with no counterpart in the reference: the deterministic grid search of the same utility over many blocks
+// (iq_calib_search, iqgpu_iq_optimizer_calibrate; include/iqgpu.h "I/Q calibration"), which the device path shares (iq_calib.cpp).
 // Not replicated: the reference calls this through pre_stream_iq_correction BEFORE iq_correct_init has
 // allocated fft_buffer (src/setup.c:291 vs src/pipeline.c:140), a NULL memcpy for files >= 1024 frames; here
 // the optimiser owns its buffers from create().  The FFT is liquid's in the reference (any exact DFT to float
@@ -24,8 +26,10 @@
 #include <ctime>
 #include <mutex>
 #include <new>
+#include <vector>
 
 #include "../../include/iqgpu.h"
+#include "iq_search.hpp"
 
 namespace {
 
@@ -252,4 +256,105 @@ extern "C" int iqgpu_iq_optimizer_touch(iqgpu_iq_optimizer *o, double now_sec)
     if (!o) return IQGPU_EINVAL;
     o->last_time = now_sec < 0.0 ? monotonic_now() : now_sec;
     return IQGPU_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// I/Q calibration (include/iqgpu.h): ONE search, whose evaluator is the host metric above or k_iq_metric (iq_calib.cpp)
+// ------------------------------------------------------------------------------------------------
+extern "C" void iqgpu_iq_calib_opts_init(iqgpu_iq_calib_opts *o)
+{
+    if (!o) return;
+    memset(o, 0, sizeof(*o));
+    o->max_blocks = 64; o->grid = 9; o->span = 0.1f;
+    o->min_step = kIncrement; o->power_threshold_db = kPowerDb;
+}
+
+int iqgpu::iq_calib_check_opts(const iqgpu_iq_calib_opts *o, const char **why)
+{
+    const char *w = nullptr;
+    if (!o) w = "NULL options";
+    else if (o->grid < 3 || o->grid > 15 || (o->grid & 1u) == 0) w = "grid must be odd and in [3, 15]";
+    else if (o->max_blocks == 0) w = "max_blocks must be positive";
+    else if (!std::isfinite(o->span) || !(o->span > 0.0f)) w = "span must be finite and positive";
+    else if (!std::isfinite(o->min_step) || !(o->min_step > 0.0f)) w = "min_step must be finite and positive";
+    else if (!std::isfinite(o->power_threshold_db)) w = "power_threshold_db must be finite";
+    else if (!std::isfinite(o->center_mag) || !std::isfinite(o->center_phase)) w = "the centre must be finite";
+    if (why) *why = w;
+    return w ? IQGPU_EINVAL : IQGPU_OK;
+}
+
+int iqgpu::iq_calib_search(const iqgpu_iq_calib_opts &o, size_t n_blocks, IqCalibEval eval, void *user, iqgpu_iq_calib_report *rep)
+{
+    memset(rep, 0, sizeof(*rep));
+    const int g = (int)o.grid, h = (g - 1) / 2, nc = g * g;
+    std::vector<iqgpu_iq_cand> cands;
+    std::vector<float> metric, range;
+    std::vector<double> total;
+    try { cands.resize((size_t)nc); metric.resize(n_blocks * (size_t)nc); range.resize(n_blocks); total.resize((size_t)nc); }
+    catch (const std::bad_alloc &) { return IQGPU_ENOMEM; }
+    float cm = o.center_mag, cp = o.center_phase;
+    float step = 2.0f * o.span / (float)(g - 1);
+    rep->blocks_taken = (uint32_t)n_blocks;
+    rep->mag = cm; rep->phase = cp;
+    for (int level = 0; level < 16; ++level) {
+        for (int im = 0; im < g; ++im)
+            for (int ip = 0; ip < g; ++ip)
+                cands[(size_t)(im * g + ip)] = iqgpu_iq_cand{cm + (float)(im - h) * step, cp + (float)(ip - h) * step};
+        const int rc = eval(user, cands.data(), (size_t)nc, metric.data(), level == 0 ? range.data() : nullptr);
+        if (rc != IQGPU_OK) { memset(rep, 0, sizeof(*rep)); return rc; }
+        rep->evaluations += (uint32_t)nc;
+        if (level == 0) {
+            for (size_t b = 0; b < n_blocks; ++b) rep->blocks_used += range[b] >= o.power_threshold_db ? 1u : 0u;
+            if (rep->blocks_used == 0) return IQGPU_OK;               // found = 0: the centre stands
+        }
+        for (int c = 0; c < nc; ++c) total[(size_t)c] = 0.0;
+        for (size_t b = 0; b < n_blocks; ++b) {
+            if (!(range[b] >= o.power_threshold_db)) continue;
+            for (int c = 0; c < nc; ++c) total[(size_t)c] += (double)metric[b * (size_t)nc + (size_t)c];
+        }
+        int pick = h * g + h, pick_d = 0;                              // the centre: nearest to itself
+        for (int c = 0; c < nc; ++c) {
+            const int dm = c / g - h, dp = c % g - h, d = dm * dm + dp * dp;
+            if (total[(size_t)c] > total[(size_t)pick] || (total[(size_t)c] == total[(size_t)pick] && d < pick_d)) { pick = c; pick_d = d; }
+        }
+        if (level == 0) rep->total_at_center0 = total[(size_t)(h * g + h)];
+        iqgpu_iq_calib_level &lv = rep->level[level];
+        lv.center_mag = cm; lv.center_phase = cp; lv.step = step; lv.pick = (uint32_t)pick; lv.total_at_pick = total[(size_t)pick];
+        rep->n_levels = (uint32_t)level + 1;
+        rep->total_at_best = total[(size_t)pick];
+        cm = cands[(size_t)pick].mag; cp = cands[(size_t)pick].phase;
+        if (step <= o.min_step) break;
+        step = step * 2.0f / (float)(g - 1);
+    }
+    rep->found = 1; rep->mag = cm; rep->phase = cp;
+    return IQGPU_OK;
+}
+
+namespace {
+struct HostEval { iqgpu_iq_optimizer *o; const cfl *blocks; size_t n_blocks, stride; };
+int host_eval(void *user, const iqgpu_iq_cand *cands, size_t n_cand, float *metric, float *power_range_db)
+{
+    const HostEval &e = *(const HostEval *)user;
+    for (size_t b = 0; b < e.n_blocks; ++b) {
+        const cfl *blk = e.blocks + b * e.stride;
+        if (power_range_db) {                                         // (the optimiser's own last estimate stays: get_stats reports it)
+            const float avg = e.o->average_power, range = e.o->power_range;
+            e.o->estimate_power(blk);
+            power_range_db[b] = e.o->power_range;
+            e.o->average_power = avg; e.o->power_range = range;
+        }
+        for (size_t c = 0; c < n_cand; ++c) metric[b * n_cand + c] = e.o->metric(blk, cands[c].mag, cands[c].phase);
+    }
+    return IQGPU_OK;
+}
+} // namespace
+
+extern "C" int iqgpu_iq_optimizer_calibrate(iqgpu_iq_optimizer *o, const float *blocks_re_im, size_t n_blocks, size_t stride_frames,
+                                            const iqgpu_iq_calib_opts *opts, iqgpu_iq_calib_report *rep)
+{
+    if (rep) memset(rep, 0, sizeof(*rep));
+    if (!o || !blocks_re_im || !rep || n_blocks == 0 || n_blocks > 0xffffffffu || stride_frames < (size_t)kN) return IQGPU_EINVAL;
+    if (iqgpu::iq_calib_check_opts(opts, nullptr) != IQGPU_OK) return IQGPU_EINVAL;
+    HostEval e{o, (const cfl *)blocks_re_im, n_blocks, stride_frames};
+    return iqgpu::iq_calib_search(*opts, n_blocks, host_eval, &e, rep);
 }

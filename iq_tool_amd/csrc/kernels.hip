@@ -14,6 +14,7 @@
 
 #include "../../include/iqgpu.h"
 #include "dsp_device.hpp"
+#include "iq_calib.hpp"
 #include "kernels.hpp"
 
 #ifndef IQGPU_NT_DC
@@ -754,19 +755,12 @@ __global__ __launch_bounds__(64) void k_iq_probe(const IqProbeArgs a)
 {
     __shared__ cf2 x[1024];
     const int lane = threadIdx.x;
-    for (int i = lane; i < 1024; i += 64) x[i] = unpack_one(a.raw, i, a.in_fmt, a.gain);
-    __syncthreads();
+    float vr = 0.0f, vi = 0.0f;
     if (a.dc_enable && lane == 0) {
         const cd2 st = *a.dc_state;                // v[n-1] in front of this call's first sample
-        float vr = (float)st.x, vi = (float)st.y;
-        const float aa = 1.0f - a.dc_c;
-        for (int i = 0; i < 1024; ++i) {
-            const cf2 v = x[i];
-            x[i] = cf2{fmaf(-aa, vr, v.x), fmaf(-aa, vi, v.y)};
-            vr = fmaf(a.dc_c, vr, v.x); vi = fmaf(a.dc_c, vi, v.y);
-        }
+        vr = (float)st.x; vi = (float)st.y;
     }
-    __syncthreads();
+    iq_block_head(x, a.raw, 0, a.in_fmt, a.gain, a.dc_enable != 0, a.dc_c, vr, vi, lane);     // (shared with k_iq_blocks, iq_calib.hpp)
     for (int i = lane; i < 1024; i += 64) {
         cf2 v = x[i];
         if (a.iq_enable) { const float re = v.x; v.x = re * a.iq_magp1; v.y = fmaf(a.iq_phase, re, v.y); }
