@@ -775,6 +775,69 @@ int   iqgpu_chain_calibrate_iq_blocks(iqgpu_chain *c, const void *raw_in, size_t
 int   iqgpu_chain_calibrate_iq_blocks_device(iqgpu_chain *c, const void *d_raw_in, size_t frames_in, uint32_t max_blocks,
                                              float *blocks_re_im, size_t cap_blocks, size_t *n_blocks);
 
+/* ---- power spectrum of a stream: an averaged (Welch) periodogram with a max-hold trace, accumulated on the device (additive, still ABI v9) ----
+ * No counterpart in the reference.  An accumulator over ONE stream of frames in ONE sample format, independent of any chain: it
+ * serves the raw capture (a chain's in_format) and a chain's output (its out_format, packed integer output included: what the
+ * writer writes) alike.  Where does the signal sit in the capture, is the stop band down in the output: both are read off it.
+ * Segments: segment s is frames [s hop, s hop + nfft) of everything pushed since the last reset;
+ * segments = frames < nfft ? 0 : (frames - nfft) / hop + 1.  The grid belongs to the stream, not to the calls: the accumulator carries
+ * the trailing frames a later segment still needs (at most nfft - 1) in a device buffer of its own.
+ * Per segment: x = the frame through the library's unpack (the expressions of iqgpu_convert_block_to_cf32) and the gain,
+ * X_s[k] = sum_i w[i] x[s hop + i] exp(-2 pi i ik / nfft) in float.
+ * Outputs, both in natural bin order (k = 0 is DC, k >= nfft / 2 the negative frequencies), either pointer may be NULL:
+ *   sum_power[k]  = sum_s |X_s[k]|^2: each term the float value re^2 + im^2, summed in double.  Nothing is normalised.
+ *   peak_power[k] = max_s |X_s[k]|^2 in float.
+ * window_sum and window_sum_sq (the sums of w and w^2 over the float table, in double) are what a caller needs for the dBFS of a tone,
+ * sum / (segments window_sum^2), or for power per Hz, sum / (segments rate window_sum_sq).
+ * Windows: periodic (DFT-even) forms evaluated in double, rounded once to float, uploaded at create; iqgpu_psd_window returns the
+ * same table.  HANN 0.5 - 0.5 cos(2 pi i / N); HAMMING 0.54 - 0.46 cos(2 pi i / N); BLACKMAN_HARRIS, 4 terms: 0.35875, 0.48829,
+ * 0.14128, 0.01168.
+ * THE RESULT IS A FUNCTION OF THE PUSHED FRAMES AND THE OPTIONS ALONE, BIT FOR BIT: any split of the stream into push calls, host or
+ * device, of any lengths (one frame; lengths that are no multiples of hop) gives the same sum_power, peak_power and info -- the
+ * convention of the chain above carried over.  The summation order belongs to the stream: segments are grouped by stream index into
+ * pages of segments_per_page (iqgpu_psd_geometry) consecutive segments; a page is summed per bin in segment order, the total is
+ * the pages added in page order, the open page (the one the stream position lies in) is kept apart and continued by the next push,
+ * and read reports total + open.  Shards that each accumulate a range add their sum_power, take the max of their peak_power and add
+ * their segments on the host: that sum is NOT promised bit-equal to the single stream's, and segments that straddle a cut are simply
+ * not taken.
+ * Errors: IQGPU_EINVAL for a NULL argument (of iqgpu_psd_window: o or w; sum and sum_sq may be NULL), nfft / hop / window outside
+ * the lists, a gain that is not finite, cap < nfft; IQGPU_EFORMAT for an unknown format; IQGPU_ENODEV from create without a usable
+ * device; IQGPU_ENOMEM; IQGPU_EHIP.  A refused call leaves the accumulator as it was; frames == 0 succeeds and changes nothing; one
+ * thread per handle.  Non-finite input frames propagate by IEEE rules into the sum_power bins of their segments; what peak_power
+ * reports for those segments is unspecified; accumulators that never see such frames are unaffected.
+ * Streams: push_device is asynchronous on the stream it is given (NULL: the null stream) and the input must stay valid until that
+ * stream has passed the work, as for iqgpu_chain_process_device; a push on another stream than the previous push's first waits for
+ * that push's work.  push stages host memory through a device buffer of the handle, in bounded slices, on a stream of the handle,
+ * and returns with the work queued and the caller's memory free.  read and reset synchronise, and behind either the handle refers to
+ * no stream of the caller's (destroy waits for the stream of a push that nothing has waited for since).  d_raw needs frame alignment only.
+ * Behind iqgpu_chain_process_device(c, .., d_out, .., &n) the spectrum of the output is
+ * iqgpu_psd_push_device(p, d_out, n, iqgpu_chain_get_stream(c)). */
+enum { IQGPU_PSD_RECT = 0, IQGPU_PSD_HANN = 1, IQGPU_PSD_HAMMING = 2, IQGPU_PSD_BLACKMAN_HARRIS = 3 };
+typedef struct {
+    uint32_t nfft;                /* 1024, 2048 or 4096 (1024) */
+    uint32_t hop;                 /* frames between segment starts: nfft, nfft / 2 or nfft / 4 (nfft / 2) */
+    int      window;              /* IQGPU_PSD_* (HANN) */
+    float    gain;                /* applied at unpack, as iqgpu_chain_desc.gain (1) */
+} iqgpu_psd_opts;
+typedef struct {
+    uint64_t frames, segments;    /* pushed since the last reset; segments accumulated */
+    uint32_t nfft, hop;
+    double   window_sum, window_sum_sq;
+} iqgpu_psd_info;
+typedef struct iqgpu_psd iqgpu_psd;
+void  iqgpu_psd_opts_init(iqgpu_psd_opts *o);                      /* the defaults in parentheses above */
+/* no device: the window table of the options (cap: room in w, in values) and its two sums; the segments of a stream of `frames` */
+int   iqgpu_psd_window(const iqgpu_psd_opts *o, float *w, size_t cap, double *sum, double *sum_sq);
+int   iqgpu_psd_segments(const iqgpu_psd_opts *o, uint64_t frames, uint64_t *segments);
+/* diagnostics, for tests: the segments of a page -- what it takes to reach the page boundaries, nothing a caller has to know */
+void  iqgpu_psd_geometry(size_t *segments_per_page);
+int   iqgpu_psd_create(int device, int format, const iqgpu_psd_opts *o, iqgpu_psd **out);
+void  iqgpu_psd_destroy(iqgpu_psd *p);
+int   iqgpu_psd_reset(iqgpu_psd *p);
+int   iqgpu_psd_push(iqgpu_psd *p, const void *raw, size_t frames);                                  /* host memory */
+int   iqgpu_psd_push_device(iqgpu_psd *p, const void *d_raw, size_t frames, void *hip_stream);      /* device memory, asynchronous on hip_stream */
+int   iqgpu_psd_read(iqgpu_psd *p, double *sum_power, float *peak_power, iqgpu_psd_info *info);     /* [nfft] each; synchronises */
+
 /* ---- WAV capture metadata -> frequency shift (host only): the step in front of the path for real captures ----
  * SdrMetadata and its parsers (src/input_wav.c:54-100, 146-438), the shift rule of wav_initialize (592-629). */
 enum { IQGPU_SDR_UNKNOWN = 0, IQGPU_SDR_CONSOLE = 1, IQGPU_SDR_SHARP = 2, IQGPU_SDR_UNO = 3, IQGPU_SDR_CONNECT = 4 };

@@ -110,6 +110,20 @@ class IqCalibReport(C.Structure):
                 ("level", IqCalibLevel * 16)]
 
 
+PSD_WINDOW = dict(rect=0, hann=1, hamming=2, blackman_harris=3)
+
+
+class PsdOpts(C.Structure):
+    """iqgpu_psd_opts: the options of a power-spectrum accumulator (iqgpu_psd_opts_init sets the defaults)"""
+    _fields_ = [("nfft", C.c_uint32), ("hop", C.c_uint32), ("window", C.c_int), ("gain", C.c_float)]
+
+
+class PsdInfo(C.Structure):
+    """iqgpu_psd_info: what iqgpu_psd_read reports beside the two arrays"""
+    _fields_ = [("frames", C.c_uint64), ("segments", C.c_uint64), ("nfft", C.c_uint32), ("hop", C.c_uint32),
+                ("window_sum", C.c_double), ("window_sum_sq", C.c_double)]
+
+
 class WavInfo(C.Structure):
     _fields_ = [("source_software", C.c_int),
                 ("software_name", C.c_char * 64), ("software_version", C.c_char * 64), ("radio_model", C.c_char * 128),
@@ -213,6 +227,16 @@ SYMBOLS = [
     ("iqgpu_iq_optimizer_calibrate", C.c_int, [_vp, _vp, _sz, _sz, C.POINTER(IqCalibOpts), C.POINTER(IqCalibReport)]),
     *_with_device("iqgpu_chain_calibrate_iq", C.c_int, [_vp, _vp, _sz, C.POINTER(IqCalibOpts), C.POINTER(IqCalibReport)]),
     *_with_device("iqgpu_chain_calibrate_iq_blocks", C.c_int, [_vp, _vp, _sz, C.c_uint32, _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_psd_opts_init", None, [C.POINTER(PsdOpts)]),
+    ("iqgpu_psd_window", C.c_int, [C.POINTER(PsdOpts), _vp, _sz, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("iqgpu_psd_segments", C.c_int, [C.POINTER(PsdOpts), C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("iqgpu_psd_geometry", None, [C.POINTER(_sz)]),
+    ("iqgpu_psd_create", C.c_int, [C.c_int, C.c_int, C.POINTER(PsdOpts), C.POINTER(_vp)]),
+    ("iqgpu_psd_destroy", None, [_vp]),
+    ("iqgpu_psd_reset", C.c_int, [_vp]),
+    ("iqgpu_psd_push", C.c_int, [_vp, _vp, _sz]),
+    ("iqgpu_psd_push_device", C.c_int, [_vp, _vp, _sz, _vp]),
+    ("iqgpu_psd_read", C.c_int, [_vp, _vp, _vp, C.POINTER(PsdInfo)]),
     ("iqgpu_wav_info_init", None, [C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_auxi", C.c_int, [_vp, _sz, C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_filename", C.c_int, [C.c_char_p, C.POINTER(WavInfo)]),

@@ -69,6 +69,11 @@
  * of its own (iq_tool_amd/synth.py hash_stream restates it): configs[4] at its real size -- 8 x 2.5 G frames -- without 80 GB of
  * files, every range of every shard reproducible by the checker.  With --seamless the job is ONE stream of seed SEED indexed by the
  * global frame number.
+ *
+ * --psd PREFIX (plain single-stream runs only: no --shards, no --seamless* mode, no --iq-calibrate): one iqgpu_psd accumulator on the
+ * input bytes and one on the output bytes, at the library's defaults (Hann, 1024 bins, hop 512), fed on the chain's stream behind every
+ * call; behind the run PREFIX.in.f64 and PREFIX.out.f64 hold sum_power (1024 little-endian doubles, bin 0 = DC) and PREFIX.json both
+ * info records and the two rates.
  */
 #define _GNU_SOURCE
 #define _FILE_OFFSET_BITS 64
@@ -147,6 +152,7 @@ typedef struct {
     int dry;                          /* --dry-placement: plan, bind, size the buffers, report -- no GPU call */
     int quiet;
     int iq_calibrate, have_iq_factors;   /* --iq-calibrate: the I/Q factors come from the head of the input (calibrate_head); --iq-factors was given */
+    const char *psd_prefix;           /* --psd PREFIX: the power spectra of the input and of the output, written behind the run (write_psd) */
 } Options;
 
 typedef struct {
@@ -192,6 +198,8 @@ typedef struct {
     int in_fd, out_fd;
     void *pre; size_t np;             /* the preroll in front of first_frame (load_preroll) */
     size_t agc_cap;                   /* rows sh->rows has room for (alloc_agc_table) */
+    iqgpu_psd *psd_in, *psd_out;      /* --psd: one accumulator on the input bytes, one on the output bytes (the library's defaults) */
+    iqgpu_psd_opts psd_opts;          /* ... the options both were created with */
 } Ctx;
 
 /* the modes with passes: all shard threads meet behind a measure pass and again behind the walk, which shard 0's thread does in between */
@@ -491,6 +499,11 @@ static int ctx_open(Ctx *x)
         CK(iqgpu_device_malloc(dev, x->out_cap, &x->d_out[b]));
         CK(iqgpu_event_create(&x->e_in[b])); CK(iqgpu_event_create(&x->e_k[b])); CK(iqgpu_event_create(&x->e_out[b]));
     }
+    if (o->psd_prefix) {
+        iqgpu_psd_opts_init(&x->psd_opts);
+        CK(iqgpu_psd_create(dev, x->d.in_format, &x->psd_opts, &x->psd_in));
+        CK(iqgpu_psd_create(dev, x->d.out_format, &x->psd_opts, &x->psd_out));
+    }
     if (o->synthetic_frames <= 0) {
         x->in_fd = open(o->in_path, O_RDONLY);
         if (x->in_fd < 0) FAIL("open %s: %s", o->in_path, strerror(errno));
@@ -510,6 +523,7 @@ static void ctx_close(Ctx *x)
     const int dev = x->d.device_ordinal;
     free(x->pre);
     if (x->chain) iqgpu_chain_synchronize(x->chain);
+    iqgpu_psd_destroy(x->psd_in); iqgpu_psd_destroy(x->psd_out);     /* (in front of the stream they last worked on) */
     for (int b = 0; b < NBUF; b++) {
         if (x->e_in[b]) iqgpu_event_destroy(x->e_in[b]);
         if (x->e_k[b]) iqgpu_event_destroy(x->e_k[b]);
@@ -651,6 +665,9 @@ static int stream_range(Ctx *x)
             CK(iqgpu_event_record(x->e_in[b], x->s_in));
             CK(iqgpu_stream_wait_event(x->s_k, x->e_in[b]));
             CK(iqgpu_chain_process_device(x->chain, x->d_in[b], n, x->d_out[b], x->out_cap, &out_frames[b]));
+            /* --psd: behind the chain on its stream, in front of e_k: both buffers stay as they are until the accumulators have read them */
+            if (x->psd_in) CK(iqgpu_psd_push_device(x->psd_in, x->d_in[b], n, x->s_k));
+            if (x->psd_out) CK(iqgpu_psd_push_device(x->psd_out, x->d_out[b], out_frames[b], x->s_k));
             CK(iqgpu_event_record(x->e_k[b], x->s_k));
             CK(iqgpu_stream_wait_event(x->s_out, x->e_k[b]));
             if (out_frames[b]) CK(iqgpu_memcpy_d2h_async(x->h_out[b], x->d_out[b], out_frames[b] * x->obps, x->s_out));
@@ -671,6 +688,54 @@ static int stream_range(Ctx *x)
     sh->frames_out = written;
     sh->stream_seconds = now_s() - t_loop;
     if (written != sh->planned_out) FAIL("shard %d produced %lld frames, its place in the output was planned for %lld", sh->shard, written, sh->planned_out);
+    return 0;
+}
+
+/* --psd PREFIX: PREFIX.in.f64 and PREFIX.out.f64 -- sum_power of the input and of the output, nfft little-endian doubles each, natural
+ * bin order -- and PREFIX.json with both info records and the two rates */
+/* s as the inside of a JSON string: quotes, backslashes and control characters escaped */
+static void json_put(FILE *f, const char *s)
+{
+    for (; *s; s++) {
+        const unsigned char c = (unsigned char)*s;
+        if (c == '"' || c == '\\') fprintf(f, "\\%c", c);
+        else if (c < 0x20) fprintf(f, "\\u%04x", c);
+        else fputc(c, f);
+    }
+}
+
+static int write_psd(Ctx *x)
+{
+    static const char *const window_name[4] = {"rect", "hann", "hamming", "blackman_harris"};   /* IQGPU_PSD_* */
+    Shard *sh = x->sh;
+    const Options *o = x->o;
+    iqgpu_psd *acc[2] = {x->psd_in, x->psd_out};
+    static const char *const side[2] = {"in", "out"};
+    const double rate[2] = {x->d.input_rate_hz, x->d.target_rate_hz};
+    iqgpu_psd_info info[2];
+    char path[4096];
+    for (int k = 0; k < 2; k++) {
+        double sum[4096];
+        CK(iqgpu_psd_read(acc[k], sum, NULL, &info[k]));
+        snprintf(path, sizeof(path), "%s.%s.f64", o->psd_prefix, side[k]);
+        FILE *f = fopen(path, "wb");
+        if (!f) FAIL("writing %.160s: %s", path, strerror(errno));
+        const int short_write = fwrite(sum, sizeof(double), info[k].nfft, f) != info[k].nfft;
+        if ((fclose(f) != 0) | short_write) FAIL("writing %.160s: %s", path, strerror(errno));
+    }
+    snprintf(path, sizeof(path), "%s.json", o->psd_prefix);
+    FILE *f = fopen(path, "w");
+    if (!f) FAIL("writing %.160s: %s", path, strerror(errno));
+    fprintf(f, "{");
+    for (int k = 0; k < 2; k++) {
+        fprintf(f, "%s\"%s\": {\"rate_hz\": %.17g, \"frames\": %llu, \"segments\": %llu, \"nfft\": %u, \"hop\": %u, \"window\": \"%s\", \"window_sum\": %.17g, "
+                "\"window_sum_sq\": %.17g, \"file\": \"", k ? ", " : "", side[k], rate[k], (unsigned long long)info[k].frames,
+                (unsigned long long)info[k].segments, info[k].nfft, info[k].hop, window_name[x->psd_opts.window & 3], info[k].window_sum, info[k].window_sum_sq);
+        json_put(f, o->psd_prefix);
+        fprintf(f, ".%s.f64\"}", side[k]);
+    }
+    fprintf(f, "}\n");
+    if (fclose(f) != 0) FAIL("writing %.160s: %s", path, strerror(errno));
     return 0;
 }
 
@@ -707,7 +772,7 @@ static void *run_shard(void *arg)
 
     if (o->dry) dry_shard(&x);
     else {
-        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && MODES[o->mode].certify) save_checkpoint(&x);
+        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
         /* (a shard that fails early still keeps the rendezvous of the passes: the others wait there) */
         while (sh->barriers < MODES[o->mode].barriers) rendezvous(&x, NULL, NULL);
     }
@@ -730,6 +795,7 @@ static void usage(void)
             "          [--seamless-rms (--seamless for chains with the dx / local output AGC: seek from a bounded window, seams certified, a range behind a seam that is not is redone)]\n"
             "          [--seamless-dc-rms (the exact --seamless for --dc-block chains with the dx / local AGC: DC measure, walk, then --seamless-rms's seek, certificate and redo)]\n"
             "          [--seamless-dc-agc (the exact --seamless for --dc-block chains with the digital AGC: DC measure, walk, shadow AGC measure, walk, then the ordinary pass)]\n"
+            "          [--psd PREFIX (plain single-stream runs: the power spectra of the input and of the output -- Hann, 1024 bins -- as PREFIX.in.f64, PREFIX.out.f64, PREFIX.json)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
             "          [--dry-placement (plan the shards, bind every shard thread, size its buffers, report as JSON: no GPU call)]\n");
 }
@@ -756,6 +822,7 @@ static int parse_args(int argc, char **argv, Options *o)
         else if (!strcmp(a, "--dc-block")) o->desc.dc_block_enable = 1;
         else if (!strcmp(a, "--iq-factors")) { o->desc.iq_correct_enable = 1; o->have_iq_factors = 1; sscanf(NEXT, "%f:%f", &o->desc.iq_mag, &o->desc.iq_phase); }
         else if (!strcmp(a, "--iq-calibrate")) o->iq_calibrate = 1;
+        else if (!strcmp(a, "--psd")) o->psd_prefix = NEXT;
         else if (!strcmp(a, "--no-resample")) o->desc.no_resample = 1;
         else if (!strcmp(a, "--lowpass") || !strcmp(a, "--highpass")) {
             if (o->desc.n_filters >= 5) REFUSE(2, "at most 5 filters\n");
@@ -820,6 +887,10 @@ static int validate(const Options *o)
     const size_t agc_chunk = agc_chunk_of(&o->desc);
     if (o->clash != M_INDEPENDENT) REFUSE(2, "%s excludes %s\n", m->flag, MODES[o->clash].flag);
     if (o->iq_calibrate && o->have_iq_factors) REFUSE(2, "--iq-calibrate excludes --iq-factors\n");
+    /* (the spectrum of ONE stream as one accumulator sees it: sharded spectra are a sum on the host that nothing here defines yet) */
+    if (o->psd_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
+        REFUSE(2, "usage: --psd is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
+    if (o->psd_prefix && strlen(o->psd_prefix) > 3000) REFUSE(2, "usage: --psd: the prefix is too long\n");
     for (const unsigned char *c = m->checks; *c != C_END; c++) switch (*c) {
     case C_SHARDS: if (!o->have_shards) REFUSE(2, "%s needs --shards N\n", m->flag); break;
     case C_HAS_AGC: if (o->desc.agc_enable) REFUSE(1, "%s: a chain with the output AGC is not covered (its measure route may cut a call into other segments "
