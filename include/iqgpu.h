@@ -838,6 +838,75 @@ int   iqgpu_psd_push(iqgpu_psd *p, const void *raw, size_t frames);             
 int   iqgpu_psd_push_device(iqgpu_psd *p, const void *d_raw, size_t frames, void *hip_stream);      /* device memory, asynchronous on hip_stream */
 int   iqgpu_psd_read(iqgpu_psd *p, double *sum_power, float *peak_power, iqgpu_psd_info *info);     /* [nfft] each; synchronises */
 
+/* ---- spectrogram: the power spectrum per time row, emitted as the stream goes by (additive, still ABI v9) ----
+ * No counterpart in the reference.  iqgpu_psd answers where a signal sits; the rows of this accumulator answer when: is the carrier
+ * there from the start, does it drift, is the interferer a burst.  One stream of frames in one sample format, independent of any
+ * chain, with the calling convention of iqgpu_chain_process[_device]: stream-continuous, output the caller owns, a capacity check,
+ * a row count back.
+ * The options are iqgpu_psd_opts' (nfft, hop, window, gain: same lists, same meaning) and row_segments = R, 1 .. 2^20.
+ * Segments: the power spectrum's grid.  Segment s is frames [s hop, s hop + nfft) of everything pushed since the last reset, and
+ * X_s[k], p_s[k] = re^2 + im^2 in float are computed exactly as there: same unpack, gain, window table and transform.
+ * Rows: row r is segments [r R, (r + 1) R): it starts at frame r R hop and spans (R - 1) hop + nfft frames;
+ * rows = segments / R, rounded down.  Per finished row, [nfft] floats each, natural bin order (k = 0 is DC), nothing normalised:
+ *   row_sum[r][k]  = sum over the row's segments of p_s[k], summed in double in the order below, rounded ONCE to float (nearest even)
+ *   row_peak[r][k] = max over the row's segments of p_s[k], in float.
+ * Summation order: it belongs to the stream, not to the calls.  A row is cut into cells of segments_per_page (iqgpu_psd_geometry: 32)
+ * consecutive segments counted from the row's first segment, the last cell may be short; a cell is summed per bin in segment order
+ * from 0.0 in double; the row is ((0.0 + cell 0) + cell 1) + ... in double.
+ * EQUALITY WITH THE POWER SPECTRUM: row r equals, bit for bit, a fresh iqgpu_psd of the same nfft / hop / window / gain that was
+ * pushed exactly the row's frames [r R hop, r R hop + (R - 1) hop + nfft): (float)sum_power[k] == row_sum[r][k] and
+ * peak_power[k] == row_peak[r][k].  (That accumulator's pages are this row's cells.)
+ * The open row: the segments behind the last finished row stay on the device.  iqgpu_sgram_read_open returns them as sum_power
+ * (double, not rounded) and peak_power with info.open_segments = segments % R -- equal, bit for bit, to iqgpu_psd_read of a fresh
+ * iqgpu_psd pushed the frames of those segments, all zero when open_segments == 0 -- so a caller can flush the ragged end of a stream.
+ * It observes and does not disturb.
+ * ROWS AND OPEN ROW ARE A FUNCTION OF THE PUSHED FRAMES AND THE OPTIONS ALONE, BIT FOR BIT: any split of the stream into push calls,
+ * host or device, of any lengths (one frame; no multiple of hop; ending inside a cell or on a row boundary) gives the same rows in
+ * the same order -- the rows each call returned, concatenated -- and the same open row.
+ * push / push_device: row_sum and row_peak receive the rows the call finishes, [rows][nfft] floats densely packed, in host / device
+ * memory; either may be NULL (that plane is not produced).  *rows (rows may be NULL) is pure arithmetic and is set when the call
+ * returns, for the asynchronous push_device too; iqgpu_sgram_max_rows(p, frames) is what the NEXT push of `frames` would return,
+ * exact, from the handle's position.  cap_rows (the room in each plane given, in rows) smaller than that: IQGPU_ECAPACITY before
+ * anything is queued, the handle as it was, *rows = 0.
+ * Errors: IQGPU_EINVAL for a NULL argument (p; raw with frames > 0; o; out; iqgpu_sgram_rows' rows), nfft / hop / window outside the
+ * lists, a gain that is not finite, row_segments outside 1 .. 2^20; IQGPU_EFORMAT for an unknown format; IQGPU_ENODEV from create
+ * without a usable device; IQGPU_ECAPACITY; IQGPU_ENOMEM; IQGPU_EHIP.  A refused call leaves the accumulator as it was; frames == 0
+ * succeeds with *rows = 0 and changes nothing; a push that failed half way poisons the handle (IQGPU_EHIP from push / read_open)
+ * until reset; one thread per handle.  Non-finite input frames propagate as documented for the power spectrum: by IEEE rules into
+ * the row_sum bins of the rows of their segments, row_peak of those rows unspecified, other rows unaffected.
+ * Streams: as for iqgpu_psd_push_device.  push_device is asynchronous on the stream it is given (NULL: the null stream); input and
+ * output planes must stay valid until that stream has passed the work; a push on another stream than the previous push's first waits
+ * for that push's work.  push stages host memory through device buffers of the handle, in bounded slices, on a stream of the handle,
+ * and returns with the caller's input free and the rows in host memory.  read_open and reset synchronise, and behind either the
+ * handle refers to no stream of the caller's; destroy waits for the stream of a push that nothing has waited for since.
+ * Behind iqgpu_chain_process_device(c, .., d_out, .., &n) the rows of the output are
+ * iqgpu_sgram_push_device(p, d_out, n, d_rows, NULL, cap, &rows, iqgpu_chain_get_stream(c)). */
+typedef struct {
+    uint32_t nfft;                /* 1024, 2048 or 4096 (1024) */
+    uint32_t hop;                 /* frames between segment starts: nfft, nfft / 2 or nfft / 4 (nfft / 2) */
+    int      window;              /* IQGPU_PSD_* (HANN) */
+    float    gain;                /* applied at unpack, as iqgpu_chain_desc.gain (1) */
+    uint32_t row_segments;        /* R: segments summed into one row, 1 .. 2^20 (32) */
+} iqgpu_sgram_opts;
+typedef struct {
+    uint64_t frames, segments, rows;      /* pushed since the last reset; whole segments of them; rows finished = segments / R */
+    uint32_t open_segments;               /* segments of the open row = segments % R */
+    uint32_t nfft, hop, row_segments;
+    double   window_sum, window_sum_sq;   /* as in iqgpu_psd_info */
+} iqgpu_sgram_info;
+typedef struct iqgpu_sgram iqgpu_sgram;
+void   iqgpu_sgram_opts_init(iqgpu_sgram_opts *o);                  /* the defaults in parentheses above */
+/* no device: the rows a stream of `frames` frames finishes */
+int    iqgpu_sgram_rows(const iqgpu_sgram_opts *o, uint64_t frames, uint64_t *rows);
+int    iqgpu_sgram_create(int device, int format, const iqgpu_sgram_opts *o, iqgpu_sgram **out);
+void   iqgpu_sgram_destroy(iqgpu_sgram *p);
+int    iqgpu_sgram_reset(iqgpu_sgram *p);
+size_t iqgpu_sgram_max_rows(const iqgpu_sgram *p, size_t frames);   /* rows the NEXT push of `frames` finishes: exact; 0 for a NULL handle */
+int    iqgpu_sgram_push(iqgpu_sgram *p, const void *raw, size_t frames, float *row_sum, float *row_peak, size_t cap_rows, size_t *rows);   /* host memory */
+int    iqgpu_sgram_push_device(iqgpu_sgram *p, const void *d_raw, size_t frames, float *d_row_sum, float *d_row_peak, size_t cap_rows,
+                               size_t *rows, void *hip_stream);     /* device memory, asynchronous on hip_stream */
+int    iqgpu_sgram_read_open(iqgpu_sgram *p, double *sum_power, float *peak_power, iqgpu_sgram_info *info);   /* [nfft] each, either may be NULL; synchronises */
+
 /* ---- WAV capture metadata -> frequency shift (host only): the step in front of the path for real captures ----
  * SdrMetadata and its parsers (src/input_wav.c:54-100, 146-438), the shift rule of wav_initialize (592-629). */
 enum { IQGPU_SDR_UNKNOWN = 0, IQGPU_SDR_CONSOLE = 1, IQGPU_SDR_SHARP = 2, IQGPU_SDR_UNO = 3, IQGPU_SDR_CONNECT = 4 };

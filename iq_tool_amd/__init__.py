@@ -5,5 +5,6 @@ from ._lib import FMT, IqgpuError, LIB_PATH, load          # noqa: F401
 from .chain import Chain, DeviceBuffer, PinnedBuffer, bind_thread_to_device, design_out_frames, design_out_frames_range, design_preroll_frames, design_preroll_frames_dcrms, design_preroll_frames_rms, design_state_size, make_desc, state_inspect   # noqa: F401
 from .iq_optimizer import IqOptimizer                            # noqa: F401
 from .psd import Psd                                             # noqa: F401
+from .sgram import Sgram                                         # noqa: F401
 
-__all__ = ["Chain", "DeviceBuffer", "PinnedBuffer", "IqOptimizer", "Psd", "make_desc", "FMT", "IqgpuError", "load", "LIB_PATH"]
+__all__ = ["Chain", "DeviceBuffer", "PinnedBuffer", "IqOptimizer", "Psd", "Sgram", "make_desc", "FMT", "IqgpuError", "load", "LIB_PATH"]

@@ -124,6 +124,18 @@ class PsdInfo(C.Structure):
                 ("window_sum", C.c_double), ("window_sum_sq", C.c_double)]
 
 
+class SgramOpts(C.Structure):
+    """iqgpu_sgram_opts: the options of a row accumulator (iqgpu_sgram_opts_init sets the defaults)"""
+    _fields_ = [("nfft", C.c_uint32), ("hop", C.c_uint32), ("window", C.c_int), ("gain", C.c_float), ("row_segments", C.c_uint32)]
+
+
+class SgramInfo(C.Structure):
+    """iqgpu_sgram_info: what iqgpu_sgram_read_open reports beside the two arrays"""
+    _fields_ = [("frames", C.c_uint64), ("segments", C.c_uint64), ("rows", C.c_uint64), ("open_segments", C.c_uint32),
+                ("nfft", C.c_uint32), ("hop", C.c_uint32), ("row_segments", C.c_uint32),
+                ("window_sum", C.c_double), ("window_sum_sq", C.c_double)]
+
+
 class WavInfo(C.Structure):
     _fields_ = [("source_software", C.c_int),
                 ("software_name", C.c_char * 64), ("software_version", C.c_char * 64), ("radio_model", C.c_char * 128),
@@ -237,6 +249,15 @@ SYMBOLS = [
     ("iqgpu_psd_push", C.c_int, [_vp, _vp, _sz]),
     ("iqgpu_psd_push_device", C.c_int, [_vp, _vp, _sz, _vp]),
     ("iqgpu_psd_read", C.c_int, [_vp, _vp, _vp, C.POINTER(PsdInfo)]),
+    ("iqgpu_sgram_opts_init", None, [C.POINTER(SgramOpts)]),
+    ("iqgpu_sgram_rows", C.c_int, [C.POINTER(SgramOpts), C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("iqgpu_sgram_create", C.c_int, [C.c_int, C.c_int, C.POINTER(SgramOpts), C.POINTER(_vp)]),
+    ("iqgpu_sgram_destroy", None, [_vp]),
+    ("iqgpu_sgram_reset", C.c_int, [_vp]),
+    ("iqgpu_sgram_max_rows", _sz, [_vp, _sz]),
+    ("iqgpu_sgram_push", C.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_sgram_push_device", C.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    ("iqgpu_sgram_read_open", C.c_int, [_vp, _vp, _vp, C.POINTER(SgramInfo)]),
     ("iqgpu_wav_info_init", None, [C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_auxi", C.c_int, [_vp, _sz, C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_filename", C.c_int, [C.c_char_p, C.POINTER(WavInfo)]),

@@ -74,6 +74,11 @@
  * input bytes and one on the output bytes, at the library's defaults (Hann, 1024 bins, hop 512), fed on the chain's stream behind every
  * call; behind the run PREFIX.in.f64 and PREFIX.out.f64 hold sum_power (1024 little-endian doubles, bin 0 = DC) and PREFIX.json both
  * info records and the two rates.
+ *
+ * --sgram PREFIX [--sgram-row-segments R] (the same runs as --psd, and it may stand beside --psd): one iqgpu_sgram accumulator on the
+ * input bytes and one on the output bytes, at the library's defaults with R segments a row (32), fed on the chain's stream behind every
+ * call.  PREFIX.in.f32 and PREFIX.out.f32 receive row_sum of every row as it finishes (1024 little-endian floats a row, bin 0 = DC);
+ * the partial last row is not written.  PREFIX.json holds both info records -- rows, segments, open_segments among them -- and the rates.
  */
 #define _GNU_SOURCE
 #define _FILE_OFFSET_BITS 64
@@ -153,6 +158,8 @@ typedef struct {
     int quiet;
     int iq_calibrate, have_iq_factors;   /* --iq-calibrate: the I/Q factors come from the head of the input (calibrate_head); --iq-factors was given */
     const char *psd_prefix;           /* --psd PREFIX: the power spectra of the input and of the output, written behind the run (write_psd) */
+    const char *sgram_prefix;         /* --sgram PREFIX: the rows of the input and of the output, appended as they finish (write_sgram_rows) */
+    unsigned sgram_row_segments;      /* --sgram-row-segments R (0: the library's default) */
 } Options;
 
 typedef struct {
@@ -200,6 +207,10 @@ typedef struct {
     size_t agc_cap;                   /* rows sh->rows has room for (alloc_agc_table) */
     iqgpu_psd *psd_in, *psd_out;      /* --psd: one accumulator on the input bytes, one on the output bytes (the library's defaults) */
     iqgpu_psd_opts psd_opts;          /* ... the options both were created with */
+    /* --sgram, side 0 = input, 1 = output: the accumulator, its file, per pipeline buffer the device and pinned host planes of the rows a
+     * call finishes (sg_cap rows each) and how many the call in flight there did finish */
+    iqgpu_sgram *sg[2]; iqgpu_sgram_opts sg_opts; FILE *sg_f[2];
+    void *sg_d[2][NBUF], *sg_h[2][NBUF]; size_t sg_cap[2], sg_rows[2][NBUF];
 } Ctx;
 
 /* the modes with passes: all shard threads meet behind a measure pass and again behind the walk, which shard 0's thread does in between */
@@ -504,6 +515,26 @@ static int ctx_open(Ctx *x)
         CK(iqgpu_psd_create(dev, x->d.in_format, &x->psd_opts, &x->psd_in));
         CK(iqgpu_psd_create(dev, x->d.out_format, &x->psd_opts, &x->psd_out));
     }
+    if (o->sgram_prefix) {
+        static const char *const side[2] = {"in", "out"};
+        const int fmt[2] = {x->d.in_format, x->d.out_format};
+        const size_t most[2] = {x->chunk, x->out_cap / x->obps};      /* frames of one call */
+        char path[4096];
+        iqgpu_sgram_opts_init(&x->sg_opts);
+        if (o->sgram_row_segments) x->sg_opts.row_segments = o->sgram_row_segments;
+        for (int k = 0; k < 2; k++) {
+            CK(iqgpu_sgram_create(dev, fmt[k], &x->sg_opts, &x->sg[k]));
+            /* rows one call can finish: the segments that start in it and the one its first frames complete, behind an open row */
+            x->sg_cap[k] = (most[k] / x->sg_opts.hop + 1) / x->sg_opts.row_segments + 1;
+            for (int b = 0; b < NBUF; b++) {
+                CK(iqgpu_device_malloc(dev, x->sg_cap[k] * x->sg_opts.nfft * sizeof(float), &x->sg_d[k][b]));
+                CK(iqgpu_host_malloc_pinned(x->sg_cap[k] * x->sg_opts.nfft * sizeof(float), &x->sg_h[k][b]));
+            }
+            snprintf(path, sizeof(path), "%s.%s.f32", o->sgram_prefix, side[k]);
+            x->sg_f[k] = fopen(path, "wb");
+            if (!x->sg_f[k]) FAIL("writing %.160s: %s", path, strerror(errno));
+        }
+    }
     if (o->synthetic_frames <= 0) {
         x->in_fd = open(o->in_path, O_RDONLY);
         if (x->in_fd < 0) FAIL("open %s: %s", o->in_path, strerror(errno));
@@ -524,6 +555,14 @@ static void ctx_close(Ctx *x)
     free(x->pre);
     if (x->chain) iqgpu_chain_synchronize(x->chain);
     iqgpu_psd_destroy(x->psd_in); iqgpu_psd_destroy(x->psd_out);     /* (in front of the stream they last worked on) */
+    for (int k = 0; k < 2; k++) {
+        iqgpu_sgram_destroy(x->sg[k]);
+        if (x->sg_f[k]) fclose(x->sg_f[k]);
+        for (int b = 0; b < NBUF; b++) {
+            if (x->sg_d[k][b]) iqgpu_device_free(dev, x->sg_d[k][b]);
+            if (x->sg_h[k][b]) iqgpu_host_free_pinned(x->sg_h[k][b]);
+        }
+    }
     for (int b = 0; b < NBUF; b++) {
         if (x->e_in[b]) iqgpu_event_destroy(x->e_in[b]);
         if (x->e_k[b]) iqgpu_event_destroy(x->e_k[b]);
@@ -668,6 +707,13 @@ static int stream_range(Ctx *x)
             /* --psd: behind the chain on its stream, in front of e_k: both buffers stay as they are until the accumulators have read them */
             if (x->psd_in) CK(iqgpu_psd_push_device(x->psd_in, x->d_in[b], n, x->s_k));
             if (x->psd_out) CK(iqgpu_psd_push_device(x->psd_out, x->d_out[b], out_frames[b], x->s_k));
+            /* --sgram: the same place; the rows a call finishes follow on the same stream into pinned memory, so e_out covers them too */
+            for (int k = 0; k < 2 && x->sg[k]; k++) {
+                const size_t row_bytes = x->sg_opts.nfft * sizeof(float);
+                CK(iqgpu_sgram_push_device(x->sg[k], k ? x->d_out[b] : x->d_in[b], k ? out_frames[b] : n, (float *)x->sg_d[k][b], NULL, x->sg_cap[k],
+                                           &x->sg_rows[k][b], x->s_k));
+                if (x->sg_rows[k][b]) CK(iqgpu_memcpy_d2h_async(x->sg_h[k][b], x->sg_d[k][b], x->sg_rows[k][b] * row_bytes, x->s_k));
+            }
             CK(iqgpu_event_record(x->e_k[b], x->s_k));
             CK(iqgpu_stream_wait_event(x->s_out, x->e_k[b]));
             if (out_frames[b]) CK(iqgpu_memcpy_d2h_async(x->h_out[b], x->d_out[b], out_frames[b] * x->obps, x->s_out));
@@ -683,6 +729,8 @@ static int stream_range(Ctx *x)
                 if (pwrite(x->out_fd, x->h_out[b], nb, sh->out_offset_bytes + written * (long long)x->obps) != (ssize_t)nb) FAIL("pwrite: %s", strerror(errno));
             }
             written += (long long)out_frames[b];
+            for (int k = 0; k < 2 && x->sg[k]; k++)
+                if (fwrite(x->sg_h[k][b], x->sg_opts.nfft * sizeof(float), x->sg_rows[k][b], x->sg_f[k]) != x->sg_rows[k][b]) FAIL("writing the rows of --sgram: %s", strerror(errno));
         }
     }
     sh->frames_out = written;
@@ -739,6 +787,38 @@ static int write_psd(Ctx *x)
     return 0;
 }
 
+/* --sgram PREFIX: the row files are complete (stream_range appended every finished row); PREFIX.json with both info records and the two
+ * rates.  The partial last row stays unwritten: open_segments says how many segments it held */
+static int write_sgram(Ctx *x)
+{
+    static const char *const window_name[4] = {"rect", "hann", "hamming", "blackman_harris"};   /* IQGPU_PSD_* */
+    static const char *const side[2] = {"in", "out"};
+    Shard *sh = x->sh;
+    const Options *o = x->o;
+    const double rate[2] = {x->d.input_rate_hz, x->d.target_rate_hz};
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.json", o->sgram_prefix);
+    FILE *f = fopen(path, "w");
+    if (!f) FAIL("writing %.160s: %s", path, strerror(errno));
+    fprintf(f, "{");
+    for (int k = 0; k < 2; k++) {
+        iqgpu_sgram_info info;
+        FILE *rows = x->sg_f[k];
+        x->sg_f[k] = NULL;
+        if (fclose(rows) != 0) { fclose(f); FAIL("writing %.160s.%s.f32: %s", o->sgram_prefix, side[k], strerror(errno)); }
+        if (iqgpu_sgram_read_open(x->sg[k], NULL, NULL, &info) != IQGPU_OK) { fclose(f); FAIL("%s", iqgpu_last_error()); }
+        fprintf(f, "%s\"%s\": {\"rate_hz\": %.17g, \"frames\": %llu, \"segments\": %llu, \"rows\": %llu, \"open_segments\": %u, \"nfft\": %u, \"hop\": %u, "
+                "\"row_segments\": %u, \"window\": \"%s\", \"window_sum\": %.17g, \"window_sum_sq\": %.17g, \"file\": \"", k ? ", " : "", side[k], rate[k],
+                (unsigned long long)info.frames, (unsigned long long)info.segments, (unsigned long long)info.rows, info.open_segments, info.nfft, info.hop,
+                info.row_segments, window_name[x->sg_opts.window & 3], info.window_sum, info.window_sum_sq);
+        json_put(f, o->sgram_prefix);
+        fprintf(f, ".%s.f32\"}", side[k]);
+    }
+    fprintf(f, "}\n");
+    if (fclose(f) != 0) FAIL("writing %.160s: %s", path, strerror(errno));
+    return 0;
+}
+
 /* --seamless-rms, --seamless-dc-rms: what the seam behind this range is checked against, and what the range behind it restarts from if the check fails */
 static int save_checkpoint(Ctx *x)
 {
@@ -772,7 +852,7 @@ static void *run_shard(void *arg)
 
     if (o->dry) dry_shard(&x);
     else {
-        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
+        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && !(o->sgram_prefix && write_sgram(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
         /* (a shard that fails early still keeps the rendezvous of the passes: the others wait there) */
         while (sh->barriers < MODES[o->mode].barriers) rendezvous(&x, NULL, NULL);
     }
@@ -796,6 +876,7 @@ static void usage(void)
             "          [--seamless-dc-rms (the exact --seamless for --dc-block chains with the dx / local AGC: DC measure, walk, then --seamless-rms's seek, certificate and redo)]\n"
             "          [--seamless-dc-agc (the exact --seamless for --dc-block chains with the digital AGC: DC measure, walk, shadow AGC measure, walk, then the ordinary pass)]\n"
             "          [--psd PREFIX (plain single-stream runs: the power spectra of the input and of the output -- Hann, 1024 bins -- as PREFIX.in.f64, PREFIX.out.f64, PREFIX.json)]\n"
+            "          [--sgram PREFIX [--sgram-row-segments R] (the same runs: the spectrum per row of R segments (32) of the input and of the output, rows appended as they finish to PREFIX.in.f32, PREFIX.out.f32; PREFIX.json)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
             "          [--dry-placement (plan the shards, bind every shard thread, size its buffers, report as JSON: no GPU call)]\n");
 }
@@ -823,6 +904,8 @@ static int parse_args(int argc, char **argv, Options *o)
         else if (!strcmp(a, "--iq-factors")) { o->desc.iq_correct_enable = 1; o->have_iq_factors = 1; sscanf(NEXT, "%f:%f", &o->desc.iq_mag, &o->desc.iq_phase); }
         else if (!strcmp(a, "--iq-calibrate")) o->iq_calibrate = 1;
         else if (!strcmp(a, "--psd")) o->psd_prefix = NEXT;
+        else if (!strcmp(a, "--sgram")) o->sgram_prefix = NEXT;
+        else if (!strcmp(a, "--sgram-row-segments")) { const long long r = atoll(NEXT); o->sgram_row_segments = r >= 1 && r <= (1 << 20) ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--no-resample")) o->desc.no_resample = 1;
         else if (!strcmp(a, "--lowpass") || !strcmp(a, "--highpass")) {
             if (o->desc.n_filters >= 5) REFUSE(2, "at most 5 filters\n");
@@ -891,6 +974,10 @@ static int validate(const Options *o)
     if (o->psd_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
         REFUSE(2, "usage: --psd is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
     if (o->psd_prefix && strlen(o->psd_prefix) > 3000) REFUSE(2, "usage: --psd: the prefix is too long\n");
+    if (o->sgram_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
+        REFUSE(2, "usage: --sgram is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
+    if (o->sgram_prefix && strlen(o->sgram_prefix) > 3000) REFUSE(2, "usage: --sgram: the prefix is too long\n");
+    if (o->sgram_row_segments && (!o->sgram_prefix || o->sgram_row_segments == ~0u)) REFUSE(2, "usage: --sgram-row-segments R goes with --sgram PREFIX, R in 1 .. 1048576\n");
     for (const unsigned char *c = m->checks; *c != C_END; c++) switch (*c) {
     case C_SHARDS: if (!o->have_shards) REFUSE(2, "%s needs --shards N\n", m->flag); break;
     case C_HAS_AGC: if (o->desc.agc_enable) REFUSE(1, "%s: a chain with the output AGC is not covered (its measure route may cut a call into other segments "

@@ -50,6 +50,21 @@ uint64_t segments_of(const iqgpu_psd_opts &o, uint64_t frames) { return frames <
 
 } // namespace
 
+// what sgram.cpp shares (psd.hpp): the same checks, table and grid, so the two accumulators cannot drift apart
+namespace iqgpu {
+int psd_check_opts(const iqgpu_psd_opts *o, const char *who) { return check_opts(o, who); }
+void psd_fill_tables(const iqgpu_psd_opts &o, float *tab, double *sum, double *sum_sq)
+{
+    fill_window(o, tab, sum, sum_sq);
+    for (uint32_t k = 0; k < o.nfft; ++k) {                           // exp(-2 pi i k / nfft): double, rounded once
+        const double a = -2.0 * kPi * (double)k / (double)o.nfft;
+        tab[o.nfft + 2 * k] = (float)std::cos(a); tab[o.nfft + 2 * k + 1] = (float)std::sin(a);
+    }
+}
+uint64_t psd_segments_of(const iqgpu_psd_opts &o, uint64_t frames) { return segments_of(o, frames); }
+int psd_log2n(uint32_t nfft) { return log2n_of(nfft); }
+} // namespace iqgpu
+
 struct iqgpu_psd {
     int device = 0, format = 0, log2n = 0;
     size_t bps = 0;
@@ -197,11 +212,7 @@ extern "C" int iqgpu_psd_create(int device, int format, const iqgpu_psd_opts *o,
     try { tab.resize(3 * (size_t)o->nfft); } catch (const std::bad_alloc &) { delete p; p = nullptr; }
     if (!p) return fail(IQGPU_ENOMEM, "iqgpu_psd_create: out of host memory");
     p->device = device; p->format = format; p->log2n = log2n_of(o->nfft); p->bps = bytes_per_frame(format); p->o = *o;
-    fill_window(*o, tab.data(), &p->window_sum, &p->window_sum_sq);
-    for (uint32_t k = 0; k < o->nfft; ++k) {                          // exp(-2 pi i k / nfft): double, rounded once
-        const double a = -2.0 * kPi * (double)k / (double)o->nfft;
-        tab[o->nfft + 2 * k] = (float)std::cos(a); tab[o->nfft + 2 * k + 1] = (float)std::sin(a);
-    }
+    psd_fill_tables(*o, tab.data(), &p->window_sum, &p->window_sum_sq);
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->own, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&p->staged, hipEventDisableTiming);

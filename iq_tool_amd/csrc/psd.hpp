@@ -44,4 +44,12 @@ hipError_t launch_psd_fold(const PsdFoldArgs &a, hipStream_t s);
 struct PsdCarryArgs { const unsigned char *carry, *raw; int64_t split_bytes, first; int32_t bytes; unsigned char *dst; };
 hipError_t launch_psd_carry(const PsdCarryArgs &a, hipStream_t s);
 
+// host side, no device (psd.cpp), shared with the row accumulator (sgram.cpp): the option checks (`who` names the caller in the error
+// text), the device tables -- [nfft] window, then [nfft] twiddles exp(-2 pi i k / nfft) as (cos, sin) pairs: 3 nfft floats -- with the
+// window's two sums, the whole segments of `frames` frames, and log2 nfft (0: no size of the list)
+int psd_check_opts(const iqgpu_psd_opts *o, const char *who);
+void psd_fill_tables(const iqgpu_psd_opts &o, float *tab, double *sum, double *sum_sq);
+uint64_t psd_segments_of(const iqgpu_psd_opts &o, uint64_t frames);
+int psd_log2n(uint32_t nfft);
+
 } // namespace iqgpu
