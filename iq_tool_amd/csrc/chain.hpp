@@ -9,7 +9,7 @@
 //   pipeline.cpp   iqgpu_chain_submit / _measure_submit / _collect (pinned host buffers, three stages moved along by the host)
 //   iq_calib.cpp   I/Q calibration: iqgpu_iq_metric_batch, iqgpu_chain_calibrate_iq (the search itself: iq_optimizer.cpp, no HIP)
 //   psd.cpp        power spectrum of a stream: the iqgpu_psd accumulator (a handle of its own, independent of any chain; kernels psd.hip)
-//   sgram.cpp      the power spectrum per time row: the iqgpu_sgram accumulator (as psd.cpp, whose options, tables and carry it shares; kernels sgram.hip)
+//   sgram.cpp      the power spectrum per time row: the iqgpu_sgram accumulator (around psd.cpp's stream core PsdStream; kernels sgram.hip)
 //   state.cpp      checkpoint / resume: iqgpu_chain_tell, iqgpu_chain_save_state / _load_state, iqgpu_design_state_size (the blob's
 //                  header, checksum and iqgpu_state_inspect: state_blob.cpp, which includes nothing of HIP)
 #pragma once

@@ -69,32 +69,15 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void k_psd_pages(const PsdPagesA
     for (int r = 0; r < 16; ++r) { dsum[tid + r * T] = acc[r]; dpk[tid + r * T] = pk[r]; }
 }
 
-template <int LOG2N>
-static hipError_t launch_psd_pages_n(const PsdPagesArgs &a, unsigned grid, hipStream_t s)
-{
-    constexpr unsigned T = (1u << LOG2N) / 16;
-    switch (a.fmt) {
-    case IQGPU_FMT_CS16: hipLaunchKernelGGL((k_psd_pages<LOG2N, IQGPU_FMT_CS16>), dim3(grid), dim3(T), 0, s, a); break;
-    case IQGPU_FMT_CU8:  hipLaunchKernelGGL((k_psd_pages<LOG2N, IQGPU_FMT_CU8>), dim3(grid), dim3(T), 0, s, a); break;
-    case IQGPU_FMT_CS8:  hipLaunchKernelGGL((k_psd_pages<LOG2N, IQGPU_FMT_CS8>), dim3(grid), dim3(T), 0, s, a); break;
-    case IQGPU_FMT_CF32: hipLaunchKernelGGL((k_psd_pages<LOG2N, IQGPU_FMT_CF32>), dim3(grid), dim3(T), 0, s, a); break;
-    default:             hipLaunchKernelGGL((k_psd_pages<LOG2N, -1>), dim3(grid), dim3(T), 0, s, a); break;
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_psd_pages(const PsdPagesArgs &a, hipStream_t s)
 {
     if (a.n_seg <= 0) return hipSuccess;
     const int64_t G = kPsdPageSegments;
     const int64_t pages = (a.seg0 + a.n_seg - 1) / G - a.seg0 / G + 1;
     if (pages * ((int64_t)1 << a.log2n) > kPsdPageBufBins) return hipErrorInvalidValue;      // (the page buffer's bound: psd.cpp cuts longer pushes)
-    switch (a.log2n) {
-    case 10: return launch_psd_pages_n<10>(a, (unsigned)pages, s);
-    case 11: return launch_psd_pages_n<11>(a, (unsigned)pages, s);
-    case 12: return launch_psd_pages_n<12>(a, (unsigned)pages, s);
-    default: return hipErrorInvalidValue;
-    }
+    return psd_dispatch(a.log2n, a.fmt, [&](auto L, auto F) {
+        hipLaunchKernelGGL((k_psd_pages<decltype(L)::value, decltype(F)::value>), dim3((unsigned)pages), dim3((1u << decltype(L)::value) / 16), 0, s, a);
+    });
 }
 
 __global__ __launch_bounds__(64) void k_psd_fold(const PsdFoldArgs a)

@@ -1,7 +1,8 @@
 // psd.hpp -- power spectrum of a stream on the device (include/iqgpu.h "power spectrum"): the argument blocks and launchers of
-// k_psd_pages / k_psd_fold / k_psd_carry (psd.hip; host side psd.cpp).
+// k_psd_pages / k_psd_fold / k_psd_carry (psd.hip; host side psd.cpp), and the host's stream core PsdStream, which the
+// row accumulator (sgram.hpp) holds too.
 #pragma once
-#include "kernels.hpp"
+#include "chain.hpp"
 
 namespace iqgpu {
 
@@ -45,11 +46,50 @@ struct PsdCarryArgs { const unsigned char *carry, *raw; int64_t split_bytes, fir
 hipError_t launch_psd_carry(const PsdCarryArgs &a, hipStream_t s);
 
 // host side, no device (psd.cpp), shared with the row accumulator (sgram.cpp): the option checks (`who` names the caller in the error
-// text), the device tables -- [nfft] window, then [nfft] twiddles exp(-2 pi i k / nfft) as (cos, sin) pairs: 3 nfft floats -- with the
-// window's two sums, the whole segments of `frames` frames, and log2 nfft (0: no size of the list)
+// text) and the whole segments of `frames` frames
 int psd_check_opts(const iqgpu_psd_opts *o, const char *who);
-void psd_fill_tables(const iqgpu_psd_opts &o, float *tab, double *sum, double *sum_sq);
 uint64_t psd_segments_of(const iqgpu_psd_opts &o, uint64_t frames);
-int psd_log2n(uint32_t nfft);
+
+// One push: n frames of device memory at raw on stream s; the stream's frames and whole segments with them, m of the segments new
+struct PsdPush { const void *raw; size_t n; hipStream_t s; uint64_t frames, segs; int64_t m; };
+
+// The stream core both handles hold (psd.cpp): the position in the stream, the carry of trailing frames in two buffers (the launches of
+// a push read carry[cur], its last launch writes carry[cur ^ 1]), the device tables, the stream of its own and the one of the previous
+// push.  What a handle accumulates, and its open state, are the handle's.
+struct PsdStream {
+    int device = 0, format = 0, log2n = 0;
+    size_t bps = 0;
+    iqgpu_psd_opts q{};
+    double window_sum = 0.0, window_sum_sq = 0.0;
+    uint64_t frames = 0, segments = 0;    // pushed since the last reset; whole segments of them (all accumulated)
+    size_t carry_n = 0;                   // frames in carry[cur]: stream frames segments * hop .. frames - 1
+    int cur = 0;
+    bool poisoned = false;                // a push failed half way: rewind() clears it
+    hipStream_t own = nullptr, last = nullptr; bool has_last = false;     // last: the stream of the previous push
+    DevBuf tables, carry[2], stage;       // tables: [nfft] window, then [nfft] twiddles as (cos, sin) pairs
+    const float *window() const { return (const float *)tables.p; }
+    const cf2 *twiddle() const { return (const cf2 *)((const float *)tables.p + q.nfft); }
+
+    // The checks of a create in their order -- options, format, device count and range, host memory (st NULL: no handle could be
+    // allocated) -- then stream, buffers and the tables' upload, queued on `own` from `tab`: the caller queues the zero fill of its
+    // open state behind it and synchronises once, with `tab` alive until then.  `who` leads the error texts.
+    static int open(PsdStream *st, int device, int format, const iqgpu_psd_opts *o, const char *who, std::vector<float> &tab);
+    void close();                         // waits for `last` and `own`, then frees
+    // NULL (st, or !args_ok) and poisoned, in the handles' texts (`reset` names the call that clears a poisoned handle), then hipSetDevice
+    static int guard(const PsdStream *st, bool args_ok, const char *who, const char *reset, bool set_device = true);
+    int settle();                         // everything queued by earlier pushes has run; the handle then holds on to no stream of the caller's
+    // a reset: `last` waited for (a failed push may have left an error there: ignored), the caller zero-fills its state on `own`, then
+    int begin_reset() { HIP_TRY(hipSetDevice(device)); if (has_last) (void)hipStreamSynchronize(last); return IQGPU_OK; }
+    void rewind() { frames = segments = 0; carry_n = 0; cur = 0; has_last = false; last = nullptr; poisoned = false; }   // ... as created
+    int enter(const void *d_raw, size_t n, hipStream_t s, PsdPush *u);   // the previous push's stream waited for if it is another; s remembered
+    // what PsdPagesArgs and SgramCellsArgs have in common, for the launch over segments [j, j + cnt) of the push, but for open_*: the handle's
+    template <class Args> void fill(const PsdPush &u, int64_t j, int64_t cnt, Args *a) const
+    {
+        a->carry = carry[cur].p; a->raw = u.raw; a->split = (int64_t)carry_n; a->first = j * (int64_t)q.hop;
+        a->fmt = format; a->log2n = log2n; a->hop = (int32_t)q.hop; a->gain = q.gain;
+        a->seg0 = (int64_t)segments + j; a->n_seg = cnt; a->window = window(); a->twiddle = twiddle();
+    }
+    int finish(const PsdPush &u);         // the trailing frames into the other carry buffer, the position behind the push, poisoned cleared
+};
 
 } // namespace iqgpu

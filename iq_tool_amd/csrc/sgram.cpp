@@ -1,7 +1,7 @@
 // sgram.cpp -- host side of the row accumulator (include/iqgpu.h "spectrogram"; kernels sgram.hip): the options and the
-// row arithmetic (no device), and the iqgpu_sgram handle -- stream position, the carry of trailing frames, the open row (the total of
-// its closed cells and its open cell, two buffers each) -- with push / push_device / read_open / reset.  Independent of any chain.
-// Options, tables, segment grid and carry kernel are the power spectrum's (psd.hpp).
+// row arithmetic (no device), and the iqgpu_sgram handle -- the stream core and the open row (the total of its closed cells and its
+// open cell, two buffers each) -- with push / push_device / read_open / reset.  Independent of any chain.
+// Options, tables, segment grid, stream position and carry are the power spectrum's: PsdStream (psd.hpp, psd.cpp).
 #include "chain.hpp"
 #include "sgram.hpp"
 
@@ -9,7 +9,9 @@ namespace {
 
 constexpr size_t kPushSliceFrames = (size_t)1 << 20;     // of a host push: frames staged per slice (its rows come back per slice)
 constexpr uint32_t kMaxRowSegments = (uint32_t)1 << 20;
+const char *const kReset = "iqgpu_sgram_reset";
 
+// o's part that is the power spectrum's
 iqgpu_psd_opts psd_part(const iqgpu_sgram_opts &o)
 {
     iqgpu_psd_opts q{};
@@ -30,80 +32,59 @@ int check_opts(const iqgpu_sgram_opts *o, const char *who)
 } // namespace
 
 struct iqgpu_sgram {
-    int device = 0, format = 0, log2n = 0;
-    size_t bps = 0;
+    PsdStream st;
     iqgpu_sgram_opts o{};
-    iqgpu_psd_opts q{};                   // o's part that is the power spectrum's
-    double window_sum = 0.0, window_sum_sq = 0.0;
-    uint64_t frames = 0, segments = 0;    // pushed since the last reset; whole segments of them
-    size_t carry_n = 0;                   // frames in carry[cur]: stream frames segments * hop .. frames - 1
-    int cur = 0;
     int open_cur = 0;                     // which half of `open` holds the open row (a launch writes the other: sgram.hip)
-    bool poisoned = false;
-    hipStream_t own = nullptr, last = nullptr; bool has_last = false;
-    DevBuf tables, carry[2], open, cells, stage, rows_out;
+    DevBuf open, cells, rows_out;
     size_t cell_bins = 0;                 // of cells: [cell_bins] doubles, then [cell_bins] floats
     // open: 2 x { [nfft] total, [nfft] open cell } doubles, then 2 x { [nfft] total peak, [nfft] open-cell peak } floats
-    const float *window() const { return (const float *)tables.p; }
-    const cf2 *twiddle() const { return (const cf2 *)((const float *)tables.p + o.nfft); }
     double *tot_sum(int i) const { return (double *)open.p + (size_t)(2 * i) * o.nfft; }
     double *cell_sum(int i) const { return (double *)open.p + (size_t)(2 * i + 1) * o.nfft; }
     float *tot_pk(int i) const { return (float *)((double *)open.p + 4 * (size_t)o.nfft) + (size_t)(2 * i) * o.nfft; }
     float *cell_pk(int i) const { return (float *)((double *)open.p + 4 * (size_t)o.nfft) + (size_t)(2 * i + 1) * o.nfft; }
     size_t open_bytes() const { return (size_t)o.nfft * 4 * (sizeof(double) + sizeof(float)); }
-    uint64_t rows_after(size_t n) const { return psd_segments_of(q, frames + n) / o.row_segments; }
+    uint64_t rows_after(size_t n) const { return psd_segments_of(st.q, st.frames + n) / o.row_segments; }
 };
 
 namespace {
 
+PsdStream *core(iqgpu_sgram *p) { return p ? &p->st : nullptr; }
+
 void destroy(iqgpu_sgram *p)
 {
     if (!p) return;
-    (void)hipSetDevice(p->device);
-    if (p->has_last) (void)hipStreamSynchronize(p->last);
-    if (p->own) { (void)hipStreamSynchronize(p->own); (void)hipStreamDestroy(p->own); }
-    p->tables.release(); p->carry[0].release(); p->carry[1].release(); p->open.release(); p->cells.release(); p->stage.release(); p->rows_out.release();
+    p->st.close();
+    p->open.release(); p->cells.release(); p->rows_out.release();
     delete p;
-}
-
-int settle(iqgpu_sgram *p)
-{
-    if (p->has_last) HIP_TRY(hipStreamSynchronize(p->last));
-    p->has_last = false; p->last = nullptr;
-    return IQGPU_OK;
 }
 
 // n frames of device memory behind everything pushed so far, on s; the rows they complete into d_sum / d_pk (device, either may be NULL)
 int push_frames(iqgpu_sgram *p, const void *d_raw, size_t n, float *d_sum, float *d_pk, hipStream_t s)
 {
-    if (p->has_last && p->last != s) HIP_TRY(hipStreamSynchronize(p->last));      // the previous push's work comes first
-    p->has_last = true; p->last = s;
-    const iqgpu_sgram_opts &o = p->o;
-    const int64_t R = o.row_segments, C = sgram_cells_per_row(R), N = o.nfft;
+    PsdStream &st = p->st;
+    PsdPush u;
+    int rc = st.enter(d_raw, n, s, &u); if (rc) return rc;
+    const int64_t R = p->o.row_segments, C = sgram_cells_per_row(R), N = p->o.nfft, m = u.m;
     const int64_t cap = C == 1 ? kSgramDirectCells : kSgramCellBufBins / N;       // cells a launch
-    const uint64_t frames = p->frames + n, segs = psd_segments_of(p->q, frames);
-    const int64_t m = (int64_t)(segs - p->segments);
     // the cell buffer (R > 32 only): one slot for every cell the longest launch of this push touches (psd.cpp on growing such a buffer)
     if (m > 0 && C > 1) {
-        const int64_t touched = sgram_cell_of((int64_t)segs - 1, R) - sgram_cell_of((int64_t)p->segments, R) + 1;
+        const int64_t touched = sgram_cell_of((int64_t)u.segs - 1, R) - sgram_cell_of((int64_t)st.segments, R) + 1;
         const size_t bins = (size_t)((touched < cap ? touched : cap) * N);
         if (bins > p->cell_bins) {
-            const int rc = p->cells.ensure(bins * (sizeof(double) + sizeof(float))); if (rc) return rc;
+            rc = p->cells.ensure(bins * (sizeof(double) + sizeof(float))); if (rc) return rc;
             p->cell_bins = bins;
         }
     }
-    p->poisoned = true;                                                           // (until everything below is queued)
+    st.poisoned = true;                                                           // (until finish() has queued the last of the push)
     for (int64_t j = 0; j < m;) {
-        const int64_t seg0 = (int64_t)p->segments + j, g0 = sgram_cell_of(seg0, R), r0 = seg0 / R;
+        const int64_t seg0 = (int64_t)st.segments + j, g0 = sgram_cell_of(seg0, R), r0 = seg0 / R;
         const int64_t room = sgram_cell_end(g0 + cap - 1, R) - seg0;              // whole cells up to the bound
         const int64_t cnt = m - j < room ? m - j : room, seg_end = seg0 + cnt;
         SgramCellsArgs a{};
-        a.carry = p->carry[p->cur].p; a.raw = d_raw; a.split = (int64_t)p->carry_n; a.first = j * (int64_t)o.hop;
-        a.fmt = p->format; a.log2n = p->log2n; a.hop = (int32_t)o.hop; a.gain = o.gain;
-        a.seg0 = seg0; a.n_seg = cnt; a.R = R; a.C = C; a.g0 = g0; a.r0 = r0;
-        a.window = p->window(); a.twiddle = p->twiddle();
+        st.fill(u, j, cnt, &a);
         a.open_sum_in = p->cell_sum(p->open_cur); a.open_pk_in = p->cell_pk(p->open_cur);
         a.open_sum_out = p->cell_sum(p->open_cur ^ 1); a.open_pk_out = p->cell_pk(p->open_cur ^ 1);
+        a.R = R; a.C = C; a.g0 = g0; a.r0 = r0;
         a.cell_sum = (double *)p->cells.p; a.cell_pk = p->cells.p ? (float *)((double *)p->cells.p + p->cell_bins) : nullptr;
         a.row_sum = d_sum; a.row_pk = d_pk;
         HIP_TRY(launch_sgram_cells(a, s));
@@ -124,16 +105,7 @@ int push_frames(iqgpu_sgram *p, const void *d_raw, size_t n, float *d_sum, float
         if (d_pk) d_pk += done * N;
         j += cnt;
     }
-    // the trailing frames the next segment starts with, into the other buffer (the cell kernels above read this one)
-    const size_t carry_n = (size_t)(frames - segs * o.hop);
-    PsdCarryArgs c{};
-    c.carry = (const unsigned char *)p->carry[p->cur].p; c.raw = (const unsigned char *)d_raw;
-    c.split_bytes = (int64_t)(p->carry_n * p->bps); c.first = (int64_t)((p->carry_n + n - carry_n) * p->bps);
-    c.bytes = (int32_t)(carry_n * p->bps); c.dst = (unsigned char *)p->carry[p->cur ^ 1].p;
-    HIP_TRY(launch_psd_carry(c, s));
-    p->cur ^= 1; p->carry_n = carry_n; p->frames = frames; p->segments = segs;
-    p->poisoned = false;
-    return IQGPU_OK;
+    return st.finish(u);
 }
 
 // the checks of both pushes, in front of anything queued; *need = the rows the push completes
@@ -141,12 +113,11 @@ int begin_push(iqgpu_sgram *p, const void *raw, size_t frames, const float *row_
                size_t *need, const char *who)
 {
     if (rows) *rows = 0;
-    if (!p || (!raw && frames)) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
-    if (p->poisoned) return fail(IQGPU_EHIP, "%s: an earlier push failed half way through: the accumulator is undefined until iqgpu_sgram_reset()", who);
-    *need = (size_t)(p->rows_after(frames) - p->segments / p->o.row_segments);
+    const int rc = PsdStream::guard(core(p), raw || !frames, who, kReset, false); if (rc) return rc;
+    *need = (size_t)(p->rows_after(frames) - p->st.segments / p->o.row_segments);
     if ((row_sum || row_peak) && *need > cap_rows)
         return fail(IQGPU_ECAPACITY, "%s: room for %zu rows, the push completes %zu (iqgpu_sgram_max_rows)", who, cap_rows, *need);
-    if (frames) HIP_TRY(hipSetDevice(p->device));
+    if (frames) HIP_TRY(hipSetDevice(p->st.device));
     return IQGPU_OK;
 }
 
@@ -169,30 +140,19 @@ extern "C" int iqgpu_sgram_rows(const iqgpu_sgram_opts *o, uint64_t frames, uint
 
 extern "C" int iqgpu_sgram_create(int device, int format, const iqgpu_sgram_opts *o, iqgpu_sgram **out)
 {
+    const char *who = "iqgpu_sgram_create";
     if (out) *out = nullptr;
-    if (!out) return fail(IQGPU_EINVAL, "iqgpu_sgram_create: NULL argument");
-    int rc = check_opts(o, "iqgpu_sgram_create"); if (rc) return rc;
-    if (!bytes_per_frame(format)) return fail(IQGPU_EFORMAT, "iqgpu_sgram_create: unhandled sample format %d", format);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(IQGPU_ENODEV, "iqgpu_sgram_create: no HIP device available");
-    if (device < 0 || device >= ndev) return fail(IQGPU_ENODEV, "iqgpu_sgram_create: device %d out of range (%d devices)", device, ndev);
+    if (!out) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
+    int rc = check_opts(o, who); if (rc) return rc;
+    const iqgpu_psd_opts q = psd_part(*o);
     iqgpu_sgram *p = new (std::nothrow) iqgpu_sgram;
-    std::vector<float> tab;
-    try { tab.resize(3 * (size_t)o->nfft); } catch (const std::bad_alloc &) { delete p; p = nullptr; }
-    if (!p) return fail(IQGPU_ENOMEM, "iqgpu_sgram_create: out of host memory");
-    p->device = device; p->format = format; p->log2n = psd_log2n(o->nfft); p->bps = bytes_per_frame(format); p->o = *o; p->q = psd_part(*o);
-    psd_fill_tables(p->q, tab.data(), &p->window_sum, &p->window_sum_sq);
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&p->own, hipStreamNonBlocking);
-    if (e != hipSuccess) { rc = fail(IQGPU_EHIP, "iqgpu_sgram_create: %s", hipGetErrorString(e)); destroy(p); return rc; }
-    rc = p->tables.ensure(tab.size() * sizeof(float));
-    for (int i = 0; i < 2 && rc == IQGPU_OK; ++i) rc = p->carry[i].ensure((size_t)o->nfft * p->bps);
-    if (rc == IQGPU_OK) rc = p->open.ensure(p->open_bytes());
+    std::vector<float> tab;                                          // the source of the table upload: until the synchronise below
+    rc = PsdStream::open(core(p), device, format, &q, who, tab);
+    if (rc == IQGPU_OK) { p->o = *o; rc = p->open.ensure(p->open_bytes()); }
     if (rc == IQGPU_OK) {
-        e = hipMemcpyAsync(p->tables.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, p->own);
-        if (e == hipSuccess) e = hipMemsetAsync(p->open.p, 0, p->open_bytes(), p->own);
-        if (e == hipSuccess) e = hipStreamSynchronize(p->own);
-        if (e != hipSuccess) rc = fail(IQGPU_EHIP, "iqgpu_sgram_create: %s", hipGetErrorString(e));
+        hipError_t e = hipMemsetAsync(p->open.p, 0, p->open_bytes(), p->st.own);
+        if (e == hipSuccess) e = hipStreamSynchronize(p->st.own);
+        if (e != hipSuccess) rc = fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e));
     }
     if (rc != IQGPU_OK) { destroy(p); return rc; }
     *out = p;
@@ -204,17 +164,16 @@ extern "C" void iqgpu_sgram_destroy(iqgpu_sgram *p) { destroy(p); }
 extern "C" int iqgpu_sgram_reset(iqgpu_sgram *p)
 {
     if (!p) return fail(IQGPU_EINVAL, "iqgpu_sgram_reset: NULL argument");
-    HIP_TRY(hipSetDevice(p->device));
-    if (p->has_last) (void)hipStreamSynchronize(p->last);            // (a failed push may have left an error there: the fill below decides)
-    HIP_TRY(hipMemsetAsync(p->open.p, 0, p->open_bytes(), p->own));
-    HIP_TRY(hipStreamSynchronize(p->own));
-    p->frames = p->segments = 0; p->carry_n = 0; p->cur = 0; p->open_cur = 0; p->has_last = false; p->last = nullptr; p->poisoned = false;
+    const int rc = p->st.begin_reset(); if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(p->open.p, 0, p->open_bytes(), p->st.own));
+    HIP_TRY(hipStreamSynchronize(p->st.own));
+    p->st.rewind(); p->open_cur = 0;
     return IQGPU_OK;
 }
 
 extern "C" size_t iqgpu_sgram_max_rows(const iqgpu_sgram *p, size_t frames)
 {
-    return p ? (size_t)(p->rows_after(frames) - p->segments / p->o.row_segments) : 0;
+    return p ? (size_t)(p->rows_after(frames) - p->st.segments / p->o.row_segments) : 0;
 }
 
 extern "C" int iqgpu_sgram_push_device(iqgpu_sgram *p, const void *d_raw, size_t frames, float *d_row_sum, float *d_row_peak, size_t cap_rows,
@@ -232,11 +191,12 @@ extern "C" int iqgpu_sgram_push(iqgpu_sgram *p, const void *raw, size_t frames, 
     size_t need = 0;
     int rc = begin_push(p, raw, frames, row_sum, row_peak, cap_rows, rows, &need, "iqgpu_sgram_push"); if (rc) return rc;
     if (frames == 0) return IQGPU_OK;
+    PsdStream &st = p->st;
     const size_t slice = frames < kPushSliceFrames ? frames : kPushSliceFrames, N = p->o.nfft;
     // rows of one slice, whatever the position: the segments that start in a slice, and the one a carry completes
     const size_t slice_rows = (slice / p->o.hop + 1) / p->o.row_segments + 1;
     const int planes = (row_sum ? 1 : 0) + (row_peak ? 1 : 0);
-    rc = p->stage.ensure(slice * p->bps); if (rc) return rc;
+    rc = st.stage.ensure(slice * st.bps); if (rc) return rc;
     if (planes) { rc = p->rows_out.ensure((size_t)planes * slice_rows * N * sizeof(float)); if (rc) return rc; }
     float *d_sum = row_sum ? (float *)p->rows_out.p : nullptr;
     float *d_pk = row_peak ? (float *)p->rows_out.p + (row_sum ? slice_rows * N : 0) : nullptr;
@@ -245,13 +205,13 @@ extern "C" int iqgpu_sgram_push(iqgpu_sgram *p, const void *raw, size_t frames, 
         const size_t n = frames - at < kPushSliceFrames ? frames - at : kPushSliceFrames;
         const size_t done = iqgpu_sgram_max_rows(p, n);
         if (done > slice_rows) return fail(IQGPU_EHIP, "iqgpu_sgram_push: a slice completes %zu rows, the buffer holds %zu", done, slice_rows);
-        HIP_TRY(hipMemcpyAsync(p->stage.p, (const char *)raw + at * p->bps, n * p->bps, hipMemcpyHostToDevice, p->own));
-        rc = push_frames(p, p->stage.p, n, d_sum, d_pk, p->own); if (rc) return rc;
-        p->poisoned = true;                                              // (until the slice's rows are in the caller's memory)
-        if (row_sum && done) HIP_TRY(hipMemcpyAsync(row_sum, d_sum, done * N * sizeof(float), hipMemcpyDeviceToHost, p->own));
-        if (row_peak && done) HIP_TRY(hipMemcpyAsync(row_peak, d_pk, done * N * sizeof(float), hipMemcpyDeviceToHost, p->own));
-        HIP_TRY(hipStreamSynchronize(p->own));                          // the one staging pair: the next slice overwrites both
-        p->poisoned = false;
+        HIP_TRY(hipMemcpyAsync(st.stage.p, (const char *)raw + at * st.bps, n * st.bps, hipMemcpyHostToDevice, st.own));
+        rc = push_frames(p, st.stage.p, n, d_sum, d_pk, st.own); if (rc) return rc;
+        st.poisoned = true;                                              // (until the slice's rows are in the caller's memory)
+        if (row_sum && done) HIP_TRY(hipMemcpyAsync(row_sum, d_sum, done * N * sizeof(float), hipMemcpyDeviceToHost, st.own));
+        if (row_peak && done) HIP_TRY(hipMemcpyAsync(row_peak, d_pk, done * N * sizeof(float), hipMemcpyDeviceToHost, st.own));
+        HIP_TRY(hipStreamSynchronize(st.own));                          // the one staging pair: the next slice overwrites both
+        st.poisoned = false;
         if (row_sum) row_sum += done * N;
         if (row_peak) row_peak += done * N;
         at += n;
@@ -261,12 +221,10 @@ extern "C" int iqgpu_sgram_push(iqgpu_sgram *p, const void *raw, size_t frames, 
 
 extern "C" int iqgpu_sgram_read_open(iqgpu_sgram *p, double *sum_power, float *peak_power, iqgpu_sgram_info *info)
 {
-    if (!p) return fail(IQGPU_EINVAL, "iqgpu_sgram_read_open: NULL argument");
-    if (p->poisoned) return fail(IQGPU_EHIP, "iqgpu_sgram_read_open: an earlier push failed half way through: the accumulator is undefined until iqgpu_sgram_reset()");
-    HIP_TRY(hipSetDevice(p->device));
-    int rc = settle(p); if (rc) return rc;
+    int rc = PsdStream::guard(core(p), true, "iqgpu_sgram_read_open", kReset); if (rc) return rc;
+    rc = p->st.settle(); if (rc) return rc;
     const size_t n = p->o.nfft;
-    const uint32_t open_segments = (uint32_t)(p->segments % p->o.row_segments);
+    const uint32_t open_segments = (uint32_t)(p->st.segments % p->o.row_segments);
     if (sum_power || peak_power) {
         // the open row's closed cells are in the total, its open cell beside it; what the arithmetic says is empty is not looked at
         const bool has_tot = open_segments >= (uint32_t)kPsdPageSegments, has_cell = open_segments % (uint32_t)kPsdPageSegments != 0;
@@ -287,9 +245,9 @@ extern "C" int iqgpu_sgram_read_open(iqgpu_sgram *p, double *sum_power, float *p
     }
     if (info) {
         memset(info, 0, sizeof(*info));
-        info->frames = p->frames; info->segments = p->segments; info->rows = p->segments / p->o.row_segments; info->open_segments = open_segments;
+        info->frames = p->st.frames; info->segments = p->st.segments; info->rows = p->st.segments / p->o.row_segments; info->open_segments = open_segments;
         info->nfft = p->o.nfft; info->hop = p->o.hop; info->row_segments = p->o.row_segments;
-        info->window_sum = p->window_sum; info->window_sum_sq = p->window_sum_sq;
+        info->window_sum = p->st.window_sum; info->window_sum_sq = p->st.window_sum_sq;
     }
     return IQGPU_OK;
 }

@@ -9,9 +9,8 @@
 //   k_sgram_fold   R > 32: one thread per (row, bin) adds a row's cells in cell order, behind the open row's total where the row began
 //                  before the launch; finished rows are rounded once into the caller's planes, the open row's total goes to the other
 //                  total buffer.
-// Ordering: as in psd.hip, a launch may hold both the workgroup that starts from the open state and the one that leaves it, so the
-// open cell and the open total are two buffers each; a launch reads [cur] and writes [cur ^ 1], and the host flips cur behind every
-// launch.  Within a launch every address is read only or written by exactly one workgroup (cells) or thread (fold).
+// Ordering: the argument of psd.hip, for the open cell and the open total alike -- two buffers each, and the host flips cur behind
+// every launch.  Within a launch every address is read only or written by exactly one workgroup (cells) or thread (fold).
 #include <hip/hip_runtime.h>
 
 #include "fft16.hpp"
@@ -83,20 +82,6 @@ __global__ __launch_bounds__((1 << LOG2N) / 16) void k_sgram_cells(const SgramCe
     for (int r = 0; r < 16; ++r) { dsum[tid + r * T] = acc[r]; dpk[tid + r * T] = pk[r]; }
 }
 
-template <int LOG2N>
-static hipError_t launch_sgram_cells_n(const SgramCellsArgs &a, unsigned grid, hipStream_t s)
-{
-    constexpr unsigned T = (1u << LOG2N) / 16;
-    switch (a.fmt) {
-    case IQGPU_FMT_CS16: hipLaunchKernelGGL((k_sgram_cells<LOG2N, IQGPU_FMT_CS16>), dim3(grid), dim3(T), 0, s, a); break;
-    case IQGPU_FMT_CU8:  hipLaunchKernelGGL((k_sgram_cells<LOG2N, IQGPU_FMT_CU8>), dim3(grid), dim3(T), 0, s, a); break;
-    case IQGPU_FMT_CS8:  hipLaunchKernelGGL((k_sgram_cells<LOG2N, IQGPU_FMT_CS8>), dim3(grid), dim3(T), 0, s, a); break;
-    case IQGPU_FMT_CF32: hipLaunchKernelGGL((k_sgram_cells<LOG2N, IQGPU_FMT_CF32>), dim3(grid), dim3(T), 0, s, a); break;
-    default:             hipLaunchKernelGGL((k_sgram_cells<LOG2N, -1>), dim3(grid), dim3(T), 0, s, a); break;
-    }
-    return hipGetLastError();
-}
-
 hipError_t launch_sgram_cells(const SgramCellsArgs &a, hipStream_t s)
 {
     if (a.n_seg <= 0) return hipSuccess;
@@ -104,12 +89,9 @@ hipError_t launch_sgram_cells(const SgramCellsArgs &a, hipStream_t s)
     const int64_t cells = sgram_cell_of(a.seg0 + a.n_seg - 1, a.R) - a.g0 + 1;
     // (the bounds of the cell buffer and of the grid: sgram.cpp cuts longer pushes)
     if (a.C == 1 ? cells > kSgramDirectCells : cells * ((int64_t)1 << a.log2n) > kSgramCellBufBins) return hipErrorInvalidValue;
-    switch (a.log2n) {
-    case 10: return launch_sgram_cells_n<10>(a, (unsigned)cells, s);
-    case 11: return launch_sgram_cells_n<11>(a, (unsigned)cells, s);
-    case 12: return launch_sgram_cells_n<12>(a, (unsigned)cells, s);
-    default: return hipErrorInvalidValue;
-    }
+    return psd_dispatch(a.log2n, a.fmt, [&](auto L, auto F) {
+        hipLaunchKernelGGL((k_sgram_cells<decltype(L)::value, decltype(F)::value>), dim3((unsigned)cells), dim3((1u << decltype(L)::value) / 16), 0, s, a);
+    });
 }
 
 __global__ __launch_bounds__(256) void k_sgram_fold(const SgramFoldArgs a)

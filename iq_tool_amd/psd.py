@@ -44,22 +44,13 @@ def geometry():
     return int(g.value)
 
 
-class Psd:
-    """One accumulator (iqgpu_psd).  push takes host frames (any array: its bytes), push_device a device pointer; read returns
-    (sum_power float64[nfft], peak_power float32[nfft], info dict) in natural bin order and synchronises."""
-
-    def __init__(self, format, nfft=1024, hop=None, window="hann", gain=1.0, device=0):
-        self._h = C.c_void_p()
-        self._lib = _lib.load()
-        self.format = FMT[format] if isinstance(format, str) else int(format)
-        self.opts = psd_opts(nfft, hop, window, gain)
-        self.nfft, self.hop = int(self.opts.nfft), int(self.opts.hop)
-        check(self._lib.iqgpu_psd_create(int(device), self.format, C.byref(self.opts), C.byref(self._h)))
-        self.bytes_per_frame = BYTES_PER_FRAME[self.format]
+class _Accumulator:
+    """What Psd and Sgram (sgram.py) share: the life of the handle `_h`, destroyed by the library call named `_destroy`, and the
+    bytes of a host push."""
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.iqgpu_psd_destroy(self._h)
+            getattr(self._lib, self._destroy)(self._h)
             self._h = None
 
     __del__ = close
@@ -70,11 +61,31 @@ class Psd:
     def __exit__(self, *exc):
         self.close()
 
-    def push(self, frames):
+    def _whole_frames(self, frames):
+        """(the bytes of `frames` as a contiguous uint8 array, how many frames they are)"""
         raw = np.ascontiguousarray(frames).view(np.uint8).reshape(-1)
         if raw.size % self.bytes_per_frame:
             raise ValueError("%d bytes are no whole number of %d-byte frames" % (raw.size, self.bytes_per_frame))
-        check(self._lib.iqgpu_psd_push(self._h, raw.ctypes.data_as(C.c_void_p), raw.size // self.bytes_per_frame))
+        return raw, raw.size // self.bytes_per_frame
+
+
+class Psd(_Accumulator):
+    """One accumulator (iqgpu_psd).  push takes host frames (any array: its bytes), push_device a device pointer; read returns
+    (sum_power float64[nfft], peak_power float32[nfft], info dict) in natural bin order and synchronises."""
+    _destroy = "iqgpu_psd_destroy"
+
+    def __init__(self, format, nfft=1024, hop=None, window="hann", gain=1.0, device=0):
+        self._h = C.c_void_p()
+        self._lib = _lib.load()
+        self.format = FMT[format] if isinstance(format, str) else int(format)
+        self.opts = psd_opts(nfft, hop, window, gain)
+        self.nfft, self.hop = int(self.opts.nfft), int(self.opts.hop)
+        check(self._lib.iqgpu_psd_create(int(device), self.format, C.byref(self.opts), C.byref(self._h)))
+        self.bytes_per_frame = BYTES_PER_FRAME[self.format]
+
+    def push(self, frames):
+        raw, n = self._whole_frames(frames)
+        check(self._lib.iqgpu_psd_push(self._h, raw.ctypes.data_as(C.c_void_p), n))
 
     def push_device(self, ptr, frames, stream=None):
         check(self._lib.iqgpu_psd_push_device(self._h, C.c_void_p(ptr), int(frames), C.c_void_p(stream)))

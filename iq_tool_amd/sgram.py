@@ -7,6 +7,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import BYTES_PER_FRAME, FMT, PSD_WINDOW, SgramInfo, SgramOpts, check
+from .psd import _Accumulator
 
 
 def sgram_opts(nfft=1024, hop=None, window="hann", gain=1.0, row_segments=32):
@@ -29,10 +30,11 @@ def rows(frames, nfft=1024, hop=None, row_segments=32):
     return int(n.value)
 
 
-class Sgram:
+class Sgram(_Accumulator):
     """One row accumulator (iqgpu_sgram).  push takes host frames (any array: its bytes) and returns the rows they finish as
     (row_sum, row_peak), float32 [rows, nfft] in natural bin order; push_device takes device pointers for input and output planes
     (0 / None: that plane is not produced) and returns the row count; read_open returns the partial last row and synchronises."""
+    _destroy = "iqgpu_sgram_destroy"
 
     def __init__(self, format, nfft=1024, hop=None, window="hann", gain=1.0, row_segments=32, device=0):
         self._h = C.c_void_p()
@@ -43,28 +45,12 @@ class Sgram:
         check(self._lib.iqgpu_sgram_create(int(device), self.format, C.byref(self.opts), C.byref(self._h)))
         self.bytes_per_frame = BYTES_PER_FRAME[self.format]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.iqgpu_sgram_destroy(self._h)
-            self._h = None
-
-    __del__ = close
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
     def max_rows(self, frames):
         """rows the next push of `frames` frames finishes, from the handle's position: exact"""
         return int(self._lib.iqgpu_sgram_max_rows(self._h, int(frames)))
 
     def push(self, frames):
-        raw = np.ascontiguousarray(frames).view(np.uint8).reshape(-1)
-        if raw.size % self.bytes_per_frame:
-            raise ValueError("%d bytes are no whole number of %d-byte frames" % (raw.size, self.bytes_per_frame))
-        n = raw.size // self.bytes_per_frame
+        raw, n = self._whole_frames(frames)
         cap, got = self.max_rows(n), C.c_size_t(0)
         row_sum, row_peak = np.empty((cap, self.nfft), np.float32), np.empty((cap, self.nfft), np.float32)
         check(self._lib.iqgpu_sgram_push(self._h, raw.ctypes.data_as(C.c_void_p), n, row_sum.ctypes.data_as(C.c_void_p),

@@ -2,7 +2,8 @@
 
 1. Rows equal the power spectrum's, bit for bit: every finished row is float32(sum_power) / peak_power of a `Psd` pushed exactly the
    row's frames, the open row is the `Psd` of the remaining segments' frames (doubles as bytes).  R = 1, 3, 32, 33, 70: a row of one
-   segment, of one short cell, of exactly one cell, of a cell and a one-segment cell, of two cells and a short one.
+   segment, of one short cell, of exactly one cell, of a cell and a one-segment cell, of two cells and a short one.  Those run Hann
+   at gain 1; Blackman-Harris at gain 0.5 and the rectangular window at gain 2 at R = 3 pin how the two options reach the stream core.
 2. Against float64, independent of the PSD code.  `want` is the numpy float64 periodogram of the frames unpacked by the oracle's
    conversion and windowed with the library's float32 table, summed (row_sum) or maximised (row_peak) per row.  Bar, per row and bin:
    |got - want| <= A want + B max_row(want).  A and B are 8 x the error of a FLOAT32 transform (scipy.fft.fft on complex64, powers
@@ -110,6 +111,30 @@ def test_rows_equal_the_psd_of_their_frames(gpu, fmt, nfft, hop, R):
     assert ref_info["segments"] == info["open_segments"]
     assert (ref_info["window_sum"], ref_info["window_sum_sq"]) == (info["window_sum"], info["window_sum_sq"])
     assert open_sum.tobytes() == s.tobytes() and open_peak.tobytes() == k.tobytes()
+
+
+@pytest.mark.parametrize("window,gain", [("blackman_harris", 0.5), ("rect", 2.0)])
+def test_window_and_gain_reach_the_rows_as_they_reach_the_psd(gpu, window, gain):
+    """the other tests run Hann at gain 1: here the two options travel from iqgpu_sgram_opts into the stream core that the Psd holds too"""
+    fmt, nfft, hop, R, bpf = "cs16", 1024, 256, 3, 4
+    raw = case_input(fmt, nfft, hop, R)
+    assert raw.size // bpf == 2597
+    acc = gpu.Sgram(fmt, nfft=nfft, hop=hop, window=window, gain=gain, row_segments=R)
+    row_sum, row_peak = acc.push(raw)
+    open_sum, open_peak, info = acc.read_open()
+    assert row_sum.shape == row_peak.shape == (2, nfft) and info["open_segments"] == 1
+    for r in range(3):                     # the two finished rows, then the open one
+        first, segs = r * R * hop, R if r < 2 else 1
+        ref = gpu.Psd(fmt, nfft=nfft, hop=hop, window=window, gain=gain)
+        ref.push(raw[first * bpf:(first + frames_for(segs, nfft, hop)) * bpf])
+        s, k, ref_info = ref.read()
+        assert ref_info["segments"] == segs and s.any()
+        assert (ref_info["window_sum"], ref_info["window_sum_sq"]) == (info["window_sum"], info["window_sum_sq"])
+        if r < 2:
+            assert row_sum[r].tobytes() == s.astype(np.float32).tobytes(), "row_sum of row %d" % r
+            assert row_peak[r].tobytes() == k.tobytes(), "row_peak of row %d" % r
+        else:
+            assert open_sum.tobytes() == s.tobytes() and open_peak.tobytes() == k.tobytes()
 
 
 @pytest.mark.parametrize("R,open_segs", [(70, 31), (70, 32), (70, 33), (70, 69), (33, 32), (3, 2), (40, 0)])
