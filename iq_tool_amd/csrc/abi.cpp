@@ -142,66 +142,9 @@ extern "C" void iqgpu_chain_desc_init(iqgpu_chain_desc *d)
 // ------------------------------------------------------------------------------------------------
 // create / destroy
 // ------------------------------------------------------------------------------------------------
-static void free_device_state(iqgpu_chain *c)
-{
-    (void)hipSetDevice(c->device);
-    if (c->d_nco_tab) (void)hipFree(c->d_nco_tab);
-    if (c->d_arb) (void)hipFree(c->d_arb);
-    if (c->d_hb) (void)hipFree(c->d_hb);
-    if (c->d_ftaps) (void)hipFree(c->d_ftaps);
-    if (c->d_hfreq) (void)hipFree(c->d_hfreq);
-    if (c->d_ihb) (void)hipFree(c->d_ihb);
-    if (c->d_agc_state) (void)hipFree(c->d_agc_state);
-    c->abuf.release(); c->agc_peak.release(); c->agc_gain.release(); c->agc_peak_b.release(); c->agc_hist.release();
-    c->agc_rows.release(); c->agc_walk.release(); c->agc_scratch.release();
-    if (c->d_agc_flag) (void)hipFree(c->d_agc_flag);
-    if (c->h_agc_verdict) (void)hipHostFree((void *)c->h_agc_verdict);
-    if (c->d_twiddle) (void)hipFree(c->d_twiddle);
-    for (int i = 0; i < 2; ++i) if (c->d_hist[i]) (void)hipFree(c->d_hist[i]);
-    for (int i = 0; i < 2; ++i) if (c->d_hist2[i]) (void)hipFree(c->d_hist2[i]);
-    c->mid.release();
-    if (c->d_dc_state) (void)hipFree(c->d_dc_state);
-    if (c->d_sink) (void)hipFree(c->d_sink);
-    c->steal_buf.release();
-    c->dc_agg.release(); c->dc_carry.release(); c->dc_walk.release();
-    c->dc_range_tab.release(); c->dc_range_map.release(); c->dc_range_in[0].release(); c->dc_range_in[1].release();
-    for (int i = 0; i < 2; ++i) {
-        if (c->dc_range_in_done[i]) (void)hipEventDestroy(c->dc_range_in_done[i]);
-        if (c->dc_range_k_done[i]) (void)hipEventDestroy(c->dc_range_k_done[i]);
-    }
-    if (c->dc_range_h2d) (void)hipStreamDestroy(c->dc_range_h2d);
-    c->fbuf[0].release(); c->fbuf[1].release();
-    c->ibuf[0].release(); c->ibuf[1].release();
-    c->stage_in.release(); c->stage_out.release(); c->seek_sink.release(); c->seek_win.release();
-    c->iq_cal_tab.release(); c->iq_cal_in.release(); c->iq_cal_blocks.release(); c->iq_cal_work.release();
-    if (c->d_probe) (void)hipFree(c->d_probe);
-    if (c->h_probe) (void)hipHostFree(c->h_probe);
-    if (c->probe_done) (void)hipEventDestroy(c->probe_done);
-    for (auto &ps : c->pipe) {
-        ps.d_in.release(); ps.d_out.release(); ps.d_rows.release();
-        if (ps.in_done) (void)hipEventDestroy(ps.in_done);
-        if (ps.k_done) (void)hipEventDestroy(ps.k_done);
-        if (ps.all_done) (void)hipEventDestroy(ps.all_done);
-    }
-    for (hipStream_t st : c->pipe_h2d) if (st) (void)hipStreamDestroy(st);
-    for (hipStream_t st : c->pipe_d2h) if (st) (void)hipStreamDestroy(st);
-    for (auto &pe : c->pending_events) { (void)hipEventDestroy(pe.second.first); (void)hipEventDestroy(pe.second.second); }
-    for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
-}
-
 // the eight words behind d_agc_flag as a chain starts (and restarts, iqgpu_chain_reset) with them; static storage: the reset's
 // asynchronous copy reads it after the call has returned
 const int32_t kAgcFlagInit[8] = {0, 0, 0, -1, 0, 0, 0, 0};
-
-template <typename T>
-static int upload(T **dst, const T *src, size_t n)
-{
-    if (n == 0) { *dst = nullptr; return IQGPU_OK; }
-    if (hipMalloc((void **)dst, n * sizeof(T)) != hipSuccess) return fail(IQGPU_ENOMEM, "hipMalloc(%zu) failed", n * sizeof(T));
-    HIP_TRY(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
-    return IQGPU_OK;
-}
 
 // Everything create() derives on the host: validation (the reference's fatal paths), ratio,
 // operator constants, resampler / filter plans and launch geometry.  Touches no device.
@@ -345,190 +288,179 @@ int design_chain(iqgpu_chain *c, const iqgpu_chain_desc *d)
     return IQGPU_OK;
 }
 
+// overlap-save path: every FFT-kind filter, and FIR-kind ones long enough that two transforms
+// per window beat the direct form (the two are the same linear convolution, SPEC B.3): the transform size, the fused kernel's
+// window geometry, H and the twiddle table
+static int setup_overlap_save(iqgpu_chain *c)
+{
+    const size_t Lt = c->fp.taps.size();
+    if (!(c->fp.enabled && !c->sw.force_generic && Lt >= 2 && 2 * (Lt - 1) <= (size_t)kMaxFftN &&
+          (c->fp.block > 0 || Lt >= (size_t)kFftMinTaps))) return IQGPU_OK;
+    // N = 4 (L-1) rounded up to a power of two in [256, 4096], larger (up to 16384, in place in LDS) only
+    // when the taps need it; measured with k_fftconv16 (round 4: first and last pass in registers) on config 3 (1025 taps):
+    // N 2048 0.25 ms, 4096 0.15, 8192 0.16, 16384 0.21; on config 4 (4097 taps): N 8192 0.105 ms, 16384 0.114
+    // (from 1024 points up: the radix-16 kernel.  Round 5: the 97-tap band-pass of the cs16 -usb / -lsb presets ran the
+    //  radix-4 ping-pong kernel at N = 512 and took 1.49 ms for 83 M outputs; at N = 1024 it takes a fifth of that)
+    int lg = (c->sw.dbg & kDbgFftNoR16) ? 8 : 10;
+    while ((size_t)(1 << lg) < 4 * (Lt - 1) && (1 << lg) < 4096) ++lg;
+    while ((size_t)(1 << lg) < 2 * (Lt - 1)) ++lg;
+    // round 6: a chain WITHOUT a half-band stage whose filter stands behind the resampler CAN run both in one kernel (k_p0fft16,
+    // p0fft.hpp: no cf32 stream in HBM) -- built, byte-equal to the two kernels on the same windows, and slower than they are
+    // (1.43 ms against 1.17 - 1.25 per 2^28 cu8 frames: the polyphase role's registers leave the transforms two waves per SIMD,
+    // profiles/r06_fused_filter.md): opt-in, iqgpu_debug_set("fuse_filter", "1").  That kernel's workgroup carries 35 KB of tap
+    // planes beside its transform buffer, which wants 4096 points (four waves per workgroup, two workgroups per CU) -- the
+    // chain's transform is then that size on either path
+    // (diagnostics: "fft_geometry" = "keep" runs the two kernels at the fused kernel's transform size and on its windows -- win
+    //  stream samples and vout outputs per block -- so that the two paths can be compared byte for byte)
+    if (c->decim && c->S == 0 && !c->late && c->fp.post_resample && !(c->sw.dbg & (kDbgFftNoR16 | kDbgNoP0 | kDbgNoFusedMove)) &&
+        ((c->sw.dbg & kDbgFuseFilter) || c->sw.fft_keep_geometry)) {
+        FrontArgs ff{};
+        ff.dbg = c->sw.dbg; ff.S = 0; ff.in_fmt = c->desc.in_format; ff.gain = c->desc.gain;
+        ff.iq_enable = c->desc.iq_correct_enable ? 1 : 0; ff.dc_enable = c->dc ? 1 : 0; ff.nco_mode = c->nco_mode; ff.pnco_mode = 0;
+        ff.step = c->rp.step;
+        const int lgf = lg < 12 ? 12 : lg;
+        if (p0fft_shape(ff, lgf, (int)Lt) && p0fft_geometry(lgf, (int)Lt, &c->fuse_win, &c->fuse_vout)) {
+            c->fuse_filter = (c->sw.dbg & kDbgFuseFilter) != 0; lg = lgf;
+        }
+    }
+    if (c->sw.fft_log2n && (size_t)(1 << c->sw.fft_log2n) >= 2 * (Lt - 1)) lg = c->sw.fft_log2n;
+    if (c->fuse_win > 0 && !p0fft_geometry(lg, (int)Lt, &c->fuse_win, &c->fuse_vout)) { c->fuse_filter = false; c->fuse_win = c->fuse_vout = 0; }   // (a transform size forced by hand)
+    const int N = 1 << lg;
+    c->fft_log2n = lg;
+    // H = FFT_N(taps) / N and the twiddle table, in double on the host (once per chain)
+    std::vector<double> ct((size_t)N), st((size_t)N);
+    const double w0 = -2.0 * 3.14159265358979323846 / (double)N;
+    for (int k = 0; k < N; ++k) { ct[(size_t)k] = std::cos(w0 * k); st[(size_t)k] = std::sin(w0 * k); }
+    std::vector<cf2> tw((size_t)N), hf((size_t)N);
+    for (int k = 0; k < N; ++k) tw[(size_t)k] = cf2{(float)ct[(size_t)k], (float)st[(size_t)k]};
+    for (int p = 0; p < N; ++p) {
+        double hr = 0.0, hi = 0.0;
+        unsigned idx = 0;                                  // p k mod N
+        for (size_t k = 0; k < Lt; ++k) {
+            const double cr = ct[idx], ci = st[idx];
+            hr += c->fp.taps[k].re * cr - c->fp.taps[k].im * ci;
+            hi += c->fp.taps[k].re * ci + c->fp.taps[k].im * cr;
+            idx = (idx + (unsigned)p) & (unsigned)(N - 1);
+        }
+        hf[(size_t)p] = cf2{(float)(hr / N), (float)(hi / N)};
+    }
+    int rc = c->d_twiddle.upload(tw.data(), tw.size()); if (rc) return rc;
+    return c->d_hfreq.upload(hf.data(), hf.size());
+}
+
 extern "C" int iqgpu_chain_create(const iqgpu_chain_desc *d, iqgpu_chain **out)
 {
     if (!d || !out) return fail(IQGPU_EINVAL, "iqgpu_chain_create: NULL argument");
     *out = nullptr;
-    iqgpu_chain *c = new (std::nothrow) iqgpu_chain();
+    struct Owner { iqgpu_chain *c; ~Owner() { delete c; } } owner{new (std::nothrow) iqgpu_chain()};   // a create that fails frees what it got so far
+    iqgpu_chain *c = owner.c;
     if (!c) return fail(IQGPU_ENOMEM, "out of host memory");
-    { const int drc = design_chain(c, d); if (drc != IQGPU_OK) { delete c; return drc; } }
+    int rc = design_chain(c, d); if (rc) return rc;
 
     // ---- device ----
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { int rc = fail(IQGPU_ENODEV, "no HIP device available"); delete c;
-        return rc; }
-    if (c->device < 0 || c->device >= ndev) { int rc = fail(IQGPU_ENODEV, "device_ordinal %d out of range (%d devices)", c->device,
-        ndev); delete c; return rc; }
-    int rc = IQGPU_OK;
-#define CREATE_TRY(expr)                                                                                         \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) { rc = fail(IQGPU_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); goto bad; } \
-    } while (0)
-#define CREATE_RC(expr) do { rc = (expr); if (rc != IQGPU_OK) goto bad; } while (0)
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(IQGPU_ENODEV, "no HIP device available");
+    if (c->device < 0 || c->device >= ndev) return fail(IQGPU_ENODEV, "device_ordinal %d out of range (%d devices)", c->device, ndev);
+    HIP_TRY(hipSetDevice(c->device));
     {
-        CREATE_TRY(hipSetDevice(c->device));
-        {
-            int ncu = 0;
-            if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && ncu > 0) c->n_cu = ncu;
-            // (diagnostic: cus=n plans every launch for n CUs -- how does a CU's throughput depend on how many of them work?)
-            if (c->sw.cus >= 8 && c->sw.cus <= c->n_cu) c->n_cu = c->sw.cus;
-        }
-        CREATE_TRY(hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking));
-        c->stream = c->own_stream;
-        std::vector<cfloat> tab(1024);
-        nco_fill_sincos(tab.data());
-        CREATE_RC(upload(&c->d_nco_tab, (const cf2 *)tab.data(), 1024));
-        if (c->late) {
-            CREATE_RC(upload(&c->d_arb, c->rp.arb_table.data(), c->rp.arb_table.size()));
-            std::vector<float> hb;
-            for (int s2 = 0; s2 < c->ia.S; ++s2)
-                for (float v : c->rp.stages[(size_t)(c->ia.S - 1 - s2)].branch) hb.push_back(v);
-            if (hb.empty()) hb.push_back(0.0f);
-            CREATE_RC(upload(&c->d_ihb, hb.data(), hb.size()));
-            for (int i = 0; i < 2; ++i) {
-                CREATE_RC(c->ibuf[i].ensure(((size_t)c->ihist + 1) * sizeof(cf2)));
-                CREATE_TRY(hipMemset(c->ibuf[i].p, 0, c->ibuf[i].cap));
-            }
-        }
-        if (c->decim) {
-            CREATE_RC(upload(&c->d_arb, c->rp.arb_table.data(), c->rp.arb_table.size()));
-            std::vector<float> hb;
-            for (int i = 0; i < c->S; ++i) {
-                c->tap_off[i] = (int)hb.size();
-                for (float v : c->rp.stages[(size_t)i].branch) hb.push_back(0.5f * v);   // per-stage gain 1/2 (exact)
-            }
-            c->n_hb_taps = (int)hb.size();
-            if (hb.empty()) hb.push_back(0.0f);
-            CREATE_RC(upload(&c->d_hb, hb.data(), hb.size()));
-            for (int i = 0; i < 2; ++i) {
-                CREATE_TRY(hipMalloc((void **)&c->d_hist[i], (size_t)c->hist_cap * sizeof(cf2)));
-                CREATE_TRY(hipMemset(c->d_hist[i], 0, (size_t)c->hist_cap * sizeof(cf2)));
-                if (c->cascade) {
-                    CREATE_TRY(hipMalloc((void **)&c->d_hist2[i], (size_t)c->hist2_cap * sizeof(cf2)));
-                    CREATE_TRY(hipMemset(c->d_hist2[i], 0, (size_t)c->hist2_cap * sizeof(cf2)));
-                }
-            }
-        }
-        if (c->agc) {
-            CREATE_TRY(hipMalloc((void **)&c->d_agc_state, sizeof(AgcState)));
-            c->agc_init = AgcState{0, c->agc_rms_alpha > 0.0f ? 1.0f : 0.05f, 1.0f, 0, c->desc.agc_clock == IQGPU_AGC_CLOCK_WALL
-                ? monotonic_sec() : 0.0, 0};
-            CREATE_TRY(hipMemcpy(c->d_agc_state, &c->agc_init, sizeof(AgcState), hipMemcpyHostToDevice));
-            {   // [0] verdict of the verifier, [1] ratchet seen, [2] weak chunk seen, [3] last healthy chunk (agc.hip)
-                // ... [4] the tickets of k_agc_classify's workgroups (kAgcFlagInit)
-                CREATE_TRY(hipMalloc((void **)&c->d_agc_flag, sizeof(kAgcFlagInit)));
-                CREATE_TRY(hipMemcpy(c->d_agc_flag, kAgcFlagInit, sizeof(kAgcFlagInit), hipMemcpyHostToDevice));
-                // the verdict's second home: one word of pinned, device-visible host memory (chain.hpp, h_agc_verdict)
-                void *hv = nullptr, *dv = nullptr;
-                CREATE_TRY(hipHostMalloc(&hv, 64, hipHostMallocMapped | hipHostMallocCoherent));
-                c->h_agc_verdict = (volatile int32_t *)hv; c->h_agc_verdict[0] = 0;
-                CREATE_TRY(hipHostGetDevicePointer(&dv, hv, 0));
-                c->d_agc_verdict = (int32_t *)dv;
-            }
-            // the fused path exists for the specialised front kernel: the shipped cs16 NRSC-5 preset shape
-            FrontArgs fa{};
-            fa.dbg = c->sw.dbg;
-            fa.S = c->S; fa.in_fmt = c->desc.in_format; fa.out_fmt = c->desc.out_format; fa.gain = c->desc.gain;
-            fa.iq_enable = c->desc.iq_correct_enable ? 1 : 0; fa.dc_enable = c->dc ? 1 : 0;
-            fa.nco_mode = c->nco_mode; fa.pnco_mode = c->pnco_mode; fa.agc_chunk_frames = c->agc_chunk; fa.agc_shift = c->S;
-            if (c->cascade) { fa.S = 1; fa.in_fmt = IQGPU_FMT_CF32; }      // k_cascade in front: the last stage sees cf32, one half-band
-            if (c->agc_rms_alpha > 0.0f) {
-                int64_t chunk = 0; int32_t nch = 0;
-                agc_rms_geometry(c->agc_rms_alpha, 0, 0, &chunk, &c->agc_rms_warm, &nch);
-                CREATE_RC(c->agc_hist.ensure(((size_t)c->agc_rms_warm + 1) * sizeof(cf2)));
-                CREATE_TRY(hipMemset(c->agc_hist.p, 0, c->agc_hist.cap));
-            }
-            c->agc_fusable = c->agc_rms_alpha == 0.0f && c->decim && !c->late && !c->sw.force_generic && !c->fp.enabled &&
-                             (c->cascade || c->S == 0 || (c->S == 1 && c->rp.stages[0].m == 10)) && front_s1_agc_fusable(fa);
-        }
-        if (c->fp.enabled) CREATE_RC(upload(&c->d_ftaps, (const cf2 *)c->fp.taps.data(), c->fp.taps.size()));
-        // overlap-save path: every FFT-kind filter, and FIR-kind ones long enough that two transforms
-        // per window beat the direct form (the two are the same linear convolution, SPEC B.3)
-        const size_t Lt = c->fp.taps.size();
-        if (c->fp.enabled && !c->sw.force_generic && Lt >= 2 && 2 * (Lt - 1) <= (size_t)kMaxFftN &&
-            (c->fp.block > 0 || Lt >= (size_t)kFftMinTaps)) {
-            // N = 4 (L-1) rounded up to a power of two in [256, 4096], larger (up to 16384, in place in LDS) only
-            // when the taps need it; measured with k_fftconv16 (round 4: first and last pass in registers) on config 3 (1025 taps):
-            // N 2048 0.25 ms, 4096 0.15, 8192 0.16, 16384 0.21; on config 4 (4097 taps): N 8192 0.105 ms, 16384 0.114
-            // (from 1024 points up: the radix-16 kernel.  Round 5: the 97-tap band-pass of the cs16 -usb / -lsb presets ran the
-            //  radix-4 ping-pong kernel at N = 512 and took 1.49 ms for 83 M outputs; at N = 1024 it takes a fifth of that)
-            int lg = (c->sw.dbg & kDbgFftNoR16) ? 8 : 10;
-            while ((size_t)(1 << lg) < 4 * (Lt - 1) && (1 << lg) < 4096) ++lg;
-            while ((size_t)(1 << lg) < 2 * (Lt - 1)) ++lg;
-            // round 6: a chain WITHOUT a half-band stage whose filter stands behind the resampler CAN run both in one kernel (k_p0fft16,
-            // p0fft.hpp: no cf32 stream in HBM) -- built, byte-equal to the two kernels on the same windows, and slower than they are
-            // (1.43 ms against 1.17 - 1.25 per 2^28 cu8 frames: the polyphase role's registers leave the transforms two waves per SIMD,
-            // profiles/r06_fused_filter.md): opt-in, iqgpu_debug_set("fuse_filter", "1").  That kernel's workgroup carries 35 KB of tap
-            // planes beside its transform buffer, which wants 4096 points (four waves per workgroup, two workgroups per CU) -- the
-            // chain's transform is then that size on either path
-            // (diagnostics: "fft_geometry" = "keep" runs the two kernels at the fused kernel's transform size and on its windows -- win
-            //  stream samples and vout outputs per block -- so that the two paths can be compared byte for byte)
-            if (c->decim && c->S == 0 && !c->late && c->fp.post_resample && !(c->sw.dbg & (kDbgFftNoR16 | kDbgNoP0 | kDbgNoFusedMove)) &&
-                ((c->sw.dbg & kDbgFuseFilter) || c->sw.fft_keep_geometry)) {
-                FrontArgs ff{};
-                ff.dbg = c->sw.dbg; ff.S = 0; ff.in_fmt = c->desc.in_format; ff.gain = c->desc.gain;
-                ff.iq_enable = c->desc.iq_correct_enable ? 1 : 0; ff.dc_enable = c->dc ? 1 : 0; ff.nco_mode = c->nco_mode; ff.pnco_mode = 0;
-                ff.step = c->rp.step;
-                const int lgf = lg < 12 ? 12 : lg;
-                if (p0fft_shape(ff, lgf, (int)Lt) && p0fft_geometry(lgf, (int)Lt, &c->fuse_win, &c->fuse_vout)) {
-                    c->fuse_filter = (c->sw.dbg & kDbgFuseFilter) != 0; lg = lgf;
-                }
-            }
-            if (c->sw.fft_log2n && (size_t)(1 << c->sw.fft_log2n) >= 2 * (Lt - 1)) lg = c->sw.fft_log2n;
-            if (c->fuse_win > 0 && !p0fft_geometry(lg, (int)Lt, &c->fuse_win, &c->fuse_vout)) { c->fuse_filter = false; c->fuse_win = c->fuse_vout = 0; }   // (a transform size forced by hand)
-            const int N = 1 << lg;
-            c->fft_log2n = lg;
-            // H = FFT_N(taps) / N and the twiddle table, in double on the host (once per chain)
-            std::vector<double> ct((size_t)N), st((size_t)N);
-            const double w0 = -2.0 * 3.14159265358979323846 / (double)N;
-            for (int k = 0; k < N; ++k) { ct[(size_t)k] = std::cos(w0 * k); st[(size_t)k] = std::sin(w0 * k); }
-            std::vector<cf2> tw((size_t)N), hf((size_t)N);
-            for (int k = 0; k < N; ++k) tw[(size_t)k] = cf2{(float)ct[(size_t)k], (float)st[(size_t)k]};
-            for (int p = 0; p < N; ++p) {
-                double hr = 0.0, hi = 0.0;
-                unsigned idx = 0;                                  // p k mod N
-                for (size_t k = 0; k < Lt; ++k) {
-                    const double cr = ct[idx], ci = st[idx];
-                    hr += c->fp.taps[k].re * cr - c->fp.taps[k].im * ci;
-                    hi += c->fp.taps[k].re * ci + c->fp.taps[k].im * cr;
-                    idx = (idx + (unsigned)p) & (unsigned)(N - 1);
-                }
-                hf[(size_t)p] = cf2{(float)(hr / N), (float)(hi / N)};
-            }
-            CREATE_RC(upload(&c->d_twiddle, tw.data(), tw.size()));
-            CREATE_RC(upload(&c->d_hfreq, hf.data(), hf.size()));
-        }
-        // the digital AGC behind a post-resample filter on the overlap-save path: gain and per-chunk peaks in k_fftconv16's epilogue past
-        // the lock.  A block of the filter must not hold more than one chunk boundary: a chunk's outputs (less the block quantisation's
-        // slack) have to outnumber a workgroup's
-        if (c->agc && c->agc_rms_alpha == 0.0f && c->decim && !c->late && !c->sw.force_generic && c->fp.enabled && c->fp.post_resample && c->d_hfreq &&
-            fftconv_agc_fusable(c->fft_log2n, (int)c->fp.taps.size(), c->sw.dbg)) {
-            const double chunk_out = (double)c->agc_chunk * (double)c->ratio - (double)c->fp.block - 2.0;
-            c->agc_fusable_filter = chunk_out >= (double)(1 << c->fft_log2n);
-        }
-        CREATE_TRY(hipMalloc((void **)&c->d_dc_state, sizeof(cd2)));
-        CREATE_TRY(hipMemset(c->d_dc_state, 0, sizeof(cd2)));
-        CREATE_TRY(hipMalloc(&c->d_sink, 64 * 1024));
-        CREATE_TRY(hipMemset(c->d_sink, 0, 64 * 1024));
-        if (c->fp.enabled) {
-            // the filter-input buffer starts as ntaps-1 zeros of history
-            const size_t h = c->fp.taps.size() - 1;
-            for (int i = 0; i < 2; ++i) {
-                CREATE_RC(c->fbuf[i].ensure((h + 1) * sizeof(cf2)));
-                CREATE_TRY(hipMemset(c->fbuf[i].p, 0, c->fbuf[i].cap));
-            }
-        }
-        CREATE_TRY(hipDeviceSynchronize());
+        int ncu = 0;
+        if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device) == hipSuccess && ncu > 0) c->n_cu = ncu;
+        // (diagnostic: cus=n plans every launch for n CUs -- how does a CU's throughput depend on how many of them work?)
+        if (c->sw.cus >= 8 && c->sw.cus <= c->n_cu) c->n_cu = c->sw.cus;
     }
-    *out = c;
+    HIP_TRY(c->own_stream.create());
+    c->stream = c->own_stream;
+    std::vector<cfloat> tab(1024);
+    nco_fill_sincos(tab.data());
+    rc = c->d_nco_tab.upload((const cf2 *)tab.data(), 1024); if (rc) return rc;
+    if (c->late) {
+        rc = c->d_arb.upload(c->rp.arb_table.data(), c->rp.arb_table.size()); if (rc) return rc;
+        std::vector<float> hb;
+        for (int s2 = 0; s2 < c->ia.S; ++s2)
+            for (float v : c->rp.stages[(size_t)(c->ia.S - 1 - s2)].branch) hb.push_back(v);
+        if (hb.empty()) hb.push_back(0.0f);
+        rc = c->d_ihb.upload(hb.data(), hb.size()); if (rc) return rc;
+        for (int i = 0; i < 2; ++i) {
+            rc = c->ibuf[i].ensure(((size_t)c->ihist + 1) * sizeof(cf2)); if (rc) return rc;
+            HIP_TRY(hipMemset(c->ibuf[i].p, 0, c->ibuf[i].cap));
+        }
+    }
+    if (c->decim) {
+        rc = c->d_arb.upload(c->rp.arb_table.data(), c->rp.arb_table.size()); if (rc) return rc;
+        std::vector<float> hb;
+        for (int i = 0; i < c->S; ++i) {
+            c->tap_off[i] = (int)hb.size();
+            for (float v : c->rp.stages[(size_t)i].branch) hb.push_back(0.5f * v);   // per-stage gain 1/2 (exact)
+        }
+        c->n_hb_taps = (int)hb.size();
+        if (hb.empty()) hb.push_back(0.0f);
+        rc = c->d_hb.upload(hb.data(), hb.size()); if (rc) return rc;
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(c->d_hist[i].alloc((size_t)c->hist_cap));
+            HIP_TRY(hipMemset(c->d_hist[i], 0, (size_t)c->hist_cap * sizeof(cf2)));
+            if (c->cascade) {
+                HIP_TRY(c->d_hist2[i].alloc((size_t)c->hist2_cap));
+                HIP_TRY(hipMemset(c->d_hist2[i], 0, (size_t)c->hist2_cap * sizeof(cf2)));
+            }
+        }
+    }
+    if (c->agc) {
+        HIP_TRY(c->d_agc_state.alloc(1));
+        c->agc_init = AgcState{0, c->agc_rms_alpha > 0.0f ? 1.0f : 0.05f, 1.0f, 0, c->desc.agc_clock == IQGPU_AGC_CLOCK_WALL
+            ? monotonic_sec() : 0.0, 0};
+        HIP_TRY(hipMemcpy(c->d_agc_state, &c->agc_init, sizeof(AgcState), hipMemcpyHostToDevice));
+        {   // [0] verdict of the verifier, [1] ratchet seen, [2] weak chunk seen, [3] last healthy chunk (agc.hip)
+            // ... [4] the tickets of k_agc_classify's workgroups (kAgcFlagInit)
+            HIP_TRY(c->d_agc_flag.alloc(sizeof(kAgcFlagInit) / sizeof(int32_t)));
+            HIP_TRY(hipMemcpy(c->d_agc_flag, kAgcFlagInit, sizeof(kAgcFlagInit), hipMemcpyHostToDevice));
+            // the verdict's second home: one word of pinned, device-visible host memory (chain.hpp, h_agc_verdict)
+            void *dv = nullptr;
+            HIP_TRY(c->h_agc_verdict.alloc(16, hipHostMallocMapped | hipHostMallocCoherent));
+            c->h_agc_verdict[0] = 0;
+            HIP_TRY(hipHostGetDevicePointer(&dv, (void *)c->h_agc_verdict.p, 0));
+            c->d_agc_verdict = (int32_t *)dv;
+        }
+        // the fused path exists for the specialised front kernel: the shipped cs16 NRSC-5 preset shape
+        FrontArgs fa{};
+        fa.dbg = c->sw.dbg;
+        fa.S = c->S; fa.in_fmt = c->desc.in_format; fa.out_fmt = c->desc.out_format; fa.gain = c->desc.gain;
+        fa.iq_enable = c->desc.iq_correct_enable ? 1 : 0; fa.dc_enable = c->dc ? 1 : 0;
+        fa.nco_mode = c->nco_mode; fa.pnco_mode = c->pnco_mode; fa.agc_chunk_frames = c->agc_chunk; fa.agc_shift = c->S;
+        if (c->cascade) { fa.S = 1; fa.in_fmt = IQGPU_FMT_CF32; }      // k_cascade in front: the last stage sees cf32, one half-band
+        if (c->agc_rms_alpha > 0.0f) {
+            int64_t chunk = 0; int32_t nch = 0;
+            agc_rms_geometry(c->agc_rms_alpha, 0, 0, &chunk, &c->agc_rms_warm, &nch);
+            rc = c->agc_hist.ensure(((size_t)c->agc_rms_warm + 1) * sizeof(cf2)); if (rc) return rc;
+            HIP_TRY(hipMemset(c->agc_hist.p, 0, c->agc_hist.cap));
+        }
+        c->agc_fusable = c->agc_rms_alpha == 0.0f && c->decim && !c->late && !c->sw.force_generic && !c->fp.enabled &&
+                         (c->cascade || c->S == 0 || (c->S == 1 && c->rp.stages[0].m == 10)) && front_s1_agc_fusable(fa);
+    }
+    if (c->fp.enabled) { rc = c->d_ftaps.upload((const cf2 *)c->fp.taps.data(), c->fp.taps.size()); if (rc) return rc; }
+    rc = setup_overlap_save(c); if (rc) return rc;
+    // the digital AGC behind a post-resample filter on the overlap-save path: gain and per-chunk peaks in k_fftconv16's epilogue past
+    // the lock.  A block of the filter must not hold more than one chunk boundary: a chunk's outputs (less the block quantisation's
+    // slack) have to outnumber a workgroup's
+    if (c->agc && c->agc_rms_alpha == 0.0f && c->decim && !c->late && !c->sw.force_generic && c->fp.enabled && c->fp.post_resample && c->d_hfreq &&
+        fftconv_agc_fusable(c->fft_log2n, (int)c->fp.taps.size(), c->sw.dbg)) {
+        const double chunk_out = (double)c->agc_chunk * (double)c->ratio - (double)c->fp.block - 2.0;
+        c->agc_fusable_filter = chunk_out >= (double)(1 << c->fft_log2n);
+    }
+    HIP_TRY(c->d_dc_state.alloc(1));
+    HIP_TRY(hipMemset(c->d_dc_state, 0, sizeof(cd2)));
+    HIP_TRY(c->d_sink.alloc(64 * 1024));
+    HIP_TRY(hipMemset(c->d_sink, 0, 64 * 1024));
+    if (c->fp.enabled) {
+        // the filter-input buffer starts as ntaps-1 zeros of history
+        const size_t h = c->fp.taps.size() - 1;
+        for (int i = 0; i < 2; ++i) {
+            rc = c->fbuf[i].ensure((h + 1) * sizeof(cf2)); if (rc) return rc;
+            HIP_TRY(hipMemset(c->fbuf[i].p, 0, c->fbuf[i].cap));
+        }
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    *out = c; owner.c = nullptr;
     return IQGPU_OK;
-bad:
-    free_device_state(c);
-    delete c;
-    return rc;
-#undef CREATE_TRY
-#undef CREATE_RC
 }
 
 extern "C" void iqgpu_chain_destroy(iqgpu_chain *c)
@@ -540,7 +472,6 @@ extern "C" void iqgpu_chain_destroy(iqgpu_chain *c)
     (void)agc_resolve_pending(c);
     (void)hipStreamSynchronize(c->stream);
     for (hipStream_t st : c->pipe_d2h) if (st) (void)hipStreamSynchronize(st);
-    free_device_state(c);
     delete c;
 }
 
@@ -613,19 +544,13 @@ extern "C" int iqgpu_chain_enable_iq_probe(iqgpu_chain *c, int enable)
     HIP_TRY(hipSetDevice(c->device));
     if (enable && !(c->d_probe && c->h_probe && c->probe_done)) {
         // all three resources or none: a partial failure leaves nothing behind, so that a second enable() starts over
-        cf2 *dp = nullptr, *hp = nullptr; hipEvent_t ev = nullptr;
-        const bool ok = hipMalloc((void **)&dp, 1024 * sizeof(cf2)) == hipSuccess &&
-                        hipHostMalloc((void **)&hp, 1024 * sizeof(cf2), hipHostMallocDefault) == hipSuccess &&
-                        hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess;
-        if (!ok) {
-            if (ev) (void)hipEventDestroy(ev);
-            if (hp) (void)hipHostFree(hp);
-            if (dp) (void)hipFree(dp);
+        DevMem<cf2> dp; HostMem<cf2> hp; Event ev;
+        if (dp.alloc(1024) != hipSuccess || hp.alloc(1024, hipHostMallocDefault) != hipSuccess || ev.create(hipEventDisableTiming) != hipSuccess) {
             (void)hipGetLastError();
             return fail(IQGPU_ENOMEM, "iqgpu_chain_enable_iq_probe: could not allocate the probe buffers");
         }
         std::lock_guard<std::mutex> g(c->aux_mu);
-        c->d_probe = dp; c->h_probe = hp; c->probe_done = ev;
+        c->d_probe = std::move(dp); c->h_probe = std::move(hp); c->probe_done = std::move(ev);
     }
     { std::lock_guard<std::mutex> g(c->aux_mu); c->probe_on = enable != 0; }     // process_one reads it under the same lock
     return IQGPU_OK;

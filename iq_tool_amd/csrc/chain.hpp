@@ -25,6 +25,8 @@
 #include <mutex>
 #include <new>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/iqgpu.h"
@@ -87,9 +89,24 @@ std::string debug_value(const char *name);             // ... one raw value ("" 
 // ------------------------------------------------------------------------------------------------
 // the chain object
 // ------------------------------------------------------------------------------------------------
+// Owners of device resources (host only: psd.hip and sgram.hip see this header through psd.hpp and use none of it).  A member of one
+// of these types is freed with the object that holds it, in reverse order of declaration: there is no list of releases to keep.  All
+// are move-only -- a move leaves the source empty -- and none creates anything in a constructor.
+// (IQGPU_LOCAL: the library is not built with -fvisibility=hidden, so without it every inline member of the owners would enter the
+//  dynamic symbol table as a weak symbol; with it the table stays as it was)
+#define IQGPU_LOCAL __attribute__((visibility("hidden")))
+// a device buffer that grows on demand
 struct DevBuf {
     void *p = nullptr;
     size_t cap = 0;
+    DevBuf() = default;
+    IQGPU_LOCAL DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    IQGPU_LOCAL DevBuf &operator=(DevBuf &&o) noexcept
+    {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
+    IQGPU_LOCAL ~DevBuf() { release(); }
     int ensure(size_t bytes)
     {
         if (bytes <= cap) return IQGPU_OK;
@@ -106,16 +123,81 @@ struct DevBuf {
         DevBuf nb;
         int rc = nb.ensure(bytes); if (rc) return rc;
         if (p && keep_bytes) {
-            if (hipMemcpyAsync(nb.p, p, keep_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-                nb.release(); return fail(IQGPU_EHIP, "device copy failed while growing a stream buffer");
-            }
+            if (hipMemcpyAsync(nb.p, p, keep_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+                return fail(IQGPU_EHIP, "device copy failed while growing a stream buffer");
         }
-        release();
-        p = nb.p; cap = nb.cap;
+        *this = std::move(nb);
         return IQGPU_OK;
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+
+// n elements of device memory, allocated once: empty, or uploaded from the host (n == 0 leaves it empty)
+template <typename T> struct IQGPU_LOCAL DevMem {
+    T *p = nullptr;
+    DevMem() = default;
+    DevMem(DevMem &&o) noexcept : p(o.p) { o.p = nullptr; }
+    DevMem &operator=(DevMem &&o) noexcept { if (this != &o) { release(); p = o.p; o.p = nullptr; } return *this; }
+    ~DevMem() { release(); }
+    operator T *() const { return p; }
+    hipError_t alloc(size_t n)
+    {
+        release();
+        const hipError_t e = n ? hipMalloc((void **)&p, n * sizeof(T)) : hipSuccess;
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    int upload(const T *src, size_t n)
+    {
+        if (alloc(n) != hipSuccess) return fail(IQGPU_ENOMEM, "hipMalloc(%zu) failed", n * sizeof(T));
+        if (n) HIP_TRY(hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice));
+        return IQGPU_OK;
+    }
+    void release() { if (p) (void)hipFree(p); p = nullptr; }
+};
+
+// n elements of pinned host memory (flags: hipHostMalloc's)
+template <typename T> struct IQGPU_LOCAL HostMem {
+    T *p = nullptr;
+    HostMem() = default;
+    HostMem(HostMem &&o) noexcept : p(o.p) { o.p = nullptr; }
+    HostMem &operator=(HostMem &&o) noexcept { if (this != &o) { release(); p = o.p; o.p = nullptr; } return *this; }
+    ~HostMem() { release(); }
+    operator T *() const { return p; }
+    hipError_t alloc(size_t n, unsigned flags)
+    {
+        release();
+        const hipError_t e = hipHostMalloc((void **)&p, n * sizeof(T), flags);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    void release() { if (p) (void)hipHostFree((void *)p); p = nullptr; }
+};
+
+// an event and a stream.  create() on a live owner is a no-op: a lazy set-up that failed half way and runs again keeps what it has
+struct IQGPU_LOCAL Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept { if (this != &o) { release(); e = o.e; o.e = nullptr; } return *this; }
+    ~Event() { release(); }
+    operator hipEvent_t() const { return e; }
+    hipError_t create(unsigned flags) { return e ? hipSuccess : hipEventCreateWithFlags(&e, flags); }
+    void release() { if (e) (void)hipEventDestroy(e); e = nullptr; }
+};
+struct IQGPU_LOCAL Stream {
+    hipStream_t s = nullptr;
+    Stream() = default;
+    Stream(Stream &&o) noexcept : s(o.s) { o.s = nullptr; }
+    Stream &operator=(Stream &&o) noexcept { if (this != &o) { release(); s = o.s; o.s = nullptr; } return *this; }
+    ~Stream() { release(); }
+    operator hipStream_t() const { return s; }
+    hipError_t create() { return s ? hipSuccess : hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+    void release() { if (s) (void)hipStreamDestroy(s); s = nullptr; }
+};
+static_assert(!std::is_copy_constructible<DevBuf>::value && !std::is_copy_assignable<DevBuf>::value, "DevBuf owns its memory");
+static_assert(!std::is_copy_constructible<DevMem<float>>::value && !std::is_copy_constructible<HostMem<float>>::value, "owners do not copy");
+static_assert(!std::is_copy_constructible<Event>::value && !std::is_copy_constructible<Stream>::value, "owners do not copy");
 
 struct iqgpu_chain {
     static constexpr int kPipeSlots = 8;
@@ -152,16 +234,17 @@ struct iqgpu_chain {
     // iqgpu_chain_tell, the header of a saved state
     uint64_t total_in = 0, total_out = 0;
     // device state
-    hipStream_t own_stream = nullptr, stream = nullptr;
-    cf2 *d_nco_tab = nullptr; float *d_arb = nullptr; float *d_hb = nullptr; cf2 *d_ftaps = nullptr;
-    cf2 *d_hfreq = nullptr, *d_twiddle = nullptr; int fft_log2n = 0;   // overlap-save path of FFT-kind filters
-    cf2 *d_hist[2] = {nullptr, nullptr}; int hist_cur = 0;
+    // (own_stream in front of every buffer and event: it is destroyed behind them.  stream: the one in use, not owned -- iqgpu_chain_set_stream)
+    Stream own_stream; hipStream_t stream = nullptr;
+    DevMem<cf2> d_nco_tab; DevMem<float> d_arb, d_hb; DevMem<cf2> d_ftaps;
+    DevMem<cf2> d_hfreq, d_twiddle; int fft_log2n = 0;   // overlap-save path of FFT-kind filters
+    DevMem<cf2> d_hist[2]; int hist_cur = 0;
     // S >= 2 without a dc blocker: k_cascade (stages 0 .. S-2) -> mid -> k_front_s1 (last stage + polyphase)
     bool cascade = false; int hist2_cap = 0, casc_warm = 1;
-    cf2 *d_hist2[2] = {nullptr, nullptr}; int hist2_cur = 0;
+    DevMem<cf2> d_hist2[2]; int hist2_cur = 0;
     DevBuf mid;
-    cd2 *d_dc_state = nullptr;
-    void *d_sink = nullptr;      // diagnostic scratch of k_front_s1 (iqgpu_chain_debug_read_scratch)
+    DevMem<cd2> d_dc_state;
+    DevMem<unsigned char> d_sink;     // diagnostic scratch of k_front_s1 (iqgpu_chain_debug_read_scratch)
     // run descriptors of k_front_mid (kernels.hpp, FrontArgs::w_steal; sw.steal*): one per wave of a launch; all exhausted between
     // launches (zeroed when the array is (re)allocated)
     DevBuf steal_buf;
@@ -171,11 +254,11 @@ struct iqgpu_chain {
     // ... and the measure pass over a whole range (iqgpu_chain_*_dc_measure_range): the entry table and the maps of all its pieces;
     // the host variants' two staging slices, their copy stream and, per slice, "copy landed" / "kernels done" (created on first use)
     DevBuf dc_range_tab, dc_range_map, dc_range_in[2];
-    hipStream_t dc_range_h2d = nullptr; hipEvent_t dc_range_in_done[2] = {}, dc_range_k_done[2] = {};
+    Stream dc_range_h2d; Event dc_range_in_done[2], dc_range_k_done[2];
     DevBuf fbuf[2]; int fcur = 0;
     // output AGC (digital profile)
     bool agc = false; float agc_target = 0.9f; int64_t agc_chunk = 16384;
-    AgcState *d_agc_state = nullptr; AgcState agc_init{};
+    DevMem<AgcState> d_agc_state; AgcState agc_init{};
     float agc_rms_alpha = 0.0f;     // > 0: profile dx / local (liquid agc_crcf), AgcState.gain = g, .peak_memory = y2_prime
     DevBuf abuf, agc_peak, agc_gain, agc_peak_b;
     // dx / local: the chunk grid of the parallel scheme belongs to the stream -- its position since the last reset, and the last
@@ -190,7 +273,7 @@ struct iqgpu_chain {
     // "has the stream locked" (a closed form: the first chunk that starts after AGC_DIGITAL_LOCK_TIME of output), the
     // flag the verifier leaves for the fallback launches
     bool agc_fusable = false, agc_locked_host = false; uint64_t agc_seen_host = 0;
-    int32_t *d_agc_flag = nullptr;
+    DevMem<int32_t> d_agc_flag;
     // The verdict on the HOST (round 5).  On the paths where the host waits for a call's output anyway -- iqgpu_chain_process, and
     // submit / collect, whose host moves every batch from stage to stage -- the fallback kernels are not queued behind a fused
     // launch as four launches that normally return at once (~19 us of a 400 us step): k_agc_classify's verdict also lands in a
@@ -198,7 +281,7 @@ struct iqgpu_chain {
     // (the next call into the chain, the batch's D2H copy, reset / synchronize / get_agc_state) reads the word and launches them
     // only when it is set.  iqgpu_chain_process_device keeps the queued scheme: its caller owns the stream and its synchronisation.
     // h_agc_verdict[0]: -1 = a verdict is awaited, 0 / 1 = k_agc_classify's answer
-    volatile int32_t *h_agc_verdict = nullptr; int32_t *d_agc_verdict = nullptr;   // the same word, host and device address
+    HostMem<volatile int32_t> h_agc_verdict; int32_t *d_agc_verdict = nullptr;   // the same word, host and device address (the second: not owned)
     struct PendingVerdict { bool valid = false; bool filter = false; FrontArgs fb; FftConvArgs fc; AgcArgs ga; } pend;
     // ... and the AGC fused into the user filter's epilogue (k_fftconv16) where a filter stands between the resampler and the AGC:
     // the shipped -usb / -lsb presets
@@ -209,15 +292,15 @@ struct iqgpu_chain {
     DevBuf ibuf[2]; int icur = 0;  // k_interp input: [ihist history][new samples]
     InterpArgs ia{};              // geometry of the r >= 1 path
     int ihist = 0;
-    float *d_ihb = nullptr;
+    DevMem<float> d_ihb;
     DevBuf stage_in, stage_out;
     DevBuf seek_sink;             // where iqgpu_chain_seek's warm-up run writes what it emits (dropped)
     DevBuf seek_win;              // iqgpu_chain_dcrms_seek: the cf32 output of all its preroll calls, contiguous, for k_agc_rms_seek
     // pipelined host entry point (iqgpu_chain_submit / _measure_submit / _collect): kPipeSlots batches in flight.  H2D copies,
     // kernels (the chain's stream) and D2H copies each have their own stream; a batch moves to the next stage inside a later
     // submit / collect, once the host has seen the previous stage finish (no device-side event waits: see pipe_advance)
-    struct PipeSlot {
-        hipEvent_t in_done = nullptr, k_done = nullptr, all_done = nullptr;
+    struct IQGPU_LOCAL PipeSlot {
+        Event in_done, k_done, all_done;
         DevBuf d_in, d_out; uint64_t ticket = 0; bool busy = false;
         size_t frames_in = 0, n_emit = 0; void *out = nullptr;
         float iq_mag = 0.0f, iq_phase = 0.0f;          // correction factors as of submit()
@@ -227,7 +310,7 @@ struct iqgpu_chain {
     };
     PipeSlot pipe[kPipeSlots];
     static constexpr int kCopyStreams = 4;                // small copies rotate over them, large ones keep to the first
-    hipStream_t pipe_h2d[kCopyStreams] = {}, pipe_d2h[kCopyStreams] = {};
+    Stream pipe_h2d[kCopyStreams], pipe_d2h[kCopyStreams];
     bool pipe_ready = false;
     uint64_t pipe_seq = 0;        // tickets handed out
     uint64_t pipe_launched = 0;   // tickets whose kernels have been queued (<= pipe_seq)
@@ -240,7 +323,7 @@ struct iqgpu_chain {
     std::mutex aux_mu;
     bool probe_on = false, probe_pending = false, probe_valid = false;
     uint64_t probe_gen = 0;       // counts probe_drop calls: a reader that waited for a copy meanwhile dropped does not publish it
-    cf2 *d_probe = nullptr; cf2 *h_probe = nullptr; hipEvent_t probe_done = nullptr;
+    DevMem<cf2> d_probe; HostMem<cf2> h_probe; Event probe_done;
     cf2 probe_last[1024];
     // I/Q calibration (iq_calib.cpp; buffers of its own, so that a call touches nothing the stream carries): window + twiddle table
     // (uploaded when allocated), the host form's raw blocks, the gathered cf32 blocks, candidates + metrics + power statistics
@@ -253,9 +336,12 @@ struct iqgpu_chain {
     int nco_hold6 = 0, nco_hold8 = 0;
     // profiling
     bool profiling = false;
-    std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending_events;
-    std::vector<hipEvent_t> event_pool;
+    struct IQGPU_LOCAL TimedLaunch { int kind; Event a, b; };
+    std::vector<TimedLaunch> pending_events;
+    std::vector<Event> event_pool;
     iqgpu_profile prof{};
+    // the members free themselves, in reverse order of declaration (a chain that never reached the device holds none: no HIP call)
+    ~iqgpu_chain() { if (own_stream) (void)hipSetDevice(device); }
 };
 
 // ---- create-time design (abi.cpp): validation, ratio, operator constants, plans, launch geometry; touches no device ----
@@ -295,17 +381,17 @@ uint64_t seek_preroll_frames(const iqgpu_chain *c, bool with_dc = true);
 uint64_t seek_rms_preroll_frames(const iqgpu_chain *c);
 
 // ---- profiling (process.cpp): HIP events around every launch while profiling is on ----
-hipEvent_t get_event(iqgpu_chain *c);
+Event get_event(iqgpu_chain *c);
 void drain_events(iqgpu_chain *c);
 struct KernelTimer {
-    iqgpu_chain *c; int kind; hipEvent_t a = nullptr, b = nullptr;
-    KernelTimer(iqgpu_chain *c_, int kind_) : c(c_), kind(kind_)
+    iqgpu_chain *c; int kind; Event a, b;
+    IQGPU_LOCAL KernelTimer(iqgpu_chain *c_, int kind_) : c(c_), kind(kind_)
     {
         if (c->profiling) { a = get_event(c); b = get_event(c); (void)hipEventRecord(a, c->stream); }
     }
     ~KernelTimer()
     {
-        if (c->profiling) { (void)hipEventRecord(b, c->stream); c->pending_events.push_back({kind, {a, b}}); }
+        if (c->profiling) { (void)hipEventRecord(b, c->stream); c->pending_events.push_back({kind, std::move(a), std::move(b)}); }
     }
 };
 

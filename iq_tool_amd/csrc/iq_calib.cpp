@@ -29,9 +29,11 @@ const IqTables &iq_tables()
 int ensure_tables(DevBuf &tab, hipStream_t s)
 {
     if (tab.p) return IQGPU_OK;
-    const int rc = tab.ensure(sizeof(IqTables)); if (rc) return rc;
-    const hipError_t e = hipMemcpyAsync(tab.p, &iq_tables(), sizeof(IqTables), hipMemcpyHostToDevice, s);
-    if (e != hipSuccess) { tab.release(); return fail(IQGPU_EHIP, "uploading the calibration tables failed: %s", hipGetErrorString(e)); }   // (allocated = uploaded)
+    DevBuf nb;                                                        // (allocated = uploaded: tab takes it once the copy is queued)
+    const int rc = nb.ensure(sizeof(IqTables)); if (rc) return rc;
+    const hipError_t e = hipMemcpyAsync(nb.p, &iq_tables(), sizeof(IqTables), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return fail(IQGPU_EHIP, "uploading the calibration tables failed: %s", hipGetErrorString(e));
+    tab = std::move(nb);
     return IQGPU_OK;
 }
 
@@ -96,8 +98,7 @@ int metric_batch_impl(int device, const float *blocks, size_t n_blocks, size_t s
         DevEval ev{s, d_blocks, d_stride, n_blocks, (const IqTables *)tab.p, &work};
         rc = dev_eval(&ev, cands, n_cand, metric, power_range_db);
     }
-    (void)hipStreamSynchronize(s);                                    // (an error path: nothing in flight reads what is freed next)
-    tab.release(); in.release(); work.release();
+    (void)hipStreamSynchronize(s);                                    // (an error path: nothing in flight reads what tab, in and work free next)
     return rc;
 }
 

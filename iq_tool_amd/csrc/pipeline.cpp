@@ -21,12 +21,13 @@ static constexpr size_t kSmallCopy = (size_t)8 << 20;      // copies up to this 
 static int pipe_init(iqgpu_chain *c)
 {
     if (c->pipe_ready) return IQGPU_OK;
-    for (hipStream_t &st : c->pipe_h2d) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    for (hipStream_t &st : c->pipe_d2h) HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    // (a set-up that failed half way runs again from the start: create() on an owner that holds a handle keeps it)
+    for (Stream &st : c->pipe_h2d) HIP_TRY(st.create());
+    for (Stream &st : c->pipe_d2h) HIP_TRY(st.create());
     for (auto &ps : c->pipe) {
-        HIP_TRY(hipEventCreateWithFlags(&ps.in_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ps.k_done, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ps.all_done, hipEventDisableTiming));
+        HIP_TRY(ps.in_done.create(hipEventDisableTiming));
+        HIP_TRY(ps.k_done.create(hipEventDisableTiming));
+        HIP_TRY(ps.all_done.create(hipEventDisableTiming));
     }
     c->pipe_ready = true;
     return IQGPU_OK;

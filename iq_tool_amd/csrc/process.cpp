@@ -5,24 +5,24 @@
 // ------------------------------------------------------------------------------------------------
 // profiling helpers
 // ------------------------------------------------------------------------------------------------
-hipEvent_t get_event(iqgpu_chain *c)
+Event get_event(iqgpu_chain *c)
 {
-    if (!c->event_pool.empty()) { hipEvent_t e = c->event_pool.back(); c->event_pool.pop_back(); return e; }
-    hipEvent_t e = nullptr;
-    (void)hipEventCreate(&e);
+    Event e;
+    if (!c->event_pool.empty()) { e = std::move(c->event_pool.back()); c->event_pool.pop_back(); }
+    else (void)e.create(hipEventDefault);                            // (a failure: an empty owner, and every call on it fails in turn)
     return e;
 }
 void drain_events(iqgpu_chain *c)
 {
     for (auto &pe : c->pending_events) {
         float ms = 0.0f;
-        (void)hipEventSynchronize(pe.second.second);
-        if (hipEventElapsedTime(&ms, pe.second.first, pe.second.second) == hipSuccess) {
-            c->prof.ms[pe.first] += (double)ms;
-            c->prof.launches[pe.first] += 1;
+        (void)hipEventSynchronize(pe.b);
+        if (hipEventElapsedTime(&ms, pe.a, pe.b) == hipSuccess) {
+            c->prof.ms[pe.kind] += (double)ms;
+            c->prof.launches[pe.kind] += 1;
         }
-        c->event_pool.push_back(pe.second.first);
-        c->event_pool.push_back(pe.second.second);
+        c->event_pool.push_back(std::move(pe.a));
+        c->event_pool.push_back(std::move(pe.b));
     }
     c->pending_events.clear();
 }

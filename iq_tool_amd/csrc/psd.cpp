@@ -76,7 +76,7 @@ int PsdStream::open(PsdStream *st, int device, int format, const iqgpu_psd_opts 
     st->device = device; st->format = format; st->log2n = log2n_of(o->nfft); st->bps = bytes_per_frame(format); st->q = *o;
     fill_tables(*o, tab.data(), &st->window_sum, &st->window_sum_sq);
     hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&st->own, hipStreamNonBlocking);
+    if (e == hipSuccess) e = st->own.create();
     if (e != hipSuccess) return fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e));
     rc = st->tables.ensure(tab.size() * sizeof(float));
     for (int i = 0; i < 2 && rc == IQGPU_OK; ++i) rc = st->carry[i].ensure((size_t)o->nfft * st->bps);
@@ -90,8 +90,7 @@ void PsdStream::close()
     if (!own) return;                                                // (open() got no further than its checks: nothing is held)
     (void)hipSetDevice(device);
     if (has_last) (void)hipStreamSynchronize(last);
-    (void)hipStreamSynchronize(own); (void)hipStreamDestroy(own);
-    tables.release(); carry[0].release(); carry[1].release(); stage.release();
+    (void)hipStreamSynchronize(own);
 }
 
 int PsdStream::guard(const PsdStream *st, bool args_ok, const char *who, const char *reset, bool set_device)
@@ -135,7 +134,7 @@ int PsdStream::finish(const PsdPush &u)
 struct iqgpu_psd {
     PsdStream st;
     int open_cur = 0;                     // which of the two open-page buffers holds the open page (the page kernel writes the other: psd.hip)
-    hipEvent_t staged = nullptr;          // a host push: the slice has left the caller's memory
+    Event staged;                         // a host push: the slice has left the caller's memory
     DevBuf sums, pages;
     size_t page_bins = 0;                 // of pages: [page_bins] doubles, then [page_bins] floats
     // sums: [nfft] total, 2 x [nfft] open (double), then [nfft] peak, 2 x [nfft] open peak (float)
@@ -144,20 +143,12 @@ struct iqgpu_psd {
     float *total_pk() const { return (float *)((double *)sums.p + 3 * (size_t)st.q.nfft); }
     float *open_pk(int i) const { return total_pk() + (size_t)(1 + i) * st.q.nfft; }
     size_t sums_bytes() const { return (size_t)st.q.nfft * (3 * sizeof(double) + 3 * sizeof(float)); }
+    IQGPU_LOCAL ~iqgpu_psd() { st.close(); }          // the waits first: the members free themselves behind them
 };
 
 namespace {
 
 PsdStream *core(iqgpu_psd *p) { return p ? &p->st : nullptr; }
-
-void destroy(iqgpu_psd *p)
-{
-    if (!p) return;
-    p->st.close();
-    if (p->staged) (void)hipEventDestroy(p->staged);
-    p->sums.release(); p->pages.release();
-    delete p;
-}
 
 // n frames of device memory behind everything pushed so far, on s
 int push_frames(iqgpu_psd *p, const void *d_raw, size_t n, hipStream_t s)
@@ -236,17 +227,17 @@ extern "C" int iqgpu_psd_create(int device, int format, const iqgpu_psd_opts *o,
     int rc = PsdStream::open(core(p), device, format, o, who, tab);
     if (rc == IQGPU_OK) rc = p->sums.ensure(p->sums_bytes());
     if (rc == IQGPU_OK) {
-        hipError_t e = hipEventCreateWithFlags(&p->staged, hipEventDisableTiming);
+        hipError_t e = p->staged.create(hipEventDisableTiming);
         if (e == hipSuccess) e = hipMemsetAsync(p->sums.p, 0, p->sums_bytes(), p->st.own);
         if (e == hipSuccess) e = hipStreamSynchronize(p->st.own);
         if (e != hipSuccess) rc = fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e));
     }
-    if (rc != IQGPU_OK) { destroy(p); return rc; }
+    if (rc != IQGPU_OK) { delete p; return rc; }
     *out = p;
     return IQGPU_OK;
 }
 
-extern "C" void iqgpu_psd_destroy(iqgpu_psd *p) { destroy(p); }
+extern "C" void iqgpu_psd_destroy(iqgpu_psd *p) { delete p; }
 
 extern "C" int iqgpu_psd_reset(iqgpu_psd *p)
 {

@@ -65,7 +65,7 @@ struct PsdStream {
     size_t carry_n = 0;                   // frames in carry[cur]: stream frames segments * hop .. frames - 1
     int cur = 0;
     bool poisoned = false;                // a push failed half way: rewind() clears it
-    hipStream_t own = nullptr, last = nullptr; bool has_last = false;     // last: the stream of the previous push
+    Stream own; hipStream_t last = nullptr; bool has_last = false;        // last: the stream of the previous push (not owned)
     DevBuf tables, carry[2], stage;       // tables: [nfft] window, then [nfft] twiddles as (cos, sin) pairs
     const float *window() const { return (const float *)tables.p; }
     const cf2 *twiddle() const { return (const cf2 *)((const float *)tables.p + q.nfft); }
@@ -74,7 +74,8 @@ struct PsdStream {
     // allocated) -- then stream, buffers and the tables' upload, queued on `own` from `tab`: the caller queues the zero fill of its
     // open state behind it and synchronises once, with `tab` alive until then.  `who` leads the error texts.
     static int open(PsdStream *st, int device, int format, const iqgpu_psd_opts *o, const char *who, std::vector<float> &tab);
-    void close();                         // waits for `last` and `own`, then frees
+    IQGPU_LOCAL ~PsdStream() = default;   // frees the stream and the buffers; the waits in front of that are close()
+    void close();                         // waits for `last` and `own`: the holder's destructor calls it in front of the members' frees
     // NULL (st, or !args_ok) and poisoned, in the handles' texts (`reset` names the call that clears a poisoned handle), then hipSetDevice
     static int guard(const PsdStream *st, bool args_ok, const char *who, const char *reset, bool set_device = true);
     int settle();                         // everything queued by earlier pushes has run; the handle then holds on to no stream of the caller's

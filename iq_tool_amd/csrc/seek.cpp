@@ -499,10 +499,10 @@ static int dc_measure_range_run(iqgpu_chain *c, const char *who, uint64_t first_
         size_t most = 0;
         for (const RangeSlice &sl : slices) most = sl.len > most ? sl.len : most;
         for (size_t b = 0; b < 2 && b < slices.size(); ++b) { rc = c->dc_range_in[b].ensure(most * ibps); if (rc) return rc; }
-        if (!c->dc_range_h2d) HIP_TRY(hipStreamCreateWithFlags(&c->dc_range_h2d, hipStreamNonBlocking));
+        HIP_TRY(c->dc_range_h2d.create());                               // (on first use: create() keeps a handle it holds)
         for (int b = 0; b < 2; ++b) {
-            if (!c->dc_range_in_done[b]) HIP_TRY(hipEventCreateWithFlags(&c->dc_range_in_done[b], hipEventDisableTiming));
-            if (!c->dc_range_k_done[b]) HIP_TRY(hipEventCreateWithFlags(&c->dc_range_k_done[b], hipEventDisableTiming));
+            HIP_TRY(c->dc_range_in_done[b].create(hipEventDisableTiming));
+            HIP_TRY(c->dc_range_k_done[b].create(hipEventDisableTiming));
         }
     }
     // where slice s lies on the device, and the table: every piece planned from the address its frames will have

@@ -44,19 +44,12 @@ struct iqgpu_sgram {
     float *cell_pk(int i) const { return (float *)((double *)open.p + 4 * (size_t)o.nfft) + (size_t)(2 * i + 1) * o.nfft; }
     size_t open_bytes() const { return (size_t)o.nfft * 4 * (sizeof(double) + sizeof(float)); }
     uint64_t rows_after(size_t n) const { return psd_segments_of(st.q, st.frames + n) / o.row_segments; }
+    IQGPU_LOCAL ~iqgpu_sgram() { st.close(); }        // the waits first: the members free themselves behind them
 };
 
 namespace {
 
 PsdStream *core(iqgpu_sgram *p) { return p ? &p->st : nullptr; }
-
-void destroy(iqgpu_sgram *p)
-{
-    if (!p) return;
-    p->st.close();
-    p->open.release(); p->cells.release(); p->rows_out.release();
-    delete p;
-}
 
 // n frames of device memory behind everything pushed so far, on s; the rows they complete into d_sum / d_pk (device, either may be NULL)
 int push_frames(iqgpu_sgram *p, const void *d_raw, size_t n, float *d_sum, float *d_pk, hipStream_t s)
@@ -154,12 +147,12 @@ extern "C" int iqgpu_sgram_create(int device, int format, const iqgpu_sgram_opts
         if (e == hipSuccess) e = hipStreamSynchronize(p->st.own);
         if (e != hipSuccess) rc = fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e));
     }
-    if (rc != IQGPU_OK) { destroy(p); return rc; }
+    if (rc != IQGPU_OK) { delete p; return rc; }
     *out = p;
     return IQGPU_OK;
 }
 
-extern "C" void iqgpu_sgram_destroy(iqgpu_sgram *p) { destroy(p); }
+extern "C" void iqgpu_sgram_destroy(iqgpu_sgram *p) { delete p; }
 
 extern "C" int iqgpu_sgram_reset(iqgpu_sgram *p)
 {
