@@ -51,16 +51,7 @@ inline double monotonic_sec() // get_monotonic_time_sec, src/utils.c
     return (double)ts.tv_sec + 1e-9 * (double)ts.tv_nsec;
 }
 
-inline size_t bytes_per_frame(int fmt)
-{
-    switch (fmt) { // get_bytes_per_sample, src/sample_convert.c:102-122 (complex formats)
-    case IQGPU_FMT_CS8: case IQGPU_FMT_CU8: return 2;
-    case IQGPU_FMT_CS16: case IQGPU_FMT_CU16: case IQGPU_FMT_SC16Q11: return 4;
-    case IQGPU_FMT_CS24: return 6;
-    case IQGPU_FMT_CS32: case IQGPU_FMT_CU32: case IQGPU_FMT_CF32: return 8;
-    default: return 0;
-    }
-}
+inline size_t bytes_per_frame(int fmt) { return (size_t)frame_bytes(fmt); }   // (kernels.hpp; size_t for the buffer arithmetic of the call sites)
 
 // ---- diagnostic switches (iqgpu_debug_set; parse rules: abi.cpp kSwitches): one chain's snapshot, with the defaults ----
 struct DebugSwitches {

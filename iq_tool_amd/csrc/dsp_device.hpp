@@ -24,7 +24,25 @@ __device__ __forceinline__ float up_u(float v, float off, float norm, float gain
     return __fmul_rn(__fmul_rn(__fsub_rn(v, off), norm), gain);
 }
 
-// one frame, any format (slow path: tile edges, unaligned calls, rare formats)
+// one 4-byte frame (cs16 / sc16q11 / cu16) from its 32-bit word, one 2-byte frame (cu8 / cs8) from the low 16 bits of h: THE word
+// forms of the five small input formats.  unpack_four_fast, psd_unpack (psd_stream.hpp) and dc_prefix_segment (kernels.hip) fetch words
+// and come here; unpack_one below is the same arithmetic on byte-wise loads
+__device__ __forceinline__ cf2 unpack_b16(uint32_t w, int fmt, float gain)
+{
+    if (fmt == IQGPU_FMT_CU16)
+        return cf2{up_u((float)(w & 0xffffu), 32767.5f, 1.0f / 32768.0f, gain), up_u((float)(w >> 16), 32767.5f, 1.0f / 32768.0f, gain)};
+    const float norm = (fmt == IQGPU_FMT_SC16Q11) ? 1.0f / 2048.0f : 1.0f / 32768.0f;
+    return cf2{up_s((float)(short)(w & 0xffffu), norm, gain), up_s((float)(short)(w >> 16), norm, gain)};
+}
+__device__ __forceinline__ cf2 unpack_b8(uint32_t h, int fmt, float gain)
+{
+    if (fmt == IQGPU_FMT_CU8)
+        return cf2{up_u((float)(h & 0xffu), 127.5f, 1.0f / 128.0f, gain), up_u((float)((h >> 8) & 0xffu), 127.5f, 1.0f / 128.0f, gain)};
+    return cf2{up_s((float)(signed char)(h & 0xffu), 1.0f / 128.0f, gain), up_s((float)(signed char)((h >> 8) & 0xffu), 1.0f / 128.0f, gain)};
+}
+
+// one frame, any format (slow path: tile edges, unaligned calls, rare formats).  The any-alignment path: raw + j frames may sit at an
+// odd byte address, so every component is loaded on its own (no word is fetched, hence no unpack_b16 / unpack_b8 here)
 __device__ __forceinline__ cf2 unpack_one(const void *raw, int64_t j, int fmt, float gain)
 {
     cf2 r;
@@ -77,44 +95,17 @@ __device__ __forceinline__ cf2 unpack_one(const void *raw, int64_t j, int fmt, f
 __device__ __forceinline__ bool unpack_four_fast(const void *raw, int64_t j, int fmt, float gain, cf2 x[4])
 {
     switch (fmt) {
-    case IQGPU_FMT_CS16: case IQGPU_FMT_SC16Q11: {
-        const float norm = (fmt == IQGPU_FMT_CS16) ? 1.0f / 32768.0f : 1.0f / 2048.0f;
+    case IQGPU_FMT_CS16: case IQGPU_FMT_SC16Q11: case IQGPU_FMT_CU16: {
         const uint4 v = *(const uint4 *)((const char *)raw + 4 * j);
         const unsigned w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            x[s].x = up_s((float)(short)(w[s] & 0xffffu), norm, gain);
-            x[s].y = up_s((float)(short)(w[s] >> 16), norm, gain);
-        }
+        for (int s = 0; s < 4; ++s) x[s] = unpack_b16(w[s], fmt, gain);
         return true; }
-    case IQGPU_FMT_CU16: {
-        const uint4 v = *(const uint4 *)((const char *)raw + 4 * j);
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            x[s].x = up_u((float)(w[s] & 0xffffu), 32767.5f, 1.0f / 32768.0f, gain);
-            x[s].y = up_u((float)(w[s] >> 16), 32767.5f, 1.0f / 32768.0f, gain);
-        }
-        return true; }
-    case IQGPU_FMT_CU8: {
+    case IQGPU_FMT_CU8: case IQGPU_FMT_CS8: {
         const uint2 v = *(const uint2 *)((const char *)raw + 2 * j);
         const unsigned w[2] = {v.x, v.y};
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const unsigned h = w[s >> 1] >> ((s & 1) * 16);
-            x[s].x = up_u((float)(h & 0xffu), 127.5f, 1.0f / 128.0f, gain);
-            x[s].y = up_u((float)((h >> 8) & 0xffu), 127.5f, 1.0f / 128.0f, gain);
-        }
-        return true; }
-    case IQGPU_FMT_CS8: {
-        const uint2 v = *(const uint2 *)((const char *)raw + 2 * j);
-        const unsigned w[2] = {v.x, v.y};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const unsigned h = w[s >> 1] >> ((s & 1) * 16);
-            x[s].x = up_s((float)(signed char)(h & 0xffu), 1.0f / 128.0f, gain);
-            x[s].y = up_s((float)(signed char)((h >> 8) & 0xffu), 1.0f / 128.0f, gain);
-        }
+        for (int s = 0; s < 4; ++s) x[s] = unpack_b8(w[s >> 1] >> ((s & 1) * 16), fmt, gain);
         return true; }
     case IQGPU_FMT_CF32: {
         const float4 v0 = *(const float4 *)((const char *)raw + 8 * j);
@@ -150,6 +141,9 @@ __device__ __forceinline__ unsigned pk_unsigned(float x, float scale, float off,
 // one cs16 frame as 32 bits: same result as
 // src/sample_convert.c:40-57 for every finite input -- +-0.5 by sign is a copysign (0 gives 0 either
 // way), truncation then int16 saturation equals float clamp then truncation.
+// A different, faster expression than pack_b16's cs16 case, and NOT interchangeable with it: the two differ on non-finite input, which
+// tests/test_gpu_rails.py pins per kernel.  Its sites: pack_store_at and the deferred stores of front_tiles.hpp, front_mid.hip,
+// front_p0.hip, front_fat.hip, fft16.hpp.  Every other cs16 frame leaves through pack_b16.
 __device__ __forceinline__ uint32_t pack_cs16(cf2 v)
 {
     typedef float f2 __attribute__((ext_vector_type(2)));           // (both components in one packed multiply and one packed add)
@@ -159,37 +153,37 @@ __device__ __forceinline__ uint32_t pack_cs16(cf2 v)
     const s2 pk = __builtin_amdgcn_cvt_pk_i16((int)s.x, (int)s.y);
     return __builtin_bit_cast(uint32_t, pk);
 }
-// cu8 / cs8: one frame as 16 bits (src/sample_convert.c:40-73, the arithmetic of pack_store)
+// THE output words of the five small formats (src/sample_convert.c:40-73): pack_store's cases and pack_store_group's vector stores are
+// these two, and the wave kernels' deferred 2-byte stores call pack_b8 directly.
+// cu8 / cs8: one frame as 16 bits
 __device__ __forceinline__ uint32_t pack_b8(cf2 v, bool is_unsigned)
 {
     if (is_unsigned) return pk_unsigned(v.x, 127.0f, 127.5f, 255.0f) | (pk_unsigned(v.y, 127.0f, 127.5f, 255.0f) << 8);
     return ((unsigned)pk_signed(v.x, 127.0f, -128.0f, 127.0f) & 0xffu) | (((unsigned)pk_signed(v.y, 127.0f, -128.0f, 127.0f) & 0xffu) << 8);
 }
+// cs16 / sc16q11 / cu16: one frame as 32 bits
+__device__ __forceinline__ uint32_t pack_b16(cf2 v, int fmt)
+{
+    if (fmt == IQGPU_FMT_CU16) return pk_unsigned(v.x, 32767.0f, 32767.5f, 65535.0f) | (pk_unsigned(v.y, 32767.0f, 32767.5f, 65535.0f) << 16);
+    const float s = (fmt == IQGPU_FMT_CS16) ? 32767.0f : 2048.0f;
+    return ((unsigned)pk_signed(v.x, s, -32768.0f, 32767.0f) & 0xffffu) | (((unsigned)pk_signed(v.y, s, -32768.0f, 32767.0f) & 0xffffu) << 16);
+}
 // one frame -> out[idx] in any format (src/sample_convert.c:213-309)
 __device__ __forceinline__ void pack_store(void *out, int64_t idx, int fmt, cf2 v)
 {
     switch (fmt) {
-    case IQGPU_FMT_CS16: case IQGPU_FMT_SC16Q11: {
-        const float s = (fmt == IQGPU_FMT_CS16) ? 32767.0f : 2048.0f;
-        const unsigned a = (unsigned)pk_signed(v.x, s, -32768.0f, 32767.0f) & 0xffffu;
-        const unsigned b = (unsigned)pk_signed(v.y, s, -32768.0f, 32767.0f) & 0xffffu;
-        ((unsigned *)out)[idx] = a | (b << 16);
-        break; }
-    case IQGPU_FMT_CU16: {
-        const unsigned a = pk_unsigned(v.x, 32767.0f, 32767.5f, 65535.0f);
-        const unsigned b = pk_unsigned(v.y, 32767.0f, 32767.5f, 65535.0f);
-        ((unsigned *)out)[idx] = a | (b << 16);
-        break; }
-    case IQGPU_FMT_CS8: {
-        const unsigned a = (unsigned)pk_signed(v.x, 127.0f, -128.0f, 127.0f) & 0xffu;
-        const unsigned b = (unsigned)pk_signed(v.y, 127.0f, -128.0f, 127.0f) & 0xffu;
-        ((unsigned short *)out)[idx] = (unsigned short)(a | (b << 8));
-        break; }
-    case IQGPU_FMT_CU8: {
-        const unsigned a = pk_unsigned(v.x, 127.0f, 127.5f, 255.0f);
-        const unsigned b = pk_unsigned(v.y, 127.0f, 127.5f, 255.0f);
-        ((unsigned short *)out)[idx] = (unsigned short)(a | (b << 8));
-        break; }
+    case IQGPU_FMT_CS16: case IQGPU_FMT_SC16Q11:
+        ((unsigned *)out)[idx] = pack_b16(v, fmt);
+        break;
+    case IQGPU_FMT_CU16:
+        ((unsigned *)out)[idx] = pack_b16(v, IQGPU_FMT_CU16);
+        break;
+    case IQGPU_FMT_CS8:
+        ((unsigned short *)out)[idx] = (unsigned short)pack_b8(v, false);
+        break;
+    case IQGPU_FMT_CU8:
+        ((unsigned short *)out)[idx] = (unsigned short)pack_b8(v, true);
+        break;
     case IQGPU_FMT_CS24: {
         const float fa = __fmul_rn(v.x, 8388607.0f), fb = __fmul_rn(v.y, 8388607.0f);
         int a = (int)((fa > 0.0f) ? __fadd_rn(fa, 0.5f) : __fsub_rn(fa, 0.5f));
@@ -220,6 +214,43 @@ __device__ __forceinline__ void pack_store(void *out, int64_t idx, int fmt, cf2 
     default: // IQGPU_FMT_CF32: memcpy (src/sample_convert.c:301-303)
         ((cf2 *)out)[idx] = v;
         break;
+    }
+}
+
+// N = 2 or 4 consecutive frames -> out[idx ..], frame s only where st[s].  A thread's frames leave as ONE piece where all of them are
+// stored and the format allows it (cf32: 16-byte stores of two frames, 4-byte frames: one store of 4 N bytes, 2-byte frames: one of
+// 2 N bytes; idx is any frame, so the vector types are aligned to a frame only) instead of N stores of one frame each -- N instructions
+// that each touched 64 pieces N frames apart, every cache line written N times (the store shape that cost k_front_p0's cf32 output
+// 21 %).  The words are pack_store's own (pack_b16 / pack_b8), so the group and the per-frame path beside it -- the
+// stream's first and last frames, odd pairs -- cannot encode differently.  k_front's no-resampler path (N = 4), k_interp (N = 2).
+template <int N>
+__device__ __forceinline__ void pack_store_group(void *out, int64_t idx, int fmt, const cf2 (&v)[N], const bool (&st)[N])
+{
+    static_assert(N == 2 || N == 4, "a pair or a quad");
+    bool all = true;
+#pragma unroll
+    for (int s = 0; s < N; ++s) all = all && st[s];
+    const int fb = valid_frame_bytes(fmt);
+    if (all && fmt == IQGPU_FMT_CF32) {
+        typedef float f4a8 __attribute__((ext_vector_type(4), aligned(8)));
+#pragma unroll
+        for (int s = 0; s < N; s += 2) *(f4a8 *)((char *)out + 8 * (idx + s)) = f4a8{v[s].x, v[s].y, v[s + 1].x, v[s + 1].y};
+    } else if (all && fb == 4) {
+        typedef uint32_t wa4 __attribute__((ext_vector_type(N), aligned(4)));
+        wa4 w;
+#pragma unroll
+        for (int s = 0; s < N; ++s) w[s] = pack_b16(v[s], fmt);
+        *(wa4 *)((char *)out + 4 * idx) = w;
+    } else if (all && fb == 2) {
+        typedef uint32_t wa2 __attribute__((ext_vector_type(N / 2), aligned(2)));
+        const bool uns = fmt == IQGPU_FMT_CU8;
+        wa2 w;
+#pragma unroll
+        for (int s = 0; s < N; s += 2) w[s / 2] = pack_b8(v[s], uns) | (pack_b8(v[s + 1], uns) << 16);
+        *(wa2 *)((char *)out + 2 * idx) = w;
+    } else {
+#pragma unroll
+        for (int s = 0; s < N; ++s) if (st[s]) pack_store(out, idx + s, fmt, v[s]);
     }
 }
 

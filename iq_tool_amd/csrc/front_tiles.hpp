@@ -41,12 +41,6 @@ __device__ __forceinline__ void pack_store_at(char *base, uint32_t idx, int fmt,
     }
 }
 
-__device__ __forceinline__ int out_bytes(int fmt)
-{
-    return (fmt == IQGPU_FMT_CS8 || fmt == IQGPU_FMT_CU8) ? 2 : (fmt == IQGPU_FMT_CS24) ? 6
-         : (fmt == IQGPU_FMT_CS32 || fmt == IQGPU_FMT_CU32 || fmt == IQGPU_FMT_CF32) ? 8 : 4;
-}
-
 // ---- optional in-kernel stamps (diagnostic build only: -DIQGPU_STAMPS; never in the shipped .so).
 // Per-phase cycle sums of every wave are added into a.sink[32 KiB ...] as u64 counters.
 #ifdef IQGPU_STAMPS
@@ -173,7 +167,7 @@ __device__ __forceinline__ void run_tiles(const FrontArgs &a, const WaveLds &w, 
     uint64_t k_tile0 = first_k_at((uint64_t)(t_emit0 * 256) << 24, a.phi0, step);
     uint32_t delta0 = (uint32_t)(a.phi0 + k_tile0 * (uint64_t)step - ((uint64_t)(t_emit0 * 256) << 24));   // < step
     // (the streaming FAST instantiations write cs16; their EDGE siblings may be asked for cf32 as well: k_front_mid in front of a user filter)
-    const int obps = (FAST && !EDGE) ? 4 : out_bytes(a.out_fmt);
+    const int obps = (FAST && !EDGE) ? 4 : valid_frame_bytes(a.out_fmt);
     const bool unit_gain = FAST || a.gain == 1.0f;
     // FAST: the same outputs-per-tile count and lane phases without a division in the loop
     const uint32_t n_est = (uint32_t)(((uint64_t)1 << 32) / step);

@@ -49,19 +49,6 @@ __device__ __forceinline__ cf2 interp_branch(const cf2 *p, const float *taps, in
     return cf2{ar, ai};
 }
 
-// one frame of a 4-byte / 2-byte output format as the word pack_store would write (dsp_device.hpp: the same expressions, case by case)
-__device__ __forceinline__ uint32_t interp_word32(int fmt, cf2 v)
-{
-    if (fmt == IQGPU_FMT_CU16) return pk_unsigned(v.x, 32767.0f, 32767.5f, 65535.0f) | (pk_unsigned(v.y, 32767.0f, 32767.5f, 65535.0f) << 16);
-    const float s = (fmt == IQGPU_FMT_CS16) ? 32767.0f : 2048.0f;
-    return ((unsigned)pk_signed(v.x, s, -32768.0f, 32767.0f) & 0xffffu) | (((unsigned)pk_signed(v.y, s, -32768.0f, 32767.0f) & 0xffffu) << 16);
-}
-__device__ __forceinline__ uint32_t interp_word16(int fmt, cf2 v)
-{
-    if (fmt == IQGPU_FMT_CU8) return pk_unsigned(v.x, 127.0f, 127.5f, 255.0f) | (pk_unsigned(v.y, 127.0f, 127.5f, 255.0f) << 8);
-    return ((unsigned)pk_signed(v.x, 127.0f, -128.0f, 127.0f) & 0xffu) | (((unsigned)pk_signed(v.y, 127.0f, -128.0f, 127.0f) & 0xffu) << 8);
-}
-
 __global__ __launch_bounds__(kThreads) void k_interp(const InterpArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -152,20 +139,9 @@ __global__ __launch_bounds__(kThreads) void k_interp(const InterpArgs a)
                     y0 = nco_mix(y0, nco_phasor(s_nco, a.pnco_theta0 + (uint32_t)k0 * a.pnco_dtheta), a.pnco_mode);
                     y1 = nco_mix(y1, nco_phasor(s_nco, a.pnco_theta0 + (uint32_t)(k0 + 1) * a.pnco_dtheta), a.pnco_mode);
                 }
-                const int of = a.out_fmt;
-                if (st0 && st1 && of == IQGPU_FMT_CF32) {
-                    typedef float f4a8 __attribute__((ext_vector_type(4), aligned(8)));
-                    *(f4a8 *)((char *)a.out + 8 * k0) = f4a8{y0.x, y0.y, y1.x, y1.y};
-                } else if (st0 && st1 && (of == IQGPU_FMT_CS16 || of == IQGPU_FMT_SC16Q11 || of == IQGPU_FMT_CU16)) {
-                    typedef uint32_t u2a4 __attribute__((ext_vector_type(2), aligned(4)));
-                    *(u2a4 *)((char *)a.out + 4 * k0) = u2a4{interp_word32(of, y0), interp_word32(of, y1)};
-                } else if (st0 && st1 && (of == IQGPU_FMT_CS8 || of == IQGPU_FMT_CU8)) {
-                    typedef uint32_t u1a2 __attribute__((aligned(2)));
-                    *(u1a2 *)((char *)a.out + 2 * k0) = interp_word16(of, y0) | (interp_word16(of, y1) << 16);
-                } else {
-                    if (st0) pack_store(a.out, k0, of, y0);
-                    if (st1) pack_store(a.out, k0 + 1, of, y1);
-                }
+                const cf2 yv[2] = {y0, y1};
+                const bool st[2] = {st0, st1};
+                pack_store_group<2>(a.out, k0, a.out_fmt, yv, st);      // the pair as one piece (dsp_device.hpp)
             } else {
                 s_lvl[a.lvl_off[0] + i0] = y0;
                 if (has1) s_lvl[a.lvl_off[0] + i0 + 1] = y1;
@@ -205,27 +181,13 @@ __global__ __launch_bounds__(kThreads) void k_interp(const InterpArgs a)
                 }
                 if (last) {
                     const bool st_e = has_e && u < a.n_emit, st_o = has_o && u + 1 < a.n_emit;
-                    cf2 y0 = ye, y1 = yo;
+                    cf2 yv[2] = {ye, yo};
                     if (a.pnco_mode != 0) {
-                        y0 = nco_mix(y0, nco_phasor(s_nco, a.pnco_theta0 + (uint32_t)u * a.pnco_dtheta), a.pnco_mode);
-                        y1 = nco_mix(y1, nco_phasor(s_nco, a.pnco_theta0 + (uint32_t)(u + 1) * a.pnco_dtheta), a.pnco_mode);
+                        yv[0] = nco_mix(yv[0], nco_phasor(s_nco, a.pnco_theta0 + (uint32_t)u * a.pnco_dtheta), a.pnco_mode);
+                        yv[1] = nco_mix(yv[1], nco_phasor(s_nco, a.pnco_theta0 + (uint32_t)(u + 1) * a.pnco_dtheta), a.pnco_mode);
                     }
-                    // Round 6: the pair leaves as ONE piece where the format allows it (two stores of one frame each had every cache line
-                    // written twice: the store shape of DESIGN 3.3); the same expressions as pack_store
-                    const int of = a.out_fmt;
-                    if (st_e && st_o && of == IQGPU_FMT_CF32) {
-                        typedef float f4a8 __attribute__((ext_vector_type(4), aligned(8)));
-                        *(f4a8 *)((char *)a.out + 8 * u) = f4a8{y0.x, y0.y, y1.x, y1.y};
-                    } else if (st_e && st_o && (of == IQGPU_FMT_CS16 || of == IQGPU_FMT_SC16Q11 || of == IQGPU_FMT_CU16)) {
-                        typedef uint32_t u2a4 __attribute__((ext_vector_type(2), aligned(4)));
-                        *(u2a4 *)((char *)a.out + 4 * u) = u2a4{interp_word32(of, y0), interp_word32(of, y1)};
-                    } else if (st_e && st_o && (of == IQGPU_FMT_CS8 || of == IQGPU_FMT_CU8)) {
-                        typedef uint32_t u1a2 __attribute__((aligned(2)));
-                        *(u1a2 *)((char *)a.out + 2 * u) = interp_word16(of, y0) | (interp_word16(of, y1) << 16);
-                    } else {
-                        if (st_e) pack_store(a.out, u, of, y0);
-                        if (st_o) pack_store(a.out, u + 1, of, y1);
-                    }
+                    const bool st[2] = {st_e, st_o};
+                    pack_store_group<2>(a.out, u, a.out_fmt, yv, st);    // the pair as one piece (dsp_device.hpp)
                 } else {
                     if (has_e) dst[u - u_lo] = ye;
                     if (has_o) dst[u + 1 - u_lo] = yo;

@@ -18,7 +18,7 @@
 #include "kernels.hpp"
 
 #ifndef IQGPU_NT_DC
-#define IQGPU_NT_DC 1      // k_dc_prefix reads the call's frames once, with the non-temporal hint (0.116 -> 0.105 ms on config 3)
+#define IQGPU_NT_DC 1      // k_dc_prefix's streaming loop (both widths) reads the call's frames once, with the non-temporal hint (0.116 -> 0.105 ms on config 3)
 #endif
 
 namespace iqgpu {
@@ -69,19 +69,6 @@ __device__ __forceinline__ void hb_stage(const cf2 *src, cf2 *dst, const float *
 //   blocks are independent; inside a block the tiles run in order and all state (dc blocker
 //   value, stage histories, next output index) is carried in registers / LDS.
 // ============================================================================================
-// one frame of a 4-byte / 2-byte output format as the word pack_store would write (dsp_device.hpp: the same expressions, case by case)
-__device__ __forceinline__ uint32_t pack_word32(int fmt, cf2 v)
-{
-    if (fmt == IQGPU_FMT_CU16) return pk_unsigned(v.x, 32767.0f, 32767.5f, 65535.0f) | (pk_unsigned(v.y, 32767.0f, 32767.5f, 65535.0f) << 16);
-    const float s = (fmt == IQGPU_FMT_CS16) ? 32767.0f : 2048.0f;
-    return ((unsigned)pk_signed(v.x, s, -32768.0f, 32767.0f) & 0xffffu) | (((unsigned)pk_signed(v.y, s, -32768.0f, 32767.0f) & 0xffffu) << 16);
-}
-__device__ __forceinline__ uint32_t pack_word16(int fmt, cf2 v)
-{
-    if (fmt == IQGPU_FMT_CU8) return pk_unsigned(v.x, 127.0f, 127.5f, 255.0f) | (pk_unsigned(v.y, 127.0f, 127.5f, 255.0f) << 8);
-    return ((unsigned)pk_signed(v.x, 127.0f, -128.0f, 127.0f) & 0xffu) | (((unsigned)pk_signed(v.y, 127.0f, -128.0f, 127.0f) & 0xffu) << 8);
-}
-
 __global__ __launch_bounds__(kThreads) void k_front(const FrontArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -110,9 +97,7 @@ __global__ __launch_bounds__(kThreads) void k_front(const FrontArgs a)
     if (t_emit1 > a.total_tiles || b == (int)gridDim.x - 1) t_emit1 = a.total_tiles;
     const int64_t t_begin = t_emit0 - a.warm_tiles;
     const int TG = kTile >> S;
-    const int bps = (a.in_fmt == IQGPU_FMT_CS8 || a.in_fmt == IQGPU_FMT_CU8) ? 2
-                  : (a.in_fmt == IQGPU_FMT_CS24) ? 6
-                  : (a.in_fmt == IQGPU_FMT_CS32 || a.in_fmt == IQGPU_FMT_CU32 || a.in_fmt == IQGPU_FMT_CF32) ? 8 : 4;
+    const int bps = valid_frame_bytes(a.in_fmt);
 
     // ---- block 0 keeps the part of the old history that this (short) call does not replace ----
     if (b == 0 && a.frames_in < (int64_t)a.hist_cap) {
@@ -261,28 +246,7 @@ __global__ __launch_bounds__(kThreads) void k_front(const FrontArgs a)
                     yv[s] = y;
                     th += a.pnco_dtheta;
                 }
-                // Round 6: a thread's four frames leave as ONE piece where the format allows it (cf32: two 16-byte stores, 4-byte frames:
-                // one 16-byte store, 2-byte frames: one 8-byte store) instead of four stores of one frame each -- four instructions
-                // that each touched 64 pieces 4 frames apart, every cache line written four times (the store shape that cost
-                // k_front_p0's cf32 output 21 %).  Same arithmetic as pack_store (pack_word32 / pack_word16 restate its
-                // cases); the stream's first and last frames keep the per-frame path.
-                const bool all4 = is_new[0] && is_new[1] && is_new[2] && is_new[3];
-                const int of = a.out_fmt;
-                if (all4 && of == IQGPU_FMT_CF32) {
-                    typedef float f4a8 __attribute__((ext_vector_type(4), aligned(8)));
-                    char *o = (char *)a.out + 8 * j;
-                    *(f4a8 *)o = f4a8{yv[0].x, yv[0].y, yv[1].x, yv[1].y};
-                    *(f4a8 *)(o + 16) = f4a8{yv[2].x, yv[2].y, yv[3].x, yv[3].y};
-                } else if (all4 && (of == IQGPU_FMT_CS16 || of == IQGPU_FMT_SC16Q11 || of == IQGPU_FMT_CU16)) {
-                    typedef uint32_t u4a4 __attribute__((ext_vector_type(4), aligned(4)));
-                    *(u4a4 *)((char *)a.out + 4 * j) = u4a4{pack_word32(of, yv[0]), pack_word32(of, yv[1]), pack_word32(of, yv[2]), pack_word32(of, yv[3])};
-                } else if (all4 && (of == IQGPU_FMT_CS8 || of == IQGPU_FMT_CU8)) {
-                    typedef uint32_t u2a2 __attribute__((ext_vector_type(2), aligned(2)));
-                    *(u2a2 *)((char *)a.out + 2 * j) = u2a2{pack_word16(of, yv[0]) | (pack_word16(of, yv[1]) << 16), pack_word16(of, yv[2]) | (pack_word16(of, yv[3]) << 16)};
-                } else {
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) if (is_new[s]) pack_store(a.out, j + s, of, yv[s]);
-                }
+                pack_store_group<4>(a.out, j, a.out_fmt, yv, is_new);     // whole quads as one piece (dsp_device.hpp)
             }
         }
         if (a.mode != 1) continue;
@@ -370,6 +334,49 @@ hipError_t launch_front(const FrontArgs &a, int n_blocks, hipStream_t s)
 // ============================================================================================
 // DC-blocker carries
 // ============================================================================================
+// a thread's four frames of one chunk (zeros where the chunk is padding) by Horner, folded into its accumulator: THE chunk arithmetic of
+// dc_prefix_segment, whichever way the frames were loaded
+__device__ __forceinline__ void dc_fold_chunk(float &accr, float &acci, const cf2 (&x)[4], float c, float c1024)
+{
+    float lr = 0.0f, li = 0.0f;
+#pragma unroll
+    for (int s = 0; s < 4; ++s) { lr = fmaf(lr, c, x[s].x); li = fmaf(li, c, x[s].y); }
+    accr = fmaf(accr, c1024, lr); acci = fmaf(acci, c1024, li);
+}
+
+// whole rounds of NL chunks from chunk ch on, a thread's NL loads in flight at once; returns the first chunk not done.  The format is a
+// compile-time argument and sets the width: FB bytes a frame, so a thread's four frames are one load of 4 FB bytes (16 for the 16-bit
+// formats, 8 for the 8-bit ones) and NL = 16 / FB of them (4 / 8) are in flight.  base: the thread's four frames of chunk 0, aligned to a
+// load.  One load at a time left the kernel at 4.4 TB/s on 16-bit frames (32 KiB in flight per CU) and at 1.2 TB/s on an RTL-SDR's cu8
+// capture (late round 5: 0.42 ms per 2^28 frames, more than the resampler behind it).  Same arithmetic as the general chunk, same order.
+template <int FMT>
+__device__ __forceinline__ int64_t dc_stream_chunks(float &accr, float &acci, const char *base, int64_t ch, int64_t n_chunks, float gain, float c, float c1024)
+{
+    constexpr int FB = frame_bytes(FMT), NL = 16 / FB;
+    static_assert(FB == 2 || FB == 4, "the 8-bit and 16-bit formats");
+    typedef uint32_t wv __attribute__((ext_vector_type(FB)));      // four frames: FB words
+    for (; ch + NL <= n_chunks; ch += NL) {
+        wv v[NL];
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            const wv *p = (const wv *)(base + (ch + i) * (1024 * FB));
+#if IQGPU_NT_DC
+            v[i] = __builtin_nontemporal_load(p);
+#else
+            v[i] = *p;
+#endif
+        }
+#pragma unroll
+        for (int i = 0; i < NL; ++i) {
+            cf2 x[4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s) x[s] = (FB == 4) ? unpack_b16(v[i][s], FMT, gain) : unpack_b8(v[i][s >> 1] >> (16 * (s & 1)), FMT, gain);
+            dc_fold_chunk(accr, acci, x, c, c1024);
+        }
+    }
+    return ch;
+}
+
 // One workgroup per segment: A = sum_k c^(end-1-k) x[k] over the segment's new samples.  ONE definition of a segment's aggregate:
 // k_dc_prefix (a call) and k_dc_prefix_batch (the calls of a range, iqgpu_chain_*_dc_measure_range) both run it
 __device__ __forceinline__ void dc_prefix_segment(const DcPrefixArgs &a, const int sgm)
@@ -380,119 +387,42 @@ __device__ __forceinline__ void dc_prefix_segment(const DcPrefixArgs &a, const i
     const int64_t end = (sgm == a.geom.n_seg - 1) ? a.geom.frames_in : dc_seg_start(a.geom, sgm + 1);
     const int64_t len = end - beg;
     float accr = 0.0f, acci = 0.0f;
-    const int vb = (a.in_fmt == IQGPU_FMT_CS8 || a.in_fmt == IQGPU_FMT_CU8) ? 2
-                 : (a.in_fmt == IQGPU_FMT_CS16 || a.in_fmt == IQGPU_FMT_CU16 || a.in_fmt == IQGPU_FMT_SC16Q11) ? 4
-                 : (a.in_fmt == IQGPU_FMT_CF32) ? 8 : 0;
+    const int fb = frame_bytes(a.in_fmt);
+    const bool vec_fmt = fb == 2 || fb == 4 || a.in_fmt == IQGPU_FMT_CF32;     // the formats of unpack_four_fast
     if (len > 0) {
         // left-pad the segment to whole chunks of 1024 so that the last chunk ends at `end`
         const int64_t n_chunks = (len + 1023) >> 10;
         const int64_t pad = (n_chunks << 10) - len;
         const float c = a.c;
         const float c1024 = (float)exp(1024.0 * a.logc);
-        int64_t ch = 0;
-        // 16-bit formats, 16-byte aligned chunks: four chunks' loads in flight per thread (one at a time left the kernel at
-        // 4.4 TB/s: 32 KiB in flight per CU; same arithmetic, same order)
-        if (vb == 4 && a.raw_aligned && (((beg - pad) * 4) & 15) == 0 && n_chunks > 5) {
-            {   // the first chunk holds the padding: the general path below, once
-                const int64_t u = 4 * tid;
-                float lr = 0.0f, li = 0.0f;
-                const int64_t k0 = beg + u - pad;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    cf2 x{0.0f, 0.0f};
-                    if (u + s >= pad) x = unpack_one(a.raw, k0 + s, a.in_fmt, a.gain);
-                    lr = fmaf(lr, c, x.x); li = fmaf(li, c, x.y);
-                }
-                accr = fmaf(accr, c1024, lr); acci = fmaf(acci, c1024, li);
-                ch = 1;
-            }
-            const float norm = (a.in_fmt == IQGPU_FMT_SC16Q11) ? 1.0f / 2048.0f : 1.0f / 32768.0f;
-            const bool uns = a.in_fmt == IQGPU_FMT_CU16;
-            const char *base = (const char *)a.raw + (beg - pad + 4 * tid) * 4;
-            for (; ch + 4 <= n_chunks; ch += 4) {
-                uint4 v[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-#if IQGPU_NT_DC
-                    typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-                    const u4v q = __builtin_nontemporal_load((const u4v *)(base + ((ch + i) << 12)));
-                    v[i] = make_uint4(q.x, q.y, q.z, q.w);
-#else
-                    v[i] = *(const uint4 *)(base + ((ch + i) << 12));
-#endif
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const unsigned w[4] = {v[i].x, v[i].y, v[i].z, v[i].w};
-                    float lr = 0.0f, li = 0.0f;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        float xr, xi;
-                        if (uns) { xr = up_u((float)(w[s] & 0xffffu), 32767.5f, 1.0f / 32768.0f, a.gain); xi = up_u((float)(w[s] >> 16), 32767.5f, 1.0f / 32768.0f, a.gain); }
-                        else { xr = up_s((float)(short)(w[s] & 0xffffu), norm, a.gain); xi = up_s((float)(short)(w[s] >> 16), norm, a.gain); }
-                        lr = fmaf(lr, c, xr); li = fmaf(li, c, xi);
-                    }
-                    accr = fmaf(accr, c1024, lr); acci = fmaf(acci, c1024, li);
-                }
-            }
-        }
-        // 8-bit formats (late round 5: the loop below, one 8-byte load at a time, read an RTL-SDR's cu8 capture at 1.2 TB/s --
-        // 0.42 ms per 2^28 frames, more than the resampler behind it): eight chunks' loads in flight per thread, same arithmetic, same order
-        if (vb == 2 && a.raw_aligned && (((beg - pad) * 2) & 15) == 0 && n_chunks > 9) {
-            {   // the first chunk holds the padding: the general path, once
-                const int64_t u = 4 * tid;
-                float lr = 0.0f, li = 0.0f;
-                const int64_t k0 = beg + u - pad;
-#pragma unroll
-                for (int s = 0; s < 4; ++s) {
-                    cf2 x{0.0f, 0.0f};
-                    if (u + s >= pad) x = unpack_one(a.raw, k0 + s, a.in_fmt, a.gain);
-                    lr = fmaf(lr, c, x.x); li = fmaf(li, c, x.y);
-                }
-                accr = fmaf(accr, c1024, lr); acci = fmaf(acci, c1024, li);
-                ch = 1;
-            }
-            const bool uns = a.in_fmt == IQGPU_FMT_CU8;
-            const char *base = (const char *)a.raw + (beg - pad + 4 * tid) * 2;
-            for (; ch + 8 <= n_chunks; ch += 8) {
-                uint2 v[8];
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    typedef uint32_t u2v __attribute__((ext_vector_type(2)));
-                    const u2v q = __builtin_nontemporal_load((const u2v *)(base + ((ch + i) << 11)));
-                    v[i] = make_uint2(q.x, q.y);
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    float lr = 0.0f, li = 0.0f;
-#pragma unroll
-                    for (int s = 0; s < 4; ++s) {
-                        const unsigned h = ((s & 2) ? v[i].y : v[i].x) >> (16 * (s & 1));
-                        float xr, xi;
-                        if (uns) { xr = up_u((float)(h & 0xffu), 127.5f, 1.0f / 128.0f, a.gain); xi = up_u((float)((h >> 8) & 0xffu), 127.5f, 1.0f / 128.0f, a.gain); }
-                        else { xr = up_s((float)(signed char)(h & 0xffu), 1.0f / 128.0f, a.gain); xi = up_s((float)(signed char)((h >> 8) & 0xffu), 1.0f / 128.0f, a.gain); }
-                        lr = fmaf(lr, c, xr); li = fmaf(li, c, xi);
-                    }
-                    accr = fmaf(accr, c1024, lr); acci = fmaf(acci, c1024, li);
-                }
-            }
-        }
-        for (; ch < n_chunks; ++ch) {
+        // chunk ch, any format and alignment; the first one holds the padding
+        auto chunk = [&](int64_t ch) {
             const int64_t u = (ch << 10) + 4 * tid;       // padded position of this thread's 4 samples
-            float lr = 0.0f, li = 0.0f;
             const int64_t k0 = beg + u - pad;
-            cf2 xv[4];
+            cf2 x[4];
             // one coalesced vector load when the four frames are real and 16-byte aligned
-            const bool vec = vb != 0 && a.raw_aligned && u >= pad && ((k0 * vb) & 15) == 0 && unpack_four_fast(a.raw, k0, a.in_fmt, a.gain, xv);
+            const bool vec = vec_fmt && a.raw_aligned && u >= pad && ((k0 * fb) & 15) == 0 && unpack_four_fast(a.raw, k0, a.in_fmt, a.gain, x);
+            if (!vec) {
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                cf2 x{0.0f, 0.0f};
-                if (vec) x = xv[s];
-                else if (u + s >= pad) x = unpack_one(a.raw, k0 + s, a.in_fmt, a.gain);
-                lr = fmaf(lr, c, x.x); li = fmaf(li, c, x.y);
+                for (int s = 0; s < 4; ++s) x[s] = (u + s >= pad) ? unpack_one(a.raw, k0 + s, a.in_fmt, a.gain) : cf2{0.0f, 0.0f};
             }
-            accr = fmaf(accr, c1024, lr); acci = fmaf(acci, c1024, li);
+            dc_fold_chunk(accr, acci, x, c, c1024);
+        };
+        int64_t ch = 0;
+        // 16-bit and 8-bit formats whose chunks start 16-byte aligned: the padded chunk, then whole rounds of four / eight chunks with
+        // their loads in flight together (entered with more than 5 / 9 chunks: the padded one, a round, and a tail)
+        if ((fb == 4 ? n_chunks > 5 : fb == 2 && n_chunks > 9) && a.raw_aligned && (((beg - pad) * fb) & 15) == 0) {
+            chunk(0);
+            const char *base = (const char *)a.raw + (beg - pad + 4 * tid) * fb;
+            switch (a.in_fmt) {
+            case IQGPU_FMT_CS16:    ch = dc_stream_chunks<IQGPU_FMT_CS16>(accr, acci, base, 1, n_chunks, a.gain, c, c1024); break;
+            case IQGPU_FMT_CU16:    ch = dc_stream_chunks<IQGPU_FMT_CU16>(accr, acci, base, 1, n_chunks, a.gain, c, c1024); break;
+            case IQGPU_FMT_SC16Q11: ch = dc_stream_chunks<IQGPU_FMT_SC16Q11>(accr, acci, base, 1, n_chunks, a.gain, c, c1024); break;
+            case IQGPU_FMT_CU8:     ch = dc_stream_chunks<IQGPU_FMT_CU8>(accr, acci, base, 1, n_chunks, a.gain, c, c1024); break;
+            default:                ch = dc_stream_chunks<IQGPU_FMT_CS8>(accr, acci, base, 1, n_chunks, a.gain, c, c1024); break;
+            }
         }
+        for (; ch < n_chunks; ++ch) chunk(ch);
         const float wt = (float)exp((double)(1020 - 4 * tid) * a.logc);  // to the end of the chunk
         accr *= wt; acci *= wt;
     }
@@ -507,11 +437,13 @@ __device__ __forceinline__ void dc_prefix_segment(const DcPrefixArgs &a, const i
     }
 }
 
-__global__ __launch_bounds__(kThreads) void k_dc_prefix(const DcPrefixArgs a) { dc_prefix_segment(a, (int)blockIdx.x); }
+// (7 waves per SIMD, the occupancy the kernel has run at: without the bound the scheduler converts all the frames of a round ahead of the
+//  folds and takes 76 registers -- 6 waves; held to it, it converts as the loads arrive, in 45)
+__global__ __launch_bounds__(kThreads, 7) void k_dc_prefix(const DcPrefixArgs a) { dc_prefix_segment(a, (int)blockIdx.x); }
 
 // grid (segment, entry): entry blockIdx.y of the table is one piece of one call -- its geometry, where its frames start in raw, the
 // alignment of that address, where its aggregates go -- and this workgroup does for segment blockIdx.x of it what k_dc_prefix does
-__global__ __launch_bounds__(kThreads) void k_dc_prefix_batch(const DcPrefixBatchArgs b)
+__global__ __launch_bounds__(kThreads, 7) void k_dc_prefix_batch(const DcPrefixBatchArgs b)
 {
     const DcBatchEntry e = b.entries[blockIdx.y];
     if ((int)blockIdx.x >= e.geom.n_seg) return;

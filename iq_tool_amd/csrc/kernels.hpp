@@ -19,6 +19,20 @@
 
 namespace iqgpu {
 
+// bytes of one complex frame (get_bytes_per_sample, src/sample_convert.c:102-122).  THE definition, host and device: the host's buffer
+// sizes, the kernels' byte offsets and alignment tests all come from here.  frame_bytes is 0 for an unknown tag; valid_frame_bytes is
+// the bare ladder, for device code behind a chain's create-time check of its formats (the wave kernels' prologues, front_tiles.hpp:
+// the test for an unknown tag there would cost scalar instructions and another register allocation in every instantiation)
+IQGPU_HD constexpr int valid_frame_bytes(int fmt)
+{
+    return (fmt == IQGPU_FMT_CS8 || fmt == IQGPU_FMT_CU8) ? 2 : (fmt == IQGPU_FMT_CS24) ? 6
+         : (fmt == IQGPU_FMT_CS32 || fmt == IQGPU_FMT_CU32 || fmt == IQGPU_FMT_CF32) ? 8 : 4;      // cs16, cu16, sc16q11
+}
+IQGPU_HD constexpr int frame_bytes(int fmt)
+{
+    return (fmt < IQGPU_FMT_CU8 || fmt > IQGPU_FMT_SC16Q11) ? 0 : valid_frame_bytes(fmt);      // (the nine tags are consecutive, iqgpu.h)
+}
+
 constexpr int kTile = 2048;        // input samples per workgroup tile
 constexpr int kThreads = 256;      // 4 wavefronts of 64
 constexpr int kMaxS = 12;

@@ -7,19 +7,14 @@
 
 namespace iqgpu {
 
-// one frame of a format known at compile time: unpack_one's expressions, with the frame fetched as one word where its alignment allows
+// one frame of a format known at compile time, fetched as one word where its alignment allows (unpack_b16 / unpack_b8, dsp_device.hpp)
 template <int FMT>
 __device__ __forceinline__ cf2 psd_unpack(const void *raw, int64_t j, int fmt, float gain)
 {
     if constexpr (FMT == IQGPU_FMT_CS16) {
-        const uint32_t w = ((const uint32_t *)raw)[j];
-        return cf2{up_s((float)(short)(w & 0xffffu), 1.0f / 32768.0f, gain), up_s((float)(short)(w >> 16), 1.0f / 32768.0f, gain)};
-    } else if constexpr (FMT == IQGPU_FMT_CU8) {
-        const uint32_t h = ((const uint16_t *)raw)[j];
-        return cf2{up_u((float)(h & 0xffu), 127.5f, 1.0f / 128.0f, gain), up_u((float)(h >> 8), 127.5f, 1.0f / 128.0f, gain)};
-    } else if constexpr (FMT == IQGPU_FMT_CS8) {
-        const uint32_t h = ((const uint16_t *)raw)[j];
-        return cf2{up_s((float)(signed char)(h & 0xffu), 1.0f / 128.0f, gain), up_s((float)(signed char)(h >> 8), 1.0f / 128.0f, gain)};
+        return unpack_b16(((const uint32_t *)raw)[j], FMT, gain);
+    } else if constexpr (FMT == IQGPU_FMT_CU8 || FMT == IQGPU_FMT_CS8) {
+        return unpack_b8(((const uint16_t *)raw)[j], FMT, gain);
     } else if constexpr (FMT == IQGPU_FMT_CF32) {
         const float2 v = ((const float2 *)raw)[j];
         return cf2{__fmul_rn(v.x, gain), __fmul_rn(v.y, gain)};
