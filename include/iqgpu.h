@@ -907,6 +907,93 @@ int    iqgpu_sgram_push_device(iqgpu_sgram *p, const void *d_raw, size_t frames,
                                size_t *rows, void *hip_stream);     /* device memory, asynchronous on hip_stream */
 int    iqgpu_sgram_read_open(iqgpu_sgram *p, double *sum_power, float *peak_power, iqgpu_sgram_info *info);   /* [nfft] each, either may be NULL; synchronises */
 
+/* ---- capture statistics: counts, extrema, an amplitude histogram and the first two moments of a stream, accumulated on the device
+ * (additive, still ABI v9) ----
+ * No counterpart in the reference.  iqgpu_psd says where a signal sits and iqgpu_sgram when; this accumulator answers what a user asks
+ * before building a chain at all: is the capture clipping, how many ADC bits does it use, how large is the DC offset, what gain
+ * brings it to a sensible level, do I and Q carry the same power.  One stream of frames in one sample format, independent of any
+ * chain; it serves a raw capture and a chain's output bytes alike (rail counts behind the integer pack, level behind the AGC).
+ * There is NO gain: the result describes the bytes as they are, x = the library's unpack (the expressions of
+ * iqgpu_convert_block_to_cf32) at gain 1.  A caller scales sum by g and sum_sq / sum_iq / peak_power by g^2 itself.
+ * THE CONTRACT, per component c (0 = I, 1 = Q) of every frame, `code` the integer in the file (little endian; cs24 sign-extended):
+ *   hist[c][bin]: the bin comes from INTEGER arithmetic on the code, never from the rounded float (cs32 codes k 2^24 - 1 round up to
+ *   the next bin's edge in float).  Shifts of signed codes are arithmetic.
+ *     cu8   code                  cs8     code + 128                        cu16  code >> 8           cs16  (code >> 8) + 128
+ *     cs24  (code >> 16) + 128    sc16q11 clamp((code >> 4) + 128, 0, 255)  cu32  code >> 24          cs32  (code >> 24) + 128
+ *     cf32  clamp(floor(v * 128) + 128, 0, 255) on the finite value v (v * 128 is exact in float; the clamp is taken first)
+ *   rail_lo[c] / rail_hi[c]: components EQUAL to the format's lowest / highest code (cu8 0 / 255, cs8 -128 / 127, cu16 0 / 65535,
+ *   cs16 -32768 / 32767, cs24 -2^23 / 2^23 - 1, cu32 0 / 2^32 - 1, cs32 -2^31 / 2^31 - 1); sc16q11: code <= -2048 / code >= 2047;
+ *   cf32: v <= -1.0 / v >= 1.0.
+ *   nonfinite_frames: cf32 only, frames with a NaN or Inf component.  They are counted (in frames too, and they keep their stream
+ *   index) and enter NOTHING else, so one bad frame does not erase a report.  Below, "frame" means a finite one.
+ *   min[c] / max[c]: of x, in float.  peak_power = max over frames of (double)re * re + (double)im * im -- both products are exact in
+ *   double, the sum is rounded once; peak_frame = the stream index (frames since the last reset, from 0) of the FIRST frame that
+ *   attains it.  With no finite frame min, max and peak_power are 0 and peak_frame is 0.
+ *   sum[c] = sum of (double)x, sum_sq[c] = sum of (double)x * x, sum_iq = sum of (double)re * im: every term is exact in double, the
+ *   additions round, in the order below.
+ * ORDER-FREE FIELDS: the counts, the histogram, min / max, peak_power and peak_frame do not depend on any summation order: they are
+ * exact.  THE FIVE DOUBLE SUMS: their order belongs to the stream, as in iqgpu_psd.  Frames (non-finite ones included: they hold their
+ * place and add nothing) are grouped by stream index into pages of frames_per_page (iqgpu_stats_geometry: 65536) consecutive frames.
+ * Within a page, frame i (its index in the page) belongs to column i mod 1024; a column is summed in increasing i from 0.0; when the
+ * page closes the 1024 column sums are added in a fixed binary tree of adjacent pairs: level 0 adds columns (2 j, 2 j + 1), level 1
+ * those sums pairwise again, ... ten levels.  The total is ((0.0 + page 0) + page 1) + ... in page order.  The open page (the one the
+ * stream position lies in) is kept apart as its 1024 column sums and continued by the next push; read reports total + tree(open
+ * columns) (total alone when the position is on a page boundary).
+ * THE RESULT IS A FUNCTION OF THE PUSHED FRAMES ALONE, BIT FOR BIT: any split of the stream into push calls, host or device, of any
+ * lengths (one frame; across a page boundary) and at any frame alignment gives the same iqgpu_stats_result.
+ * Errors, streams, alignment: iqgpu_psd's.  IQGPU_EINVAL for a NULL argument; IQGPU_EFORMAT for an unknown format; IQGPU_ENODEV from
+ * create without a usable device; IQGPU_ENOMEM; IQGPU_EHIP.  A refused call leaves the accumulator as it was; frames == 0 succeeds and
+ * changes nothing; a push that failed half way poisons the handle (IQGPU_EHIP from push / read) until reset; one thread per handle.
+ * push_device is asynchronous on the stream it is given (NULL: the null stream) and the input must stay valid until that stream has
+ * passed the work; a push on another stream than the previous push's first waits for that push's work.  push stages host memory
+ * through a device buffer of the handle, in bounded slices, on a stream of the handle, and returns with the work queued and the
+ * caller's memory free.  read and reset synchronise, and behind either the handle refers to no stream of the caller's; read observes
+ * and does not disturb.  d_raw needs frame alignment only (the frame's size; cs24: 2 bytes).
+ * Behind iqgpu_chain_process_device(c, .., d_out, .., &n) the statistics of the output are
+ * iqgpu_stats_push_device(p, d_out, n, iqgpu_chain_get_stream(c)).
+ * iqgpu_stats_merge (host only, no device) CONCATENATES: `next` is the result of the stream directly behind `into`'s.  frames,
+ * nonfinite_frames, the rails and the histogram add; min / max combine; the larger peak_power wins and on a tie the earlier frame
+ * (into's); next->peak_frame is offset by into->frames; a side without finite frames is the identity for min / max / peak; the five
+ * doubles add (into + next).  ALL INTEGER, EXTREMUM AND PEAK FIELDS OF A MERGE EQUAL THE SINGLE STREAM'S EXACTLY, for any cuts and any
+ * grouping.  The five doubles of a merge are a sum of per-shard sums and, as for the power spectrum, are NOT promised bit-equal to
+ * the single stream's.
+ * iqgpu_stats_derive (host only), every figure in double in this operation order; a figure whose n or denominator is 0 (or whose
+ * logarithm / root would not be real) is 0:
+ *   n = frames - nonfinite_frames;  mean_i = sum[0] / n;  mean_q = sum[1] / n;  power = (sum_sq[0] + sum_sq[1]) / n;
+ *   rms_dbfs = 10 log10(power);  peak_dbfs = 10 log10(peak_power);  crest_db = peak_dbfs - rms_dbfs (0 unless power and peak_power > 0);
+ *   var_i = sum_sq[0] / n - mean_i * mean_i;  var_q = sum_sq[1] / n - mean_q * mean_q;
+ *   iq_gain_ratio = sqrt(var_i / var_q) (var_q > 0, var_i >= 0);
+ *   iq_phase_rad = asin(r), r = (sum_iq / n - mean_i * mean_q) / sqrt(var_i * var_q) clamped to [-1, 1] (var_i > 0 and var_q > 0);
+ *   clip_fraction = (double)(rail_lo[0] + rail_lo[1] + rail_hi[0] + rail_hi[1]) / (2.0 * n);
+ *   bins_used[c] = the non-empty bins of hist[c]. */
+typedef struct {
+    uint64_t frames;              /* pushed since the last reset */
+    uint64_t nonfinite_frames;    /* cf32 only: frames with a NaN or Inf component; they enter NOTHING below */
+    uint64_t rail_lo[2], rail_hi[2];   /* [0] = I, [1] = Q: components on the format's lowest / highest code */
+    uint64_t hist[2][256];        /* amplitude histogram per component */
+    float    min[2], max[2];      /* of the unpacked component at gain 1 */
+    double   peak_power;          /* max over frames of (double)re*re + (double)im*im, sum rounded once */
+    uint64_t peak_frame;          /* stream index of the FIRST frame that attains it */
+    double   sum[2], sum_sq[2], sum_iq;   /* of (double)x, (double)x*x, (double)re*im: exact terms, order above */
+} iqgpu_stats_result;
+typedef struct {
+    uint64_t n;                   /* finite frames */
+    double   mean_i, mean_q, power, rms_dbfs, peak_dbfs, crest_db, var_i, var_q, iq_gain_ratio, iq_phase_rad, clip_fraction;
+    uint32_t bins_used[2];
+} iqgpu_stats_derived;
+typedef struct iqgpu_stats iqgpu_stats;
+/* diagnostics, for tests: the frames of a page -- what it takes to reach the page boundaries, nothing a caller has to know */
+void  iqgpu_stats_geometry(size_t *frames_per_page);
+int   iqgpu_stats_create(int device, int format, iqgpu_stats **out);
+void  iqgpu_stats_destroy(iqgpu_stats *p);
+int   iqgpu_stats_reset(iqgpu_stats *p);
+int   iqgpu_stats_push(iqgpu_stats *p, const void *raw, size_t frames);                             /* host memory */
+int   iqgpu_stats_push_device(iqgpu_stats *p, const void *d_raw, size_t frames, void *hip_stream);  /* device memory, asynchronous on hip_stream */
+int   iqgpu_stats_read(iqgpu_stats *p, iqgpu_stats_result *r);                                      /* synchronises; observes, does not disturb */
+/* host only, no device */
+int   iqgpu_stats_merge(iqgpu_stats_result *into, const iqgpu_stats_result *next);   /* `next` is the stream directly behind `into` */
+int   iqgpu_stats_derive(const iqgpu_stats_result *r, iqgpu_stats_derived *d);
+
 /* ---- WAV capture metadata -> frequency shift (host only): the step in front of the path for real captures ----
  * SdrMetadata and its parsers (src/input_wav.c:54-100, 146-438), the shift rule of wav_initialize (592-629). */
 enum { IQGPU_SDR_UNKNOWN = 0, IQGPU_SDR_CONSOLE = 1, IQGPU_SDR_SHARP = 2, IQGPU_SDR_UNO = 3, IQGPU_SDR_CONNECT = 4 };

@@ -136,6 +136,21 @@ class SgramInfo(C.Structure):
                 ("window_sum", C.c_double), ("window_sum_sq", C.c_double)]
 
 
+class StatsResult(C.Structure):
+    """iqgpu_stats_result: what iqgpu_stats_read reports and iqgpu_stats_merge concatenates"""
+    _fields_ = [("frames", C.c_uint64), ("nonfinite_frames", C.c_uint64), ("rail_lo", C.c_uint64 * 2), ("rail_hi", C.c_uint64 * 2),
+                ("hist", (C.c_uint64 * 256) * 2), ("min", C.c_float * 2), ("max", C.c_float * 2),
+                ("peak_power", C.c_double), ("peak_frame", C.c_uint64),
+                ("sum", C.c_double * 2), ("sum_sq", C.c_double * 2), ("sum_iq", C.c_double)]
+
+
+class StatsDerived(C.Structure):
+    """iqgpu_stats_derived: the figures iqgpu_stats_derive computes from a result"""
+    _fields_ = [("n", C.c_uint64), ("mean_i", C.c_double), ("mean_q", C.c_double), ("power", C.c_double), ("rms_dbfs", C.c_double),
+                ("peak_dbfs", C.c_double), ("crest_db", C.c_double), ("var_i", C.c_double), ("var_q", C.c_double),
+                ("iq_gain_ratio", C.c_double), ("iq_phase_rad", C.c_double), ("clip_fraction", C.c_double), ("bins_used", C.c_uint32 * 2)]
+
+
 class WavInfo(C.Structure):
     _fields_ = [("source_software", C.c_int),
                 ("software_name", C.c_char * 64), ("software_version", C.c_char * 64), ("radio_model", C.c_char * 128),
@@ -258,6 +273,15 @@ SYMBOLS = [
     ("iqgpu_sgram_push", C.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, C.POINTER(_sz)]),
     ("iqgpu_sgram_push_device", C.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
     ("iqgpu_sgram_read_open", C.c_int, [_vp, _vp, _vp, C.POINTER(SgramInfo)]),
+    ("iqgpu_stats_geometry", None, [C.POINTER(_sz)]),
+    ("iqgpu_stats_create", C.c_int, [C.c_int, C.c_int, C.POINTER(_vp)]),
+    ("iqgpu_stats_destroy", None, [_vp]),
+    ("iqgpu_stats_reset", C.c_int, [_vp]),
+    ("iqgpu_stats_push", C.c_int, [_vp, _vp, _sz]),
+    ("iqgpu_stats_push_device", C.c_int, [_vp, _vp, _sz, _vp]),
+    ("iqgpu_stats_read", C.c_int, [_vp, C.POINTER(StatsResult)]),
+    ("iqgpu_stats_merge", C.c_int, [C.POINTER(StatsResult), C.POINTER(StatsResult)]),
+    ("iqgpu_stats_derive", C.c_int, [C.POINTER(StatsResult), C.POINTER(StatsDerived)]),
     ("iqgpu_wav_info_init", None, [C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_auxi", C.c_int, [_vp, _sz, C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_filename", C.c_int, [C.c_char_p, C.POINTER(WavInfo)]),

@@ -79,6 +79,12 @@
  * input bytes and one on the output bytes, at the library's defaults with R segments a row (32), fed on the chain's stream behind every
  * call.  PREFIX.in.f32 and PREFIX.out.f32 receive row_sum of every row as it finishes (1024 little-endian floats a row, bin 0 = DC);
  * the partial last row is not written.  PREFIX.json holds both info records -- rows, segments, open_segments among them -- and the rates.
+ *
+ * --stats PREFIX (plain runs and --shards N with independent shards; no --seamless* mode, no --iq-calibrate): one iqgpu_stats accumulator
+ * on the input bytes and one on the output bytes of every shard, fed on the chain's stream behind every call.  The shards' results are
+ * concatenated in shard order (iqgpu_stats_merge: every count, extremum and the peak are exactly the one stream's) and PREFIX.json
+ * holds, for "in" and "out", the complete iqgpu_stats_result -- every field, the histograms as arrays, doubles as %.17g -- and under
+ * "derived" the iqgpu_stats_derived record.
  */
 #define _GNU_SOURCE
 #define _FILE_OFFSET_BITS 64
@@ -160,6 +166,7 @@ typedef struct {
     const char *psd_prefix;           /* --psd PREFIX: the power spectra of the input and of the output, written behind the run (write_psd) */
     const char *sgram_prefix;         /* --sgram PREFIX: the rows of the input and of the output, appended as they finish (write_sgram_rows) */
     unsigned sgram_row_segments;      /* --sgram-row-segments R (0: the library's default) */
+    const char *stats_prefix;         /* --stats PREFIX: the statistics of the input and of the output bytes, merged over the shards (write_stats) */
 } Options;
 
 typedef struct {
@@ -188,6 +195,7 @@ typedef struct {
     const void *redo_blob; size_t redo_bytes;
     int certified, redone;
     int barriers;                     /* how many of its mode's barriers this thread has been through */
+    iqgpu_stats_result stats[2];      /* --stats: this shard's input and output bytes (read_stats) */
     int rc;
     char err[256];
 } Shard;
@@ -207,6 +215,7 @@ typedef struct {
     size_t agc_cap;                   /* rows sh->rows has room for (alloc_agc_table) */
     iqgpu_psd *psd_in, *psd_out;      /* --psd: one accumulator on the input bytes, one on the output bytes (the library's defaults) */
     iqgpu_psd_opts psd_opts;          /* ... the options both were created with */
+    iqgpu_stats *st[2];               /* --stats: side 0 = input bytes, 1 = output bytes */
     /* --sgram, side 0 = input, 1 = output: the accumulator, its file, per pipeline buffer the device and pinned host planes of the rows a
      * call finishes (sg_cap rows each) and how many the call in flight there did finish */
     iqgpu_sgram *sg[2]; iqgpu_sgram_opts sg_opts; FILE *sg_f[2];
@@ -515,6 +524,10 @@ static int ctx_open(Ctx *x)
         CK(iqgpu_psd_create(dev, x->d.in_format, &x->psd_opts, &x->psd_in));
         CK(iqgpu_psd_create(dev, x->d.out_format, &x->psd_opts, &x->psd_out));
     }
+    if (o->stats_prefix) {
+        CK(iqgpu_stats_create(dev, x->d.in_format, &x->st[0]));
+        CK(iqgpu_stats_create(dev, x->d.out_format, &x->st[1]));
+    }
     if (o->sgram_prefix) {
         static const char *const side[2] = {"in", "out"};
         const int fmt[2] = {x->d.in_format, x->d.out_format};
@@ -555,6 +568,7 @@ static void ctx_close(Ctx *x)
     free(x->pre);
     if (x->chain) iqgpu_chain_synchronize(x->chain);
     iqgpu_psd_destroy(x->psd_in); iqgpu_psd_destroy(x->psd_out);     /* (in front of the stream they last worked on) */
+    iqgpu_stats_destroy(x->st[0]); iqgpu_stats_destroy(x->st[1]);
     for (int k = 0; k < 2; k++) {
         iqgpu_sgram_destroy(x->sg[k]);
         if (x->sg_f[k]) fclose(x->sg_f[k]);
@@ -707,6 +721,9 @@ static int stream_range(Ctx *x)
             /* --psd: behind the chain on its stream, in front of e_k: both buffers stay as they are until the accumulators have read them */
             if (x->psd_in) CK(iqgpu_psd_push_device(x->psd_in, x->d_in[b], n, x->s_k));
             if (x->psd_out) CK(iqgpu_psd_push_device(x->psd_out, x->d_out[b], out_frames[b], x->s_k));
+            /* --stats: the same place */
+            if (x->st[0]) CK(iqgpu_stats_push_device(x->st[0], x->d_in[b], n, x->s_k));
+            if (x->st[1]) CK(iqgpu_stats_push_device(x->st[1], x->d_out[b], out_frames[b], x->s_k));
             /* --sgram: the same place; the rows a call finishes follow on the same stream into pinned memory, so e_out covers them too */
             for (int k = 0; k < 2 && x->sg[k]; k++) {
                 const size_t row_bytes = x->sg_opts.nfft * sizeof(float);
@@ -787,6 +804,52 @@ static int write_psd(Ctx *x)
     return 0;
 }
 
+/* --stats: this shard's two results, for main to merge in shard order */
+static int read_stats(Ctx *x)
+{
+    Shard *sh = x->sh;
+    for (int k = 0; k < 2; k++) CK(iqgpu_stats_read(x->st[k], &sh->stats[k]));
+    return 0;
+}
+
+static void json_u64s(FILE *f, const char *name, const uint64_t *v, int n)
+{
+    fprintf(f, "\"%s\": [", name);
+    for (int i = 0; i < n; i++) fprintf(f, "%s%llu", i ? ", " : "", (unsigned long long)v[i]);
+    fprintf(f, "]");
+}
+
+/* --stats PREFIX: PREFIX.json -- the shards' results concatenated in shard order, every field of both, and both derived records */
+static int write_stats(const Options *o, Shard *sh)
+{
+    static const char *const side[2] = {"in", "out"};
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.json", o->stats_prefix);
+    FILE *f = fopen(path, "w");
+    if (!f) REFUSE(1, "writing %.160s: %s\n", path, strerror(errno));
+    fprintf(f, "{\"shards\": %d", o->shards);
+    for (int k = 0; k < 2; k++) {
+        iqgpu_stats_result *r = &sh[0].stats[k];
+        iqgpu_stats_derived d;
+        for (int s = 1; s < o->shards; s++) iqgpu_stats_merge(r, &sh[s].stats[k]);
+        iqgpu_stats_derive(r, &d);
+        fprintf(f, ", \"%s\": {\"frames\": %llu, \"nonfinite_frames\": %llu, ", side[k], (unsigned long long)r->frames, (unsigned long long)r->nonfinite_frames);
+        json_u64s(f, "rail_lo", r->rail_lo, 2); fprintf(f, ", ");
+        json_u64s(f, "rail_hi", r->rail_hi, 2); fprintf(f, ", \"hist\": [");
+        for (int c = 0; c < 2; c++) { fprintf(f, "%s[", c ? ", " : ""); for (int b = 0; b < 256; b++) fprintf(f, "%s%llu", b ? ", " : "", (unsigned long long)r->hist[c][b]); fprintf(f, "]"); }
+        fprintf(f, "], \"min\": [%.17g, %.17g], \"max\": [%.17g, %.17g],\"peak_power\": %.17g, \"peak_frame\": %llu, \"sum\": [%.17g, %.17g], "
+                "\"sum_sq\": [%.17g, %.17g], \"sum_iq\": %.17g, ", r->min[0], r->min[1], r->max[0], r->max[1], r->peak_power, (unsigned long long)r->peak_frame,
+                r->sum[0], r->sum[1], r->sum_sq[0], r->sum_sq[1], r->sum_iq);
+        fprintf(f, "\"derived\": {\"n\": %llu, \"mean_i\": %.17g, \"mean_q\": %.17g, \"power\": %.17g, \"rms_dbfs\": %.17g, \"peak_dbfs\": %.17g, \"crest_db\": %.17g, "
+                "\"var_i\": %.17g, \"var_q\": %.17g, \"iq_gain_ratio\": %.17g, \"iq_phase_rad\": %.17g, \"clip_fraction\": %.17g, \"bins_used\": [%u, %u]}}",
+                (unsigned long long)d.n, d.mean_i, d.mean_q, d.power, d.rms_dbfs, d.peak_dbfs, d.crest_db, d.var_i, d.var_q, d.iq_gain_ratio, d.iq_phase_rad,
+                d.clip_fraction, d.bins_used[0], d.bins_used[1]);
+    }
+    fprintf(f, "}\n");
+    if (fclose(f) != 0) REFUSE(1, "writing %.160s: %s\n", path, strerror(errno));
+    return 0;
+}
+
 /* --sgram PREFIX: the row files are complete (stream_range appended every finished row); PREFIX.json with both info records and the two
  * rates.  The partial last row stays unwritten: open_segments says how many segments it held */
 static int write_sgram(Ctx *x)
@@ -852,7 +915,7 @@ static void *run_shard(void *arg)
 
     if (o->dry) dry_shard(&x);
     else {
-        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && !(o->sgram_prefix && write_sgram(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
+        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && !(o->sgram_prefix && write_sgram(&x)) && !(o->stats_prefix && read_stats(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
         /* (a shard that fails early still keeps the rendezvous of the passes: the others wait there) */
         while (sh->barriers < MODES[o->mode].barriers) rendezvous(&x, NULL, NULL);
     }
@@ -875,6 +938,7 @@ static void usage(void)
             "          [--seamless-rms (--seamless for chains with the dx / local output AGC: seek from a bounded window, seams certified, a range behind a seam that is not is redone)]\n"
             "          [--seamless-dc-rms (the exact --seamless for --dc-block chains with the dx / local AGC: DC measure, walk, then --seamless-rms's seek, certificate and redo)]\n"
             "          [--seamless-dc-agc (the exact --seamless for --dc-block chains with the digital AGC: DC measure, walk, shadow AGC measure, walk, then the ordinary pass)]\n"
+            "          [--stats PREFIX (plain runs and independent --shards: counts, rails, extrema, peak, histogram and moments of the input and of the output bytes, merged in shard order, as PREFIX.json)]\n"
             "          [--psd PREFIX (plain single-stream runs: the power spectra of the input and of the output -- Hann, 1024 bins -- as PREFIX.in.f64, PREFIX.out.f64, PREFIX.json)]\n"
             "          [--sgram PREFIX [--sgram-row-segments R] (the same runs: the spectrum per row of R segments (32) of the input and of the output, rows appended as they finish to PREFIX.in.f32, PREFIX.out.f32; PREFIX.json)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
@@ -904,6 +968,7 @@ static int parse_args(int argc, char **argv, Options *o)
         else if (!strcmp(a, "--iq-factors")) { o->desc.iq_correct_enable = 1; o->have_iq_factors = 1; sscanf(NEXT, "%f:%f", &o->desc.iq_mag, &o->desc.iq_phase); }
         else if (!strcmp(a, "--iq-calibrate")) o->iq_calibrate = 1;
         else if (!strcmp(a, "--psd")) o->psd_prefix = NEXT;
+        else if (!strcmp(a, "--stats")) o->stats_prefix = NEXT;
         else if (!strcmp(a, "--sgram")) o->sgram_prefix = NEXT;
         else if (!strcmp(a, "--sgram-row-segments")) { const long long r = atoll(NEXT); o->sgram_row_segments = r >= 1 && r <= (1 << 20) ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--no-resample")) o->desc.no_resample = 1;
@@ -974,6 +1039,10 @@ static int validate(const Options *o)
     if (o->psd_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
         REFUSE(2, "usage: --psd is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
     if (o->psd_prefix && strlen(o->psd_prefix) > 3000) REFUSE(2, "usage: --psd: the prefix is too long\n");
+    /* (statistics merge exactly: independent shards are fine; the seamless modes run passes this option has no place in yet) */
+    if (o->stats_prefix && (o->mode != M_INDEPENDENT || o->iq_calibrate))
+        REFUSE(2, "usage: --stats is for plain runs and independent --shards: it excludes every --seamless* mode and --iq-calibrate\n");
+    if (o->stats_prefix && strlen(o->stats_prefix) > 3000) REFUSE(2, "usage: --stats: the prefix is too long\n");
     if (o->sgram_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
         REFUSE(2, "usage: --sgram is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
     if (o->sgram_prefix && strlen(o->sgram_prefix) > 3000) REFUSE(2, "usage: --sgram: the prefix is too long\n");
@@ -1232,6 +1301,7 @@ int main(int argc, char **argv)
     }
     int seams[2] = {0, 0};
     if (MODES[o.mode].certify && !o.dry && rc == 0) rc = certify_seams(&o, sh, th, &frames_out, seams);
+    if (o.stats_prefix && !o.dry && rc == 0) rc = write_stats(&o, sh);
     if (o.dry || !o.quiet) report(&o, sh, total_frames, frames_out, now_s() - t0, stream_s, seams);
     for (int s = 0; s < o.shards; s++) if (sh[s].rows) iqgpu_host_free_pinned(sh[s].rows);
     for (int s = 0; s < o.shards; s++) { free(sh[s].dc_rows); free(sh[s].dc_call_rows); free(sh[s].blob); }
