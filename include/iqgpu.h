@@ -994,6 +994,85 @@ int   iqgpu_stats_read(iqgpu_stats *p, iqgpu_stats_result *r);                  
 int   iqgpu_stats_merge(iqgpu_stats_result *into, const iqgpu_stats_result *next);   /* `next` is the stream directly behind `into` */
 int   iqgpu_stats_derive(const iqgpu_stats_result *r, iqgpu_stats_derived *d);
 
+/* ---- envelope: power, peak and rail count per block of B consecutive frames, emitted as the stream goes by (additive, still ABI v9) ----
+ * No counterpart in the reference.  The cheap time axis of the family: where does the transmission begin and end, where are the
+ * dropouts, where does it clip, does the output AGC pump.  One stream of frames in one sample format, independent of any chain, with
+ * iqgpu_sgram's calling convention.  There is NO gain: like iqgpu_stats it describes the bytes, x = the library's unpack (the
+ * expressions of iqgpu_convert_block_to_cf32) at gain 1.  The only option is block_frames = B, a power of two, 2^6 .. 2^24.
+ * Rows: row r is frames [r B, (r + 1) B) of everything pushed since the last reset; rows = frames / B, rounded down; the rest is the
+ * open row.
+ * Per frame: p = (double)re * re + (double)im * im -- both products exact in double, the sum rounded once: iqgpu_stats' peak_power
+ * term.  A cf32 frame with a NaN or Inf component holds its place, enters nothing below and is counted in info.nonfinite_frames.
+ * Per finished row, densely packed, one value each:
+ *   row_sum[r]  (float)  the sum of p over the row's frames, in double in the order below, rounded ONCE to float (nearest even).  Not
+ *                        normalised: the mean power is row_sum / B.
+ *   row_peak[r] (float)  the max of p over the row's frames, rounded once to float; 0 without a finite frame.
+ *   row_rail[r] (uint32) the COMPONENTS of the row on a rail, by iqgpu_stats' rail_lo / rail_hi definition per format, 0 .. 2 B.
+ * Summation order: it belongs to the stream, and it is iqgpu_stats' order applied per row.  A row is cut into cells of 65536
+ * consecutive frames counted from the row's first frame (B <= 65536: one cell of B frames).  Within a cell, frame i (its index in the
+ * cell) belongs to column i mod 1024; a column is summed in increasing i from 0.0; the 1024 column sums are added in the fixed tree of
+ * adjacent pairs, ten levels (B <= 1024: the balanced adjacent-pair tree over the row's B terms, empty columns being +0.0); the row
+ * is ((0.0 + cell 0) + cell 1) + ... in double.
+ * ROWS AND OPEN ROW ARE A FUNCTION OF THE PUSHED FRAMES AND B ALONE, BIT FOR BIT: any split of the stream into push calls, host or
+ * device, of any lengths (one frame; ending inside a row, on a row boundary, inside a cell) at frame alignment only (the frame's
+ * size; cs24: 2 bytes) gives the same rows in the same order -- the rows each call returned, concatenated -- and the same open row.
+ * With iqgpu_stats on the same bytes, for a stream of whole rows, exactly: (float)peak_power == max over r of row_peak[r], and
+ * rail_lo[0] + rail_lo[1] + rail_hi[0] + rail_hi[1] == the sum of row_rail.
+ * The open row: iqgpu_env_read_open returns its unrounded double sum (the total of its closed cells + tree(open columns)), its peak
+ * in double and its rail count, all 0 when info.open_frames == 0.  It observes and does not disturb.
+ * push / push_device: row_sum, row_peak and row_rail receive the rows the call finishes in host / device memory; any may be NULL (that
+ * plane is not produced).  *rows (rows may be NULL) is pure arithmetic and is set when the call returns, for the asynchronous
+ * push_device too; iqgpu_env_max_rows(p, frames) is what the NEXT push of `frames` would return, exact.  cap_rows (the room in each
+ * plane given, in rows) smaller than that: IQGPU_ECAPACITY before anything is queued, the handle as it was, *rows = 0.
+ * Errors, streams, poisoning, frames == 0, one thread per handle: iqgpu_sgram's, word for word (IQGPU_EINVAL for a NULL argument or a
+ * block_frames outside the list).  Behind iqgpu_chain_process_device(c, .., d_out, .., &n) the rows of the output are
+ * iqgpu_env_push_device(p, d_out, n, d_sum, d_peak, d_rail, cap, &rows, iqgpu_chain_get_stream(c)).
+ * THE BURST FINDER (host only, no device) turns finished rows into ranges for iqgpu_chain_seek and the harness's range modes.  The
+ * mean of a row is (double)row_sum[r] / B; thresholds `on` and `off` (off <= on) are on the mean, compared in double.
+ *   A burst opens at the first row whose mean is >= on.  It closes in front of the first run of MORE than hang_rows consecutive rows
+ *   whose mean is < off (a NaN mean counts as below off); shorter dips stay inside, and without such a run it lasts to the last row.
+ *   A burst of fewer than min_rows rows is dropped.  The rest are widened by pad_rows rows on both sides, clipped to the stream, and
+ *   bursts that then touch or overlap are joined.  first_frame and frames are multiples of B; peak_row is the first row of the
+ *   (widened, joined) burst with the largest mean, peak_mean that mean.
+ *   More bursts than cap: IQGPU_ECAPACITY with *n = the number needed (the first cap are written).
+ * iqgpu_env_floor: the mean power of the row at rank floor(fraction (rows - 1)) of the ascending order of row_sum (NaN last), selected
+ * exactly on a copy; fraction in [0, 1], rows >= 1.  What a caller derives on / off from: floor * 10^(dB / 10). */
+typedef struct {
+    uint32_t block_frames;        /* B: frames of a row, a power of two, 64 .. 2^24 (4096) */
+} iqgpu_env_opts;
+typedef struct {
+    uint64_t frames, rows;        /* pushed since the last reset; rows finished = frames / B */
+    uint64_t nonfinite_frames;    /* cf32 only: frames with a NaN or Inf component */
+    uint32_t open_frames;         /* frames of the open row = frames % B */
+    uint32_t block_frames;
+} iqgpu_env_info;
+typedef struct {
+    uint32_t block_frames;        /* B of the rows */
+    uint32_t min_rows, hang_rows, pad_rows;
+    double   on, off;             /* thresholds on the mean power row_sum / B, off <= on */
+} iqgpu_env_burst_opts;
+typedef struct {
+    uint64_t first_frame, frames; /* multiples of B */
+    uint64_t peak_row;            /* the first row of the burst with the largest mean */
+    double   peak_mean;
+} iqgpu_env_burst;
+typedef struct iqgpu_env iqgpu_env;
+void   iqgpu_env_opts_init(iqgpu_env_opts *o);                      /* the default in parentheses above */
+/* no device: the rows a stream of `frames` frames finishes */
+int    iqgpu_env_rows(const iqgpu_env_opts *o, uint64_t frames, uint64_t *rows);
+int    iqgpu_env_create(int device, int format, const iqgpu_env_opts *o, iqgpu_env **out);
+void   iqgpu_env_destroy(iqgpu_env *p);
+int    iqgpu_env_reset(iqgpu_env *p);
+size_t iqgpu_env_max_rows(const iqgpu_env *p, size_t frames);       /* rows the NEXT push of `frames` finishes: exact; 0 for a NULL handle */
+int    iqgpu_env_push(iqgpu_env *p, const void *raw, size_t frames, float *row_sum, float *row_peak, uint32_t *row_rail, size_t cap_rows,
+                      size_t *rows);                                /* host memory */
+int    iqgpu_env_push_device(iqgpu_env *p, const void *d_raw, size_t frames, float *d_row_sum, float *d_row_peak, uint32_t *d_row_rail,
+                             size_t cap_rows, size_t *rows, void *hip_stream);   /* device memory, asynchronous on hip_stream */
+int    iqgpu_env_read_open(iqgpu_env *p, double *sum, double *peak, uint32_t *rail, iqgpu_env_info *info);   /* any may be NULL; synchronises */
+/* host only, no device */
+int    iqgpu_env_bursts(const float *row_sum, size_t rows, const iqgpu_env_burst_opts *o, iqgpu_env_burst *out, size_t cap, size_t *n);
+int    iqgpu_env_floor(const float *row_sum, size_t rows, uint32_t block_frames, double fraction, double *mean_power);
+
 /* ---- WAV capture metadata -> frequency shift (host only): the step in front of the path for real captures ----
  * SdrMetadata and its parsers (src/input_wav.c:54-100, 146-438), the shift rule of wav_initialize (592-629). */
 enum { IQGPU_SDR_UNKNOWN = 0, IQGPU_SDR_CONSOLE = 1, IQGPU_SDR_SHARP = 2, IQGPU_SDR_UNO = 3, IQGPU_SDR_CONNECT = 4 };

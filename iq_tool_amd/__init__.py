@@ -7,5 +7,6 @@ from .iq_optimizer import IqOptimizer                            # noqa: F401
 from .psd import Psd                                             # noqa: F401
 from .sgram import Sgram                                         # noqa: F401
 from .stats import Stats                                         # noqa: F401
+from .env import Env                                             # noqa: F401
 
-__all__ = ["Chain", "DeviceBuffer", "PinnedBuffer", "IqOptimizer", "Psd", "Sgram", "Stats","make_desc", "FMT", "IqgpuError", "load", "LIB_PATH"]
+__all__ = ["Chain", "DeviceBuffer", "PinnedBuffer", "IqOptimizer", "Psd", "Sgram", "Stats", "Env", "make_desc", "FMT", "IqgpuError", "load", "LIB_PATH"]

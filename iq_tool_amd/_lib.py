@@ -151,6 +151,28 @@ class StatsDerived(C.Structure):
                 ("iq_gain_ratio", C.c_double), ("iq_phase_rad", C.c_double), ("clip_fraction", C.c_double), ("bins_used", C.c_uint32 * 2)]
 
 
+class EnvOpts(C.Structure):
+    """iqgpu_env_opts: the option of an envelope accumulator (iqgpu_env_opts_init sets the default)"""
+    _fields_ = [("block_frames", C.c_uint32)]
+
+
+class EnvInfo(C.Structure):
+    """iqgpu_env_info: what iqgpu_env_read_open reports beside the open row"""
+    _fields_ = [("frames", C.c_uint64), ("rows", C.c_uint64), ("nonfinite_frames", C.c_uint64), ("open_frames", C.c_uint32),
+                ("block_frames", C.c_uint32)]
+
+
+class EnvBurstOpts(C.Structure):
+    """iqgpu_env_burst_opts: the rules of iqgpu_env_bursts"""
+    _fields_ = [("block_frames", C.c_uint32), ("min_rows", C.c_uint32), ("hang_rows", C.c_uint32), ("pad_rows", C.c_uint32),
+                ("on", C.c_double), ("off", C.c_double)]
+
+
+class EnvBurst(C.Structure):
+    """iqgpu_env_burst: one range iqgpu_env_bursts found"""
+    _fields_ = [("first_frame", C.c_uint64), ("frames", C.c_uint64), ("peak_row", C.c_uint64), ("peak_mean", C.c_double)]
+
+
 class WavInfo(C.Structure):
     _fields_ = [("source_software", C.c_int),
                 ("software_name", C.c_char * 64), ("software_version", C.c_char * 64), ("radio_model", C.c_char * 128),
@@ -282,6 +304,17 @@ SYMBOLS = [
     ("iqgpu_stats_read", C.c_int, [_vp, C.POINTER(StatsResult)]),
     ("iqgpu_stats_merge", C.c_int, [C.POINTER(StatsResult), C.POINTER(StatsResult)]),
     ("iqgpu_stats_derive", C.c_int, [C.POINTER(StatsResult), C.POINTER(StatsDerived)]),
+    ("iqgpu_env_opts_init", None, [C.POINTER(EnvOpts)]),
+    ("iqgpu_env_rows", C.c_int, [C.POINTER(EnvOpts), C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("iqgpu_env_create", C.c_int, [C.c_int, C.c_int, C.POINTER(EnvOpts), C.POINTER(_vp)]),
+    ("iqgpu_env_destroy", None, [_vp]),
+    ("iqgpu_env_reset", C.c_int, [_vp]),
+    ("iqgpu_env_max_rows", _sz, [_vp, _sz]),
+    ("iqgpu_env_push", C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_env_push_device", C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    ("iqgpu_env_read_open", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(EnvInfo)]),
+    ("iqgpu_env_bursts", C.c_int, [_vp, _sz, C.POINTER(EnvBurstOpts), _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_env_floor", C.c_int, [_vp, _sz, C.c_uint32, C.c_double, C.POINTER(C.c_double)]),
     ("iqgpu_wav_info_init", None, [C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_auxi", C.c_int, [_vp, _sz, C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_filename", C.c_int, [C.c_char_p, C.POINTER(WavInfo)]),

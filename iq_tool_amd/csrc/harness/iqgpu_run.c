@@ -80,6 +80,12 @@
  * call.  PREFIX.in.f32 and PREFIX.out.f32 receive row_sum of every row as it finishes (1024 little-endian floats a row, bin 0 = DC);
  * the partial last row is not written.  PREFIX.json holds both info records -- rows, segments, open_segments among them -- and the rates.
  *
+ * --envelope PREFIX [--envelope-block B] (the same runs as --psd, and it may stand beside --psd / --sgram / --stats): one iqgpu_env accumulator
+ * on the input bytes and one on the output bytes, B frames a row (the library's default, 4096), fed on the chain's stream behind every
+ * call.  PREFIX.in.f32 and PREFIX.out.f32 receive row_sum of every row as it finishes (one little-endian float a row); PREFIX.json holds
+ * B, both info records with both open rows, and the bursts of the INPUT (iqgpu_env_bursts) at on = floor(0.1) + 10 dB, off = floor(0.1)
+ * + 7 dB, min_rows 2, hang_rows 2, pad_rows 1, floor(0.1) being iqgpu_env_floor of the input's rows.
+ *
  * --stats PREFIX (plain runs and --shards N with independent shards; no --seamless* mode, no --iq-calibrate): one iqgpu_stats accumulator
  * on the input bytes and one on the output bytes of every shard, fed on the chain's stream behind every call.  The shards' results are
  * concatenated in shard order (iqgpu_stats_merge: every count, extremum and the peak are exactly the one stream's) and PREFIX.json
@@ -166,6 +172,8 @@ typedef struct {
     const char *psd_prefix;           /* --psd PREFIX: the power spectra of the input and of the output, written behind the run (write_psd) */
     const char *sgram_prefix;         /* --sgram PREFIX: the rows of the input and of the output, appended as they finish (write_sgram_rows) */
     unsigned sgram_row_segments;      /* --sgram-row-segments R (0: the library's default) */
+    const char *env_prefix;           /* --envelope PREFIX: row_sum of the input and of the output, appended as the rows finish; the bursts of the input (write_env) */
+    unsigned env_block;               /* --envelope-block B (0: the library's default) */
     const char *stats_prefix;         /* --stats PREFIX: the statistics of the input and of the output bytes, merged over the shards (write_stats) */
 } Options;
 
@@ -220,6 +228,10 @@ typedef struct {
      * call finishes (sg_cap rows each) and how many the call in flight there did finish */
     iqgpu_sgram *sg[2]; iqgpu_sgram_opts sg_opts; FILE *sg_f[2];
     void *sg_d[2][NBUF], *sg_h[2][NBUF]; size_t sg_cap[2], sg_rows[2][NBUF];
+    /* --envelope, the same shape: one float a row; ev_all keeps the input's rows for the burst finder behind the run */
+    iqgpu_env *ev[2]; iqgpu_env_opts ev_opts; FILE *ev_f[2];
+    void *ev_d[2][NBUF], *ev_h[2][NBUF]; size_t ev_cap[2], ev_rows[2][NBUF];
+    float *ev_all; size_t ev_all_n, ev_all_cap;
 } Ctx;
 
 /* the modes with passes: all shard threads meet behind a measure pass and again behind the walk, which shard 0's thread does in between */
@@ -548,6 +560,25 @@ static int ctx_open(Ctx *x)
             if (!x->sg_f[k]) FAIL("writing %.160s: %s", path, strerror(errno));
         }
     }
+    if (o->env_prefix) {
+        static const char *const side[2] = {"in", "out"};
+        const int fmt[2] = {x->d.in_format, x->d.out_format};
+        const size_t most[2] = {x->chunk, x->out_cap / x->obps};      /* frames of one call */
+        char path[4096];
+        iqgpu_env_opts_init(&x->ev_opts);
+        if (o->env_block) x->ev_opts.block_frames = o->env_block;
+        for (int k = 0; k < 2; k++) {
+            CK(iqgpu_env_create(dev, fmt[k], &x->ev_opts, &x->ev[k]));
+            x->ev_cap[k] = most[k] / x->ev_opts.block_frames + 1;     /* rows one call can finish, behind an open row */
+            for (int b = 0; b < NBUF; b++) {
+                CK(iqgpu_device_malloc(dev, x->ev_cap[k] * sizeof(float), &x->ev_d[k][b]));
+                CK(iqgpu_host_malloc_pinned(x->ev_cap[k] * sizeof(float), &x->ev_h[k][b]));
+            }
+            snprintf(path, sizeof(path), "%s.%s.f32", o->env_prefix, side[k]);
+            x->ev_f[k] = fopen(path, "wb");
+            if (!x->ev_f[k]) FAIL("writing %.160s: %s", path, strerror(errno));
+        }
+    }
     if (o->synthetic_frames <= 0) {
         x->in_fd = open(o->in_path, O_RDONLY);
         if (x->in_fd < 0) FAIL("open %s: %s", o->in_path, strerror(errno));
@@ -577,6 +608,15 @@ static void ctx_close(Ctx *x)
             if (x->sg_h[k][b]) iqgpu_host_free_pinned(x->sg_h[k][b]);
         }
     }
+    for (int k = 0; k < 2; k++) {
+        iqgpu_env_destroy(x->ev[k]);
+        if (x->ev_f[k]) fclose(x->ev_f[k]);
+        for (int b = 0; b < NBUF; b++) {
+            if (x->ev_d[k][b]) iqgpu_device_free(dev, x->ev_d[k][b]);
+            if (x->ev_h[k][b]) iqgpu_host_free_pinned(x->ev_h[k][b]);
+        }
+    }
+    free(x->ev_all);
     for (int b = 0; b < NBUF; b++) {
         if (x->e_in[b]) iqgpu_event_destroy(x->e_in[b]);
         if (x->e_k[b]) iqgpu_event_destroy(x->e_k[b]);
@@ -731,6 +771,12 @@ static int stream_range(Ctx *x)
                                            &x->sg_rows[k][b], x->s_k));
                 if (x->sg_rows[k][b]) CK(iqgpu_memcpy_d2h_async(x->sg_h[k][b], x->sg_d[k][b], x->sg_rows[k][b] * row_bytes, x->s_k));
             }
+            /* --envelope: the same place and the same way */
+            for (int k = 0; k < 2 && x->ev[k]; k++) {
+                CK(iqgpu_env_push_device(x->ev[k], k ? x->d_out[b] : x->d_in[b], k ? out_frames[b] : n, (float *)x->ev_d[k][b], NULL, NULL, x->ev_cap[k],
+                                         &x->ev_rows[k][b], x->s_k));
+                if (x->ev_rows[k][b]) CK(iqgpu_memcpy_d2h_async(x->ev_h[k][b], x->ev_d[k][b], x->ev_rows[k][b] * sizeof(float), x->s_k));
+            }
             CK(iqgpu_event_record(x->e_k[b], x->s_k));
             CK(iqgpu_stream_wait_event(x->s_out, x->e_k[b]));
             if (out_frames[b]) CK(iqgpu_memcpy_d2h_async(x->h_out[b], x->d_out[b], out_frames[b] * x->obps, x->s_out));
@@ -748,6 +794,20 @@ static int stream_range(Ctx *x)
             written += (long long)out_frames[b];
             for (int k = 0; k < 2 && x->sg[k]; k++)
                 if (fwrite(x->sg_h[k][b], x->sg_opts.nfft * sizeof(float), x->sg_rows[k][b], x->sg_f[k]) != x->sg_rows[k][b]) FAIL("writing the rows of --sgram: %s", strerror(errno));
+            for (int k = 0; k < 2 && x->ev[k]; k++) {
+                const size_t nr = x->ev_rows[k][b];
+                if (fwrite(x->ev_h[k][b], sizeof(float), nr, x->ev_f[k]) != nr) FAIL("writing the rows of --envelope: %s", strerror(errno));
+                if (k == 0 && nr) {
+                    if (x->ev_all_n + nr > x->ev_all_cap) {
+                        const size_t cap = 2 * (x->ev_all_n + nr);
+                        float *g = (float *)realloc(x->ev_all, cap * sizeof(float));
+                        if (!g) FAIL("--envelope: out of memory for the input's rows");
+                        x->ev_all = g; x->ev_all_cap = cap;
+                    }
+                    memcpy(x->ev_all + x->ev_all_n, x->ev_h[0][b], nr * sizeof(float));
+                    x->ev_all_n += nr;
+                }
+            }
         }
     }
     sh->frames_out = written;
@@ -882,6 +942,61 @@ static int write_sgram(Ctx *x)
     return 0;
 }
 
+/* --envelope PREFIX: the row files are complete (stream_range appended every finished row); PREFIX.json with B, both info records, both
+ * open rows and the bursts of the input */
+static int write_env(Ctx *x)
+{
+    static const char *const side[2] = {"in", "out"};
+    Shard *sh = x->sh;
+    const Options *o = x->o;
+    const double rate[2] = {x->d.input_rate_hz, x->d.target_rate_hz};
+    const uint32_t B = x->ev_opts.block_frames;
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.json", o->env_prefix);
+    FILE *f = fopen(path, "w");
+    if (!f) FAIL("writing %.160s: %s", path, strerror(errno));
+    fprintf(f, "{\"block_frames\": %u", B);
+    for (int k = 0; k < 2; k++) {
+        iqgpu_env_info info;
+        double sum = 0.0, peak = 0.0;
+        uint32_t rail = 0;
+        FILE *rows = x->ev_f[k];
+        x->ev_f[k] = NULL;
+        if (fclose(rows) != 0) { fclose(f); FAIL("writing %.160s.%s.f32: %s", o->env_prefix, side[k], strerror(errno)); }
+        if (iqgpu_env_read_open(x->ev[k], &sum, &peak, &rail, &info) != IQGPU_OK) { fclose(f); FAIL("%s", iqgpu_last_error()); }
+        fprintf(f, ", \"%s\": {\"rate_hz\": %.17g, \"frames\": %llu, \"rows\": %llu, \"nonfinite_frames\": %llu, \"open_frames\": %u, "
+                "\"open\": {\"sum\": %.17g, \"peak\": %.17g, \"rail\": %u}, \"file\": \"", side[k], rate[k], (unsigned long long)info.frames,
+                (unsigned long long)info.rows, (unsigned long long)info.nonfinite_frames, info.open_frames, sum, peak, rail);
+        json_put(f, o->env_prefix);
+        fprintf(f, ".%s.f32\"}", side[k]);
+    }
+    /* the bursts of the input: thresholds 10 dB and 7 dB over the row at the tenth percentile */
+    iqgpu_env_burst_opts bo;
+    memset(&bo, 0, sizeof(bo));
+    bo.block_frames = B; bo.min_rows = 2; bo.hang_rows = 2; bo.pad_rows = 1;
+    fprintf(f, ", \"min_rows\": %u, \"hang_rows\": %u, \"pad_rows\": %u", bo.min_rows, bo.hang_rows, bo.pad_rows);
+    if (x->ev_all_n == 0) {
+        fprintf(f, ", \"floor\": null, \"on\": null, \"off\": null, \"bursts\": []}\n");
+    } else {
+        double fl = 0.0;
+        size_t n = 0;
+        if (iqgpu_env_floor(x->ev_all, x->ev_all_n, B, 0.1, &fl) != IQGPU_OK) { fclose(f); FAIL("%s", iqgpu_last_error()); }
+        bo.on = fl * 10.0; bo.off = fl * 5.011872336272722;             /* 10^(10 / 10), 10^(7 / 10) */
+        (void)iqgpu_env_bursts(x->ev_all, x->ev_all_n, &bo, NULL, 0, &n);   /* (the count: IQGPU_ECAPACITY) */
+        iqgpu_env_burst *bu = (iqgpu_env_burst *)calloc(n ? n : 1, sizeof(*bu));
+        if (!bu) { fclose(f); FAIL("--envelope: out of memory for %zu bursts", n); }
+        if (iqgpu_env_bursts(x->ev_all, x->ev_all_n, &bo, bu, n, &n) != IQGPU_OK) { free(bu); fclose(f); FAIL("%s", iqgpu_last_error()); }
+        fprintf(f, ", \"floor\": %.17g, \"on\": %.17g, \"off\": %.17g, \"bursts\": [", fl, bo.on, bo.off);
+        for (size_t i = 0; i < n; i++)
+            fprintf(f, "%s{\"first_frame\": %llu, \"frames\": %llu, \"peak_row\": %llu, \"peak_mean\": %.17g}", i ? ", " : "",
+                    (unsigned long long)bu[i].first_frame, (unsigned long long)bu[i].frames, (unsigned long long)bu[i].peak_row, bu[i].peak_mean);
+        fprintf(f, "]}\n");
+        free(bu);
+    }
+    if (fclose(f) != 0) FAIL("writing %.160s: %s", path, strerror(errno));
+    return 0;
+}
+
 /* --seamless-rms, --seamless-dc-rms: what the seam behind this range is checked against, and what the range behind it restarts from if the check fails */
 static int save_checkpoint(Ctx *x)
 {
@@ -915,7 +1030,7 @@ static void *run_shard(void *arg)
 
     if (o->dry) dry_shard(&x);
     else {
-        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && !(o->sgram_prefix && write_sgram(&x)) && !(o->stats_prefix && read_stats(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
+        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && !(o->sgram_prefix && write_sgram(&x)) && !(o->env_prefix && write_env(&x)) && !(o->stats_prefix && read_stats(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
         /* (a shard that fails early still keeps the rendezvous of the passes: the others wait there) */
         while (sh->barriers < MODES[o->mode].barriers) rendezvous(&x, NULL, NULL);
     }
@@ -940,6 +1055,7 @@ static void usage(void)
             "          [--seamless-dc-agc (the exact --seamless for --dc-block chains with the digital AGC: DC measure, walk, shadow AGC measure, walk, then the ordinary pass)]\n"
             "          [--stats PREFIX (plain runs and independent --shards: counts, rails, extrema, peak, histogram and moments of the input and of the output bytes, merged in shard order, as PREFIX.json)]\n"
             "          [--psd PREFIX (plain single-stream runs: the power spectra of the input and of the output -- Hann, 1024 bins -- as PREFIX.in.f64, PREFIX.out.f64, PREFIX.json)]\n"
+            "          [--envelope PREFIX [--envelope-block B] (the same runs: the power per row of B frames (4096) of the input and of the output, rows appended as they finish to PREFIX.in.f32, PREFIX.out.f32; PREFIX.json with the bursts of the input)]\n"
             "          [--sgram PREFIX [--sgram-row-segments R] (the same runs: the spectrum per row of R segments (32) of the input and of the output, rows appended as they finish to PREFIX.in.f32, PREFIX.out.f32; PREFIX.json)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
             "          [--dry-placement (plan the shards, bind every shard thread, size its buffers, report as JSON: no GPU call)]\n");
@@ -970,6 +1086,8 @@ static int parse_args(int argc, char **argv, Options *o)
         else if (!strcmp(a, "--psd")) o->psd_prefix = NEXT;
         else if (!strcmp(a, "--stats")) o->stats_prefix = NEXT;
         else if (!strcmp(a, "--sgram")) o->sgram_prefix = NEXT;
+        else if (!strcmp(a, "--envelope")) o->env_prefix = NEXT;
+        else if (!strcmp(a, "--envelope-block")) { const long long r = atoll(NEXT); o->env_block = r >= 64 && r <= (1 << 24) && (r & (r - 1)) == 0 ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--sgram-row-segments")) { const long long r = atoll(NEXT); o->sgram_row_segments = r >= 1 && r <= (1 << 20) ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--no-resample")) o->desc.no_resample = 1;
         else if (!strcmp(a, "--lowpass") || !strcmp(a, "--highpass")) {
@@ -1046,6 +1164,10 @@ static int validate(const Options *o)
     if (o->sgram_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
         REFUSE(2, "usage: --sgram is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
     if (o->sgram_prefix && strlen(o->sgram_prefix) > 3000) REFUSE(2, "usage: --sgram: the prefix is too long\n");
+    if (o->env_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
+        REFUSE(2, "usage: --envelope is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
+    if (o->env_prefix && strlen(o->env_prefix) > 3000) REFUSE(2, "usage: --envelope: the prefix is too long\n");
+    if (o->env_block && (!o->env_prefix || o->env_block == ~0u)) REFUSE(2, "usage: --envelope-block B goes with --envelope PREFIX, B a power of two in 64 .. 16777216\n");
     if (o->sgram_row_segments && (!o->sgram_prefix || o->sgram_row_segments == ~0u)) REFUSE(2, "usage: --sgram-row-segments R goes with --sgram PREFIX, R in 1 .. 1048576\n");
     for (const unsigned char *c = m->checks; *c != C_END; c++) switch (*c) {
     case C_SHARDS: if (!o->have_shards) REFUSE(2, "%s needs --shards N\n", m->flag); break;

@@ -15,7 +15,7 @@
 //                  counts, min / max and the peak (the earlier frame of equal peaks) in a tree; block 9: sum[k] += page_sum[p][k] in page order.
 #include <hip/hip_runtime.h>
 
-#include "dsp_device.hpp"
+#include "capture_load.hpp"
 #include "stats.hpp"
 
 namespace iqgpu {
@@ -39,54 +39,6 @@ __device__ __forceinline__ void lane_init(StatsLane &L)
 __device__ __forceinline__ void peak_merge(double &pk, uint64_t &pkf, double opk, uint64_t opkf)
 {
     if (opk > pk || (opk == pk && opkf < pkf)) { pk = opk; pkf = opkf; }
-}
-
-// bin and rails of one integer code (include/iqgpu.h: the table).  c: the code, sign- or zero-extended; cu32 as its bit pattern
-__device__ __forceinline__ void classify_code(int fmt, int c, int &bin, bool &lo, bool &hi)
-{
-    switch (fmt) {
-    case IQGPU_FMT_CU8: bin = c; lo = c == 0; hi = c == 255; break;
-    case IQGPU_FMT_CS8: bin = c + 128; lo = c == -128; hi = c == 127; break;
-    case IQGPU_FMT_CU16: bin = c >> 8; lo = c == 0; hi = c == 65535; break;
-    case IQGPU_FMT_CS16: bin = (c >> 8) + 128; lo = c == -32768; hi = c == 32767; break;
-    case IQGPU_FMT_SC16Q11: {
-        const int b = (c >> 4) + 128;
-        bin = b < 0 ? 0 : b > 255 ? 255 : b; lo = c <= -2048; hi = c >= 2047;
-        break; }
-    case IQGPU_FMT_CS24: bin = (c >> 16) + 128; lo = c == -8388608; hi = c == 8388607; break;
-    case IQGPU_FMT_CU32: bin = (int)((unsigned)c >> 24); lo = c == 0; hi = (unsigned)c == 0xffffffffu; break;
-    default: /* IQGPU_FMT_CS32 */ bin = (c >> 24) + 128; lo = c == (int)0x80000000u; hi = c == 0x7fffffff; break;
-    }
-}
-
-// ... of one finite cf32 component: v * 128 is exact, the clamp comes before the conversion
-__device__ __forceinline__ void classify_float(float v, int &bin, bool &lo, bool &hi)
-{
-    float f = floorf(__fmul_rn(v, 128.0f));
-    f = f < -128.0f ? -128.0f : f > 127.0f ? 127.0f : f;
-    bin = (int)f + 128; lo = v <= -1.0f; hi = v >= 1.0f;
-}
-
-// the two codes of frame j of a format decoded at run time (the value comes from unpack_one: the loads are the same)
-__device__ __forceinline__ void codes_one(const void *raw, int64_t j, int fmt, int &ci, int &cq)
-{
-    switch (fmt) {
-    case IQGPU_FMT_CU16: { const unsigned short *p = (const unsigned short *)raw + 2 * j; ci = p[0]; cq = p[1]; break; }
-    case IQGPU_FMT_SC16Q11: { const short *p = (const short *)raw + 2 * j; ci = p[0]; cq = p[1]; break; }
-    case IQGPU_FMT_CS24: {
-        const unsigned char *p = (const unsigned char *)raw + 6 * j;
-        ci = (int)(((unsigned)p[0] << 8) | ((unsigned)p[1] << 16) | ((unsigned)p[2] << 24)) >> 8;
-        cq = (int)(((unsigned)p[3] << 8) | ((unsigned)p[4] << 16) | ((unsigned)p[5] << 24)) >> 8;
-        break; }
-    default: { /* IQGPU_FMT_CS32, IQGPU_FMT_CU32: the bit pattern */ const int *p = (const int *)raw + 2 * j; ci = p[0]; cq = p[1]; break; }
-    }
-}
-
-__device__ __forceinline__ void codes_b16(uint32_t w, int &ci, int &cq) { ci = (short)(w & 0xffffu); cq = (short)(w >> 16); }
-template <int FMT> __device__ __forceinline__ void codes_b8(uint32_t h, int &ci, int &cq)
-{
-    if constexpr (FMT == IQGPU_FMT_CU8) { ci = (int)(h & 0xffu); cq = (int)((h >> 8) & 0xffu); }
-    else { ci = (signed char)(h & 0xffu); cq = (signed char)((h >> 8) & 0xffu); }
 }
 
 // one frame into the thread's state: s = the five sums of the frame's column, H = the lane's histogram copy
@@ -114,58 +66,6 @@ __device__ __forceinline__ void take(StatsLane &L, double *s, uint32_t *H, int f
     s[0] = __dadd_rn(s[0], re); s[1] = __dadd_rn(s[1], im);
     s[2] = __dadd_rn(s[2], rr); s[3] = __dadd_rn(s[3], ii);
     s[4] = __dadd_rn(s[4], __dmul_rn(re, im));
-}
-
-// frame j of raw, alone (row ends, unaligned launches, run-time formats)
-template <int FMT>
-__device__ __forceinline__ void load_one(const void *raw, int64_t j, int fmt, int &ci, int &cq, cf2 &x)
-{
-    ci = cq = 0;
-    if constexpr (FMT == IQGPU_FMT_CS16) {
-        const uint32_t w = ((const uint32_t *)raw)[j];
-        codes_b16(w, ci, cq); x = unpack_b16(w, FMT, 1.0f);
-    } else if constexpr (FMT == IQGPU_FMT_CU8 || FMT == IQGPU_FMT_CS8) {
-        const uint32_t h = ((const uint16_t *)raw)[j];
-        codes_b8<FMT>(h, ci, cq); x = unpack_b8(h, FMT, 1.0f);
-    } else if constexpr (FMT == IQGPU_FMT_CF32) {
-        const float2 v = ((const float2 *)raw)[j];
-        x = cf2{__fmul_rn(v.x, 1.0f), __fmul_rn(v.y, 1.0f)};
-    } else {
-        codes_one(raw, j, fmt, ci, cq); x = unpack_one(raw, j, fmt, 1.0f);
-    }
-}
-
-// bytes a thread's four frames are fetched as in one piece, 0: never
-template <int FMT> constexpr int vec_bytes()
-{
-    return FMT == IQGPU_FMT_CS16 ? 16 : (FMT == IQGPU_FMT_CU8 || FMT == IQGPU_FMT_CS8) ? 8 : FMT == IQGPU_FMT_CF32 ? 16 : 0;
-}
-
-// frames j .. j + 3 of raw, all inside the launch, at an address aligned to vec_bytes<FMT>()
-template <int FMT>
-__device__ __forceinline__ void load_four(const void *raw, int64_t j, int (&ci)[4], int (&cq)[4], cf2 (&x)[4])
-{
-    if constexpr (FMT == IQGPU_FMT_CS16) {
-        const uint4 v = *(const uint4 *)((const char *)raw + 4 * j);
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { codes_b16(w[k], ci[k], cq[k]); x[k] = unpack_b16(w[k], FMT, 1.0f); }
-    } else if constexpr (FMT == IQGPU_FMT_CU8 || FMT == IQGPU_FMT_CS8) {
-        const uint2 v = *(const uint2 *)((const char *)raw + 2 * j);
-        const uint32_t w[2] = {v.x, v.y};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t h = (w[k >> 1] >> ((k & 1) * 16)) & 0xffffu;
-            codes_b8<FMT>(h, ci[k], cq[k]); x[k] = unpack_b8(h, FMT, 1.0f);
-        }
-    } else if constexpr (FMT == IQGPU_FMT_CF32) {
-        const float4 v0 = *(const float4 *)((const char *)raw + 8 * j);
-        const float4 v1 = *(const float4 *)((const char *)raw + 8 * j + 16);
-        x[0] = cf2{__fmul_rn(v0.x, 1.0f), __fmul_rn(v0.y, 1.0f)}; x[1] = cf2{__fmul_rn(v0.z, 1.0f), __fmul_rn(v0.w, 1.0f)};
-        x[2] = cf2{__fmul_rn(v1.x, 1.0f), __fmul_rn(v1.y, 1.0f)}; x[3] = cf2{__fmul_rn(v1.z, 1.0f), __fmul_rn(v1.w, 1.0f)};
-#pragma unroll
-        for (int k = 0; k < 4; ++k) ci[k] = cq[k] = 0;
-    }
 }
 
 __device__ __forceinline__ uint64_t shfl_xor_u64(uint64_t v, int m)
