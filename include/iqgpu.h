@@ -1073,6 +1073,80 @@ int    iqgpu_env_read_open(iqgpu_env *p, double *sum, double *peak, uint32_t *ra
 int    iqgpu_env_bursts(const float *row_sum, size_t rows, const iqgpu_env_burst_opts *o, iqgpu_env_burst *out, size_t cap, size_t *n);
 int    iqgpu_env_floor(const float *row_sum, size_t rows, uint32_t block_frames, double fraction, double *mean_power);
 
+/* ---- lag products: R_d = sum of x[n] conj(x[n - d]) per block of B consecutive frames, emitted as the stream goes by (additive, still ABI v9) ----
+ * No counterpart in the reference.  The cheap frequency axis of the family: arg R_1 / (2 pi) * fs is the classical coarse frequency
+ * estimate of what a row holds, |R_d| / R_0 the coherence at lag d (the cyclic-prefix test of an OFDM stream: NRSC-5 repeats at lag
+ * 2048 at 744 187.5 Hz) -- at the cost of reading the bytes once, no transform.  One stream of frames in one sample format,
+ * independent of any chain, with iqgpu_env's calling convention.  There is NO gain: x = the library's unpack at gain 1, exactly as
+ * iqgpu_env / iqgpu_stats.  Options: block_frames = B as iqgpu_env's, and 1 .. 4 strictly increasing lags, each 1 .. 65536.
+ * Rows: iqgpu_env's.  Row r is frames [r B, (r + 1) B) of everything pushed since the last reset; the rest is the open row.
+ * The lag term of frame n (its stream index since the last reset) and lag d exists for n >= d when both x[n] = a and x[n - d] = b are
+ * finite:  re = (double)a.re * b.re + (double)a.im * b.im,  im = (double)a.im * b.re - (double)a.re * b.im  -- every product exact in
+ * double, each sum or difference rounded once.  The term belongs to frame n: to its row, its cell and its column.  A frame with
+ * n < d, or a pair with a non-finite member (cf32 only), contributes nothing to that lag: its column sum stays as it was (an absent
+ * term is an absent addend, not a +0.0).  info.nonfinite_frames counts frames, as iqgpu_env's.  With this sign a tone at +f gives
+ * arg R_d = +2 pi f d / fs.
+ * Per finished row, densely packed:
+ *   row_lag[r][l][2] (float)  re, im of lag l: the double sum of the row's terms in the order below, rounded ONCE to float.
+ *   row_sum[r]       (float)  iqgpu_env's row_sum: the same per-frame term p, the same order; BIT-EQUAL to iqgpu_env's row_sum on the
+ *                             same bytes and B.  It is R_0 of the row.
+ * Summation order: iqgpu_env's (hence iqgpu_stats'), applied independently to each of the 2 n_lags + 1 components: cells of 65536
+ * frames counted from the row's first frame; frame i of a cell in column i mod 1024; a column summed in increasing i from 0.0; the
+ * ten-level tree of adjacent pairs over the columns (B <= 1024: the balanced pair tree over the row's B columns); the row is
+ * ((0.0 + cell 0) + cell 1) + ... in double.
+ * History: the partner of a frame may lie in an earlier push, an earlier row or an earlier launch.  The handle carries the last
+ * lags[n_lags - 1] frames of the stream on the device; iqgpu_lag_reset empties that history with everything else.
+ * ROWS AND OPEN ROW ARE A FUNCTION OF THE PUSHED FRAMES AND THE OPTIONS ALONE, BIT FOR BIT: any split of the stream into push calls,
+ * host or device, of any lengths (one frame; shorter than the largest lag; ending inside a row or a cell) at frame alignment only
+ * gives the same rows in the same order and the same open row.
+ * The open row: iqgpu_lag_read_open returns the unrounded doubles of the open row -- lag[n_lags][2] and sum, each the total of its
+ * closed cells + tree(open columns) -- all 0 when info.open_frames == 0.  It observes and does not disturb.
+ * push / push_device, *rows, iqgpu_lag_max_rows, cap_rows and IQGPU_ECAPACITY, streams, poisoning, frames == 0, one thread per handle
+ * and the error codes: iqgpu_env's, word for word; either plane may be NULL.  IQGPU_EINVAL also for n_lags outside 1 .. 4, a lag
+ * outside 1 .. 65536 and lags that are not strictly increasing.  Behind iqgpu_chain_process_device(c, .., d_out, .., &n) the rows of
+ * the output are iqgpu_lag_push_device(p, d_out, n, d_lag, d_sum, cap, &rows, iqgpu_chain_get_stream(c)).
+ * Cost: a lag of at most 1024 frames takes its partner from on chip; a farther one loads the stream a second time (profiles/lag.md).
+ * THE ESTIMATE (host only, no device).  iqgpu_lag_freq: hz = atan2(im, re) / (2 pi lag) * sample_rate in double, in that order of
+ * operations; 0 when re == im == 0; IQGPU_EINVAL for a non-finite value, lag == 0 or sample_rate <= 0.
+ * iqgpu_lag_estimate_rows adds (double)row_lag[r][lag_index][..] and (double)row_sum[r] over rows first_row .. first_row + n_rows - 1
+ * (inside the `rows` given, else IQGPU_EINVAL) in increasing order from 0.0, skipping a row in which one of these three values is a
+ * NaN; hz = iqgpu_lag_freq of the sums; coherence = hypot(re, im) / power, 0 unless power > 0; span_hz = sample_rate / lag, the width
+ * of the unambiguous interval (-span_hz / 2, +span_hz / 2]: a frequency outside it comes back moved by a multiple of span_hz.
+ * row_sum == NULL: power = coherence = 0.  An iqgpu_env_burst maps to first_row = first_frame / B, n_rows = frames / B.
+ * THE SIGN: the chain's NCO multiplies by exp(+j theta) for shift_hz >= 0 (it mixes UP by shift_hz), so a burst estimated at hz is
+ * centred by a chain description with shift_hz = -hz. */
+typedef struct {
+    uint32_t block_frames;        /* B: frames of a row, a power of two, 64 .. 2^24 (4096) */
+    uint32_t n_lags;              /* 1 .. 4 (1) */
+    uint32_t lags[4];             /* strictly increasing, each 1 .. 65536 ({1}) */
+} iqgpu_lag_opts;
+typedef struct {
+    uint64_t frames, rows;        /* pushed since the last reset; rows finished = frames / B */
+    uint64_t nonfinite_frames;    /* cf32 only: frames with a NaN or Inf component */
+    uint32_t open_frames;         /* frames of the open row = frames % B */
+    uint32_t block_frames, n_lags, lags[4];
+} iqgpu_lag_info;
+typedef struct {
+    double re, im, power;         /* the sums over the rows */
+    double hz, coherence, span_hz;
+} iqgpu_lag_estimate;
+typedef struct iqgpu_lag iqgpu_lag;
+void   iqgpu_lag_opts_init(iqgpu_lag_opts *o);                      /* the defaults in parentheses above */
+/* no device: the rows a stream of `frames` frames finishes */
+int    iqgpu_lag_rows(const iqgpu_lag_opts *o, uint64_t frames, uint64_t *rows);
+int    iqgpu_lag_create(int device, int format, const iqgpu_lag_opts *o, iqgpu_lag **out);
+void   iqgpu_lag_destroy(iqgpu_lag *p);
+int    iqgpu_lag_reset(iqgpu_lag *p);
+size_t iqgpu_lag_max_rows(const iqgpu_lag *p, size_t frames);       /* rows the NEXT push of `frames` finishes: exact; 0 for a NULL handle */
+int    iqgpu_lag_push(iqgpu_lag *p, const void *raw, size_t frames, float *row_lag, float *row_sum, size_t cap_rows, size_t *rows);   /* host memory */
+int    iqgpu_lag_push_device(iqgpu_lag *p, const void *d_raw, size_t frames, float *d_row_lag, float *d_row_sum, size_t cap_rows,
+                             size_t *rows, void *hip_stream);      /* device memory, asynchronous on hip_stream */
+int    iqgpu_lag_read_open(iqgpu_lag *p, double *lag /* [n_lags][2] */, double *sum, iqgpu_lag_info *info);   /* any may be NULL; synchronises */
+/* host only, no device */
+int    iqgpu_lag_freq(double re, double im, uint32_t lag, double sample_rate, double *hz);
+int    iqgpu_lag_estimate_rows(const float *row_lag, const float *row_sum, size_t rows, const iqgpu_lag_opts *o, uint32_t lag_index,
+                               size_t first_row, size_t n_rows, double sample_rate, iqgpu_lag_estimate *out);
+
 /* ---- WAV capture metadata -> frequency shift (host only): the step in front of the path for real captures ----
  * SdrMetadata and its parsers (src/input_wav.c:54-100, 146-438), the shift rule of wav_initialize (592-629). */
 enum { IQGPU_SDR_UNKNOWN = 0, IQGPU_SDR_CONSOLE = 1, IQGPU_SDR_SHARP = 2, IQGPU_SDR_UNO = 3, IQGPU_SDR_CONNECT = 4 };

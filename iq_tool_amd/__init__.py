@@ -8,5 +8,6 @@ from .psd import Psd                                             # noqa: F401
 from .sgram import Sgram                                         # noqa: F401
 from .stats import Stats                                         # noqa: F401
 from .env import Env                                             # noqa: F401
+from .lag import Lag                                             # noqa: F401
 
-__all__ = ["Chain", "DeviceBuffer", "PinnedBuffer", "IqOptimizer", "Psd", "Sgram", "Stats", "Env", "make_desc", "FMT", "IqgpuError", "load", "LIB_PATH"]
+__all__ = ["Chain", "DeviceBuffer", "PinnedBuffer", "IqOptimizer", "Psd", "Sgram", "Stats", "Env", "Lag", "make_desc", "FMT", "IqgpuError", "load", "LIB_PATH"]

@@ -162,6 +162,23 @@ class EnvInfo(C.Structure):
                 ("block_frames", C.c_uint32)]
 
 
+class LagOpts(C.Structure):
+    """iqgpu_lag_opts: the options of a lag-product accumulator (iqgpu_lag_opts_init sets the defaults)"""
+    _fields_ = [("block_frames", C.c_uint32), ("n_lags", C.c_uint32), ("lags", C.c_uint32 * 4)]
+
+
+class LagInfo(C.Structure):
+    """iqgpu_lag_info: what iqgpu_lag_read_open reports beside the open row"""
+    _fields_ = [("frames", C.c_uint64), ("rows", C.c_uint64), ("nonfinite_frames", C.c_uint64), ("open_frames", C.c_uint32),
+                ("block_frames", C.c_uint32), ("n_lags", C.c_uint32), ("lags", C.c_uint32 * 4)]
+
+
+class LagEstimate(C.Structure):
+    """iqgpu_lag_estimate: what iqgpu_lag_estimate_rows derives from a range of rows"""
+    _fields_ = [("re", C.c_double), ("im", C.c_double), ("power", C.c_double), ("hz", C.c_double), ("coherence", C.c_double),
+                ("span_hz", C.c_double)]
+
+
 class EnvBurstOpts(C.Structure):
     """iqgpu_env_burst_opts: the rules of iqgpu_env_bursts"""
     _fields_ = [("block_frames", C.c_uint32), ("min_rows", C.c_uint32), ("hang_rows", C.c_uint32), ("pad_rows", C.c_uint32),
@@ -315,6 +332,17 @@ SYMBOLS = [
     ("iqgpu_env_read_open", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(EnvInfo)]),
     ("iqgpu_env_bursts", C.c_int, [_vp, _sz, C.POINTER(EnvBurstOpts), _vp, _sz, C.POINTER(_sz)]),
     ("iqgpu_env_floor", C.c_int, [_vp, _sz, C.c_uint32, C.c_double, C.POINTER(C.c_double)]),
+    ("iqgpu_lag_opts_init", None, [C.POINTER(LagOpts)]),
+    ("iqgpu_lag_rows", C.c_int, [C.POINTER(LagOpts), C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("iqgpu_lag_create", C.c_int, [C.c_int, C.c_int, C.POINTER(LagOpts), C.POINTER(_vp)]),
+    ("iqgpu_lag_destroy", None, [_vp]),
+    ("iqgpu_lag_reset", C.c_int, [_vp]),
+    ("iqgpu_lag_max_rows", _sz, [_vp, _sz]),
+    ("iqgpu_lag_push", C.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_lag_push_device", C.c_int, [_vp, _vp, _sz, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    ("iqgpu_lag_read_open", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(LagInfo)]),
+    ("iqgpu_lag_freq", C.c_int, [C.c_double, C.c_double, C.c_uint32, C.c_double, C.POINTER(C.c_double)]),
+    ("iqgpu_lag_estimate_rows", C.c_int, [_vp, _vp, _sz, C.POINTER(LagOpts), C.c_uint32, _sz, _sz, C.c_double, C.POINTER(LagEstimate)]),
     ("iqgpu_wav_info_init", None, [C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_auxi", C.c_int, [_vp, _sz, C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_filename", C.c_int, [C.c_char_p, C.POINTER(WavInfo)]),

@@ -86,6 +86,12 @@
  * B, both info records with both open rows, and the bursts of the INPUT (iqgpu_env_bursts) at on = floor(0.1) + 10 dB, off = floor(0.1)
  * + 7 dB, min_rows 2, hang_rows 2, pad_rows 1, floor(0.1) being iqgpu_env_floor of the input's rows.
  *
+ * --lag PREFIX [--lag-list d1,d2,..] [--lag-block B] (the same runs as --envelope, and it may stand beside --psd / --sgram / --stats / --envelope):
+ * one iqgpu_lag accumulator on the input bytes and one on the output bytes, B frames a row (4096) and up to four lags (1), fed on the
+ * chain's stream behind every call.  PREFIX.in.lag.f32 / PREFIX.out.lag.f32 receive row_lag of every row as it finishes (2 n_lags
+ * little-endian floats a row), PREFIX.in.sum.f32 / PREFIX.out.sum.f32 its row_sum; PREFIX.json holds the options, both info records and
+ * iqgpu_lag_estimate_rows over the whole input and the whole output per lag, at the run's input and output rates.
+ *
  * --stats PREFIX (plain runs and --shards N with independent shards; no --seamless* mode, no --iq-calibrate): one iqgpu_stats accumulator
  * on the input bytes and one on the output bytes of every shard, fed on the chain's stream behind every call.  The shards' results are
  * concatenated in shard order (iqgpu_stats_merge: every count, extremum and the peak are exactly the one stream's) and PREFIX.json
@@ -174,6 +180,9 @@ typedef struct {
     unsigned sgram_row_segments;      /* --sgram-row-segments R (0: the library's default) */
     const char *env_prefix;           /* --envelope PREFIX: row_sum of the input and of the output, appended as the rows finish; the bursts of the input (write_env) */
     unsigned env_block;               /* --envelope-block B (0: the library's default) */
+    const char *lag_prefix;           /* --lag PREFIX: row_lag and row_sum of the input and of the output, appended as the rows finish; the estimates (write_lag) */
+    const char *lag_list;             /* --lag-list d1,d2,.. (NULL: the library's default); lag_opts_of reads both */
+    unsigned lag_block;               /* --lag-block B (0: the library's default) */
     const char *stats_prefix;         /* --stats PREFIX: the statistics of the input and of the output bytes, merged over the shards (write_stats) */
 } Options;
 
@@ -232,6 +241,10 @@ typedef struct {
     iqgpu_env *ev[2]; iqgpu_env_opts ev_opts; FILE *ev_f[2];
     void *ev_d[2][NBUF], *ev_h[2][NBUF]; size_t ev_cap[2], ev_rows[2][NBUF];
     float *ev_all; size_t ev_all_n, ev_all_cap;
+    /* --lag, the same shape: plane 0 = row_lag (2 n_lags floats a row), plane 1 = row_sum; lg_all keeps both for the estimates behind the run */
+    iqgpu_lag *lg[2]; iqgpu_lag_opts lg_opts; FILE *lg_f[2][2];
+    void *lg_d[2][2][NBUF], *lg_h[2][2][NBUF]; size_t lg_cap[2], lg_rows[2][NBUF];
+    float *lg_all[2][2]; size_t lg_all_n[2], lg_all_cap[2];
 } Ctx;
 
 /* the modes with passes: all shard threads meet behind a measure pass and again behind the walk, which shard 0's thread does in between */
@@ -283,6 +296,29 @@ static int fmt_from_name(const char *s)
 }
 
 /* n frames of the job's input from stream frame `first` into dst: the file, the counter-hash stream, or the constant filling */
+/* the options of --lag: the library's defaults, --lag-block and --lag-list d1,d2,.. (one to four decimal numbers) on top; the library
+ * checks their values (iqgpu_lag_rows).  0: fine */
+static int lag_opts_of(const Options *o, iqgpu_lag_opts *lo)
+{
+    uint64_t rows = 0;
+    iqgpu_lag_opts_init(lo);
+    if (o->lag_block) lo->block_frames = o->lag_block;
+    if (o->lag_list) {
+        const char *p = o->lag_list;
+        uint32_t n = 0;
+        if (!*p) return 1;
+        while (*p) {
+            char *end = NULL;
+            const unsigned long long v = strtoull(p, &end, 10);
+            if (*p < '0' || *p > '9' || end == p || v > 65536 || n >= 4 || (*end != ',' && *end != 0) || (*end == ',' && !end[1])) return 1;
+            lo->lags[n++] = (uint32_t)v;
+            p = *end ? end + 1 : end;
+        }
+        lo->n_lags = n;
+    }
+    return iqgpu_lag_rows(lo, 0, &rows) != IQGPU_OK;
+}
+
 static int read_frames(const Options *o, int in_fd, int fmt, size_t ibps, long long first, size_t n, void *dst, char *err, size_t errcap)
 {
     const size_t nb = n * ibps;
@@ -579,6 +615,27 @@ static int ctx_open(Ctx *x)
             if (!x->ev_f[k]) FAIL("writing %.160s: %s", path, strerror(errno));
         }
     }
+    if (o->lag_prefix) {
+        static const char *const side[2] = {"in", "out"}, *const plane[2] = {"lag", "sum"};
+        const int fmt[2] = {x->d.in_format, x->d.out_format};
+        const size_t most[2] = {x->chunk, x->out_cap / x->obps};      /* frames of one call */
+        char path[4096];
+        if (lag_opts_of(o, &x->lg_opts)) FAIL("--lag-list: %s", o->lag_list);
+        for (int k = 0; k < 2; k++) {
+            const size_t per_row[2] = {2 * (size_t)x->lg_opts.n_lags, 1};
+            CK(iqgpu_lag_create(dev, fmt[k], &x->lg_opts, &x->lg[k]));
+            x->lg_cap[k] = most[k] / x->lg_opts.block_frames + 1;     /* rows one call can finish, behind an open row */
+            for (int q = 0; q < 2; q++) {
+                for (int b = 0; b < NBUF; b++) {
+                    CK(iqgpu_device_malloc(dev, x->lg_cap[k] * per_row[q] * sizeof(float), &x->lg_d[k][q][b]));
+                    CK(iqgpu_host_malloc_pinned(x->lg_cap[k] * per_row[q] * sizeof(float), &x->lg_h[k][q][b]));
+                }
+                snprintf(path, sizeof(path), "%s.%s.%s.f32", o->lag_prefix, side[k], plane[q]);
+                x->lg_f[k][q] = fopen(path, "wb");
+                if (!x->lg_f[k][q]) FAIL("writing %.160s: %s", path, strerror(errno));
+            }
+        }
+    }
     if (o->synthetic_frames <= 0) {
         x->in_fd = open(o->in_path, O_RDONLY);
         if (x->in_fd < 0) FAIL("open %s: %s", o->in_path, strerror(errno));
@@ -606,6 +663,17 @@ static void ctx_close(Ctx *x)
         for (int b = 0; b < NBUF; b++) {
             if (x->sg_d[k][b]) iqgpu_device_free(dev, x->sg_d[k][b]);
             if (x->sg_h[k][b]) iqgpu_host_free_pinned(x->sg_h[k][b]);
+        }
+    }
+    for (int k = 0; k < 2; k++) {
+        iqgpu_lag_destroy(x->lg[k]);
+        for (int q = 0; q < 2; q++) {
+            if (x->lg_f[k][q]) fclose(x->lg_f[k][q]);
+            free(x->lg_all[k][q]);
+            for (int b = 0; b < NBUF; b++) {
+                if (x->lg_d[k][q][b]) iqgpu_device_free(dev, x->lg_d[k][q][b]);
+                if (x->lg_h[k][q][b]) iqgpu_host_free_pinned(x->lg_h[k][q][b]);
+            }
         }
     }
     for (int k = 0; k < 2; k++) {
@@ -777,6 +845,15 @@ static int stream_range(Ctx *x)
                                          &x->ev_rows[k][b], x->s_k));
                 if (x->ev_rows[k][b]) CK(iqgpu_memcpy_d2h_async(x->ev_h[k][b], x->ev_d[k][b], x->ev_rows[k][b] * sizeof(float), x->s_k));
             }
+            /* --lag: the same place and the same way, two planes */
+            for (int k = 0; k < 2 && x->lg[k]; k++) {
+                CK(iqgpu_lag_push_device(x->lg[k], k ? x->d_out[b] : x->d_in[b], k ? out_frames[b] : n, (float *)x->lg_d[k][0][b], (float *)x->lg_d[k][1][b],
+                                         x->lg_cap[k], &x->lg_rows[k][b], x->s_k));
+                if (x->lg_rows[k][b]) {
+                    CK(iqgpu_memcpy_d2h_async(x->lg_h[k][0][b], x->lg_d[k][0][b], x->lg_rows[k][b] * 2 * x->lg_opts.n_lags * sizeof(float), x->s_k));
+                    CK(iqgpu_memcpy_d2h_async(x->lg_h[k][1][b], x->lg_d[k][1][b], x->lg_rows[k][b] * sizeof(float), x->s_k));
+                }
+            }
             CK(iqgpu_event_record(x->e_k[b], x->s_k));
             CK(iqgpu_stream_wait_event(x->s_out, x->e_k[b]));
             if (out_frames[b]) CK(iqgpu_memcpy_d2h_async(x->h_out[b], x->d_out[b], out_frames[b] * x->obps, x->s_out));
@@ -807,6 +884,23 @@ static int stream_range(Ctx *x)
                     memcpy(x->ev_all + x->ev_all_n, x->ev_h[0][b], nr * sizeof(float));
                     x->ev_all_n += nr;
                 }
+            }
+            for (int k = 0; k < 2 && x->lg[k]; k++) {
+                const size_t nr = x->lg_rows[k][b], per_row[2] = {2 * (size_t)x->lg_opts.n_lags, 1};
+                if (nr && x->lg_all_n[k] + nr > x->lg_all_cap[k]) {
+                    const size_t cap = 2 * (x->lg_all_n[k] + nr);
+                    for (int q = 0; q < 2; q++) {
+                        float *g = (float *)realloc(x->lg_all[k][q], cap * per_row[q] * sizeof(float));
+                        if (!g) FAIL("--lag: out of memory for the rows");
+                        x->lg_all[k][q] = g;
+                    }
+                    x->lg_all_cap[k] = cap;
+                }
+                for (int q = 0; q < 2 && nr; q++) {
+                    if (fwrite(x->lg_h[k][q][b], per_row[q] * sizeof(float), nr, x->lg_f[k][q]) != nr) FAIL("writing the rows of --lag: %s", strerror(errno));
+                    memcpy(x->lg_all[k][q] + x->lg_all_n[k] * per_row[q], x->lg_h[k][q][b], nr * per_row[q] * sizeof(float));
+                }
+                x->lg_all_n[k] += nr;
             }
         }
     }
@@ -997,6 +1091,53 @@ static int write_env(Ctx *x)
     return 0;
 }
 
+/* --lag PREFIX: the row files are complete (stream_range appended every finished row); PREFIX.json with the options, both info records and
+ * the estimate over all rows of each side per lag */
+static int write_lag(Ctx *x)
+{
+    static const char *const side[2] = {"in", "out"}, *const plane[2] = {"lag", "sum"};
+    Shard *sh = x->sh;
+    const Options *o = x->o;
+    const double rate[2] = {x->d.input_rate_hz, x->d.target_rate_hz};
+    const iqgpu_lag_opts *lo = &x->lg_opts;
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.json", o->lag_prefix);
+    FILE *f = fopen(path, "w");
+    if (!f) FAIL("writing %.160s: %s", path, strerror(errno));
+    fprintf(f, "{\"block_frames\": %u, \"lags\": [", lo->block_frames);
+    for (uint32_t l = 0; l < lo->n_lags; l++) fprintf(f, "%s%u", l ? ", " : "", lo->lags[l]);
+    fprintf(f, "]");
+    for (int k = 0; k < 2; k++) {
+        iqgpu_lag_info info;
+        for (int q = 0; q < 2; q++) {
+            FILE *rows = x->lg_f[k][q];
+            x->lg_f[k][q] = NULL;
+            if (fclose(rows) != 0) { fclose(f); FAIL("writing %.160s.%s.%s.f32: %s", o->lag_prefix, side[k], plane[q], strerror(errno)); }
+        }
+        if (iqgpu_lag_read_open(x->lg[k], NULL, NULL, &info) != IQGPU_OK) { fclose(f); FAIL("%s", iqgpu_last_error()); }
+        fprintf(f, ", \"%s\": {\"sample_rate\": %.17g, \"frames\": %llu, \"rows\": %llu, \"nonfinite_frames\": %llu, \"open_frames\": %u, \"estimates\": [",
+                side[k], rate[k], (unsigned long long)info.frames, (unsigned long long)info.rows, (unsigned long long)info.nonfinite_frames, info.open_frames);
+        for (uint32_t l = 0; l < lo->n_lags; l++) {
+            static const float none[2] = {0.0f, 0.0f};
+            iqgpu_lag_estimate e;
+            const size_t n = x->lg_all_n[k];
+            if (iqgpu_lag_estimate_rows(n ? x->lg_all[k][0] : none, n ? x->lg_all[k][1] : none, n, lo, l, 0, n, rate[k], &e) != IQGPU_OK) {
+                fclose(f); FAIL("%s", iqgpu_last_error());
+            }
+            fprintf(f, "%s{\"lag\": %u, \"re\": %.17g, \"im\": %.17g, \"power\": %.17g, \"hz\": %.17g, \"coherence\": %.17g, \"span_hz\": %.17g}",
+                    l ? ", " : "", lo->lags[l], e.re, e.im, e.power, e.hz, e.coherence, e.span_hz);
+        }
+        fprintf(f, "], \"files\": [\"");
+        json_put(f, o->lag_prefix);
+        fprintf(f, ".%s.lag.f32\", \"", side[k]);
+        json_put(f, o->lag_prefix);
+        fprintf(f, ".%s.sum.f32\"]}", side[k]);
+    }
+    fprintf(f, "}\n");
+    if (fclose(f) != 0) FAIL("writing %.160s: %s", path, strerror(errno));
+    return 0;
+}
+
 /* --seamless-rms, --seamless-dc-rms: what the seam behind this range is checked against, and what the range behind it restarts from if the check fails */
 static int save_checkpoint(Ctx *x)
 {
@@ -1030,7 +1171,7 @@ static void *run_shard(void *arg)
 
     if (o->dry) dry_shard(&x);
     else {
-        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && !(o->sgram_prefix && write_sgram(&x)) && !(o->env_prefix && write_env(&x)) && !(o->stats_prefix && read_stats(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
+        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && !(o->sgram_prefix && write_sgram(&x)) && !(o->env_prefix && write_env(&x)) && !(o->lag_prefix && write_lag(&x)) && !(o->stats_prefix && read_stats(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
         /* (a shard that fails early still keeps the rendezvous of the passes: the others wait there) */
         while (sh->barriers < MODES[o->mode].barriers) rendezvous(&x, NULL, NULL);
     }
@@ -1055,6 +1196,7 @@ static void usage(void)
             "          [--seamless-dc-agc (the exact --seamless for --dc-block chains with the digital AGC: DC measure, walk, shadow AGC measure, walk, then the ordinary pass)]\n"
             "          [--stats PREFIX (plain runs and independent --shards: counts, rails, extrema, peak, histogram and moments of the input and of the output bytes, merged in shard order, as PREFIX.json)]\n"
             "          [--psd PREFIX (plain single-stream runs: the power spectra of the input and of the output -- Hann, 1024 bins -- as PREFIX.in.f64, PREFIX.out.f64, PREFIX.json)]\n"
+            "          [--lag PREFIX [--lag-list d1,d2,..] [--lag-block B] (the same runs: the lag products x[n] conj(x[n - d]) and the power per row of B frames (4096) of the input and of the output for up to four lags d (1), rows appended as they finish to PREFIX.in.lag.f32, PREFIX.in.sum.f32, PREFIX.out.lag.f32, PREFIX.out.sum.f32; PREFIX.json with the frequency estimate and the coherence per lag)]\n"
             "          [--envelope PREFIX [--envelope-block B] (the same runs: the power per row of B frames (4096) of the input and of the output, rows appended as they finish to PREFIX.in.f32, PREFIX.out.f32; PREFIX.json with the bursts of the input)]\n"
             "          [--sgram PREFIX [--sgram-row-segments R] (the same runs: the spectrum per row of R segments (32) of the input and of the output, rows appended as they finish to PREFIX.in.f32, PREFIX.out.f32; PREFIX.json)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
@@ -1087,6 +1229,9 @@ static int parse_args(int argc, char **argv, Options *o)
         else if (!strcmp(a, "--stats")) o->stats_prefix = NEXT;
         else if (!strcmp(a, "--sgram")) o->sgram_prefix = NEXT;
         else if (!strcmp(a, "--envelope")) o->env_prefix = NEXT;
+        else if (!strcmp(a, "--lag")) o->lag_prefix = NEXT;
+        else if (!strcmp(a, "--lag-list")) o->lag_list = NEXT;
+        else if (!strcmp(a, "--lag-block")) { const long long r = atoll(NEXT); o->lag_block = r >= 64 && r <= (1 << 24) && (r & (r - 1)) == 0 ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--envelope-block")) { const long long r = atoll(NEXT); o->env_block = r >= 64 && r <= (1 << 24) && (r & (r - 1)) == 0 ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--sgram-row-segments")) { const long long r = atoll(NEXT); o->sgram_row_segments = r >= 1 && r <= (1 << 20) ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--no-resample")) o->desc.no_resample = 1;
@@ -1164,6 +1309,15 @@ static int validate(const Options *o)
     if (o->sgram_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
         REFUSE(2, "usage: --sgram is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
     if (o->sgram_prefix && strlen(o->sgram_prefix) > 3000) REFUSE(2, "usage: --sgram: the prefix is too long\n");
+    if (o->lag_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
+        REFUSE(2, "usage: --lag is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
+    if (o->lag_prefix && strlen(o->lag_prefix) > 3000) REFUSE(2, "usage: --lag: the prefix is too long\n");
+    if (o->lag_block && (!o->lag_prefix || o->lag_block == ~0u)) REFUSE(2, "usage: --lag-block B goes with --lag PREFIX, B a power of two in 64 .. 16777216\n");
+    {
+        iqgpu_lag_opts lo;
+        if ((o->lag_list && !o->lag_prefix) || lag_opts_of(o, &lo))
+            REFUSE(2, "usage: --lag-list d1,d2,.. goes with --lag PREFIX: one to four lags, strictly increasing, each 1 .. 65536\n");
+    }
     if (o->env_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
         REFUSE(2, "usage: --envelope is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
     if (o->env_prefix && strlen(o->env_prefix) > 3000) REFUSE(2, "usage: --envelope: the prefix is too long\n");
