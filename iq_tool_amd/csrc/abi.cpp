@@ -198,6 +198,7 @@ int design_chain(iqgpu_chain *c, const iqgpu_chain_desc *d)
     }
     c->nco_hold6 = c->sw.nco_hold && c->nco_mode != 0 ? front_mid_nco_hold(c->nco_dtheta, 6) : 0;
     c->nco_hold8 = c->sw.nco_hold && c->nco_mode != 0 ? front_mid_nco_hold(c->nco_dtheta, 8) : 0;
+    c->nco_hold6_all = c->sw.nco_hold && c->nco_mode != 0 ? front_mid_nco_hold_all(c->nco_dtheta, 6) : 0;
 
     // ---- resampler (src/resampler.c:20-34, 60 dB include/constants.h:137) ----
     std::string err;

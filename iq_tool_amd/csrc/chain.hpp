@@ -325,6 +325,7 @@ struct iqgpu_chain {
     int tap_fold6 = 0, tap_fold8 = 0;
     // NCO phasor hold of k_front_mid for this chain's phase step at 6 / 8 outputs per lane (front_mid_nco_hold; off with sw.nco_hold)
     int nco_hold6 = 0, nco_hold8 = 0;
+    int nco_hold6_all = 0;        // ... for the instantiations that hold all twelve phasors of a lane (front_mid_nco_hold_all)
     // profiling
     bool profiling = false;
     struct IQGPU_LOCAL TimedLaunch { int kind; Event a, b; };

@@ -20,6 +20,7 @@
 // Order of a tile (every LDS batch one FMA run ahead of its use, the same window registers never live across two runs):
 //     pointwise(T) -> X(T) in LDS | polyphase(T - 1) + pack + store | raw frames of T + 1, half-band window reads | NCO phasors of T + 1 |
 //     half-band(T) | HB(T) -> LDS, polyphase window + first taps of T
+// (the NCO phasors: looked up only on the tiles where one of the wave's table indices moves, held in registers otherwise -- run_mid)
 // Arithmetic and summation order are k_front_s1's: bit-identical output (test_fat_kernel_equals_the_sixteen_wave_kernel).
 // Edge tiles run on the scalar-load run_tiles (front_tiles.hpp): runs of two 768-frame tiles = three of its 512-frame ones.
 #include "front_tiles.hpp"
@@ -177,32 +178,43 @@ __device__ __forceinline__ void run_mid(const FrontArgs &a, const MidLds &w, con
     // scalar unit -- a v_mul_lo_u32 per chunk and tile is a quarter-rate instruction each (4 of the tile's ~340 VALU instructions,
     // the time of 16)
     const uint32_t th_lane = a.nco_theta0 + (uint32_t)(4 * lane) * a.nco_dtheta;
-    // Phasor hold (a.nco_hold, chosen per chain by front_mid_nco_hold): a phasor is table entry (theta + 2^21) >> 22, and from one tile
+    // Phasor hold (a.nco_hold, chosen per chain and instantiation by front_mid_nco_hold / front_mid_nco_hold_all): a phasor is table entry (theta + 2^21) >> 22, and from one tile
     // to the next every phase of the wave moves by the same D = TILE dtheta (mod 2^32).  Behind a lookup the wave works out how many
-    // tiles pass before ANY of the 384 odd-stream indices moves -- per phase the distance to its cell's edge in the direction of D,
-    // over |D| -- and on those tiles the odd stream's six phasors stay in their registers (the same entries would come back; they are
-    // live across most of the tile anyway).  The even stream's six are looked up every tile: holding them too keeps 12 more registers
-    // live through the polyphase, past the 168 of three waves per SIMD.  For the shifts on the 3.125 kHz grid at 2.4 MS/s
-    // (rate / 768) the phases fall into three narrow clusters (frame mod 3) and |D| is a small multiple of 4096, so the odd lookups
-    // run on ~1 % of the tiles (+200 kHz: 24 of 1999).  hold_to (wave-uniform): the last tile the held phasors are valid for.
-    // (not in the 8-per-lane experiment, nor with both the fused AGC and run stealing: no registers are left to hold anything there)
+    // tiles pass before ANY of its held indices moves -- per phase the distance to its cell's edge in the direction of D, over |D| --
+    // and on those tiles the held phasors stay in their registers (the same entries would come back).  For the shifts on the
+    // 3.125 kHz grid at 2.4 MS/s (rate / 768) the phases fall into three narrow clusters (frame mod 3) and |D| is a small multiple
+    // of 4096, so the lookups run on ~1 % of the tiles (+200 kHz: 24 of 1999).  hold_to (wave-uniform): the last tile the held
+    // phasors are valid for.
+    //   kHold: the odd stream's six are held (they are live across most of the tile anyway) -- not in the 8-per-lane experiment, nor
+    //   with both the fused AGC and run stealing: no registers are left to hold anything there;
+    //   kHoldAll: the even stream's six are held as well, all twelve of the lane -- 12 more registers live through the polyphase,
+    //   which the instantiations without the fused AGC, the multi-run loop, the gained 16-bit unpack and the cs8 pack have inside
+    //   the 168 of three waves per SIMD (the others spill 12 .. 28 bytes with them: there the even six are looked up on every
+    //   tile, as before; tools/check_isa.py tells when the set changes).
     constexpr bool kHold = NL == 6 && !(AGC && STEAL);
+    constexpr bool kHoldAll = kHold && !AGC && !STEAL && !N16 && OUT8 != 2;
     const bool hold = kHold && a.nco_hold;
     int64_t hold_to = T_begin - 1;
     const int32_t hold_d = (int32_t)((uint32_t)G::TILE * a.nco_dtheta);
     auto nco_lookup = [&](int64_t T) {
+        if (kHoldAll && hold && T <= hold_to) return;         // (scalar branch: a kernel argument and a scalar tile index)
         const uint32_t tb = (uint32_t)__builtin_amdgcn_readfirstlane((int)((uint32_t)(T * G::TILE) * a.nco_dtheta));
-#pragma unroll
-        for (int c = 0; c < G::NC; ++c) {
-            const uint32_t th = th_lane + (tb + (uint32_t)(256 * c) * a.nco_dtheta);
-            cs_n[c][0] = nco_phasor2(w.nco, th, 0);
-            cs_n[c][1] = nco_phasor2(w.nco, th + 2u * a.nco_dtheta, 0);
-        }
-        if (hold && T <= hold_to) return;         // (scalar branch: a kernel argument and a scalar tile index)
         // the lane's least distance to a cell edge ahead: 2^22 - 1 - (u mod 2^22) for D > 0, u mod 2^22 for D < 0 (u = theta + 2^21)
         const uint32_t flip = hold_d > 0 ? 0x3fffffu : 0u;
         uint32_t room = 0x3fffffu;
-        // (the lane's share of the phase made opaque: derived here, on the tiles that look up, rather than held across the tile loop)
+        // (the lane's shares of the phase made opaque where they are only needed on the tiles that look up: derived here rather than
+        //  held across the tile loop)
+        int le = 4 * lane;
+        if (kHoldAll) asm volatile("" : "+v"(le));
+        const uint32_t the = kHoldAll ? a.nco_theta0 + (uint32_t)le * a.nco_dtheta : th_lane;
+#pragma unroll
+        for (int c = 0; c < G::NC; ++c) {
+            const uint32_t th = the + (tb + (uint32_t)(256 * c) * a.nco_dtheta);
+            cs_n[c][0] = nco_phasor2(w.nco, th, 0);
+            cs_n[c][1] = nco_phasor2(w.nco, th + 2u * a.nco_dtheta, 0);
+            if (kHoldAll && hold) room = min(room, min(((th + (1u << 21)) ^ flip) & 0x3fffffu, ((th + 2u * a.nco_dtheta + (1u << 21)) ^ flip) & 0x3fffffu));
+        }
+        if (!kHoldAll && hold && T <= hold_to) return;
         int lo = 2 * NL * lane - 19;
         asm volatile("" : "+v"(lo));
         uint32_t tho = a.nco_theta0 + (uint32_t)lo * a.nco_dtheta + tb;
@@ -781,21 +793,26 @@ int front_tap_fold(const uint32_t step, const int nl)
     return tap_gather_cycles(step, nl, true) + 1.5 < tap_gather_cycles(step, nl, false) ? 1 : 0;
 }
 
-// The phasor hold (run_mid) pays where the odd stream's phasors seldom change their table index.  A wave's odd phases sit at fixed
-// offsets f dtheta from each other (f = 2 nl lane - 19 + 2 i: the frames whose phasors are held) and all move by D = 128 nl dtheta per
+// The phasor hold (run_mid) pays where the held phasors seldom change their table index.  A wave's phases sit at fixed offsets
+// f dtheta from each other (the frames whose phasors are held: f = 2 nl lane - 19 + 2 i for the odd stream's six per lane, and for an
+// instantiation that holds all twelve f = 256 c + 4 lane + {0, 2} for the even stream's as well) and all move by D = 128 nl dtheta per
 // tile; a tile needs a lookup when a cell edge lies in the arc [p, p + |D|) of one of them.  Over tile positions the share of such
 // tiles is the measure of the union of those arcs over the cell (2^22): the sum of min(gap, |D|) over the sorted offsets.  A held
-// tile saves six lookups (~24 VALU, 6 LDS reads), a looked-up one pays ~20 VALU and a wave reduction for its countdown: hold where at
-// most a quarter of the tiles look up.  NRSC-5's +200 kHz at 6 per lane: 1.2 %.  (Six per lane only: run_mid holds nothing at 8.)
-int front_mid_nco_hold(const uint32_t dtheta, const int nl)
+// tile saves six or twelve lookups (~4 VALU and an LDS read each), a looked-up one pays ~3 VALU per phase and a wave reduction for its
+// countdown: hold where at most a quarter of the tiles look up.  NRSC-5's +200 kHz at 6 per lane: 1.2 % either way.  (Six per lane
+// only: run_mid holds nothing at 8.)
+static int nco_hold_model(const uint32_t dtheta, const int nl, const bool all)
 {
     if (nl != 6) return 0;
     const int32_t d = (int32_t)((uint32_t)(128 * nl) * dtheta);
     const uint64_t ad = d < 0 ? (uint64_t)(-(int64_t)d) : (uint64_t)d;
     if (ad >= (1u << 22)) return 0;                  // every tile moves every index
     std::vector<uint32_t> p;
-    for (int lane = 0; lane < 64; ++lane)
+    for (int lane = 0; lane < 64; ++lane) {
         for (int i = 0; i < nl; ++i) p.push_back(((uint32_t)(2 * nl * lane - 19 + 2 * i) * dtheta) & 0x3fffffu);
+        for (int c = 0; all && c < nl / 2; ++c)
+            for (int e = 0; e < 4; e += 2) p.push_back(((uint32_t)(256 * c + 4 * lane + e) * dtheta) & 0x3fffffu);
+    }
     std::sort(p.begin(), p.end());
     uint64_t cover = 0;
     for (size_t k = 0; k < p.size(); ++k) {
@@ -804,6 +821,11 @@ int front_mid_nco_hold(const uint32_t dtheta, const int nl)
     }
     return 4 * cover <= ((uint64_t)1 << 22) ? 1 : 0;
 }
+// ... for the instantiations that hold the odd stream's six, and for the ones that hold all twelve (front_mid_holds_all)
+int front_mid_nco_hold(const uint32_t dtheta, const int nl) { return nco_hold_model(dtheta, nl, false); }
+int front_mid_nco_hold_all(const uint32_t dtheta, const int nl) { return nco_hold_model(dtheta, nl, true); }
+// run_mid's kHoldAll, for the host: which instantiations keep the even stream's phasors across tiles too
+bool front_mid_holds_all(const MidSel &k) { return k.ok && k.NL == 6 && !k.NONCO && !k.AGC && !k.STEAL && k.INF != kMidN16 && k.O8 != 2; }
 
 // step classes: lo_3 = floor(3 s), lo_4 = floor(4 s) with s = step / 2^24.  Six per lane (four slots) takes 1.5 <= s < 2, eight per
 // lane (five slots) 1.6 <= s < 2

@@ -166,7 +166,7 @@ struct FrontArgs {
     uint32_t    nco_theta0;   // phase of input sample i_rel = 0
     uint32_t    nco_dtheta;
     const cf2  *nco_tab;      // 1024 x {cos, sin}
-    uint32_t    nco_hold;     // k_front_mid: hold the odd stream's phasors over the tiles on which none of their table indices moves (front_mid_nco_hold())
+    uint32_t    nco_hold;     // k_front_mid: hold the phasors (the odd stream's six, or all twelve: front_mid_holds_all()) over the tiles on which none of their table indices moves (front_mid_nco_hold())
     // resampler
     int32_t     mode;         // 0 = no resampler (pointwise only), 1 = decimating msresamp
     int32_t     S;
@@ -340,6 +340,8 @@ int front_tap_fold(uint32_t step, int nl);
 // whether the NCO phasor hold of k_front_mid pays for a chain's phase step at nl outputs per lane: 1 when a wave's odd-stream
 // phasors change their table index on at most a quarter of its tiles (a model of the wave's phase offsets), else 0 (every tile looks them up)
 int front_mid_nco_hold(uint32_t dtheta, int nl);
+int front_mid_nco_hold_all(uint32_t dtheta, int nl);      // ... for an instantiation that holds all twelve phasors of a lane
+bool front_mid_holds_all(const MidSel &k);
 hipError_t launch_front_mid(const FrontArgs &a, hipStream_t s);
 // chains without a half-band stage as an output-major polyphase kernel with register-resident taps (front_p0.hip)
 int front_p0_waves();

@@ -218,7 +218,7 @@ int Call::stage_front()
         }
         const MidSel msel = mid ? front_mid_select(a) : MidSel{};
         a.tap_fold = (uint32_t)(fat ? c->tap_fold8 : mid ? (msel.NL == 8 ? c->tap_fold8 : c->tap_fold6) : 0);
-        a.nco_hold = (uint32_t)(mid ? (msel.NL == 8 ? c->nco_hold8 : c->nco_hold6) : 0);
+        a.nco_hold = (uint32_t)(mid ? (msel.NL == 8 ? c->nco_hold8 : front_mid_holds_all(msel) ? c->nco_hold6_all : c->nco_hold6) : 0);
         // (k_front_p0: consecutive lanes are five outputs apart -- for the NRSC-5 step 16 arms -- so the lanes that re-read a slot in
         //  the same step would meet in two bank pairs of a linear plane: always the folded placement)
         if (p0) a.tap_fold = 1u;
