@@ -1,9 +1,11 @@
 // capture_load.hpp -- what the accumulators over the BYTES of a capture share on the device (k_stats_pages, stats.hip; k_env_rows,
-// env.hip): the integer codes of a frame beside its unpacked value, the bin and the rails of a code (include/iqgpu.h "capture
-// statistics": the table), and the loads -- four adjacent frames of a thread in one piece, one frame alone -- through the word
-// unpacks of dsp_device.hpp.  One definition of a format's rails, not one per accumulator.
+// env.hip; k_lag_rows, lag.hip): the integer codes of a frame beside its unpacked value, the bin and the rails of a code
+// (include/iqgpu.h "capture statistics": the table), the loads -- four adjacent frames of a thread in one piece, one frame alone --
+// through the word unpacks of dsp_device.hpp, the non-finite total of the two fold kernels, and the one ladder over formats that
+// the three page launchers go through.  One definition of a format's rails, not one per accumulator.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 
 #include "dsp_device.hpp"
 
@@ -121,6 +123,39 @@ __device__ __forceinline__ void load_four(const void *raw, int64_t j, int (&ci)[
 #pragma unroll
         for (int k = 0; k < 4; ++k) ci[k] = cq[k] = 0;
     }
+}
+
+// a fold kernel's first half, one workgroup of THREADS: *total += the groups' counts (n_groups > 0: a cf32 launch)
+template <int THREADS>
+__device__ __forceinline__ void fold_nonfinite(const uint32_t *nonfinite, int n_groups, uint64_t *total, uint64_t (&W)[THREADS])
+{
+    const int tid = threadIdx.x;
+    if (n_groups > 0) {
+        uint64_t n = 0;
+        for (int g = tid; g < n_groups; g += THREADS) n += nonfinite[g];
+        W[tid] = n;
+        __syncthreads();
+        for (int m = THREADS / 2; m >= 1; m >>= 1) {
+            if (tid < m) W[tid] += W[tid + m];
+            __syncthreads();
+        }
+        if (tid == 0) *total += W[0];
+    }
+}
+
+// the format instantiation of a page launch: launch(F) with std::integral_constant<int, format>, -1 for every format that is decoded
+// at run time (psd_stream.hpp's psd_dispatch, without the sizes)
+template <class Launch>
+static hipError_t page_dispatch(int fmt, Launch launch)
+{
+    switch (fmt) {
+    case IQGPU_FMT_CS16: launch(std::integral_constant<int, IQGPU_FMT_CS16>{}); break;
+    case IQGPU_FMT_CU8:  launch(std::integral_constant<int, IQGPU_FMT_CU8>{}); break;
+    case IQGPU_FMT_CS8:  launch(std::integral_constant<int, IQGPU_FMT_CS8>{}); break;
+    case IQGPU_FMT_CF32: launch(std::integral_constant<int, IQGPU_FMT_CF32>{}); break;
+    default:             launch(std::integral_constant<int, -1>{}); break;
+    }
+    return hipGetLastError();
 }
 
 } // namespace iqgpu

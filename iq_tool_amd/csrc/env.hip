@@ -56,7 +56,7 @@ __global__ __launch_bounds__(kEnvThreads) void k_env_rows(const EnvRowsArgs a)
     __shared__ double Ws[4], Wp[4];
     __shared__ uint32_t Wr[4], Wn[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lb = a.log2_b, lp = lb < kEnvLog2Columns ? kEnvLog2Columns : lb > kEnvLog2CellFrames ? kEnvLog2CellFrames : lb;
+    const int lb = a.log2_b, lp = lb < kEnvLog2Columns ? kEnvLog2Columns : lb > kEnvLog2CellFrames ? kEnvLog2CellFrames : lb;      // (env_log2_page)
     const int64_t P = (int64_t)1 << lp;
     const int64_t end = a.first + a.n, page_first = a.first >> lp, page_last = (end - 1) >> lp;
     const int64_t pg0 = page_first + (int64_t)blockIdx.x * a.pages_per_group;
@@ -174,40 +174,16 @@ __global__ __launch_bounds__(kEnvThreads) void k_env_rows(const EnvRowsArgs a)
 hipError_t launch_env_rows(const EnvRowsArgs &a, hipStream_t s)
 {
     if (a.n <= 0) return hipSuccess;
-    int groups = 0, ppg = 0;
-    env_grid(a.first, a.n, a.log2_b, &groups, &ppg);
-    const int lp = env_log2_page(a.log2_b);
-    const int64_t pages = ((a.first + a.n - 1) >> lp) - (a.first >> lp) + 1;
-    // (the bounds of the cell buffer and of the counters: env.cpp cuts longer pushes)
-    if (a.first < 0 || a.log2_b < kEnvLog2BlockMin || a.log2_b > kEnvLog2BlockMax || pages > ((int64_t)1 << (kEnvLog2LaunchFrames - lp)) ||
-        ppg != a.pages_per_group || (a.log2_b > kEnvLog2CellFrames && !a.cells) || (a.fmt == IQGPU_FMT_CF32 && !a.nonfinite))
-        return hipErrorInvalidValue;
-    const dim3 g((unsigned)groups), b(kEnvThreads);
-    switch (a.fmt) {
-    case IQGPU_FMT_CS16: hipLaunchKernelGGL(k_env_rows<IQGPU_FMT_CS16>, g, b, 0, s, a); break;
-    case IQGPU_FMT_CU8:  hipLaunchKernelGGL(k_env_rows<IQGPU_FMT_CU8>, g, b, 0, s, a); break;
-    case IQGPU_FMT_CS8:  hipLaunchKernelGGL(k_env_rows<IQGPU_FMT_CS8>, g, b, 0, s, a); break;
-    case IQGPU_FMT_CF32: hipLaunchKernelGGL(k_env_rows<IQGPU_FMT_CF32>, g, b, 0, s, a); break;
-    default:             hipLaunchKernelGGL(k_env_rows<-1>, g, b, 0, s, a); break;
-    }
-    return hipGetLastError();
+    int groups = 0;
+    if (!env_rows_launch_ok(a.first, a.n, a.log2_b, a.fmt, a.pages_per_group, a.cells, a.nonfinite, &groups)) return hipErrorInvalidValue;
+    return page_dispatch(a.fmt, [&](auto F) { hipLaunchKernelGGL(k_env_rows<decltype(F)::value>, dim3((unsigned)groups), dim3(kEnvThreads), 0, s, a); });
 }
 
 __global__ __launch_bounds__(kEnvThreads) void k_env_fold(const EnvFoldArgs a)
 {
     __shared__ uint64_t W[kEnvThreads];
     const int tid = threadIdx.x;
-    if (a.n_groups > 0) {
-        uint64_t n = 0;
-        for (int g = tid; g < a.n_groups; g += kEnvThreads) n += a.nonfinite[g];
-        W[tid] = n;
-        __syncthreads();
-        for (int m = kEnvThreads / 2; m >= 1; m >>= 1) {
-            if (tid < m) W[tid] += W[tid + m];
-            __syncthreads();
-        }
-        if (tid == 0) *a.nonfinite_total += W[0];
-    }
+    fold_nonfinite<kEnvThreads>(a.nonfinite, a.n_groups, a.nonfinite_total, W);
     if (!a.cells) return;
     const int lc = a.log2_cells_per_row;
     const int64_t r_first = a.c0 >> lc, r_last = (a.c0 + a.n_touched - 1) >> lc, c_end = a.c0 + a.n_closed;

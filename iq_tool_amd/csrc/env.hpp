@@ -70,4 +70,16 @@ inline void env_grid(int64_t first, int64_t n, int log2_b, int *groups, int *pag
     *pages_per_group = (int)ppg; *groups = (int)((pages + ppg - 1) / ppg);
 }
 
+// the bounds a launch of k_env_rows or k_lag_rows keeps (the cell buffer's, the counters': the host cuts longer pushes); *groups: its workgroups
+inline bool env_rows_launch_ok(int64_t first, int64_t n, int log2_b, int fmt, int pages_per_group, const void *cells, const void *nonfinite,
+                               int *groups)
+{
+    int ppg = 0;
+    env_grid(first, n, log2_b, groups, &ppg);
+    const int lp = env_log2_page(log2_b);
+    const int64_t pages = ((first + n - 1) >> lp) - (first >> lp) + 1;
+    return !(first < 0 || log2_b < kEnvLog2BlockMin || log2_b > kEnvLog2BlockMax || pages > ((int64_t)1 << (kEnvLog2LaunchFrames - lp)) ||
+             ppg != pages_per_group || (log2_b > kEnvLog2CellFrames && !cells) || (fmt == IQGPU_FMT_CF32 && !nonfinite));
+}
+
 } // namespace iqgpu

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(kEnvThreads) void k_lag_rows(const LagRowsArgs a)
     __shared__ double W[4][NC];
     __shared__ uint32_t Wn[4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lb = a.log2_b, lp = lb < kEnvLog2Columns ? kEnvLog2Columns : lb > kEnvLog2CellFrames ? kEnvLog2CellFrames : lb;
+    const int lb = a.log2_b, lp = lb < kEnvLog2Columns ? kEnvLog2Columns : lb > kEnvLog2CellFrames ? kEnvLog2CellFrames : lb;      // (env_log2_page)
     const int64_t P = (int64_t)1 << lp;
     const int64_t end = a.first + a.n, page_first = a.first >> lp, page_last = (end - 1) >> lp;
     const int64_t pg0 = page_first + (int64_t)blockIdx.x * a.pages_per_group;
@@ -221,56 +221,26 @@ __global__ __launch_bounds__(kEnvThreads) void k_lag_rows(const LagRowsArgs a)
     }
 }
 
-namespace {
-
-template <int NL> void launch_rows_nl(const LagRowsArgs &a, dim3 g, dim3 b, hipStream_t s)
-{
-    switch (a.fmt) {
-    case IQGPU_FMT_CS16: hipLaunchKernelGGL((k_lag_rows<IQGPU_FMT_CS16, NL>), g, b, 0, s, a); break;
-    case IQGPU_FMT_CU8:  hipLaunchKernelGGL((k_lag_rows<IQGPU_FMT_CU8, NL>), g, b, 0, s, a); break;
-    case IQGPU_FMT_CS8:  hipLaunchKernelGGL((k_lag_rows<IQGPU_FMT_CS8, NL>), g, b, 0, s, a); break;
-    case IQGPU_FMT_CF32: hipLaunchKernelGGL((k_lag_rows<IQGPU_FMT_CF32, NL>), g, b, 0, s, a); break;
-    default:             hipLaunchKernelGGL((k_lag_rows<-1, NL>), g, b, 0, s, a); break;
-    }
-}
-
-} // namespace
-
 hipError_t launch_lag_rows(const LagRowsArgs &a, hipStream_t s)
 {
     if (a.n <= 0) return hipSuccess;
-    int groups = 0, ppg = 0;
-    env_grid(a.first, a.n, a.log2_b, &groups, &ppg);
-    const int lp = env_log2_page(a.log2_b);
-    const int64_t pages = ((a.first + a.n - 1) >> lp) - (a.first >> lp) + 1;
-    // (the bounds of the cell buffer, of the counters and of the history: lag.cpp cuts longer pushes and keeps max_lag frames)
-    if (a.first < 0 || a.log2_b < kEnvLog2BlockMin || a.log2_b > kEnvLog2BlockMax || pages > ((int64_t)1 << (kEnvLog2LaunchFrames - lp)) ||
-        ppg != a.pages_per_group || (a.log2_b > kEnvLog2CellFrames && !a.cells) || (a.fmt == IQGPU_FMT_CF32 && !a.nonfinite) || !a.hist ||
+    int groups = 0;
+    // (env's bounds, and the history's: lag.cpp keeps max_lag frames)
+    if (!env_rows_launch_ok(a.first, a.n, a.log2_b, a.fmt, a.pages_per_group, a.cells, a.nonfinite, &groups) || !a.hist ||
         a.n_lags < 1 || a.n_lags > kLagMaxLags || a.max_lag != a.lags[a.n_lags - 1])
         return hipErrorInvalidValue;
     for (int l = 0; l < a.n_lags; ++l)
         if (a.lags[l] < 1 || a.lags[l] > kLagMaxLag || (l && a.lags[l] <= a.lags[l - 1])) return hipErrorInvalidValue;
     const dim3 g((unsigned)groups), b(kEnvThreads);
-    if (a.n_lags == 1) launch_rows_nl<1>(a, g, b, s);
-    else launch_rows_nl<kLagMaxLags>(a, g, b, s);
-    return hipGetLastError();
+    if (a.n_lags == 1) return page_dispatch(a.fmt, [&](auto F) { hipLaunchKernelGGL((k_lag_rows<decltype(F)::value, 1>), g, b, 0, s, a); });
+    return page_dispatch(a.fmt, [&](auto F) { hipLaunchKernelGGL((k_lag_rows<decltype(F)::value, kLagMaxLags>), g, b, 0, s, a); });
 }
 
 __global__ __launch_bounds__(kEnvThreads) void k_lag_fold(const LagFoldArgs a)
 {
     __shared__ uint64_t W[kEnvThreads];
     const int tid = threadIdx.x;
-    if (a.n_groups > 0) {
-        uint64_t n = 0;
-        for (int g = tid; g < a.n_groups; g += kEnvThreads) n += a.nonfinite[g];
-        W[tid] = n;
-        __syncthreads();
-        for (int m = kEnvThreads / 2; m >= 1; m >>= 1) {
-            if (tid < m) W[tid] += W[tid + m];
-            __syncthreads();
-        }
-        if (tid == 0) *a.nonfinite_total += W[0];
-    }
+    fold_nonfinite<kEnvThreads>(a.nonfinite, a.n_groups, a.nonfinite_total, W);
     if (!a.cells) return;
     const int lc = a.log2_cells_per_row, nc = 2 * a.n_lags + 1;
     const int64_t r_first = a.c0 >> lc, r_last = (a.c0 + a.n_touched - 1) >> lc, c_end = a.c0 + a.n_closed;

@@ -67,51 +67,20 @@ uint64_t iqgpu::psd_segments_of(const iqgpu_psd_opts &o, uint64_t frames) { retu
 int PsdStream::open(PsdStream *st, int device, int format, const iqgpu_psd_opts *o, const char *who, std::vector<float> &tab)
 {
     int rc = psd_check_opts(o, who); if (rc) return rc;
-    if (!bytes_per_frame(format)) return fail(IQGPU_EFORMAT, "%s: unhandled sample format %d", who, format);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(IQGPU_ENODEV, "%s: no HIP device available", who);
-    if (device < 0 || device >= ndev) return fail(IQGPU_ENODEV, "%s: device %d out of range (%d devices)", who, device, ndev);
     try { tab.resize(3 * (size_t)o->nfft); } catch (const std::bad_alloc &) { st = nullptr; }
-    if (!st) return fail(IQGPU_ENOMEM, "%s: out of host memory", who);
-    st->device = device; st->format = format; st->log2n = log2n_of(o->nfft); st->bps = bytes_per_frame(format); st->q = *o;
+    rc = AccumCore::open(st, device, format, who); if (rc) return rc;
+    st->log2n = log2n_of(o->nfft); st->q = *o;
     fill_tables(*o, tab.data(), &st->window_sum, &st->window_sum_sq);
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = st->own.create();
-    if (e != hipSuccess) return fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e));
     rc = st->tables.ensure(tab.size() * sizeof(float));
     for (int i = 0; i < 2 && rc == IQGPU_OK; ++i) rc = st->carry[i].ensure((size_t)o->nfft * st->bps);
     if (rc) return rc;
-    e = hipMemcpyAsync(st->tables.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, st->own);
+    const hipError_t e = hipMemcpyAsync(st->tables.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice, st->own);
     return e == hipSuccess ? IQGPU_OK : fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e));
-}
-
-void PsdStream::close()
-{
-    if (!own) return;                                                // (open() got no further than its checks: nothing is held)
-    (void)hipSetDevice(device);
-    if (has_last) (void)hipStreamSynchronize(last);
-    (void)hipStreamSynchronize(own);
-}
-
-int PsdStream::guard(const PsdStream *st, bool args_ok, const char *who, const char *reset, bool set_device)
-{
-    if (!st || !args_ok) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
-    if (st->poisoned) return fail(IQGPU_EHIP, "%s: an earlier push failed half way through: the accumulator is undefined until %s()", who, reset);
-    if (set_device) HIP_TRY(hipSetDevice(st->device));
-    return IQGPU_OK;
-}
-
-int PsdStream::settle()
-{
-    if (has_last) HIP_TRY(hipStreamSynchronize(last));
-    has_last = false; last = nullptr;
-    return IQGPU_OK;
 }
 
 int PsdStream::enter(const void *d_raw, size_t n, hipStream_t s, PsdPush *u)
 {
-    if (has_last && last != s) HIP_TRY(hipStreamSynchronize(last));  // the previous push's work comes first
-    has_last = true; last = s;
+    const int rc = note_stream(s); if (rc) return rc;
     u->raw = d_raw; u->n = n; u->s = s;
     u->frames = frames + n; u->segs = psd_segments_of(q, u->frames); u->m = (int64_t)(u->segs - segments);
     return IQGPU_OK;

@@ -2,6 +2,7 @@
 // k_psd_pages / k_psd_fold / k_psd_carry (psd.hip; host side psd.cpp), and the host's stream core PsdStream, which the
 // row accumulator (sgram.hpp) holds too.
 #pragma once
+#include "accum_core.hpp"
 #include "chain.hpp"
 
 namespace iqgpu {
@@ -53,35 +54,26 @@ uint64_t psd_segments_of(const iqgpu_psd_opts &o, uint64_t frames);
 // One push: n frames of device memory at raw on stream s; the stream's frames and whole segments with them, m of the segments new
 struct PsdPush { const void *raw; size_t n; hipStream_t s; uint64_t frames, segs; int64_t m; };
 
-// The stream core both handles hold (psd.cpp): the position in the stream, the carry of trailing frames in two buffers (the launches of
-// a push read carry[cur], its last launch writes carry[cur ^ 1]), the device tables, the stream of its own and the one of the previous
-// push.  What a handle accumulates, and its open state, are the handle's.
-struct PsdStream {
-    int device = 0, format = 0, log2n = 0;
-    size_t bps = 0;
+// The stream core both handles hold (psd.cpp): the handle core (accum_core.hpp: identity, position in frames, streams, guard / settle
+// / close) and what belongs to the segment grid -- the carry of trailing frames in two buffers (the launches of a push read
+// carry[cur], its last launch writes carry[cur ^ 1]) and the device tables.  What a handle accumulates, and its open state, are the handle's.
+struct IQGPU_LOCAL PsdStream : AccumCore {
+    int log2n = 0;
     iqgpu_psd_opts q{};
     double window_sum = 0.0, window_sum_sq = 0.0;
-    uint64_t frames = 0, segments = 0;    // pushed since the last reset; whole segments of them (all accumulated)
+    uint64_t segments = 0;                // whole segments of the frames pushed since the last reset (all accumulated)
     size_t carry_n = 0;                   // frames in carry[cur]: stream frames segments * hop .. frames - 1
     int cur = 0;
-    bool poisoned = false;                // a push failed half way: rewind() clears it
-    Stream own; hipStream_t last = nullptr; bool has_last = false;        // last: the stream of the previous push (not owned)
     DevBuf tables, carry[2], stage;       // tables: [nfft] window, then [nfft] twiddles as (cos, sin) pairs
     const float *window() const { return (const float *)tables.p; }
     const cf2 *twiddle() const { return (const cf2 *)((const float *)tables.p + q.nfft); }
 
-    // The checks of a create in their order -- options, format, device count and range, host memory (st NULL: no handle could be
-    // allocated) -- then stream, buffers and the tables' upload, queued on `own` from `tab`: the caller queues the zero fill of its
-    // open state behind it and synchronises once, with `tab` alive until then.  `who` leads the error texts.
+    // The checks of a create in their order -- options, then AccumCore::open's (st NULL: no handle could be allocated) -- then buffers
+    // and the tables' upload, queued on `own` from `tab`: the caller queues the zero fill of its open state behind it and synchronises
+    // once, with `tab` alive until then.  `who` leads the error texts.
     static int open(PsdStream *st, int device, int format, const iqgpu_psd_opts *o, const char *who, std::vector<float> &tab);
-    IQGPU_LOCAL ~PsdStream() = default;   // frees the stream and the buffers; the waits in front of that are close()
-    void close();                         // waits for `last` and `own`: the holder's destructor calls it in front of the members' frees
-    // NULL (st, or !args_ok) and poisoned, in the handles' texts (`reset` names the call that clears a poisoned handle), then hipSetDevice
-    static int guard(const PsdStream *st, bool args_ok, const char *who, const char *reset, bool set_device = true);
-    int settle();                         // everything queued by earlier pushes has run; the handle then holds on to no stream of the caller's
-    // a reset: `last` waited for (a failed push may have left an error there: ignored), the caller zero-fills its state on `own`, then
-    int begin_reset() { HIP_TRY(hipSetDevice(device)); if (has_last) (void)hipStreamSynchronize(last); return IQGPU_OK; }
-    void rewind() { frames = segments = 0; carry_n = 0; cur = 0; has_last = false; last = nullptr; poisoned = false; }   // ... as created
+    ~PsdStream() = default;               // frees the stream and the buffers; the waits in front of that are close()
+    void rewind() { AccumCore::rewind(); segments = 0; carry_n = 0; cur = 0; }           // ... as created
     int enter(const void *d_raw, size_t n, hipStream_t s, PsdPush *u);   // the previous push's stream waited for if it is another; s remembered
     // what PsdPagesArgs and SgramCellsArgs have in common, for the launch over segments [j, j + cnt) of the push, but for open_*: the handle's
     template <class Args> void fill(const PsdPush &u, int64_t j, int64_t cnt, Args *a) const

@@ -194,22 +194,10 @@ extern "C" int iqgpu_sgram_push(iqgpu_sgram *p, const void *raw, size_t frames, 
     float *d_sum = row_sum ? (float *)p->rows_out.p : nullptr;
     float *d_pk = row_peak ? (float *)p->rows_out.p + (row_sum ? slice_rows * N : 0) : nullptr;
     if (rows) *rows = need;
-    for (size_t at = 0; at < frames;) {
-        const size_t n = frames - at < kPushSliceFrames ? frames - at : kPushSliceFrames;
-        const size_t done = iqgpu_sgram_max_rows(p, n);
-        if (done > slice_rows) return fail(IQGPU_EHIP, "iqgpu_sgram_push: a slice completes %zu rows, the buffer holds %zu", done, slice_rows);
-        HIP_TRY(hipMemcpyAsync(st.stage.p, (const char *)raw + at * st.bps, n * st.bps, hipMemcpyHostToDevice, st.own));
-        rc = push_frames(p, st.stage.p, n, d_sum, d_pk, st.own); if (rc) return rc;
-        st.poisoned = true;                                              // (until the slice's rows are in the caller's memory)
-        if (row_sum && done) HIP_TRY(hipMemcpyAsync(row_sum, d_sum, done * N * sizeof(float), hipMemcpyDeviceToHost, st.own));
-        if (row_peak && done) HIP_TRY(hipMemcpyAsync(row_peak, d_pk, done * N * sizeof(float), hipMemcpyDeviceToHost, st.own));
-        HIP_TRY(hipStreamSynchronize(st.own));                          // the one staging pair: the next slice overwrites both
-        st.poisoned = false;
-        if (row_sum) row_sum += done * N;
-        if (row_peak) row_peak += done * N;
-        at += n;
-    }
-    return IQGPU_OK;
+    HostPlane out[2] = {{(char *)row_sum, d_sum, N * sizeof(float)}, {(char *)row_peak, d_pk, N * sizeof(float)}};
+    return push_host_slices(st, st.stage, raw, frames, kPushSliceFrames, slice_rows, out, "iqgpu_sgram_push", "completes",
+                            [&](size_t n) { return iqgpu_sgram_max_rows(p, n); },
+                            [&](const void *d_raw, size_t n) { return push_frames(p, d_raw, n, d_sum, d_pk, st.own); });
 }
 
 extern "C" int iqgpu_sgram_read_open(iqgpu_sgram *p, double *sum_power, float *peak_power, iqgpu_sgram_info *info)

@@ -2,16 +2,13 @@
 // the iqgpu_stats handle -- stream position, the totals, the open page's columns in two buffers, the slab of a launch -- with
 // push / push_device / read / reset under iqgpu_psd's stream rules, and the two host-only calls, merge and derive.  Independent of
 // any chain.
+#include "accum_core.hpp"
 #include "chain.hpp"
 #include "stats.hpp"
 
 struct iqgpu_stats {
-    int device = 0, format = 0;
-    size_t bps = 0;
-    uint64_t frames = 0;                  // pushed since the last reset
+    AccumCore core;
     int open_cur = 0;                     // which of the two open-column buffers holds the open page (the page kernel writes the other)
-    bool poisoned = false;                // a push failed half way: reset clears it
-    Stream own; hipStream_t last = nullptr; bool has_last = false;       // last: the stream of the previous push (not owned)
     Event staged;                         // a host push: the slice has left the caller's memory
     // state: StatsTotals, then 2 x [5][kStatsColumns] doubles; slab: [groups][512] uint32, [groups] StatsPartial, [pages][5] doubles
     DevBuf state, slab, stage;
@@ -22,19 +19,16 @@ struct iqgpu_stats {
     StatsPartial *slab_part() const { return (StatsPartial *)(slab_hist() + (size_t)kStatsMaxGroups * 512); }
     double *slab_sums() const { return (double *)(slab_part() + kStatsMaxGroups); }
     static constexpr size_t kSlabBytes = (size_t)kStatsMaxGroups * (512 * sizeof(uint32_t) + sizeof(StatsPartial)) + (size_t)kStatsMaxPages * 5 * sizeof(double);
-    IQGPU_LOCAL ~iqgpu_stats()
-    {
-        if (!own) return;                 // (create got no further than its checks: nothing is held)
-        (void)hipSetDevice(device);
-        if (has_last) (void)hipStreamSynchronize(last);
-        (void)hipStreamSynchronize(own);  // the waits first: the members free themselves behind them
-    }
+    IQGPU_LOCAL ~iqgpu_stats() { core.close(); }      // the waits first: the members free themselves behind them
 };
 static_assert(sizeof(StatsTotals) % sizeof(double) == 0 && sizeof(StatsPartial) % sizeof(double) == 0, "the doubles behind them stay aligned");
 
 namespace {
 
 constexpr size_t kPushSliceFrames = (size_t)1 << 22;     // of a host push: frames staged per slice
+const char *const kReset = "iqgpu_stats_reset";
+
+AccumCore *core(iqgpu_stats *p) { return p ? &p->core : nullptr; }
 
 // the state of a handle without frames, queued on `own`
 int zero_state(iqgpu_stats *p)
@@ -43,33 +37,25 @@ int zero_state(iqgpu_stats *p)
     memset(&t, 0, sizeof(t));
     t.pk = -1.0; t.pkf = 0;
     t.mn[0] = t.mn[1] = INFINITY; t.mx[0] = t.mx[1] = -INFINITY;
-    HIP_TRY(hipMemsetAsync(p->state.p, 0, iqgpu_stats::kStateBytes, p->own));
-    HIP_TRY(hipMemcpyAsync(p->state.p, &t, sizeof(t), hipMemcpyHostToDevice, p->own));
-    HIP_TRY(hipStreamSynchronize(p->own));               // (t is on this stack)
-    return IQGPU_OK;
-}
-
-int guard(const iqgpu_stats *p, bool args_ok, const char *who)
-{
-    if (!p || !args_ok) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
-    if (p->poisoned) return fail(IQGPU_EHIP, "%s: an earlier push failed half way through: the accumulator is undefined until iqgpu_stats_reset()", who);
-    HIP_TRY(hipSetDevice(p->device));
+    HIP_TRY(hipMemsetAsync(p->state.p, 0, iqgpu_stats::kStateBytes, p->core.own));
+    HIP_TRY(hipMemcpyAsync(p->state.p, &t, sizeof(t), hipMemcpyHostToDevice, p->core.own));
+    HIP_TRY(hipStreamSynchronize(p->core.own));              // (t is on this stack)
     return IQGPU_OK;
 }
 
 // n frames of device memory behind everything pushed so far, on s
 int push_frames(iqgpu_stats *p, const void *d_raw, size_t n, hipStream_t s)
 {
-    if (p->has_last && p->last != s) HIP_TRY(hipStreamSynchronize(p->last));     // the previous push's work comes first
-    p->has_last = true; p->last = s;
+    AccumCore &core = p->core;
+    const int rc = core.note_stream(s); if (rc) return rc;
     const uint64_t P = kStatsPageFrames;
-    p->poisoned = true;                                                           // (until the last launch of the push is queued)
+    core.poisoned = true;                                                          // (until the last launch of the push is queued)
     for (size_t at = 0; at < n;) {
-        const uint64_t first = p->frames;
+        const uint64_t first = core.frames;
         const uint64_t room = (uint64_t)kStatsMaxPages * P - first % P;           // whole pages up to the slab's bound
         const uint64_t cnt = n - at < room ? n - at : room;
         StatsPagesArgs a{};
-        a.raw = (const char *)d_raw + at * p->bps; a.first = (int64_t)first; a.n = (int64_t)cnt; a.fmt = p->format;
+        a.raw = (const char *)d_raw + at * core.bps; a.first = (int64_t)first; a.n = (int64_t)cnt; a.fmt = core.format;
         int groups = 0;
         stats_grid(a.first, a.n, &groups, &a.pages_per_group);
         a.open_in = p->open_cols(p->open_cur); a.open_out = p->open_cols(p->open_cur ^ 1);
@@ -80,10 +66,10 @@ int push_frames(iqgpu_stats *p, const void *d_raw, size_t n, hipStream_t s)
         f.n_pages = (int32_t)((first + cnt) / P - first / P); f.tot = p->totals();
         HIP_TRY(launch_stats_fold(f, s));
         if ((first + cnt) % P != 0) p->open_cur ^= 1;                             // the launch left an open page, in the other buffer
-        p->frames = first + cnt;
+        core.frames = first + cnt;
         at += (size_t)cnt;
     }
-    p->poisoned = false;
+    core.poisoned = false;
     return IQGPU_OK;
 }
 
@@ -101,18 +87,12 @@ extern "C" int iqgpu_stats_create(int device, int format, iqgpu_stats **out)
     const char *who = "iqgpu_stats_create";
     if (out) *out = nullptr;
     if (!out) return fail(IQGPU_EINVAL, "%s: NULL argument", who);
-    if (!bytes_per_frame(format)) return fail(IQGPU_EFORMAT, "%s: unhandled sample format %d", who, format);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(IQGPU_ENODEV, "%s: no HIP device available", who);
-    if (device < 0 || device >= ndev) return fail(IQGPU_ENODEV, "%s: device %d out of range (%d devices)", who, device, ndev);
     iqgpu_stats *p = new (std::nothrow) iqgpu_stats;
-    if (!p) return fail(IQGPU_ENOMEM, "%s: out of host memory", who);
-    p->device = device; p->format = format; p->bps = bytes_per_frame(format);
-    int rc = IQGPU_OK;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = p->own.create();
-    if (e == hipSuccess) e = p->staged.create(hipEventDisableTiming);
-    if (e != hipSuccess) rc = fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e));
+    int rc = AccumCore::open(core(p), device, format, who);
+    if (rc == IQGPU_OK) {
+        const hipError_t e = p->staged.create(hipEventDisableTiming);
+        if (e != hipSuccess) rc = fail(IQGPU_EHIP, "%s: %s", who, hipGetErrorString(e));
+    }
     if (rc == IQGPU_OK) rc = p->state.ensure(iqgpu_stats::kStateBytes);
     if (rc == IQGPU_OK) rc = p->slab.ensure(iqgpu_stats::kSlabBytes);
     if (rc == IQGPU_OK) rc = zero_state(p);
@@ -126,31 +106,32 @@ extern "C" void iqgpu_stats_destroy(iqgpu_stats *p) { delete p; }
 extern "C" int iqgpu_stats_reset(iqgpu_stats *p)
 {
     if (!p) return fail(IQGPU_EINVAL, "iqgpu_stats_reset: NULL argument");
-    HIP_TRY(hipSetDevice(p->device));
-    if (p->has_last) (void)hipStreamSynchronize(p->last);            // (a failed push may have left an error there: ignored)
-    const int rc = zero_state(p); if (rc) return rc;
-    p->frames = 0; p->open_cur = 0; p->has_last = false; p->last = nullptr; p->poisoned = false;
+    int rc = p->core.begin_reset(); if (rc) return rc;
+    rc = zero_state(p); if (rc) return rc;
+    p->core.rewind(); p->open_cur = 0;
     return IQGPU_OK;
 }
 
 extern "C" int iqgpu_stats_push_device(iqgpu_stats *p, const void *d_raw, size_t frames, void *hip_stream)
 {
     if (p && frames == 0) return IQGPU_OK;
-    const int rc = guard(p, d_raw, "iqgpu_stats_push_device"); if (rc) return rc;
+    const int rc = AccumCore::guard(core(p), d_raw, "iqgpu_stats_push_device", kReset); if (rc) return rc;
     return push_frames(p, d_raw, frames, (hipStream_t)hip_stream);
 }
 
 extern "C" int iqgpu_stats_push(iqgpu_stats *p, const void *raw, size_t frames)
 {
     if (p && frames == 0) return IQGPU_OK;
-    int rc = guard(p, raw, "iqgpu_stats_push"); if (rc) return rc;
-    rc = p->stage.ensure((frames < kPushSliceFrames ? frames : kPushSliceFrames) * p->bps); if (rc) return rc;
+    int rc = AccumCore::guard(core(p), raw, "iqgpu_stats_push", kReset); if (rc) return rc;
+    const size_t bps = p->core.bps;
+    const hipStream_t own = p->core.own;
+    rc = p->stage.ensure((frames < kPushSliceFrames ? frames : kPushSliceFrames) * bps); if (rc) return rc;
     for (size_t at = 0; at < frames;) {
         const size_t n = frames - at < kPushSliceFrames ? frames - at : kPushSliceFrames;
         // (the one staging buffer: the copy is ordered behind the kernels of the slice in front on the handle's stream)
-        HIP_TRY(hipMemcpyAsync(p->stage.p, (const char *)raw + at * p->bps, n * p->bps, hipMemcpyHostToDevice, p->own));
-        HIP_TRY(hipEventRecord(p->staged, p->own));
-        rc = push_frames(p, p->stage.p, n, p->own); if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(p->stage.p, (const char *)raw + at * bps, n * bps, hipMemcpyHostToDevice, own));
+        HIP_TRY(hipEventRecord(p->staged, own));
+        rc = push_frames(p, p->stage.p, n, own); if (rc) return rc;
         HIP_TRY(hipEventSynchronize(p->staged));                     // the caller's memory is free when the call returns
         at += n;
     }
@@ -159,17 +140,16 @@ extern "C" int iqgpu_stats_push(iqgpu_stats *p, const void *raw, size_t frames)
 
 extern "C" int iqgpu_stats_read(iqgpu_stats *p, iqgpu_stats_result *r)
 {
-    const int rc = guard(p, r, "iqgpu_stats_read"); if (rc) return rc;
-    if (p->has_last) HIP_TRY(hipStreamSynchronize(p->last));
-    p->has_last = false; p->last = nullptr;
+    int rc = AccumCore::guard(core(p), r, "iqgpu_stats_read", kReset); if (rc) return rc;
+    rc = p->core.settle(); if (rc) return rc;
     StatsTotals t;
     std::vector<double> cols;
     try { cols.resize(5 * (size_t)kStatsColumns); } catch (const std::bad_alloc &) { return fail(IQGPU_ENOMEM, "iqgpu_stats_read: out of host memory"); }
     HIP_TRY(hipMemcpy(&t, p->totals(), sizeof(t), hipMemcpyDeviceToHost));
-    const bool open = p->frames % (uint64_t)kStatsPageFrames != 0;   // else the open columns hold a page already folded, or nothing
+    const bool open = p->core.frames % (uint64_t)kStatsPageFrames != 0;   // else the open columns hold a page already folded, or nothing
     if (open) HIP_TRY(hipMemcpy(cols.data(), p->open_cols(p->open_cur), cols.size() * sizeof(double), hipMemcpyDeviceToHost));
     memset(r, 0, sizeof(*r));
-    r->frames = p->frames; r->nonfinite_frames = t.nonfinite;
+    r->frames = p->core.frames; r->nonfinite_frames = t.nonfinite;
     for (int c = 0; c < 2; ++c) {
         r->rail_lo[c] = t.rail_lo[c]; r->rail_hi[c] = t.rail_hi[c];
         for (int b = 0; b < 256; ++b) r->hist[c][b] = t.hist[c * 256 + b];

@@ -202,15 +202,7 @@ hipError_t launch_stats_pages(const StatsPagesArgs &a, hipStream_t s)
     stats_grid(a.first, a.n, &groups, &ppg);
     const int64_t pages = (a.first + a.n - 1) / kStatsPageFrames - a.first / kStatsPageFrames + 1;
     if (a.first < 0 || pages > kStatsMaxPages || ppg != a.pages_per_group) return hipErrorInvalidValue;      // (the slab's bounds: stats.cpp cuts longer pushes)
-    const dim3 g((unsigned)groups), b(kStatsThreads);
-    switch (a.fmt) {
-    case IQGPU_FMT_CS16: hipLaunchKernelGGL(k_stats_pages<IQGPU_FMT_CS16>, g, b, 0, s, a); break;
-    case IQGPU_FMT_CU8:  hipLaunchKernelGGL(k_stats_pages<IQGPU_FMT_CU8>, g, b, 0, s, a); break;
-    case IQGPU_FMT_CS8:  hipLaunchKernelGGL(k_stats_pages<IQGPU_FMT_CS8>, g, b, 0, s, a); break;
-    case IQGPU_FMT_CF32: hipLaunchKernelGGL(k_stats_pages<IQGPU_FMT_CF32>, g, b, 0, s, a); break;
-    default:             hipLaunchKernelGGL(k_stats_pages<-1>, g, b, 0, s, a); break;
-    }
-    return hipGetLastError();
+    return page_dispatch(a.fmt, [&](auto F) { hipLaunchKernelGGL(k_stats_pages<decltype(F)::value>, dim3((unsigned)groups), dim3(kStatsThreads), 0, s, a); });
 }
 
 __global__ __launch_bounds__(1024) void k_stats_fold(const StatsFoldArgs a)
