@@ -127,20 +127,15 @@ int Call::stage_agc_verify_and_fallback(const FrontArgs &spec)
 {
     KernelTimer kt(c, IQGPU_K_AGC);
     AgcArgs ga;
-    const int rc = stage_agc_verify((mid || p0) ? 1 : 0, &ga); if (rc) return rc;
+    const RouteInfo &ri = route_info(route);
+    const int rc = stage_agc_verify(ri.float_peaks ? 1 : 0, &ga); if (rc) return rc;
     FrontArgs fb = spec;
     fb.agc_fused = 0; fb.agc_state = nullptr; fb.agc_peak2 = nullptr; fb.w_steal = nullptr; fb.w_run_stride = 0;
     fb.out_fmt = IQGPU_FMT_CF32; fb.out = c->abuf.p;
     fb.run_if = c->d_agc_flag;
-    if (fat || mid || p0) {
-        // the fused launch ran on k_front_fat / k_front_mid / k_front_p0 with its own geometry: the fallback is k_front_s1's (512-frame
-        // tiles; 256 without a half-band stage)
-        const int ft = p0 ? 256 : kWTile;
-        fb.w_total_tiles = ((int64_t)fb.rem0 + fb.frames_in + ft - 1) / ft;
-        int warm = (int)((c->rp.history_in + ft - 1) / ft);
-        if (warm < 1) warm = 1;
-        plan_front_s1(fb, wave_slots(front_s1_waves(fb)), fixed_tpw(), warm, 1, ft);
-    }
+    // the fused launch ran on k_front_fat / k_front_mid / k_front_p0 with its own geometry: the fallback is k_front_s1's (512-frame
+    // tiles; 256 without a half-band stage)
+    if (ri.fallback_tile) plan_s1(fb, ri.fallback_tile);
     if (verdict_on_host()) {
         c->pend.valid = true; c->pend.filter = false; c->pend.fb = fb; c->pend.ga = ga;
         return IQGPU_OK;

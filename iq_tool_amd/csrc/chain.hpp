@@ -1,7 +1,7 @@
 // chain.hpp -- internal to libiqgpu's host side: the chain object behind the opaque iqgpu_chain handle, the per-call plan and
 // what the translation units of the C ABI share.  Not installed; include/iqgpu.h is the interface.
 //   abi.cpp        library / lifecycle / state entry points, create-time design (design_chain)
-//   plan.cpp       stream-position arithmetic (plan_call), per-call run geometry of the wave kernels (Call::plan_geometry)
+//   plan.cpp       stream-position arithmetic (plan_call), the route of a call and its run geometry (Call::choose_route, plan_route)
 //   process.cpp    one process() call: buffers, the stages in stream order, iqgpu_chain_process[_device]
 //   seek.cpp       seamless range sharding: iqgpu_chain_seek[_agc | _dc], iqgpu_chain_measure, iqgpu_chain_agc_initial_state / _advance,
 //                  iqgpu_chain_dc_measure / _dc_measure_range / _dc_advance, iqgpu_chain_dcagc_*, iqgpu_chain_dcrms_*
@@ -389,8 +389,56 @@ struct KernelTimer {
 
 // ------------------------------------------------------------------------------------------------
 // one process() call: per-call geometry, then the stages in stream order
-//   [dc carries] -> front (k_front | k_front_s1 | k_cascade + k_front_s1) -> [filter] -> [k_interp] -> [agc]
+//   [dc carries] -> front (one FrontRoute, below) -> [filter] -> [k_interp] -> [agc]
 // ------------------------------------------------------------------------------------------------
+// Which kernels the front of a call runs on: ONE value per call, chosen by Call::choose_route (plan.cpp; the order of the choice and
+// the two demotions: DESIGN.md 3.0b), one enumerator per value iqgpu_chain_front_kernel reports.  What the host reads of a route it
+// reads HERE -- from kRouteInfo, or from the switches below where the answer needs a launcher's function -- and nowhere else.
+enum class FrontRoute { Generic, GenericLate, S1, S1S0, Fat, Mid, P0, P0Fft, Cascade, Cascade2, S2 };
+struct RouteInfo {
+    const char *name;      // what iqgpu_chain_front_kernel reports (k_front_mid: with the suffix of its MidSel, stage_front)
+    int tile;              // input frames per tile of the plan (0: no wave plan; Mid: 128 per output of a lane -- route_tile)
+    int lead;              // frames a streaming run reads in front of its first tile
+    bool wave;             // wave-autonomous: cplan holds its runs, and the DC carries start where they do (dc_geom mode 1)
+    bool casc;             // stages 0 .. S-2 in front of the last one: k_cascade's intermediate stream in c->mid, the last stage on d_hist2
+    int fallback_tile;     // != 0: the fallback behind its fused-AGC launch is k_front_s1 on k_front_s1's OWN geometry of this tile (plan_s1)
+    bool float_peaks;      // its fused-AGC epilogue keeps float peaks: the verifier tests them with a margin
+};
+constexpr RouteInfo kRouteInfo[] = {
+    /* Generic     */ {"k_front",               0,          0,        false, false, 0,      false},   // the workgroup-tiled kernel
+    /* GenericLate */ {"k_front+k_interp",      0,          0,        false, false, 0,      false},   // ... pointwise, the resampler behind it (r >= 1)
+    /* S1          */ {"k_front_s1",            kWTile,     0,        true,  false, 0,      false},   // one half-band stage (m = 10)
+    /* S1S0        */ {"k_front_s1",            256,        0,        true,  false, 0,      false},   // no half-band stage: k_front_s1<S0>
+    /* Fat         */ {"k_front_fat",           kFatTile,   0,        true,  false, kWTile, false},   // S1's shape, 8 waves per CU (opt-in)
+    /* Mid         */ {"k_front_mid",           0,          kMidLead, true,  false, kWTile, true},    // S1's shape, 12 waves per CU: long calls
+    /* P0          */ {"k_front_p0",            256,        0,        true,  false, 256,    true},    // S1S0's shape, output-major: long calls
+    /* P0Fft       */ {"k_p0fft16",             256,        0,        true,  false, 0,      false},   // ... and the filter behind it, in ONE kernel launched by stage_filter (opt-in)
+    /* Cascade     */ {"k_cascade+k_front_s1",  kWTile,     0,        true,  true,  0,      false},   // S >= 2
+    /* Cascade2    */ {"k_cascade2+k_front_s1", kWTile,     kWTile,   true,  true,  0,      false},   // ... two tiles per trip: a run of an odd number of tiles starts one tile early
+    /* S2          */ {"k_front_s2",            2 * kWTile, 0,        true,  true,  0,      false},   // S == 2, both stages in one kernel: planned in tiles of the LAST stage
+};
+static_assert(sizeof(kRouteInfo) / sizeof(kRouteInfo[0]) == (size_t)FrontRoute::S2 + 1, "one row per route");
+constexpr const RouteInfo &route_info(FrontRoute r) { return kRouteInfo[(int)r]; }
+// (mid_nl: half-band outputs per lane of the call's k_front_mid instantiation, Call::mid_nl)
+inline int route_tile(FrontRoute r, int mid_nl) { return r == FrontRoute::Mid ? front_mid_tile(mid_nl) : route_info(r).tile; }
+// edge alignment: k_front_mid's 768-frame tiles hand their edge runs to the 512-frame tile routine -- edge runs of two tiles = three
+// of its tiles, the streaming part starts and ends at an even tile
+inline int route_align(FrontRoute r, int mid_nl) { return (r == FrontRoute::Mid && mid_nl == 6) ? 2 : 1; }
+inline int route_edge_tpw(FrontRoute r, int mid_nl) { return r == FrontRoute::P0 ? front_p0_edge_tpw() : route_align(r, mid_nl); }
+// waves per CU its launch is sized for (a: the plan's shape fields; the cascades need casc_wave_lds).  0: no wave plan of its own
+inline int route_waves(FrontRoute r, const FrontArgs &a)
+{
+    switch (r) {
+    case FrontRoute::S1: case FrontRoute::S1S0: case FrontRoute::P0Fft: return front_s1_waves(a);
+    case FrontRoute::Fat: return front_fat_waves();
+    case FrontRoute::Mid: return front_mid_waves();
+    case FrontRoute::P0: return front_p0_waves();
+    case FrontRoute::Cascade: case FrontRoute::Cascade2: return cascade_waves(a);
+    case FrontRoute::S2: return front_s2_waves();
+    case FrontRoute::Generic: case FrontRoute::GenericLate: break;
+    }
+    return 0;
+}
 // Seamless sharding of digital-AGC chains (ABI v8, seek.cpp).  Other than Ordinary: a call runs the chain's ordinary UNFUSED route
 // -- its last stage leaves cf32 in abuf -- and the AGC itself stays out: no scan, no apply, no pack, the AGC state and its host
 // mirrors untouched, nothing written to the caller's output.  Measure: k_agc_measure then writes one row per chunk into agc_rows
@@ -428,14 +476,10 @@ struct Call {
     bool filt; size_t L1; uint64_t fpending0;
     void *fin_out; int fin_fmt;              // where the LAST stage writes (d_out, or the AGC's cf32 buffer)
     int64_t total_tiles; int tpb, n_blocks;  // geometry of the workgroup-tiled k_front
-    bool casc, fast_s0, fast_s1;             // which front path runs
-    bool fat = false;                        // fast_s1 as k_front_fat (front_fat.hip): 8 waves per CU, 1024-frame tiles
-    bool mid = false;                        // ... or as k_front_mid (front_mid.hip): 12 waves per CU, 768-frame tiles
-    bool p0 = false;                         // fast_s0 as k_front_p0 (front_p0.hip): output-major steps, taps kept in registers
-    bool fusef = false;                      // ... or, with a post-resample filter behind it, resampler AND filter as k_p0fft16 (no front launch at all)
-    bool s2 = false;                         // casc with both stages fused into k_front_s2 (front_s2.hip); cplan is then the LAST stage's plan
-    int64_t s2_in_tiles = 0;                 //   ... and this the number of 512-frame input tiles of the call
-    int wtile, casc_K, rem_k;
+    FrontRoute route;                        // which front path runs (choose_route)
+    int mid_nl = 0;                          // Mid: half-band outputs per lane of its instantiation (6, or 8: its tile is 128 of them)
+    int64_t s2_in_tiles = 0;                 // S2 (cplan is then the LAST stage's plan): the number of 512-frame input tiles of the call
+    int wtile, casc_K, rem_k;                // input frames per tile of the plan; stages in front of the last one; open group as the first kernel sees it
     float iq_mag = 0.0f, iq_phase = 0.0f;    // the correction factors this call applies (snapshot under aux_mu)
     bool agc_fused = false;                  // this call: gain applied in the front kernel -- or, with a filter behind it, in the filter's epilogue -- and verified behind it (AgcMode::MeasureS1: that front kernel, no verdict)
     bool front_fused() const { return agc_fused && !filt; }
@@ -486,7 +530,20 @@ struct Call {
         return clean_agc_peaks();
     }
 
-    void plan_geometry();
+    // the run descriptors of k_front_mid (FrontArgs::w_steal): run stealing (rounds > 0), or one round of workgroups over more
+    // fixed-length runs than resident waves (run_stride > 0)
+    void wire_run_descriptors(FrontArgs &a, int rounds, int64_t run_stride) const
+    {
+        a.w_steal = (unsigned long long *)c->steal_buf.p; a.w_steal_min = c->sw.steal_min;
+        a.w_steal_stride = c->sw.steal_stride; a.w_steal_lanes = c->sw.steal_lanes; a.w_steal_rounds = rounds;
+        a.w_run_stride = run_stride;
+    }
+
+    void plan_geometry();                    // plan.cpp: k_front's blocks, then choose_route and plan_route
+    bool choose_route();                     // sets route; true: the choice needed the route's plan, which stands in cplan
+    void plan_route();                       // cplan, wtile (and S2: rem_k, s2_in_tiles) of the route
+    void plan_s1(FrontArgs &a, int tile, int warm_tiles = 0) const;   // THE k_front_s1 geometry of a.rem0 + a.frames_in frames
+    int front_cascade(FrontArgs &a);         // stage_front of the routes with k_cascade's stages in front
     DcGeom dc_geom() const;
     AgcGeom agc_geom() const;
     int stage_dc_carries();

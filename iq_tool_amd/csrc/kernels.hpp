@@ -116,7 +116,8 @@ inline int64_t first_k(uint64_t phi0, uint32_t step, int64_t pos)
     const uint64_t target = (uint64_t)pos << 24;
     return (int64_t)(target > phi0 ? (target - phi0 + (uint64_t)step - 1) / (uint64_t)step : 0);
 }
-// the five-slot step classes (floor(3 s), floor(4 s)) of 1.6 <= s < 2 that k_front_fat, k_front_mid<8> and k_front_p0 are compiled for
+// the five-slot step classes (floor(3 s), floor(4 s)) of 1.6 <= s < 2: which kernels are compiled per class is stated by each family's
+// *_compiled() predicate, and which routes a call can take through them by FrontRoute (chain.hpp)
 constexpr bool step_class_hi(int l3, int l4) { return (l3 == 4 && l4 == 6) || (l3 == 5 && l4 == 6) || (l3 == 5 && l4 == 7); }
 
 struct cf2 { float x, y; };

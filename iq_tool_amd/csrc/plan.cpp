@@ -232,121 +232,169 @@ void Call::plan_geometry()
     n_blocks = (int)((total_tiles + tpb - 1) / tpb);
     if (n_blocks < 1) n_blocks = 1;
 
-    // run geometry of the wave-autonomous kernels (needed by the dc carries as well)
-    //   S >= 2: k_cascade (stages 0 .. S-2) + k_front_s1 (last stage);  S == 1: k_front_s1;  S == 0: its S0 variant
-    casc = c->cascade && !c->sw.force_generic;
-    fast_s0 = c->decim && c->S == 0 && !c->sw.force_generic;          // polyphase only, 256-frame tiles
-    fast_s1 = fast_s0 || (c->decim && c->S == 1 && c->rp.stages[0].m == 10 && !c->sw.force_generic);
-    wtile = fast_s0 ? 256 : kWTile;
-    casc_K = c->S - 1;
-    rem_k = casc ? (c->rem & ((1 << casc_K) - 1)) : c->rem;
+    // the route, then the run geometry of a wave-autonomous one (needed by the dc carries as well)
     cplan = FrontArgs{};
     cplan.dbg = c->sw.dbg;
-    if (casc || fast_s1) {
-        cplan.frames_in = (int64_t)frames_in; cplan.rem0 = rem_k; cplan.hist_cap = c->hist_cap;
-        cplan.in_fmt = c->desc.in_format; cplan.out_fmt = (casc || filt) ? (int)IQGPU_FMT_CF32 : fin_fmt;
-        cplan.raw_aligned = raw_aligned();
-        cplan.agc_fused = front_fused() ? 1 : 0; cplan.agc_shift = c->S; cplan.agc_chunk_frames = c->agc_chunk;
-        cplan.S = c->S; cplan.gain = c->desc.gain; cplan.iq_enable = c->desc.iq_correct_enable ? 1 : 0;
-        cplan.dc_enable = c->dc ? 1 : 0; cplan.nco_mode = c->nco_mode;
-        if (casc) {
-            cplan.casc_K = casc_K;
-            for (int k = 0; k < casc_K; ++k) cplan.m[k] = c->rp.stages[(size_t)k].m;
-            cplan.casc_wave_lds = (int)cascade_wave_lds(cplan);      // (reads the pointwise switches above: cascade2_shape)
+    if (!choose_route()) plan_route();
+}
+
+// THE k_front_s1 / k_front_s1<S0> geometry of a.rem0 + a.frames_in frames: tiles of 512 frames (256 without a half-band stage), one run
+// per wave slot of the instantiation `a` selects or the fixed runs of block_samples, the warm-up the chain's history needs
+// (warm_tiles != 0: the last stage behind k_cascade, whose history is one tile of the intermediate stream).  The first plan of a
+// call, the plan a demoted k_front_mid falls back on and the fused-AGC fallback behind k_front_fat / _mid / _p0 are this function:
+// the fallback's bytes are the first plan's because there is no second copy to drift
+void Call::plan_s1(FrontArgs &a, int tile, int warm_tiles) const
+{
+    a.w_total_tiles = ((int64_t)a.rem0 + a.frames_in + tile - 1) / tile;
+    int warm = warm_tiles ? warm_tiles : (int)((c->rp.history_in + tile - 1) / tile);
+    if (warm < 1) warm = 1;
+    plan_front_s1(a, wave_slots(front_s1_waves(a)), fixed_tpw(), warm, 1, tile);
+}
+
+// Which route the call takes (FrontRoute, chain.hpp): the predicates in the order that decides, each family's shape
+// test from its own *_select().  Where a choice depends on the candidate's plan -- k_front_mid's edge runs, k_front_p0's streaming
+// steps, k_cascade2's run length -- that plan is made here, once, and stands when the route does (returns true: cplan is planned).
+bool Call::choose_route()
+{
+    const bool forced = (c->sw.dbg & kDbgForceFat) != 0;
+    const bool casc = c->cascade && !c->sw.force_generic;
+    const bool s0 = c->decim && c->S == 0 && !c->sw.force_generic;                                  // polyphase only
+    const bool s1 = c->decim && c->S == 1 && c->rp.stages[0].m == 10 && !c->sw.force_generic;     // one half-band stage
+    casc_K = c->S - 1;
+    rem_k = casc ? (c->rem & ((1 << casc_K) - 1)) : c->rem;
+    wtile = s0 ? 256 : kWTile;
+    route = c->late ? FrontRoute::GenericLate : FrontRoute::Generic;
+    if (!casc && !s0 && !s1) return true;                  // (the workgroup-tiled kernel: no wave plan)
+
+    // the call and the chain's shape as the *_select() functions read them
+    cplan.frames_in = (int64_t)frames_in; cplan.rem0 = rem_k; cplan.hist_cap = c->hist_cap;
+    cplan.in_fmt = c->desc.in_format; cplan.out_fmt = (filt || casc) ? (int)IQGPU_FMT_CF32 : fin_fmt;
+    cplan.raw_aligned = raw_aligned();
+    cplan.agc_fused = front_fused() ? 1 : 0; cplan.agc_shift = c->S; cplan.agc_chunk_frames = c->agc_chunk;
+    cplan.S = c->S; cplan.gain = c->desc.gain; cplan.iq_enable = c->desc.iq_correct_enable ? 1 : 0;
+    cplan.dc_enable = c->dc ? 1 : 0; cplan.nco_mode = c->nco_mode;
+    if (casc) {
+        cplan.casc_K = casc_K;
+        for (int k = 0; k < casc_K; ++k) cplan.m[k] = c->rp.stages[(size_t)k].m;
+    }
+    cplan.pnco_mode = (!filt && !c->late) ? c->pnco_mode : 0;
+    cplan.step = c->rp.step;
+    const bool s1_only = o.agc == AgcMode::MeasureS1;      // (the measure pass on k_front_s1<.., AGC>, chain.hpp)
+
+    if (casc) {
+        // S == 2: both stages in ONE kernel (k_front_s2, front_s2.hip).  Its streaming waves read the input as whole 16-byte words
+        // from the start of a decimation group; calls that do not start on one, or are shorter than the histories they have to
+        // leave behind, keep the two kernels (same bytes either way).
+        if (casc_K == 1 && c->rem == 0 && cplan.raw_aligned && !front_fused() && !(c->sw.dbg & kDbgNoS2) && front_s2_shape(cplan) &&
+            (int64_t)frames_in >= (int64_t)c->hist_cap && ((int64_t)frames_in >> 1) >= (int64_t)c->hist2_cap) {
+            route = FrontRoute::S2;
+            return false;
         }
-        cplan.pnco_mode = (!filt && !c->late) ? c->pnco_mode : 0;
-        cplan.step = c->rp.step;
+        cplan.casc_wave_lds = (int)cascade_wave_lds(cplan);      // (reads the pointwise switches above: cascade2_shape)
+        route = FrontRoute::Cascade;
+        if (!cascade2_shape(cplan)) return false;
+        // a raw cascade: k_cascade2's two-tile trips where the call's runs are long enough for them -- the evaluation of
+        // cascade2_applies that decides (launch_cascade's own test is the same function of the same plan: DESIGN.md 3.0b)
+        route = FrontRoute::Cascade2;
+        plan_route();
+        if (cascade2_applies(cplan, c->sw.casc2_min_run)) return true;
+        // (too short for two-tile trips: k_cascade's own slice -- more waves per CU -- and no lead)
+        cplan.casc_wave_lds = (int)cascade_wave_lds(cplan, false);
+        route = FrontRoute::Cascade;
+        plan_route();
+        // (two stages on 8-bit frames: k_cascade's own slice holds k_cascade2's layout too, and without the lead a run can be a tile
+        //  longer, so launch_cascade's test can pass on THIS plan: the route says what it will launch.  Every other shape fails it
+        //  by the slice)
+        if (cplan.casc_wave_lds >= cascade2_wave_lds(casc_K, cplan.in_fmt) && cascade2_applies(cplan, c->sw.casc2_min_run)) route = FrontRoute::Cascade2;
+        return true;
+    }
+    if (s1) {
         // the preset shape on a call long enough to give every one of the 8 x CUs fat waves a run of tiles: k_front_fat
         // (shorter calls keep k_front_s1's 16 x CUs waves of 512-frame tiles: what counts for them is latency; same bytes either way)
-        const bool s1_only = o.agc == AgcMode::MeasureS1;      // (the measure pass on k_front_s1<.., AGC>, chain.hpp)
-        const bool fat_ok = !s1_only && !casc && !fast_s0 && front_fat_shape(cplan) &&
-              ((c->sw.dbg & kDbgForceFat) || (int64_t)frames_in >= (int64_t)kFatMinTilesPerWave * kFatTile * wave_slots(front_fat_waves()));
-        const int mid_nl = (!casc && !fast_s0) ? front_mid_nl(cplan) : 0;
+        const bool fat_ok = !s1_only && front_fat_shape(cplan) &&
+              (forced || (int64_t)frames_in >= (int64_t)kFatMinTilesPerWave * kFatTile * wave_slots(front_fat_waves()));
+        const int nl = front_mid_nl(cplan);
         // (run descriptors hold tile indices in 32 bits)
         // (k_front_mid from 6 tiles per wave on: measured round 4 at 2^21 .. 2^25 frames, kernel ms k_front_s1 / k_front_mid:
         //  0.014 / 0.023, 0.017 / 0.023, 0.023 / 0.028, 0.039 / 0.036, 0.067 / 0.055 -- the crossover lies between 2^23 and 2^24 frames
         //  = 3.6 and 7.1 tiles per wave; the pipelined host path's 2^24-frame batches now run the headline kernel)
         constexpr int kMidMinTilesPerWave = 6;
-        const bool mid_ok = !s1_only && mid_nl != 0 && (int64_t)frames_in < ((int64_t)1 << 40) &&
-              ((c->sw.dbg & kDbgForceFat)
-                  || (int64_t)frames_in >= (int64_t)kMidMinTilesPerWave * front_mid_tile(mid_nl) * wave_slots(front_mid_waves()));
+        const bool mid_ok = !s1_only && nl != 0 && (int64_t)frames_in < ((int64_t)1 << 40) &&
+              (forced || (int64_t)frames_in >= (int64_t)kMidMinTilesPerWave * front_mid_tile(nl) * wave_slots(front_mid_waves()));
         // (measured on one box, 2^28 frames: k_front_s1 0.437 ms, k_front_fat 0.404, k_front_mid 0.381: the 12-wave kernel is the
         //  default; iqgpu_debug_set("fat", "1") selects the 8-wave one where its step class applies)
-        fat = fat_ok && ((c->sw.dbg & kDbgUseFat) || !mid_ok);
-        mid = mid_ok && !fat;
-        if (fat) wtile = kFatTile;
-        if (mid) wtile = front_mid_tile(mid_nl);
-        const int mid_align = (mid && mid_nl == 6) ? 2 : 1;      // 768-frame tiles: edge runs of two = three 512-frame tiles
-        cplan.w_total_tiles = ((int64_t)rem_k + (int64_t)frames_in + wtile - 1) / wtile;
-        int warm = casc ? c->casc_warm : (int)((c->rp.history_in + wtile - 1) / wtile);
-        if (warm < 1) warm = 1;
-        int ftpw = fixed_tpw();
-        if (ftpw > 1 && (fat || mid)) { ftpw = ftpw * kWTile / wtile; if (ftpw < 1) ftpw = 1; }
-        plan_front_s1(cplan, wave_slots(casc ? cascade_waves(cplan) : fat ? front_fat_waves() : mid ? front_mid_waves()
-            : front_s1_waves(cplan)),
-                      ftpw, warm, mid_align, wtile, mid_align,
-                      // (k_cascade2: a streaming run of an odd number of tiles starts one tile early -- that tile has to be loadable)
-                      mid ? kMidLead : (casc && cascade2_shape(cplan)) ? kWTile : 0);
-        // (a raw cascade whose call turns out too short for k_cascade2's two-tile trips: k_cascade's own slice -- more waves per CU -- and
-        //  no lead)
-        if (casc && cascade2_shape(cplan) && !cascade2_applies(cplan, c->sw.casc2_min_run)) {
-            cplan.casc_wave_lds = (int)cascade_wave_lds(cplan, false);
-            plan_front_s1(cplan, wave_slots(cascade_waves(cplan)), ftpw, warm, mid_align, wtile, mid_align, 0);
-        }
-        // k_front_mid: the three waves of a SIMD get runs in proportion to the speed their age buys them (kernels.hpp, weight_runs)
-        if (mid && ftpw == 0 && cplan.w_n_edge <= front_mid_max_edge_waves() && c->sw.run_wt[0] > 0) weight_runs(cplan, front_mid_waves(),
-            c->sw.run_wt);
-        if (mid && cplan.w_n_edge > front_mid_max_edge_waves()) {
+        route = FrontRoute::S1;
+        if (fat_ok && ((c->sw.dbg & kDbgUseFat) || !mid_ok)) route = FrontRoute::Fat;
+        else if (mid_ok) {
+            route = FrontRoute::Mid; mid_nl = nl;
+            plan_route();
+            if (cplan.w_n_edge <= front_mid_max_edge_waves()) return true;
             // (an unaligned buffer, a call that is all edges: k_front_mid keeps LDS for a handful of edge waves only)
-            mid = false; wtile = kWTile;
-            cplan.w_total_tiles = ((int64_t)rem_k + (int64_t)frames_in + wtile - 1) / wtile;
-            warm = (int)((c->rp.history_in + wtile - 1) / wtile); if (warm < 1) warm = 1;
-            plan_front_s1(cplan, wave_slots(front_s1_waves(cplan)), fixed_tpw(), warm, 1, wtile);
+            route = FrontRoute::S1; mid_nl = 0;
         }
-        // S == 0 (the cu8-nrsc5 presets): k_front_p0 on calls long enough to give every one of its 8 x CUs waves a few steps of 320
-        // outputs (shorter calls keep k_front_s1<S0>: same bytes).  Planned as k_front_s1's 256-frame tiles -- the edge runs are its
-        // run_tiles -- with the streaming tiles' OUTPUTS dealt out as steps
-        p0 = false;
-        if (fast_s0 && !casc && !s1_only && !(c->sw.dbg & kDbgNoP0)) {
-            cplan.phi0 = c->phi;
-            if (front_p0_shape(cplan) && ((int64_t)frames_in >= ((int64_t)1 << 22) || (c->sw.dbg & kDbgForceFat))) {
-                FrontArgs q = cplan;
-                plan_front_s1(q, wave_slots(front_p0_waves()), 0, warm, front_p0_edge_tpw(), 256);
-                if (q.w_n_edge <= front_p0_max_edge_waves() && q.w_edge_tb > q.w_edge_ta) {
-                    plan_front_p0(q, wave_slots(front_p0_waves()));
-                    if (q.w_n_stream > 0) { cplan = q; p0 = true; }
-                }
-            }
+        return false;
+    }
+    // S == 0 (the cu8-nrsc5 presets): k_front_p0 on calls long enough to give every one of its 8 x CUs waves a few steps of 320
+    // outputs (shorter calls keep k_front_s1<S0>: same bytes).  Planned as k_front_s1's 256-frame tiles -- the edge runs are its
+    // run_tiles -- with the streaming tiles' OUTPUTS dealt out as steps: it stands when its edge runs fit and it has steps to deal
+    route = FrontRoute::S1S0;
+    const bool long_call = (int64_t)frames_in >= ((int64_t)1 << 22) || forced;
+    bool planned = false;
+    if (!s1_only && !(c->sw.dbg & kDbgNoP0)) {
+        cplan.phi0 = c->phi;
+        if (front_p0_shape(cplan) && long_call) {
+            const FrontArgs unplanned = cplan;
+            route = FrontRoute::P0;
+            plan_route();
+            planned = cplan.w_n_stream > 0;
+            if (!planned) { cplan = unplanned; route = FrontRoute::S1S0; }
         }
-        // ... and with a user filter behind the resampler on the overlap-save path: resampler AND filter in one kernel (k_p0fft16,
-        // fftconv.hip, round 6) -- no front launch, no cf32 stream in HBM.  Long calls only (as k_front_p0); the next call's filter
-        // front (history + pending samples) is recomputed by one workgroup, so it has to be short
-        fusef = false;
-        if (c->fuse_filter && filt && fast_s0 && !casc && p.n_emit > 0 && (int64_t)(L1 + p.fpending_next) <= kP0FftMaxKeep &&
-            ((int64_t)frames_in >= ((int64_t)1 << 22) || (c->sw.dbg & kDbgForceFat))) {
-            fusef = true; p0 = false;
-        }
-        // S == 2: both stages in ONE kernel (k_front_s2, front_s2.hip), planned in tiles of the LAST stage -- 512 intermediate samples
-        // = 1024 input frames -- on the intermediate stream's own geometry.  Its streaming waves read the input as whole 16-byte
-        // words from the start of a decimation group; calls that do not start on one, or are shorter than the histories they have
-        // to leave behind, keep the two kernels (same bytes either way).
-        s2 = false;
-        const int64_t n_mid = (int64_t)frames_in >> 1;
-        if (casc && casc_K == 1 && c->rem == 0 && cplan.raw_aligned && !front_fused() && !(c->sw.dbg & kDbgNoS2) && front_s2_shape(cplan) &&
-            (int64_t)frames_in >= (int64_t)c->hist_cap && n_mid >= (int64_t)c->hist2_cap) {
-            FrontArgs p2{};
-            p2.frames_in = n_mid; p2.rem0 = 0; p2.hist_cap = c->hist2_cap; p2.in_fmt = IQGPU_FMT_CF32; p2.out_fmt = filt ? (int)IQGPU_FMT_CF32 : fin_fmt;
-            p2.raw_aligned = 1;
-            p2.w_total_tiles = (n_mid + kWTile - 1) / kWTile;
-            plan_front_s1(p2, wave_slots(front_s2_waves()), fixed_tpw(), 1, 1);
-            s2 = true;
-            const FrontArgs keep = cplan;
-            cplan = p2;                                    // the run geometry everything else reads (dc carries included)
-            cplan.casc_K = keep.casc_K; cplan.m[0] = keep.m[0]; cplan.dbg = keep.dbg;
-            s2_in_tiles = ((int64_t)frames_in + kWTile - 1) / kWTile;
-            wtile = 2 * kWTile;                            // input frames per tile of the plan
-            rem_k = 0;
-        }
+    }
+    // ... and with a user filter behind the resampler on the overlap-save path: resampler AND filter in one kernel (k_p0fft16,
+    // fftconv.hip, round 6) -- no front launch, no cf32 stream in HBM.  Long calls only (as k_front_p0); the next call's filter
+    // front (history + pending samples) is recomputed by one workgroup, so it has to be short.  (Overrules k_front_p0 and keeps
+    // the plan the call has by then -- k_front_p0's where that stood: of a route without a front launch only the run starts are read)
+    if (c->fuse_filter && filt && p.n_emit > 0 && (int64_t)(L1 + p.fpending_next) <= kP0FftMaxKeep && long_call) route = FrontRoute::P0Fft;
+    return planned;
+}
+
+// cplan and wtile of the route (S2: rem_k and s2_in_tiles too) from the shape fields choose_route has left in cplan
+void Call::plan_route()
+{
+    wtile = route_tile(route, mid_nl);
+    switch (route) {
+    case FrontRoute::Generic: case FrontRoute::GenericLate: return;
+    case FrontRoute::S1: case FrontRoute::S1S0: case FrontRoute::P0Fft: plan_s1(cplan, wtile); return;
+    case FrontRoute::S2: {
+        // planned in tiles of the LAST stage -- 512 intermediate samples = 1024 input frames -- on the intermediate stream's own
+        // geometry: the run geometry everything else reads (dc carries included)
+        cplan = FrontArgs{};
+        cplan.dbg = c->sw.dbg; cplan.casc_K = casc_K; cplan.m[0] = c->rp.stages[0].m;
+        cplan.frames_in = (int64_t)frames_in >> 1; cplan.rem0 = 0; cplan.hist_cap = c->hist2_cap;
+        cplan.in_fmt = IQGPU_FMT_CF32; cplan.out_fmt = filt ? (int)IQGPU_FMT_CF32 : fin_fmt; cplan.raw_aligned = 1;
+        cplan.w_total_tiles = (cplan.frames_in + kWTile - 1) / kWTile;
+        plan_front_s1(cplan, wave_slots(route_waves(route, cplan)), fixed_tpw(), 1, 1);
+        s2_in_tiles = ((int64_t)frames_in + kWTile - 1) / kWTile;
+        rem_k = 0;
+        return;
+    }
+    case FrontRoute::Fat: case FrontRoute::Mid: case FrontRoute::P0: case FrontRoute::Cascade: case FrontRoute::Cascade2: break;
+    }
+    const RouteInfo &ri = route_info(route);
+    cplan.w_total_tiles = ((int64_t)rem_k + (int64_t)frames_in + wtile - 1) / wtile;
+    int warm = ri.casc ? c->casc_warm : (int)((c->rp.history_in + wtile - 1) / wtile);
+    if (warm < 1) warm = 1;
+    // (block_samples counts k_front_s1's tiles; k_front_p0 deals its steps out itself)
+    int ftpw = route == FrontRoute::P0 ? 0 : fixed_tpw();
+    if (ftpw > 1) { ftpw = ftpw * kWTile / wtile; if (ftpw < 1) ftpw = 1; }
+    plan_front_s1(cplan, wave_slots(route_waves(route, cplan)), ftpw, warm, route_edge_tpw(route, mid_nl), wtile, route_align(route, mid_nl), ri.lead);
+    // k_front_mid: the three waves of a SIMD get runs in proportion to the speed their age buys them (kernels.hpp, weight_runs)
+    if (route == FrontRoute::Mid && ftpw == 0 && cplan.w_n_edge <= front_mid_max_edge_waves() && c->sw.run_wt[0] > 0)
+        weight_runs(cplan, front_mid_waves(), c->sw.run_wt);
+    // k_front_p0: the streaming tiles' outputs as steps, where the edge runs fit its LDS and there are streaming tiles at all
+    if (route == FrontRoute::P0) {
+        if (cplan.w_n_edge <= front_p0_max_edge_waves() && cplan.w_edge_tb > cplan.w_edge_ta) plan_front_p0(cplan, wave_slots(front_p0_waves()));
+        else cplan.w_n_stream = 0;
     }
 }
 
@@ -355,7 +403,7 @@ DcGeom Call::dc_geom() const
 {
     DcGeom dg{};
     dg.frames_in = (int64_t)frames_in;
-    if (casc || fast_s1) {
+    if (route_info(route).wave) {
         dg.mode = 1;
         dg.n_edge1 = cplan.w_n_edge1; dg.n_stream = cplan.w_n_stream;
         dg.edge_tpw = cplan.w_edge_tpw; dg.run_q = cplan.w_run_q; dg.run_r = cplan.w_run_r; dg.ta = cplan.w_edge_ta; dg.tb
@@ -370,3 +418,4 @@ DcGeom Call::dc_geom() const
     }
     return dg;
 }
+

@@ -1,5 +1,5 @@
 // process.cpp -- one process() call: every buffer sized first, then the stages in stream order
-//   [dc carries] -> front (k_front | k_front_s1 | k_front_mid | k_cascade + k_front_s1) -> [filter] -> [k_interp] -> [agc]
+//   [dc carries] -> front (one FrontRoute, chain.hpp) -> [filter] -> [k_interp] -> [agc]
 #include "chain.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -48,7 +48,7 @@ int Call::prepare_buffers()
 {
     if (filt) {
         // (k_p0fft16 computes the resampler's outputs inside the filter kernel: only the buffer front exists)
-        const size_t need = (L1 + (size_t)c->fpending + (fusef ? 0 : (size_t)p.n_res) + 1) * sizeof(cf2);
+        const size_t need = (L1 + (size_t)c->fpending + (route == FrontRoute::P0Fft ? 0 : (size_t)p.n_res) + 1) * sizeof(cf2);
         int rc = c->fbuf[c->fcur].ensure_keep(need, (L1 + (size_t)c->fpending) * sizeof(cf2), c->stream);
         if (rc) return rc;
         fcur = (cf2 *)c->fbuf[c->fcur].p;
@@ -69,13 +69,13 @@ int Call::prepare_buffers()
         int rc = c->dc_agg.ensure((size_t)dg.n_seg * sizeof(cf2)); if (rc) return rc;
         rc = c->dc_carry.ensure((size_t)dg.n_seg * sizeof(cd2)); if (rc) return rc;
     }
-    if (casc) {
+    if (route_info(route).casc) {
         // the intermediate stream between k_cascade and the last stage -- or, with both in k_front_s2, a few KB per edge wave
-        const int64_t n_mid = s2 ? front_s2_mid_samples(cplan) : ((int64_t)rem_k + (int64_t)frames_in) >> casc_K;
+        const int64_t n_mid = route == FrontRoute::S2 ? front_s2_mid_samples(cplan) : ((int64_t)rem_k + (int64_t)frames_in) >> casc_K;
         int rc = c->mid.ensure(((size_t)n_mid + 8) * sizeof(cf2)); if (rc) return rc;
     }
     // run descriptors of k_front_mid: a fresh array starts exhausted (all zero), a used one is left exhausted by every launch
-    if (mid && (c->sw.steal || fixed_tpw() != 0)) {
+    if (route == FrontRoute::Mid && (c->sw.steal || fixed_tpw() != 0)) {
         const void *was = c->steal_buf.p;
         const size_t slots = (size_t)(fixed_tpw() != 0 ? wave_slots(front_mid_waves()) + cplan.w_n_edge : cplan.w_n_edge + cplan.w_n_stream) + 64;
         int rc = c->steal_buf.ensure(slots * (size_t)c->sw.steal_stride * sizeof(unsigned long long)); if (rc) return rc;
@@ -101,16 +101,65 @@ int Call::prepare_buffers()
     return IQGPU_OK;
 }
 
+// the routes with k_cascade's stages in front (a: the launch arguments every route shares): stages 0 .. S-2 raw -> mid, then the
+// last stage + polyphase as a one-stage chain on the intermediate stream -- or both in k_front_s2
+int Call::front_cascade(FrontArgs &a)
+{
+    const bool s2 = route == FrontRoute::S2;
+    // ---- stages 0 .. S-2: raw -> mid (cf32 at rate / 2^K) ----
+    const int K = casc_K;
+    const int rem_1 = c->rem >> K;
+    const int64_t n_mid = ((int64_t)rem_k + (int64_t)frames_in) >> K;
+    FrontArgs a1 = a;
+    a1.rem0 = rem_k;
+    a1.nco_theta0 = c->nco_theta - (uint32_t)rem_k * c->nco_dtheta;
+    a1.casc_K = K;
+    for (int k = 0; k < K; ++k) {
+        const std::vector<float> &br = c->rp.stages[(size_t)k].branch;
+        for (size_t q = 0; q < 12; ++q) a1.casc_taps[k][q] = q < br.size() ? 0.5f * br[q] : 0.0f;
+    }
+    a1.casc_out = (cf2 *)c->mid.p; a1.casc_n_out = n_mid;
+    a1.casc_wave_lds = s2 ? (int)cascade_wave_lds(a1) : cplan.casc_wave_lds;      // (the plan's: sized for k_cascade2 where the call takes it)
+    a1.out_fmt = IQGPU_FMT_CF32; a1.pnco_mode = 0;
+    if (s2) a1.w_total_tiles = s2_in_tiles;          // (the fused kernel is planned in the last stage's tiles: cplan is a2's)
+    else {
+        copy_plan(a1);
+        // (k_cascade2 where launch_cascade's own test says so: the plan's test on the same plan -- the route says which)
+        KernelTimer kt(c, IQGPU_K_CASCADE); HIP_TRY(launch_cascade(a1, c->sw.casc2_min_run, c->stream));
+    }
+    if (n_mid <= 0) return IQGPU_OK;
+    // ---- last stage + polyphase: a one-stage chain on the intermediate stream ----
+    FrontArgs a2{};
+    a2.dbg = c->sw.dbg;
+    a2.raw = c->mid.p; a2.hist_in = c->d_hist2[c->hist2_cur]; a2.hist_out = c->d_hist2[c->hist2_cur ^ 1];
+    a2.frames_in = n_mid; a2.hist_cap = c->hist2_cap; a2.rem0 = rem_1;
+    a2.in_fmt = IQGPU_FMT_CF32; a2.gain = 1.0f; a2.raw_aligned = 1;
+    a2.nco_tab = c->d_nco_tab;
+    a2.mode = 1; a2.S = 1; a2.m[0] = c->rp.stages[(size_t)K].m;
+    a2.arb_table = c->d_arb; a2.step = c->rp.step; a2.phi0 = c->phi;
+    a2.n_groups = p.n_groups; a2.n_out = p.n_res;
+    a2.pnco_mode = a.pnco_mode; a2.pnco_theta0 = a.pnco_theta0; a2.pnco_dtheta = a.pnco_dtheta;
+    a2.out_fmt = a.out_fmt; a2.out = a.out;
+    a2.agc_fused = front_fused() ? 1 : 0;
+    if (s2) copy_plan(a2);
+    else plan_s1(a2, kWTile, 1);                     // (one warm-up tile: the last stage keeps 66 samples of history)
+    for (int q = 0; q < 20; ++q) a2.hb0[q] = 0.5f * c->rp.stages[(size_t)K].branch[(size_t)q];
+    a2.sink = c->d_sink;
+    if (front_fused()) HIP_TRY(wire_fused_agc(a2));
+    { KernelTimer kt(c, IQGPU_K_FRONT); HIP_TRY(s2 ? launch_front_s2(a1, a2, c->stream) : launch_front_s1(a2, c->stream)); }
+    if (front_fused() && !no_verdict()) { const int rc = stage_agc_verify_and_fallback(a2); if (rc) return rc; }
+    c->hist2_cur ^= 1;
+    return IQGPU_OK;
+}
+
 int Call::stage_front()
 {
-    if (fusef) {
+    const RouteInfo &ri = route_info(route);
+    if (route == FrontRoute::P0Fft) {
         // resampler and filter run as ONE kernel, launched by stage_filter (which also turns the history buffers over)
-        snprintf(c->front_kernel, sizeof(c->front_kernel), "k_p0fft16");
+        snprintf(c->front_kernel, sizeof(c->front_kernel), "%s", ri.name);
         return IQGPU_OK;
     }
-    // (the measure pass on k_front_s1<.., AGC>, a fused piece of a shadow call: the gain of a scratch state, no verdict -- only the
-    //  kernel's peak array is wanted)
-    const bool measure_s1 = no_verdict();
     FrontArgs a{};
     a.dbg = c->sw.dbg;
     a.raw = d_raw_in;
@@ -148,96 +197,64 @@ int Call::stage_front()
     else if (c->late) { a.out_fmt = IQGPU_FMT_CF32; a.out = icur + c->ihist; }
     else              { a.out_fmt = fin_fmt; a.out = fin_out; }
     a.sink = c->d_sink;
-    char mid_name[48] = "k_front_mid";
-    bool casc2 = false;
-
-    if (casc) {
-        // ---- stages 0 .. S-2: raw -> mid (cf32 at rate / 2^K) ----
-        const int K = casc_K;
-        const int rem_1 = c->rem >> K;
-        const int64_t n_mid = ((int64_t)rem_k + (int64_t)frames_in) >> K;
-        FrontArgs a1 = a;
-        a1.rem0 = rem_k;
-        a1.nco_theta0 = c->nco_theta - (uint32_t)rem_k * c->nco_dtheta;
-        a1.casc_K = K;
-        for (int k = 0; k < K; ++k) {
-            const std::vector<float> &br = c->rp.stages[(size_t)k].branch;
-            for (size_t q = 0; q < 12; ++q) a1.casc_taps[k][q] = q < br.size() ? 0.5f * br[q] : 0.0f;
-        }
-        a1.casc_out = (cf2 *)c->mid.p; a1.casc_n_out = n_mid;
-        a1.casc_wave_lds = s2 ? (int)cascade_wave_lds(a1) : cplan.casc_wave_lds;      // (the plan's: sized for k_cascade2 where the call takes it)
-        a1.out_fmt = IQGPU_FMT_CF32; a1.pnco_mode = 0;
-        if (s2) a1.w_total_tiles = s2_in_tiles;          // (the fused kernel is planned in the last stage's tiles: cplan is a2's)
-        else {
-            copy_plan(a1);
-            casc2 = cascade2_applies(a1, c->sw.casc2_min_run);   // (launch_cascade's own test: raw cu8 frames, long runs -- cascade2.hip)
-            KernelTimer kt(c, IQGPU_K_CASCADE); HIP_TRY(launch_cascade(a1, c->sw.casc2_min_run, c->stream));
-        }
-        // ---- last stage + polyphase: a one-stage chain on the intermediate stream ----
-        if (n_mid > 0) {
-            FrontArgs a2{};
-            a2.dbg = c->sw.dbg;
-            a2.raw = c->mid.p; a2.hist_in = c->d_hist2[c->hist2_cur]; a2.hist_out = c->d_hist2[c->hist2_cur ^ 1];
-            a2.frames_in = n_mid; a2.hist_cap = c->hist2_cap; a2.rem0 = rem_1;
-            a2.in_fmt = IQGPU_FMT_CF32; a2.gain = 1.0f; a2.raw_aligned = 1;
-            a2.nco_tab = c->d_nco_tab;
-            a2.mode = 1; a2.S = 1; a2.m[0] = c->rp.stages[(size_t)K].m;
-            a2.arb_table = c->d_arb; a2.step = c->rp.step; a2.phi0 = c->phi;
-            a2.n_groups = p.n_groups; a2.n_out = p.n_res;
-            a2.pnco_mode = a.pnco_mode; a2.pnco_theta0 = a.pnco_theta0; a2.pnco_dtheta = a.pnco_dtheta;
-            a2.out_fmt = a.out_fmt; a2.out = a.out;
-            a2.w_total_tiles = ((int64_t)rem_1 + n_mid + kWTile - 1) / kWTile;
-            a2.agc_fused = front_fused() ? 1 : 0;
-            if (s2) copy_plan(a2);
-            else plan_front_s1(a2, wave_slots(front_s1_waves(a2)), fixed_tpw(), 1, 1);
-            for (int q = 0; q < 20; ++q) a2.hb0[q] = 0.5f * c->rp.stages[(size_t)K].branch[(size_t)q];
-            a2.sink = c->d_sink;
-            if (front_fused()) HIP_TRY(wire_fused_agc(a2));
-            { KernelTimer kt(c, IQGPU_K_FRONT); HIP_TRY(s2 ? launch_front_s2(a1, a2, c->stream) : launch_front_s1(a2, c->stream)); }
-            if (front_fused() && !measure_s1) { const int rc = stage_agc_verify_and_fallback(a2); if (rc) return rc; }
-            c->hist2_cur ^= 1;
-        }
-    } else if (fast_s1) {
-        // wave-autonomous kernel: one half-band stage (m = 10), or none
+    // one wave-autonomous kernel on the raw input: the plan and the fused-AGC fields first (what k_front_mid's selection reads)
+    const bool one_kernel = ri.wave && !ri.casc;
+    if (one_kernel) {
         copy_plan(a);
-        if (!fast_s0) for (int q = 0; q < 20; ++q) a.hb0[q] = 0.5f * c->rp.stages[0].branch[(size_t)q];
         if (front_fused()) HIP_TRY(wire_fused_agc(a));
-        // k_front_mid, "steal" on, one run per resident wave: every wave claims its tiles through its run descriptor and waves
-        // that finish early split the runs of those that are behind (front_mid.hip; off by default, profiles/r04_steal.md)
-        if (mid && c->sw.steal && fixed_tpw() == 0 && a.w_n_stream >= 64 * (int64_t)front_mid_waves()) {
-            a.w_steal = (unsigned long long *)c->steal_buf.p; a.w_steal_min = c->sw.steal_min;
-            a.w_steal_stride = c->sw.steal_stride; a.w_steal_lanes = c->sw.steal_lanes; a.w_steal_rounds = c->sw.steal_rounds;
-        } else if (mid && front_mid_nl(a) == 6 && fixed_tpw() != 0 && a.w_n_stream > wave_slots(front_mid_waves()) - a.w_n_edge) {
-            // (the multi-run instantiation exists for six outputs per lane only: the 8-per-lane experiment, "mid8", keeps one
-            //  static run per wave over as many rounds of workgroups as the runs need -- ADVICE r4)
-            // block_samples != 0 (BASELINE configs[1] as worded: "256 k-sample blocks"): more fixed-length runs than resident waves --
-            // one round of workgroups, every streaming wave takes runs s, s + stride, ... through the multi-run instantiation
-            a.w_steal = (unsigned long long *)c->steal_buf.p; a.w_steal_min = c->sw.steal_min;
-            a.w_steal_stride = c->sw.steal_stride; a.w_steal_lanes = c->sw.steal_lanes; a.w_steal_rounds = 0;
-            a.w_run_stride = wave_slots(front_mid_waves()) - a.w_n_edge;
-        }
-        const MidSel msel = mid ? front_mid_select(a) : MidSel{};
-        a.tap_fold = (uint32_t)(fat ? c->tap_fold8 : mid ? (msel.NL == 8 ? c->tap_fold8 : c->tap_fold6) : 0);
-        a.nco_hold = (uint32_t)(mid ? (msel.NL == 8 ? c->nco_hold8 : front_mid_holds_all(msel) ? c->nco_hold6_all : c->nco_hold6) : 0);
-        // (k_front_p0: consecutive lanes are five outputs apart -- for the NRSC-5 step 16 arms -- so the lanes that re-read a slot in
-        //  the same step would meet in two bank pairs of a linear plane: always the folded placement)
-        if (p0) a.tap_fold = 1u;
-        if (mid) {
-            const bool b8 = msel.INF == IQGPU_FMT_CU8 || msel.INF == IQGPU_FMT_CS8 || msel.O8 != 0;
-            snprintf(mid_name, sizeof(mid_name), "k_front_mid<%d,%s%s%s%s>", msel.NL, msel.NONCO ? "nonco" : "nco", msel.CF ? ",cf32" : "",
-                     b8 ? ",8bit" : "", msel.INF == kMidN16 ? ",gain" : "");
-        }
-        { KernelTimer kt(c, IQGPU_K_FRONT); HIP_TRY(fat ? launch_front_fat(a, c->stream) : mid ? launch_front_mid(a, c->stream)
-            : p0 ? launch_front_p0(a, c->stream) : launch_front_s1(a, c->stream)); }
-        if (front_fused() && !measure_s1) { const int rc = stage_agc_verify_and_fallback(a); if (rc) return rc; }
-    } else {
+    }
+    const auto wire_hb0 = [&] { for (int q = 0; q < 20; ++q) a.hb0[q] = 0.5f * c->rp.stages[0].branch[(size_t)q]; };
+    char mid_name[48];
+    const char *name = ri.name;
+    hipError_t (*launch)(const FrontArgs &, hipStream_t) = nullptr;      // of a one-kernel route: wired here, launched below
+
+    switch (route) {
+    case FrontRoute::Generic: case FrontRoute::GenericLate: {
         KernelTimer kt(c, IQGPU_K_FRONT);
         HIP_TRY(launch_front(a, n_blocks, c->stream));
+        break;
+    }
+    case FrontRoute::Cascade: case FrontRoute::Cascade2: case FrontRoute::S2: {
+        const int rc = front_cascade(a); if (rc) return rc;
+        break;
+    }
+    case FrontRoute::S1: wire_hb0(); launch = launch_front_s1; break;      // one half-band stage (m = 10)
+    case FrontRoute::S1S0: launch = launch_front_s1; break;                // none
+    case FrontRoute::P0Fft: break;                                         // (no front launch: returned above)
+    case FrontRoute::Fat: wire_hb0(); a.tap_fold = (uint32_t)c->tap_fold8; launch = launch_front_fat; break;
+    // (k_front_p0: consecutive lanes are five outputs apart -- for the NRSC-5 step 16 arms -- so the lanes that re-read a slot in
+    //  the same step would meet in two bank pairs of a linear plane: always the folded placement)
+    case FrontRoute::P0: a.tap_fold = 1u; launch = launch_front_p0; break;
+    case FrontRoute::Mid: {
+        wire_hb0();
+        // "steal" on, one run per resident wave: every wave claims its tiles through its run descriptor and waves that finish
+        // early split the runs of those that are behind (front_mid.hip; off by default, profiles/r04_steal.md)
+        if (c->sw.steal && fixed_tpw() == 0 && a.w_n_stream >= 64 * (int64_t)front_mid_waves()) wire_run_descriptors(a, c->sw.steal_rounds, 0);
+        // (the multi-run instantiation exists for six outputs per lane only: the 8-per-lane experiment, "mid8", keeps one
+        //  static run per wave over as many rounds of workgroups as the runs need -- ADVICE r4)
+        // block_samples != 0 (BASELINE configs[1] as worded: "256 k-sample blocks"): more fixed-length runs than resident waves --
+        // one round of workgroups, every streaming wave takes runs s, s + stride, ... through the multi-run instantiation
+        else if (front_mid_nl(a) == 6 && fixed_tpw() != 0 && a.w_n_stream > wave_slots(front_mid_waves()) - a.w_n_edge)
+            wire_run_descriptors(a, 0, wave_slots(front_mid_waves()) - a.w_n_edge);
+        const MidSel msel = front_mid_select(a);
+        a.tap_fold = (uint32_t)(msel.NL == 8 ? c->tap_fold8 : c->tap_fold6);
+        a.nco_hold = (uint32_t)(msel.NL == 8 ? c->nco_hold8 : front_mid_holds_all(msel) ? c->nco_hold6_all : c->nco_hold6);
+        const bool b8 = msel.INF == IQGPU_FMT_CU8 || msel.INF == IQGPU_FMT_CS8 || msel.O8 != 0;
+        snprintf(mid_name, sizeof(mid_name), "%s<%d,%s%s%s%s>", ri.name, msel.NL, msel.NONCO ? "nonco" : "nco", msel.CF ? ",cf32" : "",
+                 b8 ? ",8bit" : "", msel.INF == kMidN16 ? ",gain" : "");
+        name = mid_name;
+        launch = launch_front_mid;
+        break;
+    }
+    }
+    if (launch) {
+        { KernelTimer kt(c, IQGPU_K_FRONT); HIP_TRY(launch(a, c->stream)); }
+        // (the measure pass on k_front_s1<.., AGC>, a fused piece of a shadow call: the gain of a scratch state, no verdict -- only
+        //  the kernel's peak array is wanted)
+        if (front_fused() && !no_verdict()) { const int rc = stage_agc_verify_and_fallback(a); if (rc) return rc; }
     }
     if (c->decim) c->hist_cur ^= 1;
-    snprintf(c->front_kernel, sizeof(c->front_kernel), "%s",
-             (casc && s2) ? "k_front_s2" : casc2 ? "k_cascade2+k_front_s1" : casc ? "k_cascade+k_front_s1" : fat ? "k_front_fat" : mid ? mid_name : p0 ? "k_front_p0"
-             : fast_s1 ? "k_front_s1" : c->late ? "k_front+k_interp" : "k_front");
+    snprintf(c->front_kernel, sizeof(c->front_kernel), "%s", name);
     return IQGPU_OK;
 }
 
@@ -264,7 +281,7 @@ int Call::stage_filter()
         ca.pnco_mode = fa.pnco_mode; ca.pnco_theta0 = fa.pnco_theta0; ca.pnco_dtheta = fa.pnco_dtheta; ca.nco_tab = fa.nco_tab;
         ca.out_fmt = fa.out_fmt; ca.out = fa.out;
         ca.move_dst = fa.move_dst; ca.move_src = fa.move_src; ca.move_n = fa.move_n;
-        if (fusef) {
+        if (route == FrontRoute::P0Fft) {
             // k_p0fft16: the window fill needs what the front kernel would have been given
             if (!fused_move) return fail(IQGPU_EINVAL, "internal: the fused filter path needs the history move in the kernel");
             P0Feed &f = ca.feed;
@@ -300,7 +317,7 @@ int Call::stage_filter()
     }
     c->fcur ^= 1;
     c->fpending = p.fpending_next;
-    if (fusef && c->decim) c->hist_cur ^= 1;               // (what stage_front does behind its launch)
+    if (route == FrontRoute::P0Fft && c->decim) c->hist_cur ^= 1;               // (what stage_front does behind its launch)
     return IQGPU_OK;
 }
 
