@@ -1147,6 +1147,89 @@ int    iqgpu_lag_freq(double re, double im, uint32_t lag, double sample_rate, do
 int    iqgpu_lag_estimate_rows(const float *row_lag, const float *row_sum, size_t rows, const iqgpu_lag_opts *o, uint32_t lag_index,
                                size_t first_row, size_t n_rows, double sample_rate, iqgpu_lag_estimate *out);
 
+/* ---- template correlation: the matched filter of up to eight known waveforms per block of B start positions, emitted as the stream
+ * goes by (additive, still ABI v9) ----
+ * No counterpart in the reference.  iqgpu_env finds power to within a block and not below the noise floor, iqgpu_lag finds
+ * periodicity, not position; this accumulator answers AT WHICH FRAME a waveform the caller knows starts -- a preamble, a sync word, a
+ * chirp, a pilot symbol, a PN code -- and, with a small bank of frequency-shifted copies (iqgpu_match_shift_bank), the coarse offset
+ * of a burst too short for iqgpu_lag.  One stream of frames in one sample format, independent of any chain, with iqgpu_sgram's
+ * calling convention.  There is NO gain and NO window: x = the library's unpack at gain 1, exactly as iqgpu_stats / _env / _lag.
+ * Options: nfft 1024, 2048 or 4096, 0 = the smallest of the three with nfft / 2 + 1 >= template_frames (info.nfft reports it);
+ * block_frames = B, a power of two, nfft / 2 .. 2^24; n_templates 1 .. 8; template_frames = L, 2 .. nfft / 2 + 1.
+ * Templates: n_templates * L cf32 frames in host memory, template t at templates[2 t L ..), read by iqgpu_match_create only; every
+ * value finite, every template with energy above zero.  info.template_energy[t] = sum |h_t[k]|^2 in double.
+ * Correlation: c_t[n] = sum over k < L of x[n + k] conj(h_t[k]) for start position n (a stream index since the last reset),
+ * p_t[n] = re^2 + im^2 in float.  It is computed by overlap-save: with V = nfft / 2, segment s is frames [s V, s V + nfft) -- the power
+ * spectrum's grid at hop = nfft / 2, the same count, the same carry -- and yields p_t[n] for n in [s V, (s + 1) V) as points 0 .. V - 1
+ * of IFFT(X_s G_t), X_s the float transform of the segment and G_t = conj(FFT_nfft(h_t zero-padded)) / nfft evaluated once on the host
+ * in double and rounded to float; L - 1 <= V keeps those points free of wrap-around.  START POSITIONS IN THE LAST nfft - V FRAMES OF
+ * A STREAM BELONG TO NO WHOLE SEGMENT AND ARE NOT REPORTED: a stream of F frames reports positions 0 .. segments * V - 1,
+ * segments = (F - nfft) / V + 1.  Pad the end of a capture with nfft / 2 frames of zeros to have every whole match reported.
+ * Rows: row r is start positions [r B, (r + 1) B), that is B / V consecutive segments; rows = segments / (B / V), rounded down.
+ * Per finished row, [n_templates] values each, densely packed:
+ *   row_peak[r][t] (float)   the largest p_t[n] of the row
+ *   row_at[r][t]   (uint32)  n - r B of the LOWEST n that attains it (an all-zero row: 0)
+ *   row_sum[r][t]  (float)   sum of p_t[n] over the row, summed in double in the order below, rounded ONCE to float.
+ * Summation order: it belongs to the stream, not to the calls.  Within a segment one fixed tree: thread j of nfft / 16 holds points
+ * j + i nfft / 16, i = 0 .. 7, and adds them in increasing i from 0.0; the 64 threads of a wave are combined in six levels of pairs 1, 2,
+ * 4, 8, 16 and 32 threads apart; the nfft / 1024 waves are added in wave order.  The row is ((0.0 + segment 0) + segment 1) + ... in
+ * double.  The peak follows the same walk; a value replaces the held one only where it is greater, or equal at a lower n.
+ * The open row: iqgpu_match_read_open returns sum (double, not rounded), peak and at, [n_templates] each, of the segments behind the
+ * last finished row, all 0 when info.open_segments == 0.  It observes and does not disturb.
+ * ROWS AND OPEN ROW ARE A FUNCTION OF THE PUSHED FRAMES AND THE OPTIONS ALONE, BIT FOR BIT: any split of the stream into push calls,
+ * host or device, of any lengths (one frame; no multiple of V; ending inside a row) at frame alignment only gives the same rows in
+ * the same order and the same open row.
+ * push / push_device, *rows, iqgpu_match_max_rows, cap_rows (checked when any plane is given) and IQGPU_ECAPACITY, streams, poisoning,
+ * frames == 0, one thread per handle and the error codes: iqgpu_sgram's, word for word; any plane may be NULL.  IQGPU_EINVAL also for
+ * options outside the lists above, a template value that is not finite and a template without energy.  Non-finite cf32 input
+ * propagates by IEEE rules into row_sum of the rows of its segments, as documented for the power spectrum; row_peak and row_at of
+ * those rows are unspecified; other rows are unaffected.  Behind iqgpu_chain_process_device(c, .., d_out, .., &n) the rows of the
+ * output are iqgpu_match_push_device(p, d_out, n, d_peak, d_at, d_sum, cap, &rows, iqgpu_chain_get_stream(c)).
+ * Cost: per input frame 2 (1 + n_templates) transform points where iqgpu_psd at hop = nfft / 2 spends 2 (profiles/match.md).
+ * THE BANK (host only, no device).  iqgpu_match_shift_bank: out[i][k] = tmpl[k] exp(+j 2 pi hz[i] k / sample_rate), evaluated in
+ * double and rounded to float, n members of L frames.  A burst received hz[i] off centre correlates with member i; it is centred by
+ * a chain with shift_hz = -hz[i] (the sign rule of iqgpu_lag_freq).
+ * THE DETECTIONS (host only, no device).  iqgpu_match_peaks walks rows by row, then template: (r, t) is a detection when
+ * row_peak > 0 and row_peak >= ratio * (row_sum - row_peak) / (B - 1), in double -- the peak against the mean of the row's other
+ * positions.  Each is {first_frame = r B + row_at, template_index, peak, ratio = row_peak / that mean, +inf where the mean is 0}.
+ * *n is the count found; cap smaller than that: the first cap are written and the call returns IQGPU_ECAPACITY.  A NaN row is none.
+ * Normalised correlation is the caller's: p_t[n] / (template_energy[t] * the power of x over [n, n + L)), from iqgpu_env's rows. */
+typedef struct {
+    uint32_t nfft;                /* 0, 1024, 2048 or 4096 (0: the smallest that holds the template) */
+    uint32_t block_frames;        /* B: start positions of a row, a power of two, nfft / 2 .. 2^24 (4096) */
+    uint32_t n_templates;         /* 1 .. 8 (1) */
+    uint32_t template_frames;     /* L: 2 .. nfft / 2 + 1 (0: the caller sets it) */
+} iqgpu_match_opts;
+typedef struct {
+    uint64_t frames, segments, rows;      /* pushed since the last reset; whole segments of them; rows finished = segments / (B / V) */
+    uint32_t open_segments;               /* segments of the open row = segments % (B / V) */
+    uint32_t nfft, block_frames, n_templates, template_frames, reserved;
+    double   template_energy[8];
+} iqgpu_match_info;
+typedef struct {
+    uint64_t first_frame;         /* r B + row_at: the start position of the match in the stream */
+    uint32_t template_index;
+    float    peak;
+    double   ratio;
+} iqgpu_match_peak;
+typedef struct iqgpu_match iqgpu_match;
+void   iqgpu_match_opts_init(iqgpu_match_opts *o);                  /* the defaults in parentheses above */
+/* no device: the rows a stream of `frames` frames finishes */
+int    iqgpu_match_rows(const iqgpu_match_opts *o, uint64_t frames, uint64_t *rows);
+int    iqgpu_match_create(int device, int format, const iqgpu_match_opts *o, const float *templates /* [n_templates][L][2] */, iqgpu_match **out);
+void   iqgpu_match_destroy(iqgpu_match *p);
+int    iqgpu_match_reset(iqgpu_match *p);
+size_t iqgpu_match_max_rows(const iqgpu_match *p, size_t frames);   /* rows the NEXT push of `frames` finishes: exact; 0 for a NULL handle */
+int    iqgpu_match_push(iqgpu_match *p, const void *raw, size_t frames, float *row_peak, uint32_t *row_at, float *row_sum, size_t cap_rows,
+                        size_t *rows);                              /* host memory */
+int    iqgpu_match_push_device(iqgpu_match *p, const void *d_raw, size_t frames, float *d_row_peak, uint32_t *d_row_at, float *d_row_sum,
+                               size_t cap_rows, size_t *rows, void *hip_stream);     /* device memory, asynchronous on hip_stream */
+int    iqgpu_match_read_open(iqgpu_match *p, double *sum, float *peak, uint32_t *at, iqgpu_match_info *info);   /* [n_templates] each, any may be NULL; synchronises */
+/* host only, no device */
+int    iqgpu_match_shift_bank(const float *tmpl, uint32_t template_frames, const double *hz, uint32_t n, double sample_rate, float *out);
+int    iqgpu_match_peaks(const float *row_peak, const uint32_t *row_at, const float *row_sum, size_t rows, const iqgpu_match_opts *o,
+                         double ratio, iqgpu_match_peak *out, size_t cap, size_t *n);
+
 /* ---- WAV capture metadata -> frequency shift (host only): the step in front of the path for real captures ----
  * SdrMetadata and its parsers (src/input_wav.c:54-100, 146-438), the shift rule of wav_initialize (592-629). */
 enum { IQGPU_SDR_UNKNOWN = 0, IQGPU_SDR_CONSOLE = 1, IQGPU_SDR_SHARP = 2, IQGPU_SDR_UNO = 3, IQGPU_SDR_CONNECT = 4 };

@@ -9,5 +9,6 @@ from .sgram import Sgram                                         # noqa: F401
 from .stats import Stats                                         # noqa: F401
 from .env import Env                                             # noqa: F401
 from .lag import Lag                                             # noqa: F401
+from .match import Match                                         # noqa: F401
 
-__all__ = ["Chain", "DeviceBuffer", "PinnedBuffer", "IqOptimizer", "Psd", "Sgram", "Stats", "Env", "Lag", "make_desc", "FMT", "IqgpuError", "load", "LIB_PATH"]
+__all__ = ["Chain", "DeviceBuffer", "PinnedBuffer", "IqOptimizer", "Psd", "Sgram", "Stats", "Env", "Lag", "Match", "make_desc", "FMT", "IqgpuError", "load", "LIB_PATH"]

@@ -179,6 +179,23 @@ class LagEstimate(C.Structure):
                 ("span_hz", C.c_double)]
 
 
+class MatchOpts(C.Structure):
+    """iqgpu_match_opts: the options of a template-correlation accumulator (iqgpu_match_opts_init sets the defaults)"""
+    _fields_ = [("nfft", C.c_uint32), ("block_frames", C.c_uint32), ("n_templates", C.c_uint32), ("template_frames", C.c_uint32)]
+
+
+class MatchInfo(C.Structure):
+    """iqgpu_match_info: what iqgpu_match_read_open reports beside the open row"""
+    _fields_ = [("frames", C.c_uint64), ("segments", C.c_uint64), ("rows", C.c_uint64), ("open_segments", C.c_uint32),
+                ("nfft", C.c_uint32), ("block_frames", C.c_uint32), ("n_templates", C.c_uint32), ("template_frames", C.c_uint32),
+                ("reserved", C.c_uint32), ("template_energy", C.c_double * 8)]
+
+
+class MatchPeak(C.Structure):
+    """iqgpu_match_peak: one detection iqgpu_match_peaks found"""
+    _fields_ = [("first_frame", C.c_uint64), ("template_index", C.c_uint32), ("peak", C.c_float), ("ratio", C.c_double)]
+
+
 class EnvBurstOpts(C.Structure):
     """iqgpu_env_burst_opts: the rules of iqgpu_env_bursts"""
     _fields_ = [("block_frames", C.c_uint32), ("min_rows", C.c_uint32), ("hang_rows", C.c_uint32), ("pad_rows", C.c_uint32),
@@ -343,6 +360,17 @@ SYMBOLS = [
     ("iqgpu_lag_read_open", C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(LagInfo)]),
     ("iqgpu_lag_freq", C.c_int, [C.c_double, C.c_double, C.c_uint32, C.c_double, C.POINTER(C.c_double)]),
     ("iqgpu_lag_estimate_rows", C.c_int, [_vp, _vp, _sz, C.POINTER(LagOpts), C.c_uint32, _sz, _sz, C.c_double, C.POINTER(LagEstimate)]),
+    ("iqgpu_match_opts_init", None, [C.POINTER(MatchOpts)]),
+    ("iqgpu_match_rows", C.c_int, [C.POINTER(MatchOpts), C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("iqgpu_match_create", C.c_int, [C.c_int, C.c_int, C.POINTER(MatchOpts), _vp, C.POINTER(_vp)]),
+    ("iqgpu_match_destroy", None, [_vp]),
+    ("iqgpu_match_reset", C.c_int, [_vp]),
+    ("iqgpu_match_max_rows", _sz, [_vp, _sz]),
+    ("iqgpu_match_push", C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz)]),
+    ("iqgpu_match_push_device", C.c_int, [_vp, _vp, _sz, _vp, _vp, _vp, _sz, C.POINTER(_sz), _vp]),
+    ("iqgpu_match_read_open", C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(MatchInfo)]),
+    ("iqgpu_match_shift_bank", C.c_int, [_vp, C.c_uint32, _vp, C.c_uint32, C.c_double, _vp]),
+    ("iqgpu_match_peaks", C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(MatchOpts), C.c_double, _vp, _sz, C.POINTER(_sz)]),
     ("iqgpu_wav_info_init", None, [C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_auxi", C.c_int, [_vp, _sz, C.POINTER(WavInfo)]),
     ("iqgpu_wav_parse_filename", C.c_int, [C.c_char_p, C.POINTER(WavInfo)]),

@@ -13,15 +13,15 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libiqgpu.so")
-SOURCES = ["design.cpp", "abi.cpp", "plan.cpp", "process.cpp", "seek.cpp", "state.cpp", "state_blob.cpp", "agc_host.cpp", "pipeline.cpp", "iq_optimizer.cpp", "iq_calib.cpp", "psd.cpp", "sgram.cpp", "stats.cpp", "env.cpp", "lag.cpp", "wav_meta.cpp", "topology.cpp", "kernels.hip", "front_wave.hip", "front_fat.hip", "front_mid.hip", "front_p0.hip", "front_s2.hip", "cascade_wave.hip", "cascade2.hip", "fftconv.hip", "p0fft_cu8.hip", "p0fft_cs8.hip", "p0fft_cs16.hip", "interp.hip", "agc.hip", "iq_calib.hip", "psd.hip", "sgram.hip", "stats.hip", "env.hip", "lag.hip"]
-HEADERS = ["design.hpp", "chain.hpp", "kernels.hpp", "dsp_device.hpp", "wave_common.hpp", "front_tiles.hpp", "cascade_tiles.hpp", "front_fat_common.hpp", "front_p0_common.hpp", "fft16.hpp", "p0fft.hpp", "state_blob.hpp", "iq_search.hpp", "iq_calib.hpp", "psd.hpp", "psd_stream.hpp", "sgram.hpp", "stats.hpp", "capture_load.hpp", "env.hpp", "pair_tree.hpp", "lag.hpp", "accum_core.hpp", "row_pages.hpp", os.path.join("..", "..", "include", "iqgpu.h")]
+SOURCES = ["design.cpp", "abi.cpp", "plan.cpp", "process.cpp", "seek.cpp", "state.cpp", "state_blob.cpp", "agc_host.cpp", "pipeline.cpp", "iq_optimizer.cpp", "iq_calib.cpp", "psd.cpp", "sgram.cpp", "stats.cpp", "env.cpp", "lag.cpp", "match.cpp", "wav_meta.cpp", "topology.cpp", "kernels.hip", "front_wave.hip", "front_fat.hip", "front_mid.hip", "front_p0.hip", "front_s2.hip", "cascade_wave.hip", "cascade2.hip", "fftconv.hip", "p0fft_cu8.hip", "p0fft_cs8.hip", "p0fft_cs16.hip", "interp.hip", "agc.hip", "iq_calib.hip", "psd.hip", "sgram.hip", "stats.hip", "env.hip", "lag.hip", "match.hip"]
+HEADERS = ["design.hpp", "chain.hpp", "kernels.hpp", "dsp_device.hpp", "wave_common.hpp", "front_tiles.hpp", "cascade_tiles.hpp", "front_fat_common.hpp", "front_p0_common.hpp", "fft16.hpp", "p0fft.hpp", "state_blob.hpp", "iq_search.hpp", "iq_calib.hpp", "psd.hpp", "psd_stream.hpp", "sgram.hpp", "stats.hpp", "capture_load.hpp", "env.hpp", "pair_tree.hpp", "lag.hpp", "accum_core.hpp", "row_pages.hpp", "match.hpp", os.path.join("..", "..", "include", "iqgpu.h")]
 # headers only some sources include: {header: prefixes of the sources that depend on it} (the rest depend on every header)
-PRIVATE_HEADERS = {"fft16.hpp": ("fftconv.hip", "p0fft_", "iq_calib.hip", "psd.hip", "sgram.hip"), "p0fft.hpp": ("p0fft_",), "state_blob.hpp": ("state",),
-                   "iq_search.hpp": ("iq_optimizer.cpp", "iq_calib.", "kernels.hip"), "iq_calib.hpp": ("iq_calib.", "kernels.hip"), "psd.hpp": ("psd.", "sgram."),
-                   "psd_stream.hpp": ("psd.hip", "sgram.hip"), "sgram.hpp": ("sgram.",), "stats.hpp": ("stats.", "env.", "lag."),
-                   "capture_load.hpp": ("stats.hip", "env.hip", "lag.hip"), "env.hpp": ("env.", "lag."), "pair_tree.hpp": ("env.hip", "lag.hip"),
-                   "lag.hpp": ("lag.",), "accum_core.hpp": ("psd.", "sgram.", "stats.cpp", "env.cpp", "lag.cpp"),
-                   "row_pages.hpp": ("env.cpp", "lag.cpp")}
+PRIVATE_HEADERS = {"fft16.hpp": ("fftconv.hip", "p0fft_", "iq_calib.hip", "psd.hip", "sgram.hip", "match.hip"), "p0fft.hpp": ("p0fft_",), "state_blob.hpp": ("state",),
+                   "iq_search.hpp": ("iq_optimizer.cpp", "iq_calib.", "kernels.hip"), "iq_calib.hpp": ("iq_calib.", "kernels.hip"), "psd.hpp": ("psd.", "sgram.", "match."),
+                   "psd_stream.hpp": ("psd.hip", "sgram.hip", "match.hip"), "sgram.hpp": ("sgram.",), "stats.hpp": ("stats.", "env.", "lag."),
+                   "capture_load.hpp": ("stats.hip", "env.hip", "lag.hip"), "env.hpp": ("env.", "lag."), "pair_tree.hpp": ("env.hip", "lag.hip", "match.hip"),
+                   "lag.hpp": ("lag.",), "accum_core.hpp": ("psd.", "sgram.", "match.", "stats.cpp", "env.cpp", "lag.cpp"),
+                   "row_pages.hpp": ("env.cpp", "lag.cpp"), "match.hpp": ("match.",)}
 HARNESS_SRC = os.path.join(CSRC, "harness", "iqgpu_run.c")
 HARNESS_BIN = os.path.join(LIBDIR, "iqgpu_run")
 

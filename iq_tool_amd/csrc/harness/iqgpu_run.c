@@ -91,6 +91,12 @@
  * chain's stream behind every call.  PREFIX.in.lag.f32 / PREFIX.out.lag.f32 receive row_lag of every row as it finishes (2 n_lags
  * little-endian floats a row), PREFIX.in.sum.f32 / PREFIX.out.sum.f32 its row_sum; PREFIX.json holds the options, both info records and
  * iqgpu_lag_estimate_rows over the whole input and the whole output per lag, at the run's input and output rates.
+ * --match PREFIX --match-template FILE.cf32 [--match-block B] [--match-shifts hz1,hz2,..] (the same runs as --lag, and it may stand beside the others):
+ * one iqgpu_match accumulator on the input bytes and one on the output bytes, fed on the chain's stream behind every call.  FILE.cf32 holds
+ * the template, 2 .. 2049 cf32 frames; with --match-shifts (one to eight offsets in Hz) each side correlates with the
+ * iqgpu_match_shift_bank of the template at that side's sample rate.  B start positions a row (4096), nfft the smallest that holds the
+ * template.  PREFIX.{in,out}.peak.f32 / .at.u32 / .sum.f32 receive the rows as they finish (n_templates values a row each); PREFIX.json
+ * holds the options, both info records and iqgpu_match_peaks over all rows of each side at ratio 100.
  *
  * --stats PREFIX (plain runs and --shards N with independent shards; no --seamless* mode, no --iq-calibrate): one iqgpu_stats accumulator
  * on the input bytes and one on the output bytes of every shard, fed on the chain's stream behind every call.  The shards' results are
@@ -183,6 +189,10 @@ typedef struct {
     const char *lag_prefix;           /* --lag PREFIX: row_lag and row_sum of the input and of the output, appended as the rows finish; the estimates (write_lag) */
     const char *lag_list;             /* --lag-list d1,d2,.. (NULL: the library's default); lag_opts_of reads both */
     unsigned lag_block;               /* --lag-block B (0: the library's default) */
+    const char *match_prefix;         /* --match PREFIX: row_peak, row_at and row_sum of the input and of the output, appended as the rows finish; the detections (write_match) */
+    const char *match_template;       /* --match-template FILE.cf32 */
+    const char *match_shifts;         /* --match-shifts hz1,hz2,.. (NULL: the template alone); match_shifts_of reads it */
+    unsigned match_block;             /* --match-block B (0: the library's default) */
     const char *stats_prefix;         /* --stats PREFIX: the statistics of the input and of the output bytes, merged over the shards (write_stats) */
 } Options;
 
@@ -245,6 +255,12 @@ typedef struct {
     iqgpu_lag *lg[2]; iqgpu_lag_opts lg_opts; FILE *lg_f[2][2];
     void *lg_d[2][2][NBUF], *lg_h[2][2][NBUF]; size_t lg_cap[2], lg_rows[2][NBUF];
     float *lg_all[2][2]; size_t lg_all_n[2], lg_all_cap[2];
+    /* --match, the same shape: planes 0 .. 2 = row_peak, row_at, row_sum (n_templates 4-byte values a row each); mt_all keeps them for the
+     * detections behind the run */
+    iqgpu_match *mt[2]; iqgpu_match_opts mt_opts; FILE *mt_f[2][3];
+    void *mt_d[2][3][NBUF], *mt_h[2][3][NBUF]; size_t mt_cap[2], mt_rows[2][NBUF];
+    uint32_t *mt_all[2][3]; size_t mt_all_n[2], mt_all_cap[2];
+    double mt_hz[8]; uint32_t mt_nhz;
 } Ctx;
 
 /* the modes with passes: all shard threads meet behind a measure pass and again behind the walk, which shard 0's thread does in between */
@@ -548,6 +564,42 @@ static int rendezvous(Ctx *x, int (*walk)(Ctx *), const char *what)
 }
 
 /* chain, streams, events, the NBUF buffer sets, the files */
+#define MATCH_RATIO 100.0             /* of --match's detections: the peak against the mean of the row's other positions */
+
+/* --match-shifts hz1,hz2,..: one to eight finite numbers.  0: fine (*n = 0 without the option) */
+static int match_shifts_of(const Options *o, double *hz, uint32_t *n)
+{
+    *n = 0;
+    if (!o->match_shifts) return 0;
+    const char *p = o->match_shifts;
+    for (;;) {
+        char *end;
+        const double v = strtod(p, &end);
+        if (end == p || !(v == v) || v - v != 0.0 || *n >= 8) return -1;
+        hz[(*n)++] = v;
+        if (*end == '\0') return 0;
+        if (*end != ',') return -1;
+        p = end + 1;
+    }
+}
+
+/* the template file of --match: *frames cf32 frames (2 .. 2049) in malloc'd memory, NULL with a reason in `why` */
+static float *match_template_of(const char *path, uint32_t *frames, char *why, size_t cap)
+{
+    FILE *f = fopen(path, "rb");
+    if (!f) { snprintf(why, cap, "--match-template %.160s: %s", path, strerror(errno)); return NULL; }
+    float *t = (float *)malloc(2050 * 2 * sizeof(float));
+    const size_t got = t ? fread(t, 1, 2050 * 2 * sizeof(float), f) : 0;
+    fclose(f);
+    if (!t || got % (2 * sizeof(float)) != 0 || got < 2 * 2 * sizeof(float) || got > 2049 * 2 * sizeof(float)) {
+        snprintf(why, cap, "--match-template %.160s: not 2 .. 2049 cf32 frames", path);
+        free(t);
+        return NULL;
+    }
+    *frames = (uint32_t)(got / (2 * sizeof(float)));
+    return t;
+}
+
 static int ctx_open(Ctx *x)
 {
     Shard *sh = x->sh;
@@ -636,6 +688,49 @@ static int ctx_open(Ctx *x)
             }
         }
     }
+    if (o->match_prefix) {
+        static const char *const side[2] = {"in", "out"}, *const plane[3] = {"peak.f32", "at.u32", "sum.f32"};
+        const int fmt[2] = {x->d.in_format, x->d.out_format};
+        const double rate[2] = {x->d.input_rate_hz, x->d.target_rate_hz};
+        const size_t most[2] = {x->chunk, x->out_cap / x->obps};      /* frames of one call */
+        char path[4096], why[512];
+        uint32_t L = 0;
+        float *tmpl = match_template_of(o->match_template, &L, why, sizeof(why));
+        if (!tmpl) FAIL("%.250s", why);
+        if (match_shifts_of(o, x->mt_hz, &x->mt_nhz)) { free(tmpl); FAIL("--match-shifts: %s", o->match_shifts); }
+        iqgpu_match_opts_init(&x->mt_opts);
+        if (o->match_block) x->mt_opts.block_frames = o->match_block;
+        x->mt_opts.template_frames = L;
+        x->mt_opts.n_templates = x->mt_nhz ? x->mt_nhz : 1;
+        float *bank = (float *)malloc((size_t)x->mt_opts.n_templates * L * 2 * sizeof(float));
+        if (!bank) { free(tmpl); FAIL("--match: out of memory for the templates"); }
+        for (int k = 0; k < 2; k++) {
+            int rc = IQGPU_OK;
+            if (x->mt_nhz) rc = iqgpu_match_shift_bank(tmpl, L, x->mt_hz, x->mt_nhz, rate[k], bank);
+            else memcpy(bank, tmpl, (size_t)L * 2 * sizeof(float));
+            if (rc == IQGPU_OK) rc = iqgpu_match_create(dev, fmt[k], &x->mt_opts, bank, &x->mt[k]);
+            if (rc != IQGPU_OK) { free(bank); free(tmpl); FAIL("--match: %s", iqgpu_last_error()); }
+        }
+        free(bank); free(tmpl);
+        {
+            iqgpu_match_info info;
+            CK(iqgpu_match_read_open(x->mt[0], NULL, NULL, NULL, &info));
+            x->mt_opts.nfft = info.nfft;                               /* as the handles run it */
+        }
+        for (int k = 0; k < 2; k++) {
+            const size_t row_bytes = (size_t)x->mt_opts.n_templates * 4;
+            x->mt_cap[k] = most[k] / x->mt_opts.block_frames + 1;     /* rows one call can finish, behind an open row */
+            for (int q = 0; q < 3; q++) {
+                for (int b = 0; b < NBUF; b++) {
+                    CK(iqgpu_device_malloc(dev, x->mt_cap[k] * row_bytes, &x->mt_d[k][q][b]));
+                    CK(iqgpu_host_malloc_pinned(x->mt_cap[k] * row_bytes, &x->mt_h[k][q][b]));
+                }
+                snprintf(path, sizeof(path), "%s.%s.%s", o->match_prefix, side[k], plane[q]);
+                x->mt_f[k][q] = fopen(path, "wb");
+                if (!x->mt_f[k][q]) FAIL("writing %.160s: %s", path, strerror(errno));
+            }
+        }
+    }
     if (o->synthetic_frames <= 0) {
         x->in_fd = open(o->in_path, O_RDONLY);
         if (x->in_fd < 0) FAIL("open %s: %s", o->in_path, strerror(errno));
@@ -682,6 +777,17 @@ static void ctx_close(Ctx *x)
         for (int b = 0; b < NBUF; b++) {
             if (x->ev_d[k][b]) iqgpu_device_free(dev, x->ev_d[k][b]);
             if (x->ev_h[k][b]) iqgpu_host_free_pinned(x->ev_h[k][b]);
+        }
+    }
+    for (int k = 0; k < 2; k++) {
+        iqgpu_match_destroy(x->mt[k]);
+        for (int q = 0; q < 3; q++) {
+            if (x->mt_f[k][q]) fclose(x->mt_f[k][q]);
+            free(x->mt_all[k][q]);
+            for (int b = 0; b < NBUF; b++) {
+                if (x->mt_d[k][q][b]) iqgpu_device_free(dev, x->mt_d[k][q][b]);
+                if (x->mt_h[k][q][b]) iqgpu_host_free_pinned(x->mt_h[k][q][b]);
+            }
         }
     }
     free(x->ev_all);
@@ -854,6 +960,13 @@ static int stream_range(Ctx *x)
                     CK(iqgpu_memcpy_d2h_async(x->lg_h[k][1][b], x->lg_d[k][1][b], x->lg_rows[k][b] * sizeof(float), x->s_k));
                 }
             }
+            /* --match: the same place and the same way, three planes */
+            for (int k = 0; k < 2 && x->mt[k]; k++) {
+                CK(iqgpu_match_push_device(x->mt[k], k ? x->d_out[b] : x->d_in[b], k ? out_frames[b] : n, (float *)x->mt_d[k][0][b], (uint32_t *)x->mt_d[k][1][b],
+                                           (float *)x->mt_d[k][2][b], x->mt_cap[k], &x->mt_rows[k][b], x->s_k));
+                for (int q = 0; q < 3 && x->mt_rows[k][b]; q++)
+                    CK(iqgpu_memcpy_d2h_async(x->mt_h[k][q][b], x->mt_d[k][q][b], x->mt_rows[k][b] * x->mt_opts.n_templates * 4, x->s_k));
+            }
             CK(iqgpu_event_record(x->e_k[b], x->s_k));
             CK(iqgpu_stream_wait_event(x->s_out, x->e_k[b]));
             if (out_frames[b]) CK(iqgpu_memcpy_d2h_async(x->h_out[b], x->d_out[b], out_frames[b] * x->obps, x->s_out));
@@ -901,6 +1014,23 @@ static int stream_range(Ctx *x)
                     memcpy(x->lg_all[k][q] + x->lg_all_n[k] * per_row[q], x->lg_h[k][q][b], nr * per_row[q] * sizeof(float));
                 }
                 x->lg_all_n[k] += nr;
+            }
+            for (int k = 0; k < 2 && x->mt[k]; k++) {
+                const size_t nr = x->mt_rows[k][b], per_row = x->mt_opts.n_templates;
+                if (nr && x->mt_all_n[k] + nr > x->mt_all_cap[k]) {
+                    const size_t cap = 2 * (x->mt_all_n[k] + nr);
+                    for (int q = 0; q < 3; q++) {
+                        uint32_t *g = (uint32_t *)realloc(x->mt_all[k][q], cap * per_row * 4);
+                        if (!g) FAIL("--match: out of memory for the rows");
+                        x->mt_all[k][q] = g;
+                    }
+                    x->mt_all_cap[k] = cap;
+                }
+                for (int q = 0; q < 3 && nr; q++) {
+                    if (fwrite(x->mt_h[k][q][b], per_row * 4, nr, x->mt_f[k][q]) != nr) FAIL("writing the rows of --match: %s", strerror(errno));
+                    memcpy(x->mt_all[k][q] + x->mt_all_n[k] * per_row, x->mt_h[k][q][b], nr * per_row * 4);
+                }
+                x->mt_all_n[k] += nr;
             }
         }
     }
@@ -1138,6 +1268,63 @@ static int write_lag(Ctx *x)
     return 0;
 }
 
+/* --match PREFIX: the row files are complete; PREFIX.json with the options, both info records and the detections of each side over all
+ * its rows (iqgpu_match_peaks at MATCH_RATIO) */
+static int write_match(Ctx *x)
+{
+    static const char *const side[2] = {"in", "out"}, *const plane[3] = {"peak.f32", "at.u32", "sum.f32"};
+    Shard *sh = x->sh;
+    const Options *o = x->o;
+    const double rate[2] = {x->d.input_rate_hz, x->d.target_rate_hz};
+    const iqgpu_match_opts *mo = &x->mt_opts;
+    char path[4096];
+    snprintf(path, sizeof(path), "%s.json", o->match_prefix);
+    FILE *f = fopen(path, "w");
+    if (!f) FAIL("writing %.160s: %s", path, strerror(errno));
+    fprintf(f, "{\"nfft\": %u, \"block_frames\": %u, \"n_templates\": %u, \"template_frames\": %u, \"ratio\": %.17g, \"shifts_hz\": [", mo->nfft,
+            mo->block_frames, mo->n_templates, mo->template_frames, MATCH_RATIO);
+    for (uint32_t i = 0; i < x->mt_nhz; i++) fprintf(f, "%s%.17g", i ? ", " : "", x->mt_hz[i]);
+    fprintf(f, "]");
+    for (int k = 0; k < 2; k++) {
+        static const uint32_t none[8] = {0};
+        iqgpu_match_info info;
+        const size_t n = x->mt_all_n[k];
+        size_t found = 0;
+        for (int q = 0; q < 3; q++) {
+            FILE *rows = x->mt_f[k][q];
+            x->mt_f[k][q] = NULL;
+            if (fclose(rows) != 0) { fclose(f); FAIL("writing %.160s.%s.%s: %s", o->match_prefix, side[k], plane[q], strerror(errno)); }
+        }
+        if (iqgpu_match_read_open(x->mt[k], NULL, NULL, NULL, &info) != IQGPU_OK) { fclose(f); FAIL("%s", iqgpu_last_error()); }
+        const float *pk = n ? (const float *)x->mt_all[k][0] : (const float *)none, *sm = n ? (const float *)x->mt_all[k][2] : (const float *)none;
+        const uint32_t *at = n ? x->mt_all[k][1] : none;
+        int rc = iqgpu_match_peaks(pk, at, sm, n, mo, MATCH_RATIO, NULL, 0, &found);      /* the count first */
+        iqgpu_match_peak *d = (iqgpu_match_peak *)malloc((found ? found : 1) * sizeof(*d));
+        if ((rc != IQGPU_OK && rc != IQGPU_ECAPACITY) || !d) { free(d); fclose(f); FAIL("--match: %s", d ? iqgpu_last_error() : "out of memory for the detections"); }
+        if (iqgpu_match_peaks(pk, at, sm, n, mo, MATCH_RATIO, d, found, &found) != IQGPU_OK) { free(d); fclose(f); FAIL("%s", iqgpu_last_error()); }
+        fprintf(f, ", \"%s\": {\"sample_rate\": %.17g, \"frames\": %llu, \"segments\": %llu, \"rows\": %llu, \"open_segments\": %u, \"template_energy\": [",
+                side[k], rate[k], (unsigned long long)info.frames, (unsigned long long)info.segments, (unsigned long long)info.rows, info.open_segments);
+        for (uint32_t t = 0; t < mo->n_templates; t++) fprintf(f, "%s%.17g", t ? ", " : "", info.template_energy[t]);
+        fprintf(f, "], \"detections\": [");
+        for (size_t i = 0; i < found; i++) {
+            fprintf(f, "%s{\"first_frame\": %llu, \"template\": %u, \"peak\": %.9g, \"ratio\": ", i ? ", " : "", (unsigned long long)d[i].first_frame,
+                    d[i].template_index, (double)d[i].peak);
+            if (d[i].ratio - d[i].ratio == 0.0) fprintf(f, "%.17g}", d[i].ratio); else fprintf(f, "null}");      /* (+inf: the row's other positions hold no power) */
+        }
+        free(d);
+        fprintf(f, "], \"files\": [");
+        for (int q = 0; q < 3; q++) {
+            fprintf(f, "%s\"", q ? ", " : "");
+            json_put(f, o->match_prefix);
+            fprintf(f, ".%s.%s\"", side[k], plane[q]);
+        }
+        fprintf(f, "]}");
+    }
+    fprintf(f, "}\n");
+    if (fclose(f) != 0) FAIL("writing %.160s: %s", path, strerror(errno));
+    return 0;
+}
+
 /* --seamless-rms, --seamless-dc-rms: what the seam behind this range is checked against, and what the range behind it restarts from if the check fails */
 static int save_checkpoint(Ctx *x)
 {
@@ -1171,7 +1358,7 @@ static void *run_shard(void *arg)
 
     if (o->dry) dry_shard(&x);
     else {
-        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && !(o->sgram_prefix && write_sgram(&x)) && !(o->env_prefix && write_env(&x)) && !(o->lag_prefix && write_lag(&x)) && !(o->stats_prefix && read_stats(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
+        if (!ctx_open(&x) && !enter_stream(&x) && !stream_range(&x) && !(o->psd_prefix && write_psd(&x)) && !(o->sgram_prefix && write_sgram(&x)) && !(o->env_prefix && write_env(&x)) && !(o->lag_prefix && write_lag(&x)) && !(o->match_prefix && write_match(&x)) && !(o->stats_prefix && read_stats(&x)) && MODES[o->mode].certify) save_checkpoint(&x);
         /* (a shard that fails early still keeps the rendezvous of the passes: the others wait there) */
         while (sh->barriers < MODES[o->mode].barriers) rendezvous(&x, NULL, NULL);
     }
@@ -1197,6 +1384,7 @@ static void usage(void)
             "          [--stats PREFIX (plain runs and independent --shards: counts, rails, extrema, peak, histogram and moments of the input and of the output bytes, merged in shard order, as PREFIX.json)]\n"
             "          [--psd PREFIX (plain single-stream runs: the power spectra of the input and of the output -- Hann, 1024 bins -- as PREFIX.in.f64, PREFIX.out.f64, PREFIX.json)]\n"
             "          [--lag PREFIX [--lag-list d1,d2,..] [--lag-block B] (the same runs: the lag products x[n] conj(x[n - d]) and the power per row of B frames (4096) of the input and of the output for up to four lags d (1), rows appended as they finish to PREFIX.in.lag.f32, PREFIX.in.sum.f32, PREFIX.out.lag.f32, PREFIX.out.sum.f32; PREFIX.json with the frequency estimate and the coherence per lag)]\n"
+            "          [--match PREFIX --match-template FILE.cf32 [--match-block B] [--match-shifts hz1,hz2,..] (the same runs: the correlation of the input and of the output with the template of 2 .. 2049 cf32 frames in FILE.cf32 -- with --match-shifts, with its one to eight copies shifted by those offsets in Hz -- per row of B start positions (4096): the largest power, where it is and the sum, rows appended as they finish to PREFIX.{in,out}.peak.f32 / .at.u32 / .sum.f32; PREFIX.json with the detections at ratio 100)]\n"
             "          [--envelope PREFIX [--envelope-block B] (the same runs: the power per row of B frames (4096) of the input and of the output, rows appended as they finish to PREFIX.in.f32, PREFIX.out.f32; PREFIX.json with the bursts of the input)]\n"
             "          [--sgram PREFIX [--sgram-row-segments R] (the same runs: the spectrum per row of R segments (32) of the input and of the output, rows appended as they finish to PREFIX.in.f32, PREFIX.out.f32; PREFIX.json)]\n"
             "          [--no-numa-bind] [--quiet] [--debug NAME=VALUE (iqgpu_debug_set)]\n"
@@ -1232,6 +1420,10 @@ static int parse_args(int argc, char **argv, Options *o)
         else if (!strcmp(a, "--lag")) o->lag_prefix = NEXT;
         else if (!strcmp(a, "--lag-list")) o->lag_list = NEXT;
         else if (!strcmp(a, "--lag-block")) { const long long r = atoll(NEXT); o->lag_block = r >= 64 && r <= (1 << 24) && (r & (r - 1)) == 0 ? (unsigned)r : ~0u; }
+        else if (!strcmp(a, "--match")) o->match_prefix = NEXT;
+        else if (!strcmp(a, "--match-template")) o->match_template = NEXT;
+        else if (!strcmp(a, "--match-shifts")) o->match_shifts = NEXT;
+        else if (!strcmp(a, "--match-block")) { const long long r = atoll(NEXT); o->match_block = r >= 512 && r <= (1 << 24) && (r & (r - 1)) == 0 ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--envelope-block")) { const long long r = atoll(NEXT); o->env_block = r >= 64 && r <= (1 << 24) && (r & (r - 1)) == 0 ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--sgram-row-segments")) { const long long r = atoll(NEXT); o->sgram_row_segments = r >= 1 && r <= (1 << 20) ? (unsigned)r : ~0u; }
         else if (!strcmp(a, "--no-resample")) o->desc.no_resample = 1;
@@ -1317,6 +1509,31 @@ static int validate(const Options *o)
         iqgpu_lag_opts lo;
         if ((o->lag_list && !o->lag_prefix) || lag_opts_of(o, &lo))
             REFUSE(2, "usage: --lag-list d1,d2,.. goes with --lag PREFIX: one to four lags, strictly increasing, each 1 .. 65536\n");
+    }
+    if (o->match_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
+        REFUSE(2, "usage: --match is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
+    if (o->match_prefix && strlen(o->match_prefix) > 3000) REFUSE(2, "usage: --match: the prefix is too long\n");
+    if (!o->match_prefix != !o->match_template) REFUSE(2, "usage: --match PREFIX and --match-template FILE.cf32 go together\n");
+    if (o->match_block && (!o->match_prefix || o->match_block == ~0u)) REFUSE(2, "usage: --match-block B goes with --match PREFIX, B a power of two in 512 .. 16777216\n");
+    {
+        double hz[8];
+        uint32_t nhz;
+        if ((o->match_shifts && !o->match_prefix) || match_shifts_of(o, hz, &nhz))
+            REFUSE(2, "usage: --match-shifts hz1,hz2,.. goes with --match PREFIX: one to eight offsets in Hz\n");
+    }
+    if (o->match_prefix) {
+        /* the template and the options are checked before anything is written: the file, then the library's own rules (B against nfft) */
+        char why[512];
+        uint32_t L = 0;
+        uint64_t rows;
+        iqgpu_match_opts mo;
+        float *t = match_template_of(o->match_template, &L, why, sizeof(why));
+        if (!t) REFUSE(2, "usage: %s\n", why);
+        free(t);
+        iqgpu_match_opts_init(&mo);
+        if (o->match_block) mo.block_frames = o->match_block;
+        mo.template_frames = L;
+        if (iqgpu_match_rows(&mo, 0, &rows) != IQGPU_OK) REFUSE(2, "usage: --match-block: %s\n", iqgpu_last_error());
     }
     if (o->env_prefix && (o->have_shards || o->mode != M_INDEPENDENT || o->iq_calibrate))
         REFUSE(2, "usage: --envelope is for plain single-stream runs: it excludes --shards, every --seamless* mode and --iq-calibrate\n");
